@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LAFF retrieval hot path on MI355X: text-video cosine pairs/s (+ R@1/5/10/MedR).
 
-    python bench.py [--gpus N --steps K --warmup W --workload c4_40kx10k --precision fp16]
+    python bench.py [--gpus N --steps K --warmup W --workload c4_40kx10k --precision fp16 --dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one full pass of the hot path over the synthetic workload with every input already resident in HBM:
@@ -34,6 +34,46 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 L2_PEAK_GBS = 34500.0         # MI355X_MICROARCH.md: 8 x 4 MiB L2, ~34.5 TB/s aggregate
 GRAPH_CHECK_REPLAYS = 64       # replays of the two captured steps that are checked against the eager step before the W warm-up replays
 MFMA_PEAK_TFLOPS = {'f32': 157.3, 'f16': 2500.0, 'bf16': 2500.0}
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all files together, headers included
+NPY_HEADER_BYTES = 4096        # more than the header np.save writes in front of an array
+DUMP_SAMPLE_SEED = 0           # row sample of an output too large to dump whole: depends on its shape only
+DUMPED = ('S_local', 'ranks', 'txt_emb', 'vis_emb')    # the arrays of a pass's result dict (laff_amd.dist.evaluate_sharded), + metrics
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> tensor / array / tuple; None is skipped) as out_dir/<name>.npy -- float64 when
+    it holds float64 values or integers (ranks), float32 otherwise.  1-D arrays are written whole.  An array of rows that does not fit
+    its share of what the budget leaves keeps a fixed seeded sample of its rows (ascending; their indices go to <name>_rows.npy), taken
+    on the device.  Returns {file name: shape}."""
+    arrays = {k: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a)) for k, a in arrays.items() if a is not None}
+
+    def wide(t):
+        return t.dtype == torch.float64 or not t.is_floating_point()
+
+    def host(t):
+        return t.detach().to('cpu', torch.float64 if wide(t) else torch.float32).numpy()
+
+    out = {k: host(t) for k, t in arrays.items() if t.dim() <= 1}
+    left = budget - sum(a.nbytes + NPY_HEADER_BYTES for a in out.values())
+    # arrays of rows, smallest first: what one of them leaves unused goes to the larger ones
+    rowed = sorted((k for k, t in arrays.items() if t.dim() > 1), key=lambda k: arrays[k].numel())
+    for i, k in enumerate(rowed):
+        t = arrays[k]
+        row_bytes = t[:1].numel() * (8 if wide(t) else 4)
+        n = max(0, min(t.shape[0], (left // (len(rowed) - i) - 2 * NPY_HEADER_BYTES) // (row_bytes + 8)))
+        if n < t.shape[0]:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.shape[0], n, replace=False))
+            out[k + '_rows'] = idx.astype(np.float64)
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        out[k] = host(t)
+        left -= sum(out[f].nbytes + NPY_HEADER_BYTES for f in (k, k + '_rows') if f in out)
+    total = sum(a.nbytes + NPY_HEADER_BYTES for a in out.values())
+    if total > budget:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the budget of %d' % (total, budget))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return {k + '.npy': list(a.shape) for k, a in out.items()}
 
 
 class StageTimer:
@@ -298,6 +338,8 @@ def dryrun_main(args):
         others = [k for k in ('video', 'text', 'video16') if k != head]
         el, res = out[head]
         m = res['metrics']
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {k: res.get(k) for k in DUMPED} | {'metrics': m})
 
         def gb(k):
             return gathered_bytes(k, Nt, Nv, Wt.shape[1], world, 4096) if k == 'video16' else gathered_bytes(k, Nt, Nv, Wt.shape[1], world)
@@ -515,7 +557,14 @@ def main():
     ap.add_argument('--force-dist', action='store_true', help='run the N > 1 code path (collectives included) on a 1-rank group')
     ap.add_argument('--profile-steps', type=int, default=20, help='replays of the instrumented graph (events between the launches) after the timed region')
     ap.add_argument('--seed', type=int, default=1237)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one handed its caller (scores, ranks, metrics, embeddings; rank 0) '
+                         'as DIR/<name>.npy, at most 64 MB in all (a seeded row sample of a larger output)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.emulate_shard > 1:
+        ap.error('--dump-outputs dumps the whole pass: not with --emulate-shard')
 
     if args.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         # no launcher: become the parent of N ranks (nothing in this process has touched the GPU yet)
@@ -650,6 +699,7 @@ def main():
     #                between them -- nothing RCCL-related is ever captured;
     #   --no-graph : eager launches.
     graph, graphs, runner, state, side = None, [], None, {}, None
+    graph_res = []          # what each capture returned: the tensors its replays write
     for _ in range(max(1, args.warmup)):
         res = step(False)
     torch.cuda.synchronize()
@@ -674,6 +724,7 @@ def main():
                     gph.replay()
                     torch.cuda.synchronize()
                     graphs.append(gph)
+                    graph_res.append(res)
                 graph = graphs[0]
                 if args.two_streams:
                     # steps k and k+1 on two streams: the latency-bound tail of a step (prepare / resolve / metrics, the sparse last
@@ -808,6 +859,12 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result, before anything else runs on the device
+        last = graph_res[(args.steps - 1) % 2] if graph is not None else res
+        dumped = dump_outputs(args.dump_outputs, {k: last.get(k) for k in DUMPED} | {
+            'metrics': pins[(args.steps - 1) % 2][:7] if (graph is not None or runner is not None) else last['metrics']})
+        print('dumped to %s: %s' % (args.dump_outputs, dumped), file=sys.stderr)
     breakdown = None
     if graph is not None or runner is not None:
         final_metrics = tuple(pins[(args.steps - 1) % 2][:7].tolist())
@@ -1172,7 +1229,7 @@ def main():
         os.write(json_fd, (json.dumps(line) + '\n').encode())
     # orderly teardown: captured graphs and their private pools go away while the HIP runtime is still up
     import gc
-    graph = graphs = runner = state = res = None
+    graph = graphs = graph_res = runner = state = res = None
     gc.collect()
     torch.cuda.synchronize()
     if dist.is_initialized():

@@ -74,3 +74,52 @@ def test_more_gpus_than_the_node_has_is_refused():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1'], env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 2 and 'visible GPU' in out.stderr and out.stdout.strip() == ''
+
+
+def test_dump_outputs_dryrun(tmp_path):
+    """--dump-outputs DIR writes the result of the last timed step (float32 / float64 .npy), the same from run to run and -- for the
+    replicated ranks and metrics -- the same on one rank and on two."""
+    import numpy as np
+    runs = []
+    for name, n in (('a', 1), ('b', 1), ('c', 2)):
+        line = _run(n, '--dump-outputs', str(tmp_path / name))
+        runs.append((line, {f[:-4]: np.load(str(tmp_path / name / f)) for f in os.listdir(tmp_path / name)}))
+    (line, a), (_, b), (_, c) = runs
+    assert sorted(a) == ['S_local', 'metrics', 'ranks', 'txt_emb', 'vis_emb'] and sorted(b) == sorted(a) == sorted(c)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    q = line['quality']
+    assert a['metrics'].tolist() == [q[k] for k in ('R@1', 'R@5', 'R@10', 'MedR', 'meanr', 'mir', 'mAP')]
+    assert np.array_equal(a['ranks'], c['ranks']) and np.array_equal(a['metrics'], c['metrics'])
+    assert c['S_local'].shape[1] < a['S_local'].shape[1]          # rank 0's video shard
+
+
+def test_dump_outputs_samples_rows_within_the_budget(tmp_path):
+    """An output larger than its share of the budget keeps a seeded sample of its rows (indices beside it); the rest goes whole."""
+    import numpy as np
+    import torch
+    import bench
+    g = np.random.default_rng(3)
+    arrays = {'S': torch.from_numpy(g.normal(size=(1000, 64)).astype(np.float32)), 'E': g.normal(size=(10, 8)),
+              'r': torch.arange(1, 101, dtype=torch.int32), 'm': (1.5, 2.0)}
+    budget = 100000
+    for d in ('x', 'y'):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / 'x'))
+    assert files == ['E.npy', 'S.npy', 'S_rows.npy', 'm.npy', 'r.npy'] and sorted(os.listdir(tmp_path / 'y')) == files
+    got = {f[:-4]: np.load(str(tmp_path / 'x' / f)) for f in files}
+    assert sum(os.path.getsize(str(tmp_path / 'x' / f)) for f in files) <= budget
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(str(tmp_path / 'y' / f)))
+    rows = got['S_rows'].astype(np.int64)
+    assert got['S_rows'].dtype == np.float64 and len(rows) > 100 and np.all(np.diff(rows) > 0)
+    assert got['S'].dtype == np.float32 and np.array_equal(got['S'], arrays['S'].numpy()[rows])
+    assert got['E'].dtype == np.float64 and np.array_equal(got['E'], arrays['E'])
+    assert got['r'].dtype == np.float64 and np.array_equal(got['r'], np.arange(1, 101))
+    assert got['m'].dtype == np.float64 and got['m'].tolist() == [1.5, 2.0]
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], env=dict(os.environ, LAFF_BENCH_DRYRUN='1'),
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and '--steps' in out.stderr and out.stdout.strip() == ''

@@ -351,6 +351,45 @@ def test_bench_emulate_shard_line():
         assert e['score_block'] == ([171, 192] if shard == 'text' else [512, 64])
 
 
+def test_bench_dump_outputs_are_the_timed_pass(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's scores, ranks, metrics and embeddings, the same whichever of the two captures
+    ran it (3 and 4 steps), and what the oracle computes on the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from laff_amd import synth
+    from util import oracle_towers
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for steps in (3, 4):
+        d = tmp_path / str(steps)
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'tiny', '--steps', str(steps), '--warmup', '1',
+                              '--no-cpu-baseline', '--no-extra-modes', '--dump-outputs', str(d)],
+                             capture_output=True, text=True, timeout=900, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1 and json.loads(lines[0])['steps'] == steps
+        runs.append((json.loads(lines[0]), {f[:-4]: np.load(str(d / f)) for f in os.listdir(d)}))
+    (line, got), (_, again) = runs
+    assert sorted(got) == ['S_local', 'metrics', 'ranks', 'txt_emb', 'vis_emb'] and sorted(again) == sorted(got)
+    for k in got:
+        assert got[k].dtype in (np.float32, np.float64) and np.array_equal(got[k], again[k]), k
+    Nt, Nv, H, d_, _ = synth.WORKLOADS['tiny']
+    assert got['S_local'].shape == (Nt, Nv) and got['ranks'].shape == (Nt,)
+    q = line['quality']
+    assert got['metrics'].tolist() == [q[k] for k in ('R@1', 'R@5', 'R@10', 'MedR', 'meanr', 'mir', 'mAP')]
+    assert abs(got['metrics'][0] - 100.0 * np.mean(got['ranks'] == 1)) <= 1e-9
+    dev = torch.device('cuda:0')
+    model = synth.build_model(H, d_, dev, seed=1237)
+    vis, txt, gt, _ = synth.make_features(Nt, Nv, dev, seed=1237)
+    ve, te = oracle_towers(model, synth.to_numpy_dict(vis), synth.to_numpy_dict(txt))
+    assert np.abs(got['vis_emb'].reshape(ve.shape) - ve).max() <= 1e-5 and np.abs(got['txt_emb'].reshape(te.shape) - te).max() <= 1e-5
+    assert np.abs(got['S_local'] - O.txt2vis_matrix(te, ve)).max() <= 1e-4
+    own = O.count_ranks(O.txt2vis_matrix_f64(got['txt_emb'].reshape(Nt, H, -1), got['vis_emb'].reshape(Nv, H, -1)), gt.cpu().numpy())
+    assert np.array_equal(got['ranks'], own)
+
+
 def test_evaluation_cosine_sim_golden(golden):
     """laff_amd.evaluation.cosine_sim (GPU-backed, numpy in / numpy out) against the reference's evaluation.cosine_sim
     (evaluation.py:44-49), every operand precision; a zero query row and one whose norm is comparable to the 1e-10 epsilon."""
