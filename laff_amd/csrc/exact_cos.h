@@ -18,6 +18,9 @@ __device__ __forceinline__ double group_sum_f64(double v) { return wave_allreduc
 __device__ __forceinline__ float group_sum_f32(float v) { return wave_allreduce<8>(v, [](float a, float b) { return a + b; }); }
 
 constexpr double COS_EPS = 1e-13 + 1e-14;      // loss.cosine_sim -> l2norm(eps=1e-13): X / (norm + eps + 1e-14)  (loss.py:8-13,30-34)
+// float4 columns of a lane per batch: 4 x 64 = 256 columns (8 loads in flight).  (8 -- a whole 512-d head at once -- needs 126
+// registers in the resolve kernel: 4 wavefronts per SIMD, slower)
+constexpr int EXACT_CH = 4;
 
 // Every lane of the group returns the same value; identical arithmetic (lane -> column map, fma order, reduction tree) wherever it
 // is called, so equal rows give bit-equal scores: a duplicate of the ground-truth video ties with it exactly and is not counted.
@@ -30,25 +33,13 @@ __device__ __forceinline__ double exact_cos_with(LoadT&& load_t, const float* __
         const float* vh = v + (long)h * d;
         double tt = 0.0, vv = 0.0, tv = 0.0;
         auto chain = [&](const float4& a, const float4& b) {
-#ifdef LAFF_EXACT_NOFMA
-            tt += (double)(a.x + a.y + a.z + a.w); vv += (double)(b.x + b.y + b.z + b.w); tv += 1.0;
-            return;
-#endif
-#ifdef LAFF_EXACT_TVONLY                  /* timing only: what stored row norms would leave of the chains */
-            { const double ax_ = a.x, ay_ = a.y, az_ = a.z, aw_ = a.w, bx_ = b.x, by_ = b.y, bz_ = b.z, bw_ = b.w;
-              tv = fma(ax_, bx_, tv); tv = fma(ay_, by_, tv); tv = fma(az_, bz_, tv); tv = fma(aw_, bw_, tv); tt = 1.0; vv = 1.0; }
-            return;
-#endif
             const double ax = a.x, ay = a.y, az = a.z, aw = a.w, bx = b.x, by = b.y, bz = b.z, bw = b.w;
             tt = fma(ax, ax, tt); tt = fma(ay, ay, tt); tt = fma(az, az, tt); tt = fma(aw, aw, tt);
             vv = fma(bx, bx, vv); vv = fma(by, by, vv); vv = fma(bz, bz, vv); vv = fma(bw, bw, vv);
             tv = fma(ax, bx, tv); tv = fma(ay, by, tv); tv = fma(az, bz, tv); tv = fma(aw, bw, tv);
         };
-#ifndef LAFF_EXACT_CH
-#define LAFF_EXACT_CH 4
-#endif
-        constexpr int CH = LAFF_EXACT_CH;                            // float4 columns of a lane per batch: 4 x 64 = 256 columns (8 loads in flight)
-        if (d % (RG * 4 * CH) == 0) {     // (CH = 8 -- a whole 512-d head at once -- needs 126 registers in the resolve kernel: 4 wavefronts per SIMD, slower)
+        constexpr int CH = EXACT_CH;
+        if (d % (RG * 4 * CH) == 0) {
             // Heads of whole 256-column batches: the 8 row loads of a batch are ALL requested before the first product (arrays
             // filled first, chains afterwards, in column order: the fma sequence -- and every bit of the result -- is that of the
             // rolled loop below).  With `#pragma unroll 8` on that loop hipcc issued the loads in pairs with `s_waitcnt vmcnt(0)`

@@ -113,10 +113,7 @@ __device__ __forceinline__ void dma_piece(unsigned voff, u32x4 rsrc, unsigned so
 // immediate offset: the instruction's offset field moves the LDS address as well as the global one.)
 template <int LDSOFF>
 __device__ __forceinline__ void dma_rows(unsigned voff, unsigned long long base, unsigned m0base) {
-#ifndef LAFF_FCS_XFLAVOR
-#define LAFF_FCS_XFLAVOR ""
-#endif
-    asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 " LAFF_FCS_XFLAVOR
+    asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 "
                  ::"v"(voff), "s"(base), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
 }
 // 16 bytes of the LDS staging -> a[R .. R + 3]
@@ -129,10 +126,7 @@ __device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
 // address = voff0 + ROWMUL * ldy4, made right in front of the store (one address register instead of one per accumulator)
 template <int ROWMUL>
 __device__ __forceinline__ void store_row(unsigned& tmp, float data, unsigned voff0, unsigned ldy4, u32x4 rsrc, unsigned soff) {
-#ifndef LAFF_FCS_STFLAVOR
-#define LAFF_FCS_STFLAVOR "nt"
-#endif
-    asm volatile("v_mad_u32_u24 %0, %3, %4, %2\n\tbuffer_store_dword %1, %0, %5, %6 offen " LAFF_FCS_STFLAVOR
+    asm volatile("v_mad_u32_u24 %0, %3, %4, %2\n\tbuffer_store_dword %1, %0, %5, %6 offen nt"
                  : "=&v"(tmp) : "v"(data), "v"(voff0), "s"(ldy4), "n"(ROWMUL), "s"(rsrc), "s"(soff) : "memory");
 }
 
@@ -357,11 +351,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             }
         };
         // the strip whose first three rounds this segment's last three bodies bring in: the next segment's (n >= 2: three bodies exist)
-#ifdef LAFF_FCS_NOEARLY
-        const bool has_next = false;
-#else
         const bool has_next = u0 < u1 && n >= 2;
-#endif
         int p2 = p, strip2 = strip;
         if (has_next) {
             p2 = 0;
@@ -740,8 +730,6 @@ __global__ __launch_bounds__(256) void fc_strip_pack_kernel(const float* __restr
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-int g_fc_strip = 1;          // LAFF_FC_STRIP (read when a ctx is created; the host's 0 = never take the strip form)
-
 size_t fc_strip_image_bytes(int D) { return (size_t)(D / 32) * (2 * SLOT) + (size_t)D * 16; }
 size_t fc_strip_vec_offset(int D) { return (size_t)(D / 32) * (2 * SLOT); }
 

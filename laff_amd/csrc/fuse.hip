@@ -164,10 +164,7 @@ __device__ __forceinline__ void load_gather_plane(const FuseArgs& a, int l, long
             // added, in word order.  (As the generic loop below hipcc emitted ONE load at a time with `s_waitcnt vmcnt(0)` behind it --
             // the `col < d` test makes every load its own EXEC-masked block with the same destination registers --: 28 dependent
             // round trips per item at 14 words, the 0.03 ms per row per caption of the C1 launch.)
-#ifndef LAFF_GATHER_GW
-#define LAFF_GATHER_GW 4
-#endif
-            constexpr int GW = LAFF_GATHER_GW;
+            constexpr int GW = 4;
             for (int q = 0; q < cnt; q += GW) {                  // lanes >= cnt hold (row 0, weight 0)
                 float4 r[GW][NCH];
                 float v[GW];
@@ -370,20 +367,17 @@ __device__ __forceinline__ void rank_side_idle(const FuseArgs& a) {
 }
 
 // ---- register-resident variant: d <= 256*NCH ----------------------------------------------------------------
-// Six wavefronts per SIMD (at most 80 VGPRs; <4, 2> took 84 = five): the launch is a chain of load -> ~700 VALU -> store per wavefront that
-// waits 72 % of its cycles (SQ_WAIT_ANY), so resident wavefronts are what keeps loads in flight.  C4 fuse launches 0.153 -> 0.142 ms,
-// C5 2.15 -> 2.01 (A/B on one box, profiles/r6_fuse_occupancy.txt); eight per SIMD (64 VGPRs) spills and loses (0.181).  The step gains
-// only a third of that: the pass is bound by its energy and the shorter launch draws what it saved.
-// (More than eight resident float4 planes per lane -- L * NCH > 8 --, and L = 8, do not fit 80 registers: those instantiations stay unconstrained.)
-#ifndef LAFF_FUSE_WAVES
-#define LAFF_FUSE_WAVES 6
-#endif
-#ifndef LAFF_FUSE_WAVES8
-#define LAFF_FUSE_WAVES8 5          // eight resident float4 planes per lane with all their loads in flight: 88 registers
-#endif
-#define LAFF_FUSE_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(L * NCH <= 6 ? LAFF_FUSE_WAVES : (L * NCH <= 8 && L < 8) ? LAFF_FUSE_WAVES8 : 1)))
+// Resident wavefronts per SIMD: the launch is a chain of load -> ~700 VALU -> store per wavefront that waits 72 % of its cycles
+// (SQ_WAIT_ANY), so resident wavefronts are what keeps loads in flight.  Six (at most 80 VGPRs) where L * NCH <= 6: <1..6, 1> take 58
+// VGPRs, <1, 2> 68, <2, 2> 74, <3, 2> 78.  Five (at most 96) for seven or eight resident float4 planes per lane with L < 8, which
+// need more than 80 registers with all their loads in flight: <7, 1> takes 82, <4, 2> (C4) 90.  The rest stay unconstrained:
+// <8, 1> (82), <5, 2> (104), <6, 2> (112), <7, 2> (120), <8, 2> (128).  Six against five, measured while <4, 2> still fitted 80
+// registers: C4 fuse launches 0.153 -> 0.142 ms, C5 2.15 -> 2.01 (A/B on one box, profiles/r6_fuse_occupancy.txt); eight per SIMD
+// (64 VGPRs) spills and loses (0.181).  The step gains only a third of that: the pass is bound by its energy and
+// the shorter launch draws what it saved.
 template <int L, int NCH>
-__global__ __launch_bounds__(256) LAFF_FUSE_WAVES_ATTR void fuse_reg_kernel(FuseArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(L * NCH <= 6 ? 6 : (L * NCH <= 8 && L < 8) ? 5 : 1)))
+void fuse_reg_kernel(FuseArgs a) {
     const int lane = threadIdx.x & 63;
     long n;
     int h;
@@ -432,11 +426,7 @@ __global__ __launch_bounds__(256) LAFF_FUSE_WAVES_ATTR void fuse_reg_kernel(Fuse
             for (int j = 0; j < NCH; ++j) {
                 x[l][j] = make_float4(0, 0, 0, 0);
                 if (pdense[l]) {                                             // wave-uniform
-#ifdef LAFF_FUSE_PLANE_PLAIN
-                    const nt_f32x4 nv = *(const nt_f32x4*)(psrc[l] + n * pld[l] + j * 256 + lane * 4);
-#else
                     const nt_f32x4 nv = __builtin_nontemporal_load((const nt_f32x4*)(psrc[l] + n * pld[l] + j * 256 + lane * 4));
-#endif
                     x[l][j] = make_float4(nv.x, nv.y, nv.z, nv.w);
                 }
             }

@@ -814,9 +814,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, const int r0, const
         constexpr bool LONE = ((CF::THREADS == 256 && WM * WN >= 16) || (CF::THREADS == 512 && WM * WN == 8)) && MODE != GEMM_F32 && NSUB == 4;
         u32x4 fc[LONE ? 4 : 2][WN], fr[LONE ? 4 : 2][WM];
         auto issue = [&](int kt, int ks, int b) {
-#ifdef LAFF_ABL_NOREAD
-            if (kt | ks) return;                      // ablation: fragments are read once and reused (wrong results)
-#endif
             const unsigned stg_off = (unsigned)(kt & 1) * CF::STAGEB;
             const unsigned ar = laneR + stg_off + xk[ks], ac = laneC + stg_off + xk[ks];
 #pragma unroll
@@ -1046,9 +1043,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, const int r0, const
                 asm volatile("" ::: "memory");
 #endif
                 if (kt + 2 < nkt) {                                  // slot of stage kt is free now: start refilling it
-#ifndef LAFF_ABL_NODMA
                     fill_on = true;
-#endif
                     fill_sa = lds0 + (unsigned)(kt & 1) * CF::STAGEB;
                     const unsigned long long kb0 = (unsigned long long)((long)st_kin * ROWB);
                     fillR = uniform64(curR + kb0);
@@ -1541,8 +1536,6 @@ template <int MODE>
 static hipError_t launch_x3(const GemmArgs& a, hipStream_t st);
 
 int g_num_cus = 256;       // set from the device properties when a ctx is created
-int g_gemm_variant = 0;   // tuning knob LAFF_GEMM_VARIANT: 128 / 256 / 512 force the tile configuration of the 16-bit GEMM (256 also
-                          // keeps split products in the concatenated form); 3 forces the big tiles incl. the interleaved x3 tile
 
 template <int MODE>
 static hipError_t launch_m(const GemmArgs& a, bool aligned, hipStream_t st) {
@@ -1552,15 +1545,14 @@ static hipError_t launch_m(const GemmArgs& a, bool aligned, hipStream_t st) {
     if constexpr (MODE != GEMM_F32) {
         // big tiles when there are enough of them to fill 256 CUs a few times over
         const long tiles256 = (long)((a.nR + 255) / 256) * ((a.nC + 255) / 256);
-        const bool big = g_gemm_variant == 256 || g_gemm_variant == 3 || (g_gemm_variant != 128 && tiles256 >= 512);
-        if (big && a.nseg == 3 && g_gemm_variant != 256) return launch_x3<MODE>(a, st);
+        const bool big = tiles256 >= 512;
+        if (big && a.nseg == 3) return launch_x3<MODE>(a, st);
         // long K, many tiles: 4 waves of 128x128 -- 1/3 fewer LDS fragment reads per MFMA and a K loop scheduled for a lone wave per
         // SIMD: 2,538 against 2,828 cycles per K-step at K = 4096 (tools/debug/trace_longk.py).  Its prologue and epilogue are longer
         // (4 waves do the work of 8; the banded epilogue reads its accumulators out of the AGPR half), so it pays where the K loop
         // dominates (tools/debug/time_shape.py, banded + S): 100k x 30k x 4096 bf16 23.5 -> 22.3 ms, count-only 21.7 -> 20.0 ms;
         // 59,800 x 2,990 x 4096 1.54 -> 1.59 ms (not taken: 2,808 tiles); 16384^2 x 2048 1.06 -> 1.07 ms (not taken).
-        const bool lone = g_gemm_variant == 512 || (g_gemm_variant == 0 && a.nseg == 1 && tiles256 >= 4096 &&
-                                                    (long long)a.K * ModeTraits<MODE>::ESZ >= 8192);
+        const bool lone = a.nseg == 1 && tiles256 >= 4096 && (long long)a.K * ModeTraits<MODE>::ESZ >= 8192;
         if (lone) return launch_t<MODE, 2, Cfg256L>(a, st);
         if (big) return launch_t<MODE, 2, Cfg256>(a, st);
     }
@@ -1606,7 +1598,7 @@ static hipError_t launch_grouped_x3(GroupedGemmArgs& g, hipStream_t st) {
     // tail split: the big tiles of a last round that would fill at most 3/4 of the CUs become 4 small tiles each
     const long rem = nb % g_num_cus;
     g.nbig = (int)nb;
-    if (g_gemm_variant != 4 && nb > g_num_cus && rem > 0 && rem * 4 <= 3L * g_num_cus) g.nbig = (int)(nb - rem);
+    if (nb > g_num_cus && rem > 0 && rem * 4 <= 3L * g_num_cus) g.nbig = (int)(nb - rem);
     const long grid = g.nbig + 4L * (nb - g.nbig);
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_x3_grouped_kernel<GEMM_F16>, CfgX3::SMEM); e != hipSuccess) return e;
@@ -1646,8 +1638,8 @@ hipError_t launch_gemm_nt_grouped_f16(GroupedGemmArgs& g, hipStream_t st) {
         t256 += (long)((g.p[i].nR + 255) / 256) * ((g.p[i].nC + 255) / 256);
         split = split && g.p[i].nseg == 3;
     }
-    const bool big = g_gemm_variant == 256 || g_gemm_variant == 3 || (g_gemm_variant != 128 && t256 >= 512);
-    if (big && split && g_gemm_variant != 256) return launch_grouped_x3(g, st);     // LAFF_GEMM_VARIANT=256: concatenated form
+    const bool big = t256 >= 512;
+    if (big && split) return launch_grouped_x3(g, st);
     return big ? launch_grouped_f16_t<Cfg256>(g, st) : launch_grouped_f16_t<Cfg128>(g, st);
 }
 

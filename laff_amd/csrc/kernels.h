@@ -93,11 +93,10 @@ struct StripArgs {
     unsigned* pairs;          // header {chunks taken, flag, NW | 1 << 31, NCH} | NCH per-chunk counts | NCH chunks of STRIP_CHUNK entries
     unsigned pair_cap;
     int nranges;              // == gridDim.x
-    int debug;                // g_strip_mode (3: K loops only)
     unsigned long long* trace;   // debug (LAFF_STRIP_TRACE build only): 64 cycle stamps per workgroup
     unsigned short range_of_wg[STRIP_MAX_WG];
 };
-extern int g_strip_mode, g_strip_map;
+extern int g_strip_mode;
 bool sim_strip_eligible(const GemmArgs& a, int mode, bool aligned);
 hipError_t launch_sim_strip(const GemmArgs& a, int mode, hipStream_t st);
 
@@ -121,7 +120,6 @@ struct FcStripArgs {
     FcStripProblem p[MAX_GROUP];
     unsigned short range_of_wg[STRIP_MAX_WG];
 };
-extern int g_fc_strip;
 size_t fc_strip_image_bytes(int D);
 size_t fc_strip_vec_offset(int D);
 hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
@@ -133,7 +131,6 @@ hipError_t launch_gemm_nt_grouped_f32(GroupedGemmArgs& g, int staging, hipStream
 hipError_t launch_gemm_nt_grouped_f16(GroupedGemmArgs& g, hipStream_t st);
 hipError_t launch_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, hipStream_t st);   // fp32 row operand split in the kernel   // fast staging only (packed operands)
 int staging_kind(const GemmArgs& a, int esz, bool aligned);
-extern int g_gemm_variant;
 extern int g_num_cus;
 
 constexpr int MAX_L = 8;

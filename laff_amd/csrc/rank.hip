@@ -281,7 +281,7 @@ __device__ __forceinline__ float row_pass(const float* __restrict__ e, const voi
             xe = fma(x0, ax, xe); xe = fma(x1, ay, xe); xe = fma(x2, az, xe); xe = fma(x3, aw, xe);
         };
         constexpr bool emits = EMIT && (PREC == LAFF_PREC_FP16 || PREC == LAFF_PREC_BF16);
-        constexpr int CH = LAFF_EXACT_CH;
+        constexpr int CH = EXACT_CH;
         if (d % (RG * 4 * CH) == 0) {
             // whole batches of CH column groups: every load of a batch is requested before its first value is used (exact_cos.h has the
             // reason: as one rolled / partially unrolled loop hipcc waited for each load, or pair of loads, before issuing the next);
@@ -717,11 +717,7 @@ __device__ __forceinline__ void resolve_groups(const float* __restrict__ Et, con
     const unsigned* entries = pairs + 4 + cnt_words;
     (void)pair_cap;
     auto one = [&](unsigned r, unsigned c, bool ok) {
-#ifdef LAFF_RESOLVE_HOTROWS
-        const double ex = exact_cos(Et + (long)(r & 63u) * K, Ev + (long)(c & 63u) * K, H, d, sl);
-#else
         const double ex = exact_cos(Et + (long)r * K, Ev + (long)c * K, H, d, sl);
-#endif
         const double sg = s_gt64[r];
         const bool above = ex > sg;
         if (ok && sl == 0) {
@@ -739,14 +735,12 @@ __device__ __forceinline__ void resolve_groups(const float* __restrict__ Et, con
     const unsigned group = (blockIdx.x * 256u + threadIdx.x) / RG, ngroups = gridDim.x * (256u / RG);
     unsigned qn = 0;                                                         // wave-uniform
     auto drain = [&]() {
-#ifndef LAFF_RESOLVE_SCAN_ONLY
         for (unsigned i = 0; i < qn; i += 4) {
             const unsigned j = i + sub;
             const bool ok = j < qn;
             const unsigned k = ok ? j : qn - 1;
             one(queue[wv][k][0], queue[wv][k][1], ok);
         }
-#endif
         qn = 0;
     };
     const unsigned long long trips = (slots + ngroups - 1) / ngroups;
@@ -797,11 +791,10 @@ __device__ __forceinline__ void resolve_pairs(const float* __restrict__ Et, cons
                                               long lds, unsigned* __restrict__ pairs, unsigned pair_cap,
                                               unsigned (*queue)[RESOLVE_QCAP][2]);
 
-// (six wavefronts per SIMD = the launch's 6 x CUs workgroups in one resident round: at most 80 VGPRs)
-#ifndef LAFF_RESOLVE_WAVES
-#define LAFF_RESOLVE_WAVES 5      // 94 registers with 8 row loads in flight per 16-lane group (6 = 80 registers: spills)
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LAFF_RESOLVE_WAVES))) void rank_resolve_kernel(
+// Five wavefronts per SIMD = the launch's 5 x CUs workgroups in one resident round: 84 VGPRs with 8 row loads in flight per 16-lane
+// group (six would allow at most 80: spills)
+constexpr int RESOLVE_WAVES = 5;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RESOLVE_WAVES))) void rank_resolve_kernel(
     const float* __restrict__ Et, const float* __restrict__ Ev, int H, int d, const double* __restrict__ s_gt64, int* __restrict__ count,
     float* __restrict__ S, long lds, unsigned* __restrict__ pairs, unsigned pair_cap, MetricsTail mt) {
     __shared__ __attribute__((aligned(16))) unsigned char pool[RESOLVE_POOL_BYTES];      // the pair queues, then the metrics tail's state
@@ -815,10 +808,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LAFF_RESOLV
         resolve_pairs(Et, Ev, H, d, s_gt64, count, S, lds, pairs, pair_cap, queue);
     if (mt.n <= 0) return;
     // ---- metrics tail: every block releases its counts and draws a ticket; the last one sees all of them
-    // (No fences: a release / acquire pair at agent scope is an L2 write-back + invalidate per workgroup -- with 1,536 of them the launch
-    // took 0.34 ms instead of 0.06.  What the last block needs from the others are their count updates, device-scope atomics that have
-    // been performed once s_waitcnt vmcnt(0) returns; the ticket is a relaxed device-scope atomic issued after that wait, and the last
-    // block reads the counts behind the control dependency on its ticket and ONE acquire fence of its own.)
+    // (No fences: a release / acquire pair at agent scope is an L2 write-back + invalidate per workgroup -- with 1,536 of them (the
+    // 6 x CUs grid of the time; 5 x CUs = 1,280 now) the launch took 0.34 ms instead of 0.06.  What the last block needs from the
+    // others are their count updates, device-scope atomics that have been performed once s_waitcnt vmcnt(0) returns; the ticket is a
+    // relaxed device-scope atomic issued after that wait, and the last block reads the counts behind the control dependency on its
+    // ticket and ONE acquire fence of its own.)
     // Tickets in two levels (same-address device atomics serialise at ~10 ns each: 1,536 of them on one word, arriving together at the
     // end of a balanced launch, cost 14 us): workgroup b draws from counter 1 + b % 32 (each on its own 256-byte line); the last
     // arrival of a group draws from counter 0.
@@ -1040,7 +1034,7 @@ __global__ __launch_bounds__(256) void rank_export_kernel(const double* __restri
 }
 
 // (a kernel, not hipMemsetAsync: inside a captured HIP graph the two memset nodes of this call did not re-run reliably on replay --
-// the fill counters kept growing: tools/debug/dbg_v16_rccl.py)
+// the fill counters kept growing: tools/debug/dbg_v16_rccl.py, removed; see commit e08dd52)
 __global__ __launch_bounds__(256) void rank_export_init_kernel(uint4* __restrict__ out, size_t n16, unsigned* __restrict__ fill, int world) {
     const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
     for (size_t i = i0; i < n16; i += step) out[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
@@ -1062,10 +1056,10 @@ hipError_t launch_rank_resolve(const float* Et, const float* Ev, int Nt, int Nv,
                                float* S, int lds, unsigned* pairs, unsigned pair_cap, hipStream_t st, int metrics_n, int base,
                                int* ranks_out, double* out8, double* host8, unsigned* ticket) {
     (void)Nt; (void)Nv;
-    // one resident round: ~19 KiB of LDS and ~70 VGPRs per block admit 7 blocks per CU; 6 x CUs leaves a margin (a second, sparse
-    // round of the 2,048-block grid doubled this launch's time)
+    // one resident round: ~19 KiB of LDS per block and 84 VGPRs (five wavefronts per SIMD) admit 5 blocks per CU, the RESOLVE_WAVES x
+    // CUs of the grid (a second, sparse round of the 2,048-block grid doubled this launch's time)
     MetricsTail mt{metrics_n, base, ranks_out, out8, host8, ticket};
-    hipLaunchKernelGGL(rank_resolve_kernel, dim3((unsigned)(LAFF_RESOLVE_WAVES * g_num_cus)), dim3(256), 0, st, Et, Ev, H, d, s_gt64, count, S, (long)lds, pairs,
+    hipLaunchKernelGGL(rank_resolve_kernel, dim3((unsigned)(RESOLVE_WAVES * g_num_cus)), dim3(256), 0, st, Et, Ev, H, d, s_gt64, count, S, (long)lds, pairs,
                        pair_cap, mt);
     return hipGetLastError();
 }

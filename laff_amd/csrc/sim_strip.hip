@@ -34,10 +34,6 @@
 
 #include "kernels.h"
 
-#ifndef LAFF_STRIP_ABL
-#define LAFF_STRIP_ABL 0       // ablation builds (timing only, wrong results): 1 = no fragment reads, 2 = no refill DMA / block barrier
-#endif
-
 namespace laff {
 
 namespace {
@@ -242,14 +238,12 @@ struct EpiPlan {
     bool fits;
 };
 
-// Places the stream (EPI) and counts, for a body that follows an identical body, how many LDS / VMEM operations are issued between
+// Places the stream and counts, for a body that follows an identical body, how many LDS / VMEM operations are issued between
 // an operation and the wait that needs it (LDS operations of a wavefront complete in order; so do its vector-memory operations).
-template <bool HAVE_S, bool BANDED, bool EPI>
+template <bool HAVE_S, bool BANDED>
 constexpr EpiPlan make_epi_plan() {
     EpiPlan p{};
-    EpiStream st{};
-    st.n = 0;
-    if (EPI) st = make_epi_stream<HAVE_S, BANDED>();
+    const EpiStream st = make_epi_stream<HAVE_S, BANDED>();
     // uniform density over the usable slots (a lone wavefront hides only a handful of instructions behind each MFMA: a stream
     // packed into the first half of the block left 8 instructions per slot there and nothing behind)
     int usable = 0;
@@ -324,10 +318,7 @@ constexpr EpiPlan make_epi_plan() {
 }  // namespace
 
 // MODE: GEMM_F16 / GEMM_BF16.  BANDED: exact-rank count + dumps.  HAVE_S: the fp32 score matrix is written (SCALE1: scale == 1).
-// Debug builds (timing only unless noted; tools/debug/build_strip_variant.sh): -DLAFF_STRIP_SERIAL = the K loops alone, no epilogue;
-// -DLAFF_STRIP_ABL = 1 no fragment reads / 2 no refill DMA and barrier / 3 neither; -DLAFF_STRIP_NOCHK = no band test, -DLAFF_STRIP_NODUMPBODY
-// = band test without the dump, -DLAFF_STRIP_NOSTG = no score stores; -DLAFF_STRIP_TRACE = cycle stamps (correct results);
-// -DLAFF_STRIP_STFLAVOR="..." = cache policy bits of the score stores (correct results).
+// -DLAFF_STRIP_TRACE builds cycle stamps (correct results; tools/debug/build_trace.sh).
 template <int MODE, bool BANDED, bool HAVE_S, bool SCALE1>
 __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -425,12 +416,7 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
     const unsigned slab_r = slab0 + (unsigned)(lane >> 3) * 128u + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
     const unsigned wrow = (unsigned)(PIECES * wave) * KBYTES;              // this wave's 8 columns of a block (LDS and source offset)
 
-#ifndef LAFF_STRIP_SERIAL
-    constexpr bool EPI = true;
-#else
-    constexpr bool EPI = false;
-#endif
-    constexpr EpiPlan PLAN = make_epi_plan<HAVE_S, BANDED, EPI>();
+    constexpr EpiPlan PLAN = make_epi_plan<HAVE_S, BANDED>();
     constexpr EpiStream STREAM = make_epi_stream<HAVE_S, BANDED>();
     static_assert(PLAN.fits, "the epilogue stream does not fit behind the MFMAs of one column block");
 
@@ -586,11 +572,7 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
             }
             const unsigned slot = cur_n + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
             cur_n += n;
-#ifdef LAFF_STRIP_NODUMPBODY
-            if (false) {
-#else
             if (hit) {
-#endif
                 const unsigned at = dump_base + slot * (STRIP_ENTRY_WORDS * 4u);
                 const f32x4 q0 = {x[0], x[1], x[2], x[3]}, q1 = {x[4], x[5], x[6], x[7]}, q2 = {x[8], x[9], x[10], x[11]},
                             q3 = {x[12], x[13], x[14], x[15]};
@@ -741,11 +723,7 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
                 const float w0 = (thr_hi[0] - thr_lo[0]) * 1.000002f + 1e-30f, w1 = (thr_hi[1] - thr_lo[1]) * 1.000002f + 1e-30f;
                 // (mmj: unsigned minimum of the bits of the job's 16 t values)
                 const bool hit0 = w0 >= 0.0f && mmj[0] <= __float_as_uint(w0), hit1 = w1 >= 0.0f && mmj[1] <= __float_as_uint(w1);
-#ifdef LAFF_STRIP_NOCHK
-                if (false) {
-#else
                 if (__builtin_amdgcn_ballot_w64(hit0 || hit1) != 0ull) {             // half of the blocks at C4 (fp16 operands)
-#endif
                     dump_group(hit0, row_w + l31, cbp * CB + 4 * hh, thr_lo[0], thr_hi[0], 0xffffu, gtc[0], acc[Q][0]);
                     dump_group(hit1, row_w + 32 + l31, cbp * CB + 4 * hh, thr_lo[1], thr_hi[1], 0xffffu, gtc[1], acc[Q][1]);
                 }
@@ -759,18 +737,14 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
             } else if constexpr (op.kind == OP_WAITR) {
                 wait_lgkm<PLAN.wait_r[rb][arg]>();
             } else if constexpr (op.kind == OP_STG) {
-#ifndef LAFF_STRIP_NOSTG
                 // (locals: a variable named only in an asm operand of a generic lambda is not captured.)  s_nop behind the store: a
                 // 16-byte store reads its data registers for a few cycles after issue, hipcc (which does not know this is a store) may
                 // hand them to the very next instruction -- seen: an address add landing in lanes 12..15 of the stored data
                 const unsigned vo = voffs[4 * rb + arg];
                 const u32x4 rs = rsrcSb;
                 const u32x4& data = rr[arg];
-#ifndef LAFF_STRIP_STFLAVOR
-#define LAFF_STRIP_STFLAVOR "sc0 sc1 nt"      // (write-through + streaming: 2 % over "nt", 20 % over plain at C4)
-#endif
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen " LAFF_STRIP_STFLAVOR :: "v"(data), "v"(vo), "s"(rs) : "memory");
-#endif
+                // sc0 sc1 nt: write-through + streaming (2 % over "nt", 20 % over plain at C4)
+                asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc0 sc1 nt" :: "v"(data), "v"(vo), "s"(rs) : "memory");
             }
         };
 
@@ -794,7 +768,7 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
             }
             const u32x4 rsrcL = rsrcNext;                                           // late pieces: block b + 3
             const int cbp = cb0 + b - 1;
-            if constexpr (EPI && HAVE_S) {
+            if constexpr (HAVE_S) {
                 // block b - 1's columns of the strip's score rows; b == 0: there is no previous block, an empty buffer drops the stores
                 rsrcSb.x = __builtin_amdgcn_readfirstlane((unsigned)sb_base);
                 rsrcSb.y = __builtin_amdgcn_readfirstlane((unsigned)(sb_base >> 32));
@@ -807,14 +781,10 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
             static_for<0, 32>([&](auto JC) {
                 constexpr int J = decltype(JC)::value;
                 if constexpr (J == BAR_J) {
-#if !(LAFF_STRIP_ABL & 2)
                     wait_lgkm<PLAN.lgkm_bar>();
                     wait_vm<PLAN.vm_bar>();
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
-#else
-                    wait_lgkm<0>();
-#endif
 #pragma unroll
                     for (int bb = 0; bb < 8; ++bb) X[bb] += dX;
                     if constexpr (BANDED) {
@@ -828,9 +798,7 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
                         }
                     }
                 } else if constexpr ((J & 1) == 0) {
-#if !(LAFF_STRIP_ABL & 1)
                     wait_lgkm<PLAN.wait_frag[J]>();       // (for sub-steps J and J + 1; the barrier's wait covers BAR_J and BAR_J + 1)
-#endif
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 static_for<0, 2>([&](auto MC) {
@@ -839,21 +807,15 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                     // pinned fillers
                     constexpr int rs = slot_read_sub(SG), dp = slot_dma_piece(SG);
-#if !(LAFF_STRIP_ABL & 1)
                     if constexpr (rs >= 0) lds_read128<((rs & 31) >> 3) * 256>(fr[rs & 7], X[rs & 7]);
-#endif
                     if constexpr (BANDED && SG == BAND_READ_SLOT) asm volatile("ds_read_b32 %0, %1" : "=v"(bcv) : "v"(band_addr));
-#if !(LAFF_STRIP_ABL & 2)
                     if constexpr (dp >= 2) dma_piece<dp>(lane16x, rsrcE, st_p2 + wrow);
                     else if constexpr (dp >= 0) dma_piece<dp>(lane16x, rsrcL, st_cur + wrow);
-#endif
                     // the epilogue stream's share of this slot
-                    if constexpr (EPI) {
-                        static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            epi_item(std::integral_constant<int, Q>{}, IC, cbp);
-                        });
-                    }
+                    static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        epi_item(std::integral_constant<int, Q>{}, IC, cbp);
+                    });
                     __builtin_amdgcn_sched_barrier(0);
                 });
             });
@@ -872,12 +834,12 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
             for (;;) {
                 body(I0{}, b);
                 if (b < 12) STAMP(tb + 3 + b);
-                if (++b >= n) { mfma_drain_nops(); if (EPI) drain_to_lds(I0{}); break; }
+                if (++b >= n) { mfma_drain_nops(); drain_to_lds(I0{}); break; }
                 body(I1{}, b);
                 if (b < 12) STAMP(tb + 3 + b);
-                if (++b >= n) { mfma_drain_nops(); if (EPI) drain_to_lds(I1{}); break; }
+                if (++b >= n) { mfma_drain_nops(); drain_to_lds(I1{}); break; }
             }
-            if (EPI) drain_rows(cb0 + n - 1);          // the last block's epilogue is the generic one
+            drain_rows(cb0 + n - 1);          // the last block's epilogue is the generic one
         }
         // segment end: nothing of this wave may still be in flight towards LDS or the fragment registers
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -911,7 +873,6 @@ __global__ __launch_bounds__(256, 1) void sim_strip_kernel(const StripArgs a) {
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 int g_strip_mode = 1;        // LAFF_STRIP (read when a ctx is created): 0 = never, 1 = where it is the faster kernel (default), 2 = also bf16 operands and
                              // smaller problems, 3 = wherever it can run (score rows of any pitch)
-int g_strip_map = 1;         // LAFF_STRIP_MAP: 0 = ranges to workgroups in order, 1 = grouped by column phase per XCD
 
 bool sim_strip_eligible(const GemmArgs& a, int mode, bool aligned) {
     if (g_strip_mode == 0) return false;
@@ -945,7 +906,6 @@ hipError_t launch_sim_strip(const GemmArgs& a, int mode, hipStream_t st) {
     s.T = a.R; s.V = a.C; s.nR = a.nR; s.nC = a.nC; s.out = a.out; s.ldo = a.ldo; s.scale = a.scale; s.inv_scale = 1.0f / a.scale;
     s.gt_col = a.gt_col; s.col0 = a.col0; s.s_gt64 = a.s_gt64; s.band_r = a.band_r; s.band_c = a.band_c; s.count = a.count;
     s.pairs = a.pairs; s.pair_cap = a.pair_cap;
-    s.debug = g_strip_mode;
 #ifdef LAFF_STRIP_TRACE
     if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) s.trace = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
@@ -958,7 +918,7 @@ hipError_t launch_sim_strip(const GemmArgs& a, int mode, hipStream_t st) {
     // video operand within a window of NB / 8 column blocks and their L2 fetches every video row once per sweep.
     std::vector<int> order(G);
     for (int j = 0; j < G; ++j) order[j] = j;
-    if (g_strip_map == 1 && G % 8 == 0) {
+    if (G % 8 == 0) {
         std::vector<long> phase(G);
         for (int j = 0; j < G; ++j) phase[j] = (U * j / G) % NB;
         std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return phase[x] < phase[y]; });

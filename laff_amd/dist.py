@@ -147,10 +147,7 @@ class HipBackend:
 
     def fused_prepare(self, Nt, Nv, heads, gt, col0=0):
         """An ops.FusedPrepare when both towers end in a fuse launch that can carry laff_rank_prepare's work (one head of d <= 512,
-        fp16 / bf16 operand emitted by the launch; LAFF_FUSED_PREPARE=0 turns it off), else None (separate rank_prepare launch)."""
-        import os
-        if os.environ.get('LAFF_FUSED_PREPARE', '1') == '0':
-            return None
+        fp16 / bf16 operand emitted by the launch), else None (separate rank_prepare launch)."""
         vl, tl = self.vis_layer(), self.txt_layer()
         if not (self._fused_pack(vl) and self._fused_pack(tl)):
             return None

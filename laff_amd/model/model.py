@@ -32,10 +32,6 @@ float16 = False
 #: arithmetic of the FC projections: 'fp32' (v_mfma_f32_32x32x2_f32, bit-for-bit an fp32 FMA chain) or 'fp16x3'
 #: (exact fp16 hi/lo operand split, 3 MFMA passes at the fp16 rate, ~2^-22 relative per product)
 FC_PRECISION = 'fp32'
-#: tower path: sparse (bag-of-words) features are gathered inside the fuse launch (LAFF_GATHER_IN_FUSE=0: separate FC launch)
-GATHER_IN_FUSE = os.environ.get('LAFF_GATHER_IN_FUSE', '1') != '0'
-#: fp16x3 only: split the inputs inside the GEMM instead of materialising their hi/lo planes (LAFF_FUSED_SPLIT=0 disables)
-FUSED_SPLIT = os.environ.get('LAFF_FUSED_SPLIT', '1') != '0'
 #: fp16x3 only: projections of 512-d inputs take the strip form (X stationary in registers: no row-scale pass, no split planes;
 #: laff_fc_act_bn_strip_grouped).  LAFF_FC_STRIP=0 keeps the tiled kernels.
 FC_STRIP = os.environ.get('LAFF_FC_STRIP', '1') != '0'
@@ -127,16 +123,10 @@ def _run_fc_x3_tiled(pending):
     # tile of a row block repeats the conversion, 2x at D = 512 but 16x at D = 4096, where materialising the planes once is
     # cheaper: C5 33.2 ms fused vs 32.9 ms); small launches take the materialised split, whose 128x128 tiles fill the chip
     tiles = sum(((q['x'].shape[0] + 255) // 256) * ((q['weight_split'].N + 255) // 256) for q in pending)
-    if (FUSED_SPLIT and tiles >= 512 and all(q['weight_split'].N <= 1024 for q in pending) and
+    if (tiles >= 512 and all(q['weight_split'].N <= 1024 for q in pending) and
             all(ops.fused_split_eligible(q['x'], q['weight_split']) for q in pending)):
         return ops.fc_act_bn_fused_grouped(pending)
     return ops.fc_act_bn_split_grouped(pending)
-
-
-#: tower path: leave activation + BatchNorm of the FC projections to the fuse launch (see TransformNet.plane).  Off by default:
-#: measured on C4 the GEMM launch gets 0.045 ms shorter and the fuse launches 0.047 ms longer -- the two v_exp/v_rcp per element
-#: run at quarter rate wherever they sit (1.372 ms vs 1.362 ms per step over three A/B pairs on one box).
-DEFER_ACTIVATION = os.environ.get('LAFF_DEFER_ACT', '0') == '1'
 
 
 def _initialize_weights(m):
@@ -264,7 +254,7 @@ class TransformNet(nn.Module):
         if self.fc1 is not None and x.layout == torch.sparse_csr:
             # sparse feature (bag-of-words): gather-sum of columns of W instead of a dense N x |vocab| x D GEMM
             bias = self.fc1.bias.detach() if self.fc1.bias is not None else None
-            if pending is not None and GATHER_IN_FUSE and head_dim is not None and head_dim <= 512:
+            if pending is not None and head_dim is not None and head_dim <= 512:
                 # tower path: the gather runs INSIDE the fuse launch (the projected plane is never written / re-read)
                 return (None, False, scale, shift, self.activation_name, (x.to(device), self.weight_t(), bias))
             y = ops.fc_gather_act_bn(x.to(device), self.weight_t(), bias, scale, shift, self.activation_name)
@@ -274,21 +264,14 @@ class TransformNet(nn.Module):
             prob = dict(x=x, weight=self.fc1.weight.detach(), weight_split=self.weight_split(),
                         bias=self.fc1.bias.detach() if self.fc1.bias is not None else None,
                         bn_scale=scale, bn_shift=shift, activation=self.activation_name)
-            if (FC_PRECISION == 'fp16x3' and FC_STRIP and extra_shift is None and not DEFER_ACTIVATION and
+            if (FC_PRECISION == 'fp16x3' and FC_STRIP and extra_shift is None and
                     self.fc1.in_features == 512 and self.out_features % 32 == 0):
                 prob['strip'] = self.strip_weights        # packed lazily: only if the launch takes the strip form
-            if pending is None or not DEFER_ACTIVATION:
-                if pending is None:
-                    return (run_fc([prob])[0], False, None, None)
-                y = prob['out'] = torch.empty((x.shape[0], self.out_features), device=x.device, dtype=torch.float32)
-                pending.append(prob)
-                return (y, False, None, None)
-            # tower path: the grouped GEMM writes the pre-activation x W^T + b; activation + BatchNorm ride along in the fuse
-            # launch (memory-bound, the transcendentals are free there; in the GEMM epilogue they were 17 % of the launch)
-            prob.update(bn_scale=None, bn_shift=None, activation=None)
+            if pending is None:
+                return (run_fc([prob])[0], False, None, None)
             y = prob['out'] = torch.empty((x.shape[0], self.out_features), device=x.device, dtype=torch.float32)
             pending.append(prob)
-            return (y, False, scale, shift, self.activation_name)
+            return (y, False, None, None)
         if self.activation_name is not None:
             raise NotImplementedError('activation without fc is never built by the reference towers')
         tile = heads > 1 and x.shape[1] * heads == self.out_features

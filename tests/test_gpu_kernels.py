@@ -893,7 +893,7 @@ def test_overflow_is_flagged_through_the_fused_tail(strip):
 def test_fence_free_tail_equals_the_fenced_build(mode, tmp_path):
     """The metrics tails hand partial results between workgroups without release / acquire fences (gfx9 hardware behaviour, see
     LAFF_TAIL_FENCES in rank.hip).  The memory model's own form stays one compile switch away: this test builds rank.hip with
-    -DLAFF_TAIL_FENCES, and holds 150 graph replays of {prepare, banded GEMM, tail} on a large grid (1,536 resolve workgroups; 40 metrics
+    -DLAFF_TAIL_FENCES, and holds 150 graph replays of {prepare, banded GEMM, tail} on a large grid (5 x CUs = 1,280 resolve workgroups; 40 metrics
     workgroups for 'split') of the shipped library against the fenced build: ONE metrics tuple in each, equal to each other."""
     import json
     import os

@@ -1,10 +1,21 @@
 #!/bin/bash
-# debug build of the library with s_memtime probes in the GEMM (scratch/tracelib/liblaff_hip.so)
+# Library with cycle stamps: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE [-DLAFF_STRIP_TRACE] [-DLAFF_FCS_TRACE]
+#   LAFF_GEMM_TRACE   gemm_nt: per-tile stamps, wait breakdown of the K loop, epilogue stamps
+#   LAFF_STRIP_TRACE  sim_strip: per-segment and per-block stamps of wave 0
+#   LAFF_FCS_TRACE    fc_strip: per-segment phase stamps
+# Every source is rebuilt with the given macros into scratch/trace/liblaff_hip.so: load it with LAFF_HIP_LIB (the trace_*.py scripts
+# hand their stamp buffer over through LAFF_GEMM_TRACE_PTR).  The stamps give correct results, only slower.
 set -e
+[ $# -gt 0 ] || { echo "usage: $0 -DLAFF_GEMM_TRACE|-DLAFF_STRIP_TRACE|-DLAFF_FCS_TRACE ..." >&2; exit 2; }
 cd "$(dirname "$0")/../.."
-mkdir -p scratch/tracelib
-for f in api fuse gemm_nt sim_strip rank loss; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -fno-gpu-rdc -DLAFF_GEMM_TRACE -DLAFF_STRIP_TRACE -Iinclude -c laff_amd/csrc/$f.hip -o scratch/tracelib/$f.o &
+out=scratch/trace
+mkdir -p $out
+rm -f $out/*.o
+pids=()
+for f in api comm fc_strip fuse gemm_nt loss rank sim_strip; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -fno-gpu-rdc "$@" -c laff_amd/csrc/$f.hip -o $out/$f.o &
+  pids+=($!)
 done
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scratch/tracelib/liblaff_hip.so scratch/tracelib/*.o
+for p in "${pids[@]}"; do wait $p; done
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $out/liblaff_hip.so $out/*.o
+echo $out/liblaff_hip.so

@@ -25,5 +25,5 @@ def timeit(fn, n=10):
     return best
 fl = 2.0 * Nt * Nv * K / 1e9
 a = timeit(lambda: ops.sim_gemm(T, V, out=S)); b = timeit(lambda: ops.sim_gemm_banded(st, want_scores=True, out=S)); c = timeit(lambda: ops.sim_gemm_banded(st, want_scores=False))
-print('%d x %d x %d %s  variant %s: plain+S %.4f ms %.0f TF | banded+S %.4f ms %.0f TF | banded count-only %.4f ms %.0f TF' % (
-    Nt, Nv, K, prec, os.environ.get('LAFF_GEMM_VARIANT', 'auto'), a, fl / a, b, fl / b, c, fl / c))
+print('%d x %d x %d %s: plain+S %.4f ms %.0f TF | banded+S %.4f ms %.0f TF | banded count-only %.4f ms %.0f TF' % (
+    Nt, Nv, K, prec, a, fl / a, b, fl / b, c, fl / c))

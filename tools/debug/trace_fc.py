@@ -1,4 +1,4 @@
-"""Per-tile timeline of the fused-split FC launch at C4 (debug library with LAFF_GEMM_TRACE: tools/debug/build_trace.sh)."""
+"""Per-tile timeline of the fused-split FC launch at C4 (debug library: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

@@ -1,5 +1,5 @@
-"""Per-workgroup cycle stamps of the strip FC (debug build: tools/debug/build_fcs_variant.sh trace -DLAFF_FCS_TRACE, loaded through
-LAFF_HIP_LIB=scratch/fcs_trace/liblaff_hip.so).   python tools/debug/trace_fc_strip.py"""
+"""Per-workgroup cycle stamps of the strip FC (debug build: tools/debug/build_trace.sh -DLAFF_FCS_TRACE, loaded through
+LAFF_HIP_LIB=scratch/trace/liblaff_hip.so).   python tools/debug/trace_fc_strip.py"""
 import os
 import sys
 

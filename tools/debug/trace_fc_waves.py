@@ -1,4 +1,4 @@
-"""Per-wave barrier waits in the K loop of the fused-split FC (debug library with LAFF_GEMM_TRACE)."""
+"""Per-wave barrier waits in the K loop of the fused-split FC (debug library: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

@@ -1,3 +1,5 @@
+"""Per-tile stamps of laff_sim_gemm at C4 (debug library: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE).
+   python tools/debug/trace_gemm.py [fp16|bf16] [banded|count|banded-count]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, numpy as np
@@ -24,7 +26,7 @@ def run():
     else: ops.sim_gemm(T,V,want_scores=False,gt_col=gt,s_gt=sg,count=cnt)
 for _ in range(3): run()
 torch.cuda.synchronize()
-tile = 256 if os.environ.get('LAFF_GEMM_VARIANT','256')=='256' else 128
+tile = 256                                       # the tiles the dispatch takes at this shape
 nb=((Nt+tile-1)//tile)*((Nv+tile-1)//tile)
 tr=torch.zeros(nb*24,dtype=torch.int64,device=dev)
 os.environ['LAFF_GEMM_TRACE_PTR']=str(tr.data_ptr())

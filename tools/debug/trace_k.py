@@ -1,3 +1,5 @@
+"""Per-tile stamps of laff_sim_gemm at one shape (debug library: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE).
+   python tools/debug/trace_k.py Nt Nv K"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, numpy as np

@@ -1,4 +1,4 @@
-"""Per-K-step wait breakdown of wave 0 in laff_sim_gemm at long K (debug library with LAFF_GEMM_TRACE: tools/debug/build_trace.sh)."""
+"""Per-K-step wait breakdown of wave 0 in laff_sim_gemm at long K (debug library: tools/debug/build_trace.sh -DLAFF_GEMM_TRACE)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

@@ -1,5 +1,6 @@
-"""Per-workgroup cycle stamps of the strip GEMM (debug build: tools/debug/build_trace.sh -> scratch/tracelib, loaded through
-LAFF_LIB).   python tools/debug/trace_strip.py [fp16|bf16] [mode]     mode: 2 serial (default), 3 K loops only, 1 production"""
+"""Per-workgroup cycle stamps of the strip GEMM (debug build: tools/debug/build_trace.sh -DLAFF_STRIP_TRACE, loaded through
+LAFF_HIP_LIB=scratch/trace/liblaff_hip.so).   python tools/debug/trace_strip.py [fp16|bf16] [mode] [scores]
+mode: the LAFF_STRIP value (default 2: bf16 operands take the strip kernel too)"""
 import os
 import sys
 
