@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 22
+#define LAFF_ABI_VERSION 23
 
 enum {
     LAFF_OK = 0,
@@ -168,6 +168,28 @@ enum { LAFF_LOSS_MAX_VIOLATION = 1, LAFF_LOSS_COST_MEAN = 2, LAFF_LOSS_DIR_I2T =
 int laff_margin_loss_workspace_bytes(int B, int H, int d, size_t* out);
 int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int H, int d, float margin, unsigned flags,
                      float* loss, float* d_s, float* d_im, void* workspace, size_t workspace_bytes);
+
+/* ---- text tower: the GRU caption encoder (model/model.py:323-396 GruTxtEncoder / BiGruTxtEncoder), inference, one layer ----------
+ * torch.nn.GRU arithmetic (gate order r, z, n; h0 = 0) over captions given as token ids, then pooling over each caption's steps:
+ *   LAFF_GRU_MEAN      mean of h_t                       -> H columns (bidirectional: forward mean | reverse mean, 2H)
+ *   LAFF_GRU_LAST      h at the caption's last token      -> H columns (bidirectional: the forward half only, as the reference)
+ *   LAFF_GRU_MEAN_LAST mean | last                        -> 2H columns (unidirectional only; the reference crashes on bigru)
+ * The input half is a table lookup: P = we . W_ih^T + b_ih [V, 3H] (build it with laff_fc_act_bn, act none).
+ * laff_gru_pack_whh: W_hh [3H, H] contiguous -> the step kernel's layout, 3*H*H floats, 16-byte aligned.
+ * laff_gru_encode: the rows are the captions sorted by length, longest first (stable); tokens [T, N] int32 time-major in that order
+ * (entries past a row's length are not read), lengths [N] and perm [N] (sorted row -> output row) on the device; batch_sizes [T] is
+ * HOST memory: batch_sizes[t] = number of rows with length > t (what torch's PackedSequence holds), batch_sizes[0] = N.
+ * One launch per time step (both directions in the same launch); no allocation, no host synchronisation: capturable in a HIP graph.
+ * The P_rev / whh_rev / bhh_rev set is read only when bidirectional and pooling is LAFF_GRU_MEAN.  out [N, ldo]: row perm[i] is
+ * caption i of the sorted order.  workspace: laff_gru_workspace_bytes(N, H, ...) bytes, 16-byte aligned.
+ * Limits: num_layers == 1, H % 32 == 0, 32 <= H <= 2048.  A caption's features do not depend on the rest of its batch (bitwise). */
+enum { LAFF_GRU_MEAN = 0, LAFF_GRU_LAST = 1, LAFF_GRU_MEAN_LAST = 2 };
+int laff_gru_pack_whh(laff_ctx* ctx, const float* W_hh, int H, float* packed);
+int laff_gru_workspace_bytes(int N, int H, int num_layers, int bidirectional, int pooling, size_t* out);
+int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const int* perm, const int* batch_sizes /*host*/, int T, int N,
+                    int V, int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
+                    const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
+                    void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

@@ -8,8 +8,9 @@ LIB_PATH = os.environ.get('LAFF_HIP_LIB') or os.path.join(_HERE, 'lib', 'liblaff
 # enums of include/laff_hip.h
 ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
+GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class Plane(C.Structure):
@@ -108,6 +109,10 @@ SIGNATURES = {
     'laff_v2t_count_exact': (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, C.c_uint]),
     'laff_rank_metrics': (C.c_int, [_P, _P, _I, _I, _P, C.POINTER(C.c_double)]),
     'laff_rank_metrics_async': (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    'laff_gru_pack_whh': (C.c_int, [_P, _P, _I, _P]),
+    'laff_gru_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_gru_encode': (C.c_int, [_P, _P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
+                                  C.c_size_t]),
 }
 
 _lib = None

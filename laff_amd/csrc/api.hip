@@ -306,6 +306,108 @@ int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int 
     return LAFF_OK;
 }
 
+namespace {
+// the GRU encoder's limits and workspace: per direction two ping-pong h buffers (packed) and the pooled sums, N rounded up to the
+// 64-row tile of the step kernel (its operand reads cover whole tiles; the padding rows stay zero)
+int gru_check_size(const char* fn, int H, int num_layers) {
+    if (num_layers != 1) return fail(LAFF_E_UNSUPPORTED, "%s: num_layers=%d: only one-layer GRUs are supported (rnn_layer = 1)", fn, num_layers);
+    if (H < 32 || H > 2048 || H % 32) return fail(LAFF_E_SHAPE, "%s: H=%d: the hidden size must be a multiple of 32 in [32, 2048]", fn, H);
+    return LAFF_OK;
+}
+int gru_check_mode(const char* fn, int bidirectional, int pooling) {
+    if (pooling < LAFF_GRU_MEAN || pooling > LAFF_GRU_MEAN_LAST) return fail(LAFF_E_ARG, "%s: bad pooling %d", fn, pooling);
+    if (bidirectional && pooling == LAFF_GRU_MEAN_LAST)
+        return fail(LAFF_E_UNSUPPORTED, "%s: bigru_mean_last is not supported (the reference fails on it as well)", fn);
+    return LAFF_OK;
+}
+int gru_dirs(int bidirectional, int pooling) { return bidirectional && pooling == LAFF_GRU_MEAN ? 2 : 1; }
+size_t gru_npad(int N) { return ((size_t)N + 63) / 64 * 64; }
+}  // namespace
+
+int laff_gru_pack_whh(laff_ctx* ctx, const float* W_hh, int H, float* packed) {
+    if (int rc = gru_check_size("laff_gru_pack_whh", H, 1)) return rc;
+    if (!W_hh || !packed) return fail(LAFF_E_ARG, "laff_gru_pack_whh: null argument");
+    if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "laff_gru_pack_whh: packed must be 16-byte aligned");
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_gru_pack_whh(W_hh, H, packed, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_gru_workspace_bytes(int N, int H, int num_layers, int bidirectional, int pooling, size_t* out) {
+    if (!out || N < 0) return fail(LAFF_E_ARG, "laff_gru_workspace_bytes: bad args");
+    if (int rc = gru_check_size("laff_gru_workspace_bytes", H, num_layers)) return rc;
+    if (int rc = gru_check_mode("laff_gru_workspace_bytes", bidirectional, pooling)) return rc;
+    *out = (size_t)gru_dirs(bidirectional, pooling) * 3 * gru_npad(N) * H * sizeof(float);
+    return LAFF_OK;
+}
+
+int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const int* perm, const int* batch_sizes, int T, int N, int V,
+                    int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
+                    const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
+                    void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_gru_encode";
+    // every argument is checked before any GPU work
+    if (int rc = gru_check_size(fn, H, num_layers)) return rc;
+    if (int rc = gru_check_mode(fn, bidirectional, pooling)) return rc;
+    if (N < 0 || T < 0 || V < 1) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d T=%d V=%d", fn, N, T, V);
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
+    const int ndirs = gru_dirs(bidirectional, pooling);
+    if (!tokens || !lengths || !perm || !batch_sizes || !P_fwd || !whh_fwd || !bhh_fwd || !out || !workspace ||
+        (ndirs == 2 && (!P_rev || !whh_rev || !bhh_rev)))
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    if (T < 1) return fail(LAFF_E_SHAPE, "%s: T=%d: every caption has at least one token", fn, T);
+    const int width = pooling == LAFF_GRU_LAST ? H : (pooling == LAFF_GRU_MEAN_LAST ? 2 * H : ndirs * H);
+    if (ldo < width) return fail(LAFF_E_SHAPE, "%s: ldo=%d < output width %d", fn, ldo, width);
+    if (batch_sizes[0] != N) return fail(LAFF_E_ARG, "%s: batch_sizes[0]=%d != N=%d", fn, batch_sizes[0], N);
+    for (int t = 0; t < T; ++t)
+        if (batch_sizes[t] < 1 || (t && batch_sizes[t] > batch_sizes[t - 1]))
+            return fail(LAFF_E_ARG, "%s: batch_sizes must be positive and non-increasing (batch_sizes[%d]=%d)", fn, t, batch_sizes[t]);
+    const size_t npad = gru_npad(N), plane = npad * H;
+    const size_t need = (size_t)ndirs * 3 * plane * sizeof(float);
+    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
+    if (!aligned16(workspace) || !aligned16(whh_fwd) || (ndirs == 2 && !aligned16(whh_rev)))
+        return fail(LAFF_E_ALIGN, "%s: workspace / packed W_hh must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    // h_0 = 0 and the sums start at 0; a reverse-direction row reads its buffer untouched (zero) at its first step
+    HIP_TRY(hipMemsetAsync(workspace, 0, need, ctx->stream));
+    float* ws = (float*)workspace;
+    laff::GruStepArgs a{};
+    a.tokens = tokens;
+    a.lens = lengths;
+    a.perm = perm;
+    a.N = N;
+    a.H = H;
+    a.V = V;
+    a.pooling = pooling;
+    a.out = out;
+    a.ldo = ldo;
+    laff::GruDirArgs* dir[2] = {&a.d0, &a.d1};
+    const float* P[2] = {P_fwd, P_rev};
+    const float* W[2] = {whh_fwd, whh_rev};
+    const float* bh[2] = {bhh_fwd, bhh_rev};
+    for (int d = 0; d < ndirs; ++d) {
+        dir[d]->P = P[d];
+        dir[d]->Wp = W[d];
+        dir[d]->bhh = bh[d];
+        dir[d]->sum = ws + (3 * d + 2) * plane;
+        dir[d]->col0 = d * H;
+    }
+    for (int i = 0; i < T; ++i) {
+        for (int d = 0; d < ndirs; ++d) {
+            const int t = d ? T - 1 - i : i;      // the reverse direction walks the same sorted prefix backwards
+            dir[d]->t = t;
+            dir[d]->B = batch_sizes[t];
+            dir[d]->h_in = ws + (3 * d + (i & 1)) * plane;
+            dir[d]->h_out = ws + (3 * d + ((i + 1) & 1)) * plane;
+        }
+        a.skip_gemm = i == 0;                     // h = 0 for every row of the first step of either direction
+        HIP_TRY(laff::launch_gru_step(a, ndirs, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

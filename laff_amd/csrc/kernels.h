@@ -243,4 +243,28 @@ hipError_t launch_v2t_count_exact(const float* S, int Nt, int Nv, int lds, const
                                   const float* Et, const float* Ev, int H, int d, const double* s_gt64, const float* band_t,
                                   const float* band_v, int* count, unsigned* list, unsigned cap, hipStream_t st);
 
+// gru.hip: one direction of a GRU time step (laff_gru_encode)
+struct GruDirArgs {
+    const float* P;       // [V, 3H]: we . W_ih^T + b_ih
+    const float* Wp;      // laff_gru_pack_whh(W_hh)
+    const float* bhh;     // [3H]
+    const float* h_in;    // packed h_{t-1} (zero for a row that has not started)
+    float* h_out;         // packed h_t
+    float* sum;           // [Npad, H] running sum of h over the steps taken so far
+    int B;                // active rows (a prefix of the length-sorted rows)
+    int t;                // token column of this step
+    int col0;             // output column of this direction's mean
+};
+struct GruStepArgs {
+    GruDirArgs d0, d1;    // d0 forward, d1 reverse (grid.z)
+    const int* tokens;    // [T, N] time-major, sorted row order
+    const int* lens;      // [N] sorted row order
+    const int* perm;      // [N] sorted row -> output row
+    int N, H, V, skip_gemm, pooling;
+    float* out;
+    int ldo;
+};
+hipError_t launch_gru_pack_whh(const float* W, int H, float* Wp, hipStream_t st);
+hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st);
+
 }  // namespace laff

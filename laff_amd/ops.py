@@ -9,10 +9,10 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (ACT, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
+from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
 
-__all__ = ['rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -214,6 +214,69 @@ def margin_loss(s, im, margin, max_violation=True, cost_style='sum', direction='
     _call('margin_loss', lib.laff_margin_loss, h, _ptr(s_c), _ptr(im_c), B, H, d, float(margin), flags, _ptr(loss), _ptr(d_s),
           _ptr(d_im), _ptr(ws), nbytes.value)
     return loss, d_s, d_im
+
+
+def gru_pack_whh(w_hh):
+    """laff_gru_pack_whh: W_hh [3H, H] -> the step kernel's operand layout (a flat fp32 tensor of 3*H*H)."""
+    w = _dev(w_hh, 'w_hh')
+    if w.dim() != 2 or w.shape[0] != 3 * w.shape[1]:
+        raise ValueError('w_hh must be (3H, H), got %s' % (tuple(w.shape),))
+    w = w.contiguous()
+    out = torch.empty(w.numel(), device=w.device, dtype=torch.float32)
+    lib, h = _context(w.device)
+    _call('gru_pack_whh', lib.laff_gru_pack_whh, h, _ptr(w), int(w.shape[1]), _ptr(out))
+    return out
+
+
+def gru_workspace_bytes(N, H, num_layers=1, bidirectional=False, pooling='mean'):
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_gru_workspace_bytes(int(N), int(H), int(num_layers), int(bool(bidirectional)), GRU_POOLING[pooling], C.byref(n)))
+    return n.value
+
+
+def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean', num_layers=1, out=None, workspace=None):
+    """laff_gru_encode.  tokens [T, N] int32 (time-major, length-sorted rows), lengths / perm [N] int32 on the device,
+    batch_sizes: host sequence of T ints; fwd / rev: (P [V, 3H], packed W_hh, b_hh [3H]) of each direction (rev: bidirectional).
+    Returns out [N, width] in the input order given by perm.  workspace: a uint8 device tensor of gru_workspace_bytes(...) bytes,
+    or None to allocate one here (pass one for HIP-graph capture)."""
+    tok = _dev(tokens, 'tokens', torch.int32)
+    lens = _dev(lengths, 'lengths', torch.int32)
+    prm = _dev(perm, 'perm', torch.int32)
+    T, N = tok.shape
+    P, Wp, bhh = fwd
+    V, H3 = P.shape
+    H = H3 // 3
+    for t_, nm in ((P, 'P'), (Wp, 'whh'), (bhh, 'bhh')) + (((rev[0], 'P_rev'), (rev[1], 'whh_rev'), (rev[2], 'bhh_rev')) if rev else ()):
+        _dev(t_, nm)
+        if not t_.is_contiguous():
+            raise ValueError('%s must be contiguous' % nm)
+    if not tok.is_contiguous() or lens.numel() != N or prm.numel() != N:
+        raise ValueError('tokens must be a contiguous [T, N] matrix and lengths / perm vectors of N')
+    for P_, W_, b_ in (fwd, rev) if rev else (fwd,):
+        if P_.dim() != 2 or P_.shape[1] != 3 * H or W_.numel() != 3 * H * H or b_.numel() != 3 * H:
+            raise ValueError('each direction needs P [V, 3H], a packed W_hh of 3H*H and b_hh of 3H (H=%d)' % H)
+        if P_.shape[0] != V:
+            raise ValueError('both directions must use the same vocabulary')
+    bs = (C.c_int * max(1, T))(*[int(b) for b in batch_sizes])
+    if len(batch_sizes) != T:
+        raise ValueError('batch_sizes has %d entries for T=%d' % (len(batch_sizes), T))
+    bidir = rev is not None
+    width = H if pooling == 'last' else 2 * H if (pooling == 'mean_last' or bidir) else H
+    nbytes = gru_workspace_bytes(N, H, num_layers, bidir, pooling)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=tok.device)
+    if out is None:
+        out = torch.empty((N, width), device=tok.device, dtype=torch.float32)
+    if tuple(out.shape) != (N, width):
+        raise ValueError('out must be (%d, %d), got %s' % (N, width, tuple(out.shape)))
+    o, ldo = _rows(out, 'out')
+    Pr, Wr, br = rev if bidir else (None, None, None)
+    lib, h = _context(tok.device)
+    _call('gru_encode', lib.laff_gru_encode, h, _ptr(tok), _ptr(lens), _ptr(prm), bs, T, N, V, H, int(num_layers), int(bidir),
+          GRU_POOLING[pooling], _ptr(P), _ptr(Wp), _ptr(bhh), _ptr(Pr), _ptr(Wr), _ptr(br), _ptr(o), ldo, _ptr(workspace),
+          workspace.numel())
+    return out
 
 
 class SplitOperand:

@@ -9,7 +9,11 @@ gather-sum on the GPU (`laff_fc_gather_act_bn`): bow -> a CSR count matrix that 
 
 Stop words are DATA of the deployment (the reference ships `stopwords_en.txt`); pass them in (`stopwords=`), e.g.
 `set(open('stopwords_en.txt').read().split())`.
+
+The GRU encoder (`GruTxtEncoder`) keeps the same split: the host maps captions to token ids and lays the batch out the way the
+step kernel walks it (`IdxVec.batch`); the recurrence runs on the GPU (`laff_gru_encode`).
 """
+import collections
 import pickle
 import re
 
@@ -48,6 +52,14 @@ class Vocabulary(object):
 
     def __getitem__(self, index):
         return self.idx2word[index]
+
+    def __call__(self, word):
+        """textlib.Vocabulary.__call__ (textlib.py:102-109): a 'gru' vocabulary maps an unknown word to <unk>, others raise."""
+        if word not in self.word2idx:
+            if 'gru' in self.encoding:
+                return self.word2idx['<unk>']
+            raise KeyError('word out of vocab: %s' % word)
+        return self.word2idx[word]
 
     def __len__(self):
         return len(self.word2idx)
@@ -189,3 +201,107 @@ class W2VTxtEncoder(nn.Module):
 
     def forward(self, caption_feat_dict, task3=False):
         return {'text_features': self.t2v_w2v.encode(caption_feat_dict['caption'], self.device)}
+
+
+GruBatch = collections.namedtuple('GruBatch', ['tokens', 'lengths', 'perm', 'batch_sizes'])
+GruBatch.__doc__ = """A batch of captions as the GRU step kernel takes it: rows sorted by length, longest first (stable).
+tokens [T_max, N] int32 time-major in sorted order (0 = <pad> past a row's end), lengths [N] int32 sorted, perm [N] int32
+(sorted row -> input position), batch_sizes: list of T_max ints, rows still active at step t (PackedSequence.batch_sizes)."""
+
+
+class IdxVec(object):
+    """txt2vec.IndexVec (txt2vec.py:117-131): '<start>' + tokenize(caption) + '<end>' mapped through a 'gru' vocabulary."""
+
+    def __init__(self, vocab, clean=True):
+        self.vocab = load_vocab(vocab) if isinstance(vocab, str) else vocab
+        self.ndims = len(self.vocab)
+        self.clean = clean
+
+    def __len__(self):
+        return self.ndims
+
+    def encoding(self, caption):
+        words = ['<start>'] + tokenize(caption, self.clean, False) + ['<end>']
+        return np.array([self.vocab(w) for w in words])
+
+    def batch(self, captions):
+        ids = [self.encoding(c) for c in captions]
+        lens = np.array([len(v) for v in ids], dtype=np.int64)
+        perm = np.argsort(-lens, kind='stable').astype(np.int32)
+        T = int(lens.max()) if len(ids) else 0
+        tokens = np.zeros((T, len(ids)), dtype=np.int32)
+        for j, i in enumerate(perm):
+            tokens[:lens[i], j] = ids[i]
+        slens = lens[perm].astype(np.int32)
+        batch_sizes = [int((slens > t).sum()) for t in range(T)]
+        return GruBatch(tokens, slens, perm, batch_sizes)
+
+
+class _GruWeights(nn.Module):
+    """The parameters of one torch.nn.GRU layer under nn.GRU's own names, held as plain parameters: no nn.GRU object (its .to()
+    may call into MIOpen) and no torch RNN call anywhere on the path."""
+
+    def __init__(self, input_size, hidden_size, bidirectional):
+        super().__init__()
+        k = 1.0 / hidden_size ** 0.5
+        for sfx in ('_l0', '_l0_reverse') if bidirectional else ('_l0',):
+            for name, shape in (('weight_ih', (3 * hidden_size, input_size)), ('weight_hh', (3 * hidden_size, hidden_size)),
+                                ('bias_ih', (3 * hidden_size,)), ('bias_hh', (3 * hidden_size,))):
+                self.register_parameter(name + sfx, nn.Parameter(torch.empty(shape).uniform_(-k, k)))   # nn.GRU's init
+
+
+class GruTxtEncoder(nn.Module):
+    """Drop-in for model.model.GruTxtEncoder / BiGruTxtEncoder (model/model.py:323-396), inference:
+    `txt_net.encoder.rnn_encoder = GruTxtEncoder(IdxVec(vocab), we_dim, rnn_size, bidirectional, pooling)`.
+    State-dict keys are the reference's (we.weight, rnn.weight_ih_l0, ...), so its checkpoints load with strict=True.
+    Output: {'text_features': (N, H)} for gru mean / last and bigru last, (N, 2H) for gru mean_last and bigru mean, input order.
+    P = we . W_ih^T + b_ih and the packed W_hh are cached and rebuilt whenever a parameter changes (load_state_dict, copy_, ...)."""
+
+    def __init__(self, t2v_idx, we_dim, rnn_size, bidirectional=False, pooling='mean', rnn_layer=1, device='cuda'):
+        super().__init__()
+        if int(rnn_layer) != 1:
+            raise NotImplementedError('GruTxtEncoder: rnn_layer=%d; only rnn_layer = 1 is supported' % rnn_layer)
+        if pooling not in ('mean', 'last', 'mean_last'):
+            raise ValueError("GruTxtEncoder: pooling must be 'mean', 'last' or 'mean_last', got %r" % (pooling,))
+        if bidirectional and pooling == 'mean_last':
+            raise NotImplementedError('GruTxtEncoder: bigru_mean_last is not supported (the reference fails on it as well)')
+        H = int(rnn_size)
+        if H % 32 or not 32 <= H <= 2048:
+            raise NotImplementedError('GruTxtEncoder: rnn_size=%d; the kernel takes multiples of 32 up to 2048' % H)
+        self.t2v_idx, self.device = t2v_idx, device
+        self.rnn_size, self.bigru, self.pooling = H, bool(bidirectional), pooling
+        self.we = nn.Embedding(len(t2v_idx.vocab), int(we_dim))
+        self.rnn = _GruWeights(int(we_dim), H, self.bigru)
+        self.to(device)
+        self._cache_key, self._cache = None, None
+
+    def _tables(self):
+        """(P, packed W_hh, b_hh) per direction, rebuilt when any parameter has changed since the last build."""
+        from . import ops
+        params = [self.we.weight] + list(self.rnn.parameters())
+        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
+        if key != self._cache_key:
+            with torch.no_grad():
+                r, sets = self.rnn, []
+                for sfx in ('_l0', '_l0_reverse') if self.bigru else ('_l0',):
+                    w_ih, w_hh = getattr(r, 'weight_ih' + sfx), getattr(r, 'weight_hh' + sfx)
+                    P = ops.fc_act_bn(self.we.weight.detach(), w_ih.detach(), getattr(r, 'bias_ih' + sfx).detach())
+                    sets.append((P, ops.gru_pack_whh(w_hh.detach()), getattr(r, 'bias_hh' + sfx).detach().contiguous()))
+            self._cache, self._cache_key = sets, key
+        return self._cache
+
+    def encode_batch(self, b, out=None, workspace=None):
+        """The device half of forward(): a GruBatch (IdxVec.batch) whose arrays are already device tensors."""
+        from . import ops
+        sets = self._tables()
+        rev = sets[1] if self.bigru and self.pooling == 'mean' else None
+        return ops.gru_encode(b.tokens, b.lengths, b.perm, b.batch_sizes, sets[0], rev, self.pooling, out=out, workspace=workspace)
+
+    def to_device(self, b):
+        dev = self.we.weight.device
+        return GruBatch(torch.from_numpy(b.tokens).to(dev), torch.from_numpy(b.lengths).to(dev), torch.from_numpy(b.perm).to(dev),
+                        b.batch_sizes)
+
+    def forward(self, caption_feat_dict, task3=False):
+        b = self.t2v_idx.batch(caption_feat_dict['caption'])
+        return {'text_features': self.encode_batch(self.to_device(b))}
