@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 23
+#define LAFF_ABI_VERSION 24
 
 enum {
     LAFF_OK = 0,
@@ -190,6 +190,48 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
                     int V, int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
                     const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
                     void* workspace, size_t workspace_bytes);
+
+/* ---- text tower: the CLIP text encoder (clip.model.CLIP.encode_text, model/clip/model.py:153-206, 245-358), inference -----------
+ * token + positional embedding -> layers x ResidualAttentionBlock (pre-LN, causal MHA with head dim 64, QuickGELU MLP of 4 width)
+ * -> ln_final -> the row at argmax(ids) -> . text_projection.
+ * Captions come RAGGED: caption i is its ids up to and including p_i = argmax(ids_i) (first occurrence: the row the reference pools;
+ * <|endoftext|> unless the caption was cut at the context length).  A causal mask keeps the later positions from reaching row p_i,
+ * so they are left out.  ids [R] int32 concatenates the captions; row_off [N+1] int32 (row_off[0] = 0, row_off[N] = R, every caption
+ * 1 .. context_length rows) is passed TWICE: on the device for the kernels and in HOST memory for the checks (the same values).
+ * Weights: the four matrices of every block and text_projection are packed once with laff_clip_pack_weight into the encoder's
+ * precision (LAFF_PREC_FP32, or LAFF_PREC_FP16: fp16 operands, fp32 accumulation); in_proj / out_proj / c_fc / c_proj as stored
+ * (nn.Linear's [out, in]), text_projection [width, embed] with transpose = 1.  Every other pointer is fp32 on the device.
+ * out [N, ldo] fp32: caption i's feature in row i.  workspace: laff_clip_workspace_bytes(R, ...) bytes, 16-byte aligned.
+ * Limits: width % 64 == 0, 64 <= width <= 1024, heads * 64 == width, 1 <= context_length <= 77, layers >= 1 (LAFF_E_UNSUPPORTED).
+ * No allocation, no host synchronisation: capturable in a HIP graph (one stream, no branches).  A caption's feature does not depend on
+ * the rest of its batch (bitwise), so any split of a batch into calls gives the same features. */
+typedef struct laff_clip_block {
+    const float* ln_1_weight;
+    const float* ln_1_bias;
+    const void* in_proj_weight;   /* packed [3 width, width] */
+    const float* in_proj_bias;
+    const void* out_proj_weight;  /* packed [width, width] */
+    const float* out_proj_bias;
+    const float* ln_2_weight;
+    const float* ln_2_bias;
+    const void* c_fc_weight;      /* packed [4 width, width] */
+    const float* c_fc_bias;
+    const void* c_proj_weight;    /* packed [width, 4 width] */
+    const float* c_proj_bias;
+} laff_clip_block;
+typedef struct laff_clip_text {
+    int width, layers, heads, embed_dim, context_length, vocab_size;
+    const float* token_embedding;       /* [vocab_size, width] */
+    const float* positional_embedding;  /* [context_length, width] */
+    const laff_clip_block* blocks;      /* HOST array of `layers` blocks (of device pointers) */
+    const float* ln_final_weight;
+    const float* ln_final_bias;
+    const void* text_projection;        /* packed text_projection^T [embed_dim, width] */
+} laff_clip_text;
+int laff_clip_pack_weight(laff_ctx* ctx, const float* W, int rows, int cols, int transpose, int precision, void* packed);
+int laff_clip_workspace_bytes(int R, int N, int width, int precision, size_t* out);
+int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_clip_text* model,
+                     int precision, float* out, int ldo, void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class Plane(C.Structure):
@@ -46,6 +46,18 @@ class FcSplitProblem(C.Structure):
     _fields_ = [('Xs', C.c_void_p), ('x_rscale', C.c_void_p), ('N', C.c_int), ('Dk', C.c_int), ('Ws', C.c_void_p),
                 ('w_rscale', C.c_void_p), ('bias', C.c_void_p), ('bn_scale', C.c_void_p), ('bn_shift', C.c_void_p),
                 ('D', C.c_int), ('act', C.c_int), ('Y', C.c_void_p), ('ldy', C.c_int)]
+
+
+class ClipBlock(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('ln_1_weight', 'ln_1_bias', 'in_proj_weight', 'in_proj_bias', 'out_proj_weight', 'out_proj_bias',
+                                          'ln_2_weight', 'ln_2_bias', 'c_fc_weight', 'c_fc_bias', 'c_proj_weight', 'c_proj_bias')]
+
+
+class ClipText(C.Structure):
+    _fields_ = [('width', C.c_int), ('layers', C.c_int), ('heads', C.c_int), ('embed_dim', C.c_int), ('context_length', C.c_int),
+                ('vocab_size', C.c_int), ('token_embedding', C.c_void_p), ('positional_embedding', C.c_void_p),
+                ('blocks', C.POINTER(ClipBlock)), ('ln_final_weight', C.c_void_p), ('ln_final_bias', C.c_void_p),
+                ('text_projection', C.c_void_p)]
 
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -113,6 +125,9 @@ SIGNATURES = {
     'laff_gru_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_gru_encode': (C.c_int, [_P, _P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                                   C.c_size_t]),
+    'laff_clip_pack_weight': (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    'laff_clip_workspace_bytes': (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_clip_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(ClipText), _I, _P, _I, _P, C.c_size_t]),
 }
 
 _lib = None

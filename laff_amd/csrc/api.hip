@@ -408,6 +408,106 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
     return LAFF_OK;
 }
 
+namespace {
+// the CLIP text encoder's limits and workspace: X [R, W] fp32 | A [R, W] operand | big [R, max(3W fp32, 4W operand)], each region on
+// 256 bytes
+int clip_precision(const char* fn, int precision, int* fp16) {
+    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "%s: unknown precision %d", fn, precision);
+    if (precision != LAFF_PREC_FP32 && precision != LAFF_PREC_FP16)
+        return fail(LAFF_E_UNSUPPORTED, "%s: precision %d: the CLIP encoder takes LAFF_PREC_FP32 or LAFF_PREC_FP16", fn, precision);
+    *fp16 = precision == LAFF_PREC_FP16;
+    return LAFF_OK;
+}
+int clip_check_width(const char* fn, int width) {
+    if (width < 64 || width > 1024 || width % 64)
+        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d: the width must be a multiple of 64 in [64, 1024]", fn, width);
+    return LAFF_OK;
+}
+size_t clip_round(size_t b) { return (b + 255) / 256 * 256; }
+struct ClipWs {
+    size_t x, a, big, total;
+};
+ClipWs clip_ws(int R, int width, int fp16) {
+    const size_t sz = fp16 ? 2 : 4, r = (size_t)R, w = (size_t)width;
+    ClipWs s;
+    s.x = 0;
+    s.a = clip_round(r * w * 4);
+    s.big = s.a + clip_round(r * w * sz);
+    s.total = s.big + clip_round(r * std::max(3 * w * 4, 4 * w * sz));
+    return s;
+}
+}  // namespace
+
+int laff_clip_pack_weight(laff_ctx* ctx, const float* W, int rows, int cols, int transpose, int precision, void* packed) {
+    const char* fn = "laff_clip_pack_weight";
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (rows < 1 || cols < 1) return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d", fn, rows, cols);
+    if (!W || !packed) return fail(LAFF_E_ARG, "%s: null argument", fn);
+    if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "%s: packed must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_clip_pack(W, rows, cols, transpose != 0, fp16, packed, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_clip_workspace_bytes(int R, int N, int width, int precision, size_t* out) {
+    const char* fn = "laff_clip_workspace_bytes";
+    if (!out || R < 0 || N < 0 || N > R) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = clip_check_width(fn, width)) return rc;
+    *out = clip_ws(R, width, fp16).total;
+    return LAFF_OK;
+}
+
+int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_clip_text* m,
+                     int precision, float* out, int ldo, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_clip_encode";
+    // every argument is checked before any GPU work
+    if (!m) return fail(LAFF_E_ARG, "%s: null model", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = clip_check_width(fn, m->width)) return rc;
+    if (m->heads < 1 || m->heads * 64 != m->width)
+        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d heads=%d: only a head dim of 64 is supported", fn, m->width, m->heads);
+    if (m->context_length < 1 || m->context_length > 77)
+        return fail(LAFF_E_UNSUPPORTED, "%s: context_length=%d: at most 77 positions are supported", fn, m->context_length);
+    if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
+    if (m->embed_dim < 1 || m->vocab_size < 1) return fail(LAFF_E_SHAPE, "%s: embed_dim=%d vocab_size=%d", fn, m->embed_dim, m->vocab_size);
+    if (N < 0 || R < N) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d", fn, N, R);
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
+    if (!ids || !row_off || !row_off_host || !out || !workspace || !m->token_embedding || !m->positional_embedding || !m->blocks ||
+        !m->ln_final_weight || !m->ln_final_bias || !m->text_projection)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    for (int l = 0; l < m->layers; ++l) {
+        const laff_clip_block& b = m->blocks[l];
+        if (!b.ln_1_weight || !b.ln_1_bias || !b.in_proj_weight || !b.in_proj_bias || !b.out_proj_weight || !b.out_proj_bias ||
+            !b.ln_2_weight || !b.ln_2_bias || !b.c_fc_weight || !b.c_fc_bias || !b.c_proj_weight || !b.c_proj_bias)
+            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
+        if (!aligned16(b.in_proj_weight) || !aligned16(b.out_proj_weight) || !aligned16(b.c_fc_weight) || !aligned16(b.c_proj_weight))
+            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
+    }
+    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
+    for (int i = 0; i < N; ++i) {
+        const int L = row_off_host[i + 1] - row_off_host[i];
+        if (L < 1 || L > m->context_length)
+            return fail(LAFF_E_ARG, "%s: row_off: caption %d has %d rows (1 .. context_length=%d)", fn, i, L, m->context_length);
+    }
+    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (ldo < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldo=%d < embed_dim=%d", fn, ldo, m->embed_dim);
+    const ClipWs ws = clip_ws(R, m->width, fp16);
+    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
+    if (!aligned16(workspace) || !aligned16(m->text_projection))
+        return fail(LAFF_E_ALIGN, "%s: workspace / packed text_projection must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* w = (char*)workspace;
+    laff::ClipEncodeArgs e{m, ids, row_off, N, R, (float*)(w + ws.x), w + ws.a, w + ws.big, out, ldo};
+    HIP_TRY(laff::launch_clip_encode(e, fp16, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

@@ -1,0 +1,340 @@
+// clip.hip -- the CLIP text encoder (clip.model.CLIP.encode_text, reference model/clip/model.py:153-206, 245-358), inference only.
+//
+//   x = token_embedding[id] + positional_embedding[pos]
+//   L x { x += out_proj(attn(ln_1(x)));  x += c_proj(QuickGELU(c_fc(ln_2(x)))) }     (pre-LN, causal MHA, head dim 64)
+//   feature = ln_final(x[eot row]) . text_projection
+//
+// Ragged rows.  Caption i is given by its ids up to and including p_i = argmax(ids_i) (the row the reference pools): with a causal
+// mask no later position can reach row p_i, so the rows after it are never computed.  The captions' rows are concatenated; row_off
+// [N+1] gives where each starts, and the pooled row of caption i is row_off[i+1] - 1.
+//
+// The residual stream x stays fp32 [R, W].  The matrix operands are the encoder's precision T (_Float16 or float):
+//   clip_ln_kernel     LayerNorm (fp32 statistics) of a row -> operand T; with the embedding gather for layer 0, or the pooled rows
+//   clip_gemm_kernel   out[r][c] = sum_k A[r][k] * B[c][k] (B = a packed nn.Linear weight [out, in]) with three epilogues:
+//                      + bias -> fp32 (in_proj, text_projection), + bias, QuickGELU -> T (c_fc), + bias added in place to x
+//                      (out_proj, c_proj: every element has one owner, no atomics)
+//   clip_attn_kernel   softmax(q k^T / 8 + causal) v per (caption, head), fp32, from the fp32 QKV rows -> operand T
+//
+// Batch invariance: every reduction's split and order depends on the model's dimensions only.  A GEMM output is one full-K MFMA chain
+// in ascending K-steps from zero in one wave, the LayerNorm sums are one wave's butterfly over a fixed lane map, and attention reads
+// only its own caption.  So a caption's feature is bitwise the same in any batch and any chunking of it.
+//
+// GEMM tile: 128 x 128 outputs per workgroup, 2 x 2 waves of 64 x 64 (4 x 4 MFMA blocks of 16 x 16), K-steps of 128 bytes per row
+// (64 halves or 32 floats) staged through two LDS buffers by plain 16-byte loads held in registers across the compute of the step
+// before.  LDS image: 16-byte chunk c of row r sits at chunk c ^ (r & 7) of that row.  Rows past M and columns past N are loaded
+// from the last valid row / column (every load stays inside its matrix) and not stored.
+//   fp16: v_mfma_f32_16x16x32_f16 per 16-byte chunk; lane l holds row l&15, k = 8(l>>4) .. +7 of a 32-wide slice (natural order)
+//   fp32: v_mfma_f32_16x16x4_f32 x 4 per 16-byte chunk; component j of lane l is k = 4(l>>4) + j of a 16-wide slice, the same k
+//         for both operands, so every product is summed once (the order within the chunk is fixed).
+#include <algorithm>
+
+#include "kernels.h"
+#include "wave_reduce.h"
+
+namespace laff {
+
+typedef float clip_f4 __attribute__((ext_vector_type(4)));
+typedef _Float16 clip_h8 __attribute__((ext_vector_type(8)));
+typedef unsigned clip_u4 __attribute__((ext_vector_type(4)));   // one 16-byte chunk (not HIP's clip_u4: a struct that stays in memory)
+
+constexpr int CLIP_BM = 128, CLIP_BN = 128, CLIP_THREADS = 256;
+constexpr int CLIP_CTX = 77;
+
+__device__ __forceinline__ float clip_quick_gelu(float v) { return v / (1.0f + expf(-1.702f * v)); }
+
+template <typename T>
+__device__ __forceinline__ clip_f4 clip_mfma_chunk(clip_u4 a, clip_u4 b, clip_f4 acc) {
+    if constexpr (sizeof(T) == 2) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(clip_h8, a), __builtin_bit_cast(clip_h8, b), acc, 0, 0, 0);
+    } else {
+        const clip_f4 af = __builtin_bit_cast(clip_f4, a), bf = __builtin_bit_cast(clip_f4, b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], acc, 0, 0, 0);
+        return acc;
+    }
+}
+
+template <typename T, int EPI>
+__global__ __launch_bounds__(CLIP_THREADS) void clip_gemm_kernel(ClipGemmArgs g) {
+    __shared__ clip_u4 lds[2][2][CLIP_BM * 8];               // [stage][A | B][row * 8 + chunk]: 64 KiB
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n0 = blockIdx.x * CLIP_BN, m0 = blockIdx.y * CLIP_BM;
+    const int wm = wave >> 1, wn = wave & 1;
+    const long rowb = (long)g.K * sizeof(T);               // bytes per operand row (a multiple of 128)
+    const int nk = (int)(rowb / 128);
+    const char* A = reinterpret_cast<const char*>(g.A);
+    const char* B = reinterpret_cast<const char*>(g.B);
+
+    // this thread's four 16-byte chunks of each operand per K-step: rows r0 + 32 i, chunk c (LDS index dst + 256 i)
+    const int r0 = tid >> 3, c0 = tid & 7, dst = r0 * 8 + (c0 ^ (r0 & 7));
+    long offA[4], offB[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        offA[i] = (long)min(m0 + r0 + 32 * i, g.M - 1) * rowb + c0 * 16;
+        offB[i] = (long)min(n0 + r0 + 32 * i, g.N - 1) * rowb + c0 * 16;
+    }
+    clip_u4 ra[4], rb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        ra[i] = *reinterpret_cast<const clip_u4*>(A + offA[i]);
+        rb[i] = *reinterpret_cast<const clip_u4*>(B + offB[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        lds[0][0][dst + 256 * i] = ra[i];
+        lds[0][1][dst + 256 * i] = rb[i];
+    }
+
+    clip_f4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = clip_f4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int st = kt & 1;
+        if (kt + 1 < nk)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ra[i] = *reinterpret_cast<const clip_u4*>(A + offA[i] + (long)(kt + 1) * 128);
+                rb[i] = *reinterpret_cast<const clip_u4*>(B + offB[i] + (long)(kt + 1) * 128);
+            }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int c = 4 * s + (lane >> 4);
+            clip_u4 a[4], b[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int ra_ = wm * 64 + t * 16 + (lane & 15), rb_ = wn * 64 + t * 16 + (lane & 15);
+                a[t] = lds[st][0][ra_ * 8 + (c ^ (ra_ & 7))];
+                b[t] = lds[st][1][rb_ * 8 + (c ^ (rb_ & 7))];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = clip_mfma_chunk<T>(a[i], b[j], acc[i][j]);
+        }
+        if (kt + 1 < nk)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                lds[st ^ 1][0][dst + 256 * i] = ra[i];
+                lds[st ^ 1][1][dst + 256 * i] = rb[i];
+            }
+        __syncthreads();
+    }
+
+    // C/D map of the 16 x 16 blocks: column lane & 15, row 4 (lane >> 4) + reg
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = n0 + wn * 64 + j * 16 + (lane & 15);
+        if (col >= g.N) continue;
+        const float bias = g.bias ? g.bias[col] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = m0 + wm * 64 + i * 16 + 4 * (lane >> 4) + reg;
+                if (row >= g.M) continue;
+                const float v = acc[i][j][reg] + bias;
+                const long o = (long)row * g.ldc + col;
+                if constexpr (EPI == CLIP_EPI_F32) reinterpret_cast<float*>(g.C)[o] = v;
+                else if constexpr (EPI == CLIP_EPI_GELU) reinterpret_cast<T*>(g.C)[o] = (T)clip_quick_gelu(v);
+                else reinterpret_cast<float*>(g.C)[o] += v;
+            }
+    }
+}
+
+// One wave per row: x (fp32, width W <= 1024: W / 64 values per lane, element lane + 64 k) -> LayerNorm -> operand T.
+//   CLIP_LN_ROW    x = X[row]
+//   CLIP_LN_EMBED  x = token_embedding[ids[row]] + positional_embedding[row - row_off[caption]], also written to X[row]
+//   CLIP_LN_POOL   x = X[row_off[row + 1] - 1]        (row = caption)
+template <typename T, int MODE>
+__global__ __launch_bounds__(CLIP_THREADS) void clip_ln_kernel(ClipLnArgs a) {
+    const int row = blockIdx.x * (CLIP_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= a.rows) return;                             // whole waves: the butterflies below see all 64 lanes
+    const int W = a.W, nv = W >> 6;
+    float x[16];
+    long src = row;
+    if constexpr (MODE == CLIP_LN_EMBED) {
+        int lo = 0, hi = a.N;                              // the caption: the last c with row_off[c] <= row
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (a.row_off[mid] <= row) lo = mid;
+            else hi = mid;
+        }
+        const int pos = row - a.row_off[lo], id = a.ids[row];
+        const bool ok = (unsigned)id < (unsigned)a.V && (unsigned)pos < (unsigned)a.ctx;
+        const float* te = a.tok_emb + (long)(ok ? id : 0) * W;
+        const float* pe = a.pos_emb + (long)(ok ? pos : 0) * W;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < nv) {
+                const int e = lane + 64 * k;
+                x[k] = ok ? te[e] + pe[e] : __builtin_nanf("");   // an id outside the table poisons its row instead of reading past it
+                a.X[(long)row * W + e] = x[k];
+            }
+    } else {
+        if constexpr (MODE == CLIP_LN_POOL) src = a.row_off[row + 1] - 1;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < nv) x[k] = a.X[src * W + lane + 64 * k];
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) s += x[k];
+    const float mean = wave_allsum(s) / (float)W;
+    float q = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) q = fmaf(x[k] - mean, x[k] - mean, q);
+    const float rstd = 1.0f / sqrtf(wave_allsum(q) / (float)W + 1e-5f);
+    T* out = reinterpret_cast<T*>(a.out) + (long)row * W;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) {
+            const int e = lane + 64 * k;
+            out[e] = (T)fmaf((x[k] - mean) * rstd, a.gamma[e], a.beta[e]);
+        }
+}
+
+// One workgroup per (caption, head): q, k, v of the caption's L <= 77 rows in LDS; wave w takes query rows w, w + 4, ...
+// Lane j scores key j and j + 64; the softmax is fp32 (max-subtracted exp, one butterfly each for the max and the sum); the output
+// column d = lane sums p_j v_j in ascending j.
+template <typename T>
+__global__ __launch_bounds__(CLIP_THREADS) void clip_attn_kernel(ClipAttnArgs a) {
+    __shared__ float qs[CLIP_CTX][64];
+    __shared__ float ks[CLIP_CTX][65];                     // padded: lane j reads row j
+    __shared__ float vs[CLIP_CTX][64];
+    __shared__ float ps[CLIP_THREADS / 64][2 * 64];
+    const int cap = blockIdx.x, h = blockIdx.y;
+    const int r0 = a.row_off[cap], L = min(a.row_off[cap + 1] - r0, CLIP_CTX);
+    const int W = a.W, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int e = threadIdx.x; e < L * 64; e += CLIP_THREADS) {
+        const int i = e >> 6, d = e & 63;
+        const float* p = a.qkv + (long)(r0 + i) * 3 * W + h * 64 + d;
+        qs[i][d] = p[0];
+        ks[i][d] = p[W];
+        vs[i][d] = p[2 * W];
+    }
+    __syncthreads();
+    const int j1 = min(lane + 64, CLIP_CTX - 1);
+    for (int i = wave; i < L; i += CLIP_THREADS / 64) {
+        float d0 = 0.0f, d1 = 0.0f;
+        const int j0 = min(lane, L - 1);
+#pragma unroll 8
+        for (int d = 0; d < 64; ++d) {
+            d0 = fmaf(qs[i][d], ks[j0][d], d0);
+            d1 = fmaf(qs[i][d], ks[j1][d], d1);
+        }
+        const float ninf = -__builtin_inff();
+        const float s0 = lane <= i ? d0 * 0.125f : ninf, s1 = lane + 64 <= i ? d1 * 0.125f : ninf;
+        const float m = wave_allmax(fmaxf(s0, s1));
+        const float e0 = lane <= i ? expf(s0 - m) : 0.0f, e1 = lane + 64 <= i ? expf(s1 - m) : 0.0f;
+        const float sum = wave_allsum(e0 + e1);
+        ps[wave][lane] = e0;
+        ps[wave][lane + 64] = e1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float o = 0.0f;
+        for (int j = 0; j <= i; ++j) o = fmaf(ps[wave][j], vs[j][lane], o);
+        reinterpret_cast<T*>(a.out)[(long)(r0 + i) * W + h * 64 + lane] = (T)(o / sum);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // every lane has read ps before the next row overwrites it
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void clip_pack_kernel(const float* __restrict__ W, int rows, int cols, int transpose, T* __restrict__ out) {
+    const long total = (long)rows * cols;
+    for (long o = (long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long)gridDim.x * blockDim.x) {
+        // transpose: out [cols, rows], out[c][r] = W[r][c]
+        const long src = transpose ? (o % rows) * cols + o / rows : o;
+        out[o] = (T)W[src];
+    }
+}
+
+hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int fp16, void* out, hipStream_t st) {
+    const long total = (long)rows * cols;
+    const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
+    if (fp16) clip_pack_kernel<_Float16><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, reinterpret_cast<_Float16*>(out));
+    else clip_pack_kernel<float><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, reinterpret_cast<float*>(out));
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename T>
+hipError_t clip_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi, hipStream_t st) {
+    ClipGemmArgs g{A, B, bias, C, M, N, K, ldc};
+    const dim3 grid((N + CLIP_BN - 1) / CLIP_BN, (M + CLIP_BM - 1) / CLIP_BM);
+    if (epi == CLIP_EPI_F32) clip_gemm_kernel<T, CLIP_EPI_F32><<<grid, CLIP_THREADS, 0, st>>>(g);
+    else if (epi == CLIP_EPI_GELU) clip_gemm_kernel<T, CLIP_EPI_GELU><<<grid, CLIP_THREADS, 0, st>>>(g);
+    else clip_gemm_kernel<T, CLIP_EPI_RESID><<<grid, CLIP_THREADS, 0, st>>>(g);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t clip_ln(int mode, const ClipLnArgs& a, hipStream_t st) {
+    const int blocks = (a.rows + 3) / 4;
+    if (mode == CLIP_LN_EMBED) clip_ln_kernel<T, CLIP_LN_EMBED><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else if (mode == CLIP_LN_POOL) clip_ln_kernel<T, CLIP_LN_POOL><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else clip_ln_kernel<T, CLIP_LN_ROW><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+#define CLIP_TRY(expr)                               \
+    do {                                             \
+        const hipError_t e_ = (expr);                \
+        if (e_ != hipSuccess) return e_;             \
+    } while (0)
+
+template <typename T>
+hipError_t clip_encode_t(const ClipEncodeArgs& e, hipStream_t st) {
+    const laff_clip_text& m = *e.model;
+    const int W = m.width, R = e.R, N = e.N;
+    ClipLnArgs ln{};
+    ln.ids = e.ids;
+    ln.row_off = e.row_off;
+    ln.N = N;
+    ln.V = m.vocab_size;
+    ln.ctx = m.context_length;
+    ln.tok_emb = m.token_embedding;
+    ln.pos_emb = m.positional_embedding;
+    ln.X = e.X;
+    ln.out = e.A;
+    ln.W = W;
+    ln.rows = R;
+    ClipAttnArgs at{reinterpret_cast<const float*>(e.big), e.row_off, e.A, W};
+    for (int l = 0; l < m.layers; ++l) {
+        const laff_clip_block& b = m.blocks[l];
+        ln.gamma = b.ln_1_weight;
+        ln.beta = b.ln_1_bias;
+        CLIP_TRY(clip_ln<T>(l == 0 ? CLIP_LN_EMBED : CLIP_LN_ROW, ln, st));
+        CLIP_TRY(clip_gemm<T>(e.A, b.in_proj_weight, b.in_proj_bias, e.big, R, 3 * W, W, 3 * W, CLIP_EPI_F32, st));
+        clip_attn_kernel<T><<<dim3(N, m.heads), CLIP_THREADS, 0, st>>>(at);
+        CLIP_TRY(hipGetLastError());
+        CLIP_TRY(clip_gemm<T>(e.A, b.out_proj_weight, b.out_proj_bias, e.X, R, W, W, W, CLIP_EPI_RESID, st));
+        ln.gamma = b.ln_2_weight;
+        ln.beta = b.ln_2_bias;
+        CLIP_TRY(clip_ln<T>(CLIP_LN_ROW, ln, st));
+        CLIP_TRY(clip_gemm<T>(e.A, b.c_fc_weight, b.c_fc_bias, e.big, R, 4 * W, W, 4 * W, CLIP_EPI_GELU, st));
+        CLIP_TRY(clip_gemm<T>(e.big, b.c_proj_weight, b.c_proj_bias, e.X, R, W, 4 * W, W, CLIP_EPI_RESID, st));
+    }
+    ln.gamma = m.ln_final_weight;
+    ln.beta = m.ln_final_bias;
+    ln.rows = N;
+    CLIP_TRY(clip_ln<T>(CLIP_LN_POOL, ln, st));
+    return clip_gemm<T>(e.A, m.text_projection, nullptr, e.out, N, m.embed_dim, W, e.ldo, CLIP_EPI_F32, st);
+}
+
+}  // namespace
+
+hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st) {
+    return fp16 ? clip_encode_t<_Float16>(e, st) : clip_encode_t<float>(e, st);
+}
+
+}  // namespace laff

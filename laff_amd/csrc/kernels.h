@@ -267,4 +267,46 @@ struct GruStepArgs {
 hipError_t launch_gru_pack_whh(const float* W, int H, float* Wp, hipStream_t st);
 hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st);
 
+// clip.hip: the CLIP text encoder (laff_clip_encode)
+enum { CLIP_EPI_F32 = 0, CLIP_EPI_GELU = 1, CLIP_EPI_RESID = 2 };
+enum { CLIP_LN_ROW = 0, CLIP_LN_EMBED = 1, CLIP_LN_POOL = 2 };
+struct ClipGemmArgs {
+    const void* A;        // [M, K] operand rows
+    const void* B;        // [N, K] packed weight (nn.Linear layout)
+    const float* bias;    // [N] or null
+    void* C;              // [M, ldc]: fp32 (F32, RESID: added in place) or the operand type (GELU)
+    int M, N, K, ldc;
+};
+struct ClipLnArgs {
+    const int* ids;       // [R] token ids (EMBED)
+    const int* row_off;   // [N+1] (EMBED, POOL)
+    int N, V, ctx;
+    const float* tok_emb; // [V, W]
+    const float* pos_emb; // [ctx, W]
+    float* X;             // [R, W] residual stream
+    const float* gamma;
+    const float* beta;
+    void* out;            // [rows, W] operand
+    int W, rows;
+};
+struct ClipAttnArgs {
+    const float* qkv;     // [R, 3W]
+    const int* row_off;   // [N+1]
+    void* out;            // [R, W] operand
+    int W;
+};
+struct ClipEncodeArgs {
+    const laff_clip_text* model;
+    const int* ids;
+    const int* row_off;
+    int N, R;
+    float* X;             // workspace: [R, W] fp32
+    void* A;              // workspace: [R, W] operand
+    void* big;            // workspace: [R, 3W] fp32 (QKV) / [R, 4W] operand (MLP hidden)
+    float* out;
+    int ldo;
+};
+hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int fp16, void* out, hipStream_t st);
+hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st);
+
 }  // namespace laff

@@ -6,13 +6,14 @@ CPU or eager-PyTorch fallback: CPU tensors are rejected.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
 
-__all__ = ['gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -276,6 +277,55 @@ def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean'
     _call('gru_encode', lib.laff_gru_encode, h, _ptr(tok), _ptr(lens), _ptr(prm), bs, T, N, V, H, int(num_layers), int(bidir),
           GRU_POOLING[pooling], _ptr(P), _ptr(Wp), _ptr(bhh), _ptr(Pr), _ptr(Wr), _ptr(br), _ptr(o), ldo, _ptr(workspace),
           workspace.numel())
+    return out
+
+
+def clip_pack_weight(w, precision='fp16', transpose=False):
+    """laff_clip_pack_weight: an fp32 weight [rows, cols] -> the CLIP GEMM operand in the encoder's precision (fp16 or fp32),
+    [rows, cols], or [cols, rows] with transpose (text_projection)."""
+    w = _dev(w, 'w')
+    if w.dim() != 2:
+        raise ValueError('w must be 2-D, got %s' % (tuple(w.shape),))
+    w = w.contiguous()
+    rows, cols = w.shape
+    dt = torch.float16 if precision == 'fp16' else torch.float32
+    out = torch.empty((cols, rows) if transpose else (rows, cols), device=w.device, dtype=dt)
+    lib, h = _context(w.device)
+    _call('clip_pack_weight', lib.laff_clip_pack_weight, h, _ptr(w), int(rows), int(cols), int(bool(transpose)), PREC[precision],
+          _ptr(out))
+    return out
+
+
+def clip_workspace_bytes(R, N, width, precision='fp16'):
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_clip_workspace_bytes(int(R), int(N), int(width), PREC[precision], C.byref(n)))
+    return n.value
+
+
+def clip_encode(ids, row_off, row_off_host, model, precision='fp16', out=None, workspace=None):
+    """laff_clip_encode.  ids [R] int32 (the captions' rows concatenated) and row_off [N+1] int32 on the device, row_off_host: the
+    same offsets as a host int32 array; model: a laff_amd._lib.ClipText of device pointers (ClipTxtEncoder builds it).  Returns out
+    [N, embed_dim] fp32.  workspace: a uint8 device tensor of clip_workspace_bytes(R, N, width, precision) bytes, or None to
+    allocate one here (pass one for HIP-graph capture)."""
+    ids = _dev(ids, 'ids', torch.int32)
+    row_off = _dev(row_off, 'row_off', torch.int32)
+    if not ids.is_contiguous() or not row_off.is_contiguous() or ids.dim() != 1 or row_off.dim() != 1:
+        raise ValueError('ids and row_off must be contiguous vectors')
+    R, N = ids.numel(), row_off.numel() - 1
+    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
+    if roh.shape != (N + 1,):
+        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
+    if workspace is None:
+        workspace = torch.empty(max(clip_workspace_bytes(R, N, model.width, precision), 16), dtype=torch.uint8, device=ids.device)
+    if out is None:
+        out = torch.empty((N, model.embed_dim), device=ids.device, dtype=torch.float32)
+    if tuple(out.shape) != (N, model.embed_dim):
+        raise ValueError('out must be (%d, %d), got %s' % (N, model.embed_dim, tuple(out.shape)))
+    o, ldo = _rows(out, 'out')
+    lib, h = _context(ids.device)
+    _call('clip_encode', lib.laff_clip_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
+          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
     return out
 
 
