@@ -79,6 +79,48 @@ struct DeviceGuard {
 bool is_x3(int p) { return p == LAFF_PREC_FP16X3 || p == LAFF_PREC_BF16X3; }
 int elem_size(int p) { return p == LAFF_PREC_FP32 ? 4 : 2; }
 
+// the FC epilogue of `who` (problem i, or the only one when i < 0): the activation code, bn_scale / bn_shift given together and, with
+// `align`, bias / bn_scale / bn_shift 16-byte aligned -- in that order
+int check_epilogue(const char* who, int i, int act, const float* bias, const float* bn_scale, const float* bn_shift, bool align) {
+    char at[96];
+    if (i < 0) snprintf(at, sizeof(at), "%s", who);
+    else snprintf(at, sizeof(at), "%s: problem %d", who, i);
+    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", at, act);
+    if ((bn_scale == nullptr) != (bn_shift == nullptr)) return fail(LAFF_E_ARG, "%s: bn_scale/bn_shift must come together", at);
+    if (align && ((bias && !aligned16(bias)) || (bn_scale && (!aligned16(bn_scale) || !aligned16(bn_shift)))))
+        return fail(LAFF_E_ALIGN, "%s: bias / bn_scale / bn_shift must be 16-byte aligned", at);
+    return LAFF_OK;
+}
+
+// adds a problem to a grouped GEMM launch and issues the launch once MAX_GROUP are in; the caller launches the rest
+template <typename Launch>
+hipError_t group_add(laff::GroupedGemmArgs& ga, const laff::GemmArgs& a, Launch launch) {
+    ga.p[ga.count++] = a;
+    if (ga.count < laff::MAX_GROUP) return hipSuccess;
+    const hipError_t e = launch(ga);
+    ga.count = 0;
+    return e;
+}
+
+// laff_split_rows_grouped (out != null) and laff_row_scales_grouped (out == null: per-row scales only, empty matrices skipped):
+// each run of up to 8 matrices is checked, then launched at once
+int split_rows_by_eight(laff_ctx* ctx, const char* who, int count, const float* const* X, const int* N, const int* K,
+                        const int* ldx, void* const* out, float* const* rscale) {
+    DeviceGuard g(ctx->device);
+    void* const none[8] = {};
+    for (int i0 = 0; i0 < count; i0 += 8) {
+        const int c = std::min(count - i0, 8);
+        for (int i = i0; i < i0 + c; ++i) {
+            if (!out && N[i] == 0) continue;
+            if (!X[i] || (out && !out[i]) || !rscale[i]) return fail(LAFF_E_ARG, "%s: matrix %d has a null pointer", who, i);
+            if (N[i] < 0 || K[i] < 1 || ldx[i] < K[i]) return fail(LAFF_E_SHAPE, "%s: matrix %d bad shape", who, i);
+            if (out && !aligned16(out[i])) return fail(LAFF_E_ALIGN, "%s: out %d must be 16-byte aligned", who, i);
+        }
+        HIP_TRY(laff::launch_split_rows_grouped(c, X + i0, N + i0, K + i0, ldx + i0, out ? out + i0 : none, rscale + i0, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,15 +208,13 @@ int laff_device_info(laff_ctx* ctx, int out[4]) {
     return LAFF_OK;
 }
 
-static int fc_problem_args(const laff_fc_problem& q, laff::GemmArgs& a, bool& glds, const char* who) {
+static int fc_problem_args(const laff_fc_problem& q, laff::GemmArgs& a, bool& glds, const char* who, int i) {
     if (q.N == 0) { a = laff::GemmArgs{}; glds = true; return LAFF_OK; }      /* empty problem (skipped by the callers) */
-    if (!q.X || !q.W || !q.Y) return fail(LAFF_E_ARG, "%s: null X/W/Y", who);
+    if (!q.X || !q.W || !q.Y) return fail(LAFF_E_ARG, "%s: problem %d: null X/W/Y", who, i);
     if (q.N < 0 || q.Dk < 1 || q.D < 1 || q.ldx < q.Dk || q.ldw < q.Dk || q.ldy < q.D)
-        return fail(LAFF_E_SHAPE, "%s: bad shape N=%d Dk=%d D=%d ldx=%d ldw=%d ldy=%d", who, q.N, q.Dk, q.D, q.ldx, q.ldw, q.ldy);
-    if (q.act < LAFF_ACT_NONE || q.act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", who, q.act);
-    if ((q.bn_scale == nullptr) != (q.bn_shift == nullptr)) return fail(LAFF_E_ARG, "%s: bn_scale/bn_shift must come together", who);
-    if ((q.bias && !aligned16(q.bias)) || (q.bn_scale && (!aligned16(q.bn_scale) || !aligned16(q.bn_shift))))
-        return fail(LAFF_E_ALIGN, "%s: bias / bn_scale / bn_shift must be 16-byte aligned", who);
+        return fail(LAFF_E_SHAPE, "%s: problem %d: bad shape N=%d Dk=%d D=%d ldx=%d ldw=%d ldy=%d", who, i, q.N, q.Dk, q.D, q.ldx, q.ldw,
+                    q.ldy);
+    if (int rc = check_epilogue(who, i, q.act, q.bias, q.bn_scale, q.bn_shift, true)) return rc;
     a = laff::GemmArgs{};
     a.R = q.X; a.C = q.W; a.nR = q.N; a.nC = q.D; a.K = q.Dk; a.ldR = q.ldx; a.ldC = q.ldw;
     a.nseg = 1; a.segR[0] = a.segC[0] = 0;
@@ -199,19 +239,16 @@ int laff_fc_act_bn_grouped(laff_ctx* ctx, const laff_fc_problem* problems, int c
     DeviceGuard g(ctx->device);
     // problems are grouped by staging kind (see staging_kind), at most MAX_GROUP per launch
     for (int kind = 2; kind >= 0; --kind) {
+        auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_grouped_f32(ga, kind, ctx->stream); };
         laff::GroupedGemmArgs ga{};
         for (int i = 0; i < count; ++i) {
             laff::GemmArgs a;
             bool aligned;
-            if (int rc = fc_problem_args(problems[i], a, aligned, "laff_fc_act_bn_grouped")) return rc;
+            if (int rc = fc_problem_args(problems[i], a, aligned, "laff_fc_act_bn_grouped", i)) return rc;
             if (problems[i].N == 0 || laff::staging_kind(a, 4, aligned) != kind) continue;
-            ga.p[ga.count++] = a;
-            if (ga.count == laff::MAX_GROUP) {
-                HIP_TRY(laff::launch_gemm_nt_grouped_f32(ga, kind, ctx->stream));
-                ga.count = 0;
-            }
+            HIP_TRY(group_add(ga, a, launch));
         }
-        if (ga.count) HIP_TRY(laff::launch_gemm_nt_grouped_f32(ga, kind, ctx->stream));
+        if (ga.count) HIP_TRY(launch(ga));
     }
     return LAFF_OK;
 }
@@ -224,8 +261,7 @@ int laff_fc_gather_act_bn(laff_ctx* ctx, const int* indptr, const int* indices, 
     if (!indptr || !indices || !Wt || !Y) return fail(LAFF_E_ARG, "laff_fc_gather_act_bn: null argument");
     if (N < 0 || Dk < 1 || D < 4 || (D & 3) || D > 8192 || ldwt < D || (ldwt & 3) || ldy < D || (ldy & 3))
         return fail(LAFF_E_SHAPE, "laff_fc_gather_act_bn: bad shape N=%d Dk=%d D=%d ldwt=%d ldy=%d", N, Dk, D, ldwt, ldy);
-    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "laff_fc_gather_act_bn: bad act %d", act);
-    if ((bn_scale == nullptr) != (bn_shift == nullptr)) return fail(LAFF_E_ARG, "laff_fc_gather_act_bn: bn_scale/bn_shift must come together");
+    if (int rc = check_epilogue("laff_fc_gather_act_bn", -1, act, bias, bn_scale, bn_shift, false)) return rc;
     if (!aligned16(Wt) || !aligned16(Y)) return fail(LAFF_E_ALIGN, "laff_fc_gather_act_bn: Wt / Y must be 16-byte aligned");
     if (N == 0) return LAFF_OK;
     DeviceGuard g(ctx->device);
@@ -518,45 +554,28 @@ int laff_split_rows_bytes(int N, int K, size_t* out) {
 int laff_split_rows(laff_ctx* ctx, const float* X, int N, int K, int ldx, void* out, float* rscale) {
     CHECK_CTX(ctx);
     if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
-    if (!X || !out || !rscale) return fail(LAFF_E_ARG, "laff_split_rows: null argument");
-    if (N < 0 || K < 1 || ldx < K) return fail(LAFF_E_SHAPE, "laff_split_rows: bad shape N=%d K=%d ldx=%d", N, K, ldx);
-    if (!aligned16(out)) return fail(LAFF_E_ALIGN, "laff_split_rows: out must be 16-byte aligned");
-    if (N == 0) return LAFF_OK;
-    DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_split_rows(X, N, K, ldx, (K + 63) / 64 * 64, out, rscale, ctx->stream));
-    return LAFF_OK;
+    return split_rows_by_eight(ctx, "laff_split_rows", 1, &X, &N, &K, &ldx, &out, &rscale);
 }
 
 int laff_split_rows_grouped(laff_ctx* ctx, int count, const float* const* X, const int* N, const int* K, const int* ldx,
                             void* const* out, float* const* rscale) {
     CHECK_CTX(ctx);
     if (count < 0 || (count && (!X || !N || !K || !ldx || !out || !rscale))) return fail(LAFF_E_ARG, "laff_split_rows_grouped: bad argument list");
-    DeviceGuard g(ctx->device);
-    for (int i0 = 0; i0 < count; i0 += 8) {
-        const int c = count - i0 < 8 ? count - i0 : 8;
-        for (int i = i0; i < i0 + c; ++i) {
-            if (!X[i] || !out[i] || !rscale[i]) return fail(LAFF_E_ARG, "laff_split_rows_grouped: matrix %d has a null pointer", i);
-            if (N[i] < 0 || K[i] < 1 || ldx[i] < K[i]) return fail(LAFF_E_SHAPE, "laff_split_rows_grouped: matrix %d bad shape", i);
-            if (!aligned16(out[i])) return fail(LAFF_E_ALIGN, "laff_split_rows_grouped: out %d must be 16-byte aligned", i);
-        }
-        HIP_TRY(laff::launch_split_rows_grouped(c, X + i0, N + i0, K + i0, ldx + i0, out + i0, rscale + i0, ctx->stream));
-    }
-    return LAFF_OK;
+    return split_rows_by_eight(ctx, "laff_split_rows_grouped", count, X, N, K, ldx, out, rscale);
 }
 
 int laff_fc_act_bn_split_grouped(laff_ctx* ctx, const laff_fc_split_problem* problems, int count) {
     CHECK_CTX(ctx);
     if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: bad problem list");
     DeviceGuard g(ctx->device);
+    auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_grouped_f16(ga, ctx->stream); };
     laff::GroupedGemmArgs ga{};
     for (int i = 0; i < count; ++i) {
         const laff_fc_split_problem& q = problems[i];
         if (!q.Xs || !q.Ws || !q.x_rscale || !q.w_rscale || !q.Y) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: problem %d has a null operand", i);
         if (q.N < 0 || q.Dk < 1 || q.D < 1 || q.ldy < q.D) return fail(LAFF_E_SHAPE, "laff_fc_act_bn_split_grouped: problem %d bad shape", i);
-        if (q.act < LAFF_ACT_NONE || q.act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: bad act %d", q.act);
-        if ((q.bn_scale == nullptr) != (q.bn_shift == nullptr)) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: bn_scale/bn_shift must come together");
-        if (!aligned16(q.Xs) || !aligned16(q.Ws) || (q.bias && !aligned16(q.bias)) || (q.bn_scale && (!aligned16(q.bn_scale) || !aligned16(q.bn_shift))))
-            return fail(LAFF_E_ALIGN, "laff_fc_act_bn_split_grouped: problem %d: 16-byte alignment", i);
+        if (int rc = check_epilogue("laff_fc_act_bn_split_grouped", i, q.act, q.bias, q.bn_scale, q.bn_shift, true)) return rc;
+        if (!aligned16(q.Xs) || !aligned16(q.Ws)) return fail(LAFF_E_ALIGN, "laff_fc_act_bn_split_grouped: problem %d: Xs / Ws must be 16-byte aligned", i);
         const int Kp = (q.Dk + 63) / 64 * 64;
         if ((long long)q.N * Kp * 4 >= (1ll << 32) || (long long)q.D * Kp * 4 >= (1ll << 32))
             return fail(LAFF_E_UNSUPPORTED, "laff_fc_act_bn_split_grouped: problem %d: packed operand exceeds 4 GiB", i);
@@ -570,13 +589,9 @@ int laff_fc_act_bn_split_grouped(laff_ctx* ctx, const laff_fc_split_problem* pro
         a.out = q.Y; a.ldo = q.ldy; a.scale = 1.0f;
         a.row_scale = q.x_rscale; a.col_scale = q.w_rscale;
         a.bias = q.bias; a.bn_scale = q.bn_scale; a.bn_shift = q.bn_shift; a.act = q.act;
-        ga.p[ga.count++] = a;
-        if (ga.count == laff::MAX_GROUP) {
-            HIP_TRY(laff::launch_gemm_nt_grouped_f16(ga, ctx->stream));
-            ga.count = 0;
-        }
+        HIP_TRY(group_add(ga, a, launch));
     }
-    if (ga.count) HIP_TRY(laff::launch_gemm_nt_grouped_f16(ga, ctx->stream));
+    if (ga.count) HIP_TRY(launch(ga));
     return LAFF_OK;
 }
 
@@ -584,24 +599,14 @@ int laff_row_scales_grouped(laff_ctx* ctx, int count, const float* const* X, con
                             float* const* rscale) {
     CHECK_CTX(ctx);
     if (count < 0 || (count && (!X || !N || !K || !ldx || !rscale))) return fail(LAFF_E_ARG, "laff_row_scales_grouped: bad argument list");
-    DeviceGuard g(ctx->device);
-    for (int i0 = 0; i0 < count; i0 += 8) {
-        const int c = count - i0 < 8 ? count - i0 : 8;
-        void* none[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        for (int i = i0; i < i0 + c; ++i) {
-            if (N[i] == 0) continue;
-            if (!X[i] || !rscale[i]) return fail(LAFF_E_ARG, "laff_row_scales_grouped: matrix %d has a null pointer", i);
-            if (N[i] < 0 || K[i] < 1 || ldx[i] < K[i]) return fail(LAFF_E_SHAPE, "laff_row_scales_grouped: matrix %d bad shape", i);
-        }
-        HIP_TRY(laff::launch_split_rows_grouped(c, X + i0, N + i0, K + i0, ldx + i0, none, rscale + i0, ctx->stream));
-    }
-    return LAFF_OK;
+    return split_rows_by_eight(ctx, "laff_row_scales_grouped", count, X, N, K, ldx, nullptr, rscale);
 }
 
 int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* problems, int count) {
     CHECK_CTX(ctx);
     if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_fused_grouped: bad problem list");
     DeviceGuard g(ctx->device);
+    auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_x3_fused_grouped(ga, ctx->stream); };
     laff::GroupedGemmArgs ga{};
     for (int i = 0; i < count; ++i) {
         const laff_fc_fused_problem& q = problems[i];
@@ -610,10 +615,8 @@ int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* pro
         if (q.N < 0 || q.Dk < 32 || (q.Dk & 31) || q.D < 1 || q.ldy < q.D || q.ldx < q.Dk || (q.ldx & 3))
             return fail(LAFF_E_SHAPE, "laff_fc_act_bn_fused_grouped: problem %d: need Dk %% 32 == 0, ldx %% 4 == 0 (N=%d Dk=%d D=%d ldx=%d ldy=%d)",
                         i, q.N, q.Dk, q.D, q.ldx, q.ldy);
-        if (q.act < LAFF_ACT_NONE || q.act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "laff_fc_act_bn_fused_grouped: bad act %d", q.act);
-        if ((q.bn_scale == nullptr) != (q.bn_shift == nullptr)) return fail(LAFF_E_ARG, "laff_fc_act_bn_fused_grouped: bn_scale/bn_shift must come together");
-        if (!aligned16(q.X) || !aligned16(q.Ws) || (q.bias && !aligned16(q.bias)) || (q.bn_scale && (!aligned16(q.bn_scale) || !aligned16(q.bn_shift))))
-            return fail(LAFF_E_ALIGN, "laff_fc_act_bn_fused_grouped: problem %d: 16-byte alignment", i);
+        if (int rc = check_epilogue("laff_fc_act_bn_fused_grouped", i, q.act, q.bias, q.bn_scale, q.bn_shift, true)) return rc;
+        if (!aligned16(q.X) || !aligned16(q.Ws)) return fail(LAFF_E_ALIGN, "laff_fc_act_bn_fused_grouped: problem %d: X / Ws must be 16-byte aligned", i);
         const int Kp = (q.Dk + 63) / 64 * 64;
         if ((long long)q.N * q.ldx * 4 >= (1ll << 32) || (long long)q.D * Kp * 4 >= (1ll << 32))
             return fail(LAFF_E_UNSUPPORTED, "laff_fc_act_bn_fused_grouped: problem %d: operand exceeds 4 GiB", i);
@@ -628,13 +631,9 @@ int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* pro
 #ifdef LAFF_GEMM_TRACE
         if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-        ga.p[ga.count++] = a;
-        if (ga.count == laff::MAX_GROUP) {
-            HIP_TRY(laff::launch_gemm_nt_x3_fused_grouped(ga, ctx->stream));
-            ga.count = 0;
-        }
+        HIP_TRY(group_add(ga, a, launch));
     }
-    if (ga.count) HIP_TRY(laff::launch_gemm_nt_x3_fused_grouped(ga, ctx->stream));
+    if (ga.count) HIP_TRY(launch(ga));
     return LAFF_OK;
 }
 
@@ -704,8 +703,7 @@ int laff_fc_strip_pack(laff_ctx* ctx, const float* W, int ldw, const float* bias
     if (D < 32 || (D & 31) || Dk != laff::FC_STRIP_K || ldw < Dk)
         return fail(LAFF_E_SHAPE, "laff_fc_strip_pack: need D %% 32 == 0, Dk == 512, ldw >= Dk (D=%d Dk=%d ldw=%d)", D, Dk, ldw);
     if ((long long)D * 2048 >= (1ll << 32)) return fail(LAFF_E_UNSUPPORTED, "laff_fc_strip_pack: image exceeds 4 GiB");
-    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "laff_fc_strip_pack: bad act %d", act);
-    if ((bn_scale == nullptr) != (bn_shift == nullptr)) return fail(LAFF_E_ARG, "laff_fc_strip_pack: bn_scale/bn_shift must come together");
+    if (int rc = check_epilogue("laff_fc_strip_pack", -1, act, bias, bn_scale, bn_shift, false)) return rc;
     if (!aligned16(img)) return fail(LAFF_E_ALIGN, "laff_fc_strip_pack: img must be 16-byte aligned");
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_fc_strip_pack(W, ldw, bias, bn_scale, bn_shift, D, act, img, ctx->stream));
@@ -725,7 +723,7 @@ int laff_fc_act_bn_strip_grouped(laff_ctx* ctx, const laff_fc_strip_problem* pro
         if (q.N < 0 || q.D < 32 || (q.D & 31) || q.ldy < q.D || q.ldx < laff::FC_STRIP_K || (q.ldx & 3))
             return fail(LAFF_E_SHAPE, "laff_fc_act_bn_strip_grouped: problem %d: need D %% 32 == 0, ldx >= 512, ldx %% 4 == 0 (N=%d D=%d ldx=%d ldy=%d)",
                         i, q.N, q.D, q.ldx, q.ldy);
-        if (q.act < LAFF_ACT_NONE || q.act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "laff_fc_act_bn_strip_grouped: bad act %d", q.act);
+        if (int rc = check_epilogue("laff_fc_act_bn_strip_grouped", i, q.act, nullptr, nullptr, nullptr, false)) return rc;
         if (!aligned16(q.X) || !aligned16(q.img)) return fail(LAFF_E_ALIGN, "laff_fc_act_bn_strip_grouped: problem %d: 16-byte alignment", i);
         if ((long long)laff::FC_STRIP_ROWS * q.ldy * 4 >= (1ll << 31) || (long long)q.D * 2048 >= (1ll << 32))
             return fail(LAFF_E_UNSUPPORTED, "laff_fc_act_bn_strip_grouped: problem %d: output strip / image exceeds the 32-bit buffer range", i);

@@ -979,14 +979,6 @@ hipError_t launch_split_rows_grouped(int count, const float* const* X, const int
     return hipGetLastError();
 }
 
-hipError_t launch_split_rows(const float* X, int N, int K, int ldx, int Kp, void* out, float* rscale, hipStream_t st) {
-    (void)Kp;
-    const float* xs[1] = {X};
-    void* os[1] = {out};
-    float* rs[1] = {rscale};
-    return launch_split_rows_grouped(1, xs, &N, &K, &ldx, os, rs, st);
-}
-
 hipError_t launch_pack_rows(const float* E, int N, int H, int d, int lde, int normalize, float eps, float prescale,
                             int precision, void* out, hipStream_t st) {
     const long items = (long)N * H;

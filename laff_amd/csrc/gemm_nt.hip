@@ -1559,28 +1559,32 @@ static hipError_t launch_m(const GemmArgs& a, bool aligned, hipStream_t st) {
     return launch_t<MODE, 2, Cfg128>(a, st);
 }
 
-template <int STG>
-static hipError_t launch_grouped_t(GroupedGemmArgs& g, hipStream_t st) {
+// tile_start of a grouped launch in tiles of CF: each problem's first tile, and the total at [count]; returns the total, or 0 when
+// it is empty or does not fit a 1-D grid
+template <typename CF>
+static long group_tiles(GroupedGemmArgs& g) {
     long nb = 0;
     for (int i = 0; i < g.count; ++i) {
         g.tile_start[i] = (int)nb;
-        nb += (long)((g.p[i].nR + Cfg128::TR - 1) / Cfg128::TR) * ((g.p[i].nC + Cfg128::TC - 1) / Cfg128::TC);
+        nb += (long)((g.p[i].nR + CF::TR - 1) / CF::TR) * ((g.p[i].nC + CF::TC - 1) / CF::TC);
     }
-    if (nb <= 0 || nb > 0x7fffffffL) return hipErrorInvalidValue;
+    if (nb <= 0 || nb > 0x7fffffffL) return 0;
     g.tile_start[g.count] = (int)nb;
+    return nb;
+}
+
+template <int STG>
+static hipError_t launch_grouped_t(GroupedGemmArgs& g, hipStream_t st) {
+    const long nb = group_tiles<Cfg128>(g);
+    if (nb == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL((gemm_nt_grouped_kernel<GEMM_F32, STG, Cfg128>), dim3((unsigned)nb), dim3(Cfg128::THREADS), Cfg128::SMEM, st, g);
     return hipGetLastError();
 }
 
 template <typename CF>
 static hipError_t launch_grouped_f16_t(GroupedGemmArgs& g, hipStream_t st) {
-    long nb = 0;
-    for (int i = 0; i < g.count; ++i) {
-        g.tile_start[i] = (int)nb;
-        nb += (long)((g.p[i].nR + CF::TR - 1) / CF::TR) * ((g.p[i].nC + CF::TC - 1) / CF::TC);
-    }
-    if (nb <= 0 || nb > 0x7fffffffL) return hipErrorInvalidValue;
-    g.tile_start[g.count] = (int)nb;
+    const long nb = group_tiles<CF>(g);
+    if (nb == 0) return hipErrorInvalidValue;
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_grouped_kernel<GEMM_F16, 2, CF>, CF::SMEM); e != hipSuccess) return e;
     hipLaunchKernelGGL((gemm_nt_grouped_kernel<GEMM_F16, 2, CF>), dim3((unsigned)nb), dim3(CF::THREADS), CF::SMEM, st, g);
@@ -1588,13 +1592,8 @@ static hipError_t launch_grouped_f16_t(GroupedGemmArgs& g, hipStream_t st) {
 }
 
 static hipError_t launch_grouped_x3(GroupedGemmArgs& g, hipStream_t st) {
-    long nb = 0;
-    for (int i = 0; i < g.count; ++i) {
-        g.tile_start[i] = (int)nb;
-        nb += (long)((g.p[i].nR + CfgX3::TR - 1) / CfgX3::TR) * ((g.p[i].nC + CfgX3::TC - 1) / CfgX3::TC);
-    }
-    if (nb <= 0 || nb > 0x7fffffffL) return hipErrorInvalidValue;
-    g.tile_start[g.count] = (int)nb;
+    const long nb = group_tiles<CfgX3>(g);
+    if (nb == 0) return hipErrorInvalidValue;
     // tail split: the big tiles of a last round that would fill at most 3/4 of the CUs become 4 small tiles each
     const long rem = nb % g_num_cus;
     g.nbig = (int)nb;
@@ -1607,13 +1606,8 @@ static hipError_t launch_grouped_x3(GroupedGemmArgs& g, hipStream_t st) {
 }
 
 hipError_t launch_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, hipStream_t st) {
-    long nb = 0;
-    for (int i = 0; i < g.count; ++i) {
-        g.tile_start[i] = (int)nb;
-        nb += (long)((g.p[i].nR + CfgX3::TR - 1) / CfgX3::TR) * ((g.p[i].nC + CfgX3::TC - 1) / CfgX3::TC);
-    }
-    if (nb <= 0 || nb > 0x7fffffffL) return hipErrorInvalidValue;
-    g.tile_start[g.count] = (int)nb;
+    const long nb = group_tiles<CfgX3>(g);
+    if (nb == 0) return hipErrorInvalidValue;
     g.nbig = (int)nb;
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_x3_fused_grouped_kernel<GEMM_F16>, CfgX3::SMEM); e != hipSuccess) return e;

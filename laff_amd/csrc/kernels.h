@@ -201,7 +201,6 @@ hipError_t launch_frame_fuse(const FrameGroup& g, hipStream_t st);
 
 hipError_t launch_split_rows_grouped(int count, const float* const* X, const int* N, const int* K, const int* ldx, void* const* out,
                                      float* const* rscale, hipStream_t st);
-hipError_t launch_split_rows(const float* X, int N, int K, int ldx, int Kp, void* out, float* rscale, hipStream_t st);
 hipError_t launch_loss_normalize(const float* s, const float* im, int B, int H, int d, int dp, int Bp, float eps, float* XH,
                                  float* XHT, float* nrm, float* npr, hipStream_t st);
 hipError_t launch_margin_reduce(const float* S, float* dS, float* dST, float* loss_h, float* loss, int B, int Bp, int H,

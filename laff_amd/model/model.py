@@ -18,7 +18,6 @@ Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: featu
 returning {'text_features': tensor} can be plugged into `txt_net.encoder.<name>`.
 """
 import numpy as np
-import os
 
 import torch
 import torch.nn as nn
@@ -32,9 +31,6 @@ float16 = False
 #: arithmetic of the FC projections: 'fp32' (v_mfma_f32_32x32x2_f32, bit-for-bit an fp32 FMA chain) or 'fp16x3'
 #: (exact fp16 hi/lo operand split, 3 MFMA passes at the fp16 rate, ~2^-22 relative per product)
 FC_PRECISION = 'fp32'
-#: fp16x3 only: projections of 512-d inputs take the strip form (X stationary in registers: no row-scale pass, no split planes;
-#: laff_fc_act_bn_strip_grouped).  LAFF_FC_STRIP=0 keeps the tiled kernels.
-FC_STRIP = os.environ.get('LAFF_FC_STRIP', '1') != '0'
 
 
 def _row_chunks(pending, limit_bytes=1 << 31):
@@ -92,41 +88,29 @@ def coalesce_batches(batches):
 
 
 def run_fc(pending):
-    """Launch every queued FC projection as one grouped GEMM."""
-    if FC_PRECISION == 'fp16x3':
-        whole = pending
-        pending = _row_chunks(pending)
-        if len(pending) != len(whole):          # chunked: launch the pieces, hand back one output per original problem
-            outs = _run_fc_x3(pending)
-            by_id = {id(q): o for q, o in zip(pending, outs)}
-            return [q['out'] if q.get('out') is not None else by_id[id(q)] for q in whole]
-        return _run_fc_x3(pending)
-    if FC_PRECISION != 'fp32':
+    """Launch every queued FC projection; returns their outputs in the order of `pending`.  fp32: one grouped GEMM.  fp16x3: oversized
+    problems are cut into row chunks, then each problem goes to the strip form, the fused split or the materialised split: one launch
+    per form that has problems."""
+    if FC_PRECISION == 'fp32':
+        return ops.fc_act_bn_grouped(pending)
+    if FC_PRECISION != 'fp16x3':
         raise ValueError("FC_PRECISION must be 'fp32' or 'fp16x3'")
-    return ops.fc_act_bn_grouped(pending)
-
-
-def _run_fc_x3(pending):
-    if FC_STRIP:
-        strip = [q for q in pending if q.get('strip') is not None and ops.fc_strip_eligible(q['x'], q['weight'].shape[0])]
-        if strip:
-            rest = [q for q in pending if not any(q is s for s in strip)]
-            outs = {id(q): o for q, o in zip(strip, ops.fc_act_bn_strip_grouped([dict(q, strip=q['strip']()) for q in strip]))}
-            if rest:
-                outs.update({id(q): o for q, o in zip(rest, _run_fc_x3_tiled(rest))})
-            return [outs[id(q)] for q in pending]
-    return _run_fc_x3_tiled(pending)
-
-
-def _run_fc_x3_tiled(pending):
+    strip, tiled = [], []
+    for q in _row_chunks(pending):
+        # 512-d inputs take the strip form (X stationary in registers: no row-scale pass, no split planes)
+        (strip if q.get('strip') is not None and ops.fc_strip_eligible(q['x'], q['weight'].shape[0]) else tiled).append(q)
     # big launches with a narrow output take the fused split (inputs stay fp32 in HBM, split inside the GEMM: every column
     # tile of a row block repeats the conversion, 2x at D = 512 but 16x at D = 4096, where materialising the planes once is
     # cheaper: C5 33.2 ms fused vs 32.9 ms); small launches take the materialised split, whose 128x128 tiles fill the chip
-    tiles = sum(((q['x'].shape[0] + 255) // 256) * ((q['weight_split'].N + 255) // 256) for q in pending)
-    if (tiles >= 512 and all(q['weight_split'].N <= 1024 for q in pending) and
-            all(ops.fused_split_eligible(q['x'], q['weight_split']) for q in pending)):
-        return ops.fc_act_bn_fused_grouped(pending)
-    return ops.fc_act_bn_split_grouped(pending)
+    tiles = sum(((q['x'].shape[0] + 255) // 256) * ((q['weight_split'].N + 255) // 256) for q in tiled)
+    fused = (tiles >= 512 and all(q['weight_split'].N <= 1024 for q in tiled) and
+             all(ops.fused_split_eligible(q['x'], q['weight_split']) for q in tiled))
+    outs = {}
+    if strip:
+        outs.update(zip(map(id, strip), ops.fc_act_bn_strip_grouped([dict(q, strip=q['strip']()) for q in strip])))
+    if tiled:
+        outs.update(zip(map(id, tiled), (ops.fc_act_bn_fused_grouped if fused else ops.fc_act_bn_split_grouped)(tiled)))
+    return [outs[id(q)] if id(q) in outs else q['out'] for q in pending]      # a chunked problem: the chunks wrote its 'out'
 
 
 def _initialize_weights(m):
@@ -264,7 +248,7 @@ class TransformNet(nn.Module):
             prob = dict(x=x, weight=self.fc1.weight.detach(), weight_split=self.weight_split(),
                         bias=self.fc1.bias.detach() if self.fc1.bias is not None else None,
                         bn_scale=scale, bn_shift=shift, activation=self.activation_name)
-            if (FC_PRECISION == 'fp16x3' and FC_STRIP and extra_shift is None and
+            if (FC_PRECISION == 'fp16x3' and extra_shift is None and
                     self.fc1.in_features == 512 and self.out_features % 32 == 0):
                 prob['strip'] = self.strip_weights        # packed lazily: only if the launch takes the strip form
             if pending is None:

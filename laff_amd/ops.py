@@ -107,26 +107,33 @@ def attention_flags(with_ave=False, mul=False, l2norm_each_head=False, split_hea
             (ATT_JUST_AVERAGE if just_average else 0))
 
 
-def fc_act_bn(x, weight, bias=None, bn_scale=None, bn_shift=None, activation=None, out=None):
-    """Y = act(x @ weight.T + bias) * bn_scale + bn_shift   (TransformNet.forward, eval mode)."""
-    x, ldx = _rows(x, 'x')
-    w, ldw = _rows(weight, 'weight')
-    N, Dk = x.shape
-    D = w.shape[0]
-    if w.shape[1] != Dk:
-        raise ValueError('weight is %s but x has %d columns' % (tuple(w.shape), Dk))
-    for t, nm in ((bias, 'bias'), (bn_scale, 'bn_scale'), (bn_shift, 'bn_shift')):
+def _fc_vectors(q, D):
+    """An FC problem's bias / bn_scale / bn_shift as data pointers (None where absent), each checked to be a contiguous device
+    vector of D."""
+    ptrs = []
+    for nm in ('bias', 'bn_scale', 'bn_shift'):
+        t = q.get(nm)
         if t is not None:
             _dev(t, nm)
             if t.numel() != D or not t.is_contiguous():
                 raise ValueError('%s must be a contiguous vector of %d' % (nm, D))
+        ptrs.append(t.data_ptr() if t is not None else None)
+    return ptrs
+
+
+def _fc_epilogue(q, N, D, device):
+    """(_fc_vectors(q, D), out, ldy): out is q['out'] or a new (N, D) fp32 matrix on `device`."""
+    ptrs = _fc_vectors(q, D)
+    out = q.get('out')
     if out is None:
-        out = torch.empty((N, D), device=x.device, dtype=torch.float32)
-    y, ldy = _rows(out, 'out')
-    lib, h = _context(x.device)
-    _call('fc_act_bn', lib.laff_fc_act_bn, h, _ptr(x), N, Dk, ldx, _ptr(w), ldw, _ptr(bias), _ptr(bn_scale), _ptr(bn_shift), D,
-                             ACT[activation], _ptr(y), ldy)
-    return out
+        out = torch.empty((N, D), device=device, dtype=torch.float32)
+    return ptrs, out, _rows(out, 'out')[1]
+
+
+def fc_act_bn(x, weight, bias=None, bn_scale=None, bn_shift=None, activation=None, out=None):
+    """Y = act(x @ weight.T + bias) * bn_scale + bn_shift   (TransformNet.forward, eval mode)."""
+    return fc_act_bn_grouped([dict(x=x, weight=weight, bias=bias, bn_scale=bn_scale, bn_shift=bn_shift, activation=activation,
+                                   out=out)])[0]
 
 
 def fc_act_bn_grouped(problems):
@@ -135,7 +142,7 @@ def fc_act_bn_grouped(problems):
     if not problems:
         return []
     arr = (FcProblem * len(problems))()
-    outs, keep = [], []
+    outs = []
     for i, q in enumerate(problems):
         x, ldx = _rows(q['x'], 'x')
         w, ldw = _rows(q['weight'], 'weight')
@@ -143,22 +150,9 @@ def fc_act_bn_grouped(problems):
         D = w.shape[0]
         if w.shape[1] != Dk:
             raise ValueError('problem %d: weight is %s but x has %d columns' % (i, tuple(w.shape), Dk))
-        vecs = []
-        for nm in ('bias', 'bn_scale', 'bn_shift'):
-            t = q.get(nm)
-            if t is not None:
-                _dev(t, nm)
-                if t.numel() != D or not t.is_contiguous():
-                    raise ValueError('%s must be a contiguous vector of %d' % (nm, D))
-            vecs.append(t)
-        out = q.get('out')
-        if out is None:
-            out = torch.empty((N, D), device=x.device, dtype=torch.float32)
-        y, ldy = _rows(out, 'out')
-        arr[i] = FcProblem(x.data_ptr(), N, Dk, ldx, w.data_ptr(), ldw, *[t.data_ptr() if t is not None else None for t in vecs],
-                           D, ACT[q.get('activation')], y.data_ptr(), ldy)
+        vecs, out, ldy = _fc_epilogue(q, N, D, x.device)
+        arr[i] = FcProblem(x.data_ptr(), N, Dk, ldx, w.data_ptr(), ldw, *vecs, D, ACT[q.get('activation')], out.data_ptr(), ldy)
         outs.append(out)
-        keep.append((x, w, vecs))
     lib, h = _context(problems[0]['x'].device)
     _call('fc_act_bn', lib.laff_fc_act_bn_grouped, h, arr, len(problems))
     return outs
@@ -337,15 +331,7 @@ class SplitOperand:
 
 
 def split_rows(x):
-    x, ldx = _rows(x, 'x')
-    N, K = x.shape
-    lib, h = _context(x.device)
-    nbytes = C.c_size_t()
-    check(lib.laff_split_rows_bytes(N, K, C.byref(nbytes)))
-    buf = torch.empty((max(nbytes.value, 16),), device=x.device, dtype=torch.uint8)
-    rscale = torch.empty((max(N, 1),), device=x.device, dtype=torch.float32)
-    _call('split_rows', lib.laff_split_rows, h, _ptr(x), N, K, ldx, _ptr(buf), _ptr(rscale))
-    return SplitOperand(buf, rscale, N, K)
+    return split_rows_grouped([x])[0]
 
 
 def split_rows_grouped(xs):
@@ -374,7 +360,7 @@ def fc_act_bn_split_grouped(problems):
     if not problems:
         return []
     arr = (FcSplitProblem * len(problems))()
-    outs, keep = [], []
+    outs = []
     dev = problems[0]['weight_split'].buf.device
     todo = [i for i, q in enumerate(problems) if not isinstance(q['x'], SplitOperand)]
     split = dict(zip(todo, split_rows_grouped([problems[i]['x'] for i in todo])))      # all inputs in ONE launch
@@ -384,23 +370,10 @@ def fc_act_bn_split_grouped(problems):
         if xs.K != ws.K:
             raise ValueError('problem %d: x has %d columns, weight %d' % (i, xs.K, ws.K))
         N, D = xs.N, ws.N
-        vecs = []
-        for nm in ('bias', 'bn_scale', 'bn_shift'):
-            t = q.get(nm)
-            if t is not None:
-                _dev(t, nm)
-                if t.numel() != D or not t.is_contiguous():
-                    raise ValueError('%s must be a contiguous vector of %d' % (nm, D))
-            vecs.append(t)
-        out = q.get('out')
-        if out is None:
-            out = torch.empty((N, D), device=dev, dtype=torch.float32)
-        y, ldy = _rows(out, 'out')
-        arr[i] = FcSplitProblem(xs.buf.data_ptr(), xs.rscale.data_ptr(), N, xs.K, ws.buf.data_ptr(), ws.rscale.data_ptr(),
-                                *[t.data_ptr() if t is not None else None for t in vecs], D, ACT[q.get('activation')],
-                                y.data_ptr(), ldy)
+        vecs, out, ldy = _fc_epilogue(q, N, D, dev)
+        arr[i] = FcSplitProblem(xs.buf.data_ptr(), xs.rscale.data_ptr(), N, xs.K, ws.buf.data_ptr(), ws.rscale.data_ptr(), *vecs, D,
+                                ACT[q.get('activation')], out.data_ptr(), ldy)
         outs.append(out)
-        keep.append((xs, ws, vecs))
     lib, h = _context(dev)
     _call('fc_act_bn', lib.laff_fc_act_bn_split_grouped, h, arr, len(problems))
     return outs
@@ -424,7 +397,7 @@ def fc_act_bn_fused_grouped(problems):
     lib, h = _context(dev)
     X, N, K, LD, R = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_void_p * n)()
     arr = (FcFusedProblem * n)()
-    outs, keep = [], []
+    outs = []
     total = sum(q['x'].shape[0] for q in problems)
     scales = torch.empty((max(total, 1),), device=dev, dtype=torch.float32)      # one buffer, one slice per problem
     at = 0
@@ -437,23 +410,10 @@ def fc_act_bn_fused_grouped(problems):
         at += x.shape[0]
         X[i], N[i], K[i], LD[i], R[i] = x.data_ptr(), x.shape[0], x.shape[1], ldx, rs.data_ptr()
         D = ws.N
-        vecs = []
-        for nm in ('bias', 'bn_scale', 'bn_shift'):
-            t = q.get(nm)
-            if t is not None:
-                _dev(t, nm)
-                if t.numel() != D or not t.is_contiguous():
-                    raise ValueError('%s must be a contiguous vector of %d' % (nm, D))
-            vecs.append(t)
-        out = q.get('out')
-        if out is None:
-            out = torch.empty((x.shape[0], D), device=dev, dtype=torch.float32)
-        y, ldy = _rows(out, 'out')
+        vecs, out, ldy = _fc_epilogue(q, x.shape[0], D, dev)
         arr[i] = FcFusedProblem(x.data_ptr(), ldx, rs.data_ptr(), x.shape[0], x.shape[1], ws.buf.data_ptr(), ws.rscale.data_ptr(),
-                                *[t.data_ptr() if t is not None else None for t in vecs], D, ACT[q.get('activation')],
-                                y.data_ptr(), ldy)
+                                *vecs, D, ACT[q.get('activation')], out.data_ptr(), ldy)
         outs.append(out)
-        keep.append((x, ws, vecs))
     _call('row_scales', lib.laff_row_scales_grouped, h, n, X, N, K, LD, R)
     _call('fc_act_bn', lib.laff_fc_act_bn_fused_grouped, h, arr, n)
     return outs
@@ -474,14 +434,9 @@ def fc_strip_pack(weight, bias=None, bn_scale=None, bn_shift=None, activation=No
     lib, h = _context(w.device)
     nbytes = C.c_size_t()
     check(lib.laff_fc_strip_pack_bytes(D, K, C.byref(nbytes)))
-    for t, nm in ((bias, 'bias'), (bn_scale, 'bn_scale'), (bn_shift, 'bn_shift')):
-        if t is not None:
-            _dev(t, nm)
-            if t.numel() != D or not t.is_contiguous():
-                raise ValueError('%s must be a contiguous vector of %d' % (nm, D))
+    vecs = _fc_vectors(dict(bias=bias, bn_scale=bn_scale, bn_shift=bn_shift), D)
     img = torch.empty((nbytes.value,), device=w.device, dtype=torch.uint8)
-    _call('fc_strip_pack', lib.laff_fc_strip_pack, h, _ptr(w), ldw, _ptr(bias), _ptr(bn_scale), _ptr(bn_shift), D, K, ACT[activation],
-          _ptr(img))
+    _call('fc_strip_pack', lib.laff_fc_strip_pack, h, _ptr(w), ldw, *vecs, D, K, ACT[activation], _ptr(img))
     return StripWeights(img, D, K, ACT[activation])
 
 
@@ -499,7 +454,7 @@ def fc_act_bn_strip_grouped(problems):
         return []
     n = len(problems)
     arr = (FcStripProblem * n)()
-    outs, keep = [], []
+    outs = []
     dev = problems[0]['strip'].img.device
     for i, q in enumerate(problems):
         x, ldx = _rows(q['x'], 'x')
@@ -512,7 +467,6 @@ def fc_act_bn_strip_grouped(problems):
         y, ldy = _rows(out, 'out')
         arr[i] = FcStripProblem(x.data_ptr(), max(ldx, 512), x.shape[0], sw.img.data_ptr(), sw.D, sw.act, y.data_ptr(), ldy)
         outs.append(out)
-        keep.append((x, sw))
     lib, h = _context(dev)
     _call('fc_act_bn', lib.laff_fc_act_bn_strip_grouped, h, arr, n)
     return outs

@@ -148,9 +148,9 @@ def test_fc_strip_refuses_what_it_cannot_take():
         ops.fc_act_bn_strip_grouped([dict(x=torch.zeros((8, 512)), strip=sw)])               # CPU tensor: no CPU path
 
 
-def test_towers_take_the_strip_form_and_keep_the_tolerance(monkeypatch):
+def test_towers_take_the_strip_form_and_match_the_tiled_route(monkeypatch):
     """'LAFF' towers with FC_PRECISION = 'fp16x3': the 512-d projections go through laff_fc_act_bn_strip_grouped (counted), and the
-    embeddings stay inside the tolerance of the fp32 path; LAFF_FC_STRIP=0's tiled route gives the same embeddings."""
+    embeddings stay inside the tolerance of the fp32 path; the tiled route (no input strip-eligible) gives the same embeddings."""
     from laff_amd import ops, retrieval, synth
     import laff_amd.model.model as M
     devc = torch.device('cuda')
@@ -165,7 +165,7 @@ def test_towers_take_the_strip_form_and_keep_the_tolerance(monkeypatch):
             M.FC_PRECISION = 'fp16x3'
             vs, ts = retrieval.embed(model, vis, txt)
             assert calls and sum(calls) == 8
-            monkeypatch.setattr(M, 'FC_STRIP', False)
+            monkeypatch.setattr(ops, 'fc_strip_eligible', lambda x, D: False)
             vt, tt = retrieval.embed(model, vis, txt)
             assert sum(calls) == 8
     finally:
