@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 24
+#define LAFF_ABI_VERSION 25
 
 enum {
     LAFF_OK = 0,
@@ -348,6 +348,21 @@ int laff_sim_gemm(laff_ctx* ctx, const void* T, const void* V, int Nt, int Nv, i
                   int precision, float* S, int lds, const int* gt_col, int col0, const float* s_gt,
                   int* count);
 
+/* The kernel ("route") that laff_sim_gemm / laff_sim_gemm_banded run for a problem, chosen from the shape, the K bytes, the
+ * precision, the epilogue and this process's LAFF_STRIP mode and CU count (read when a ctx is created).  Launches nothing.
+ * lds: score row pitch in floats, 0 = no scores (a non-zero lds stands for a 16-byte aligned S); count_mode: 0 = none,
+ * 1 = the approximate fused count (gt_col + s_gt), 2 = the banded count (pair_cap slots).  *route = one of LAFF_ROUTE_*. */
+enum {
+    LAFF_ROUTE_TILED128_REG = 0,     /* 128 x 128 tiles, operands staged through registers: K bytes % 16 != 0      */
+    LAFF_ROUTE_TILED128_TAIL = 1,    /* 128 x 128 tiles, LDS-DMA with a K tail: K bytes % 128 != 0, or an operand span >= 4 GiB */
+    LAFF_ROUTE_TILED128 = 2,         /* 128 x 128 tiles, fast LDS-DMA: fp32, and 16-bit problems of < 512 tiles of 256 x 256 */
+    LAFF_ROUTE_TILED256 = 3,         /* 256 x 256 tiles, 8 waves: 16-bit, >= 512 big tiles                        */
+    LAFF_ROUTE_TILED256_LONGK = 4,   /* 256 x 256 tiles, 4 waves: 16-bit one plane, >= 4096 big tiles, K bytes >= 8192 */
+    LAFF_ROUTE_X3 = 5,               /* the hi/lo split tile: FP16X3 / BF16X3, >= 512 big tiles                   */
+    LAFF_ROUTE_STRIP = 6             /* the K = 512 strip kernel (sim_strip.hip)                                   */
+};
+int laff_sim_gemm_route(laff_ctx* ctx, int Nt, int Nv, int K, int precision, int lds, int count_mode, unsigned pair_cap, int* route);
+
 /* Ground-truth pre-pass for the fused count: s_gt[t] = scale * <T[t], V[gt_col[t]-col0]> on the packed operands
  * (fp32 accumulation of the same 16-bit products), -inf when that column is outside [0,Nv).  When laff_sim_gemm is
  * then called with gt_col/s_gt it writes exactly this value at S[t, gt] so counts and S stay consistent.
@@ -407,7 +422,9 @@ int laff_rank_export_pairs(laff_ctx* ctx, const double* s_gt64, int* count, floa
  *                          |S - s_gt| <= band are listed in `pairs` (uint32: header {n_extra, overflow, A, w} then pair_cap x
  *                          {row, col}, col shard-local: A slots in per-wavefront segments of w slots -- valid pairs first, unused
  *                          slots have row 0xffffffff -- then n_extra pairs appended by wavefronts whose segment was too small);
- *                          S (nullable) receives (float)s_gt64 at the ground-truth entry.
+ *                          S (nullable) receives (float)s_gt64 at the ground-truth entry -- from the tiled kernels; the K = 512
+ *                          strip kernel (LAFF_ROUTE_STRIP) stores its own score there and lists the entry, and laff_rank_resolve
+ *                          writes (float)s_gt64 over it.
  *   laff_rank_resolve      re-scores the listed pairs: count[row] += exact > s_gt64[row]; S (nullable) takes the fp32 value of the
  *                          exact score (one ulp above (float)s_gt64 where rounding would hide a strict inequality) so that ranks
  *                          recounted from S equal count + 1.  pair_cap is used in whole groups of four slots (rounded down, >= 4).

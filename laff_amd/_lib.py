@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class Plane(C.Structure):
@@ -98,6 +98,7 @@ SIGNATURES = {
     'laff_packed_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_pack_rows': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
     'laff_sim_gemm': (C.c_int, [_P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P]),
+    'laff_sim_gemm_route': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, C.POINTER(_I)]),
     'laff_row_dot_gt': (C.c_int, [_P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P]),
     'laff_rank_prepare': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P]),
     'laff_match_ids': (C.c_int, [C.c_char_p, C.c_size_t, _I, C.c_char_p, C.c_size_t, _I, _P]),

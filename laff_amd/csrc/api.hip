@@ -928,6 +928,41 @@ int laff_pack_rows(laff_ctx* ctx, const float* E, int N, int H, int d, int lde, 
     return LAFF_OK;
 }
 
+// the GemmArgs of a similarity GEMM on laff_pack_rows operands (what laff_sim_gemm launches and laff_sim_gemm_route asks about)
+static laff::GemmArgs sim_gemm_args(const void* T, const void* V, int Nt, int Nv, int K, float scale, int precision, float* S, int lds,
+                                    const int* gt_col, int col0, const float* s_gt, int* count, const double* s_gt64, const float* band_t,
+                                    const float* band_v, unsigned* pairs, unsigned pair_cap) {
+    laff::GemmArgs a{};
+    a.R = T; a.C = V; a.nR = Nt; a.nC = Nv; a.K = K; a.ldR = K; a.ldC = K;
+    const long planeT = (long)Nt * K * 2, planeV = (long)Nv * K * 2;
+    if (is_x3(precision)) {
+        // virtual K concatenation: lo*hi, hi*lo first (small terms), hi*hi last
+        a.nseg = 3;
+        a.segR[0] = planeT; a.segC[0] = 0;
+        a.segR[1] = 0;      a.segC[1] = planeV;
+        a.segR[2] = 0;      a.segC[2] = 0;
+    } else {
+        a.nseg = 1; a.segR[0] = a.segC[0] = 0;
+    }
+    a.out = S; a.ldo = lds; a.scale = scale;
+    a.gt_col = gt_col; a.col0 = col0; a.s_gt = s_gt; a.count = gt_col ? count : nullptr;
+    a.s_gt64 = s_gt64; a.band_r = band_t; a.band_c = band_v; a.pairs = pairs; a.pair_cap = pair_cap;
+#ifdef LAFF_GEMM_TRACE
+    if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
+#endif
+    return a;
+}
+
+static int sim_gemm_mode(int precision) {
+    if (precision == LAFF_PREC_FP16 || precision == LAFF_PREC_FP16X3) return laff::GEMM_F16;
+    if (precision == LAFF_PREC_BF16 || precision == LAFF_PREC_BF16X3) return laff::GEMM_BF16;
+    return laff::GEMM_F32;
+}
+
+// rows of K elements: 16-byte aligned rows take the direct-to-LDS paths (K bytes a multiple of 128: the fast one),
+// anything else is staged through registers with element-wise K bounds
+static bool sim_gemm_aligned(int K, int precision) { return ((long)K * (precision == LAFF_PREC_FP32 ? 4 : 2)) % 16 == 0; }
+
 static int sim_gemm_impl(laff_ctx* ctx, const char* who, const void* T, const void* V, int Nt, int Nv, int K, float scale,
                          int precision, float* S, int lds, const int* gt_col, int col0, const float* s_gt, int* count,
                          const double* s_gt64, const float* band_t, const float* band_v, unsigned* pairs, unsigned pair_cap) {
@@ -948,31 +983,10 @@ static int sim_gemm_impl(laff_ctx* ctx, const char* who, const void* T, const vo
     if (!aligned16(T) || !aligned16(V)) return fail(LAFF_E_ALIGN, "%s: operands must be 16-byte aligned", who);
     if (s_gt64 && (!aligned16(gt_col) || !aligned16(s_gt64) || !aligned16(band_t) || !aligned16(band_v)))
         return fail(LAFF_E_ALIGN, "%s: gt_col, s_gt64, band_t and band_v must be 16-byte aligned (fetched in 16-byte groups)", who);
-    laff::GemmArgs a{};
-    a.R = T; a.C = V; a.nR = Nt; a.nC = Nv; a.K = K; a.ldR = K; a.ldC = K;
-    const long planeT = (long)Nt * K * 2, planeV = (long)Nv * K * 2;
-    if (is_x3(precision)) {
-        // virtual K concatenation: lo*hi, hi*lo first (small terms), hi*hi last
-        a.nseg = 3;
-        a.segR[0] = planeT; a.segC[0] = 0;
-        a.segR[1] = 0;      a.segC[1] = planeV;
-        a.segR[2] = 0;      a.segC[2] = 0;
-    } else {
-        a.nseg = 1; a.segR[0] = a.segC[0] = 0;
-    }
-    a.out = S; a.ldo = lds; a.scale = scale;
-    a.gt_col = gt_col; a.col0 = col0; a.s_gt = s_gt; a.count = gt_col ? count : nullptr;
-    a.s_gt64 = s_gt64; a.band_r = band_t; a.band_c = band_v; a.pairs = pairs; a.pair_cap = pair_cap;
-#ifdef LAFF_GEMM_TRACE
-    if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-    int mode = laff::GEMM_F32;
-    if (precision == LAFF_PREC_FP16 || precision == LAFF_PREC_FP16X3) mode = laff::GEMM_F16;
-    if (precision == LAFF_PREC_BF16 || precision == LAFF_PREC_BF16X3) mode = laff::GEMM_BF16;
+    const laff::GemmArgs a = sim_gemm_args(T, V, Nt, Nv, K, scale, precision, S, lds, gt_col, col0, s_gt, count, s_gt64, band_t, band_v,
+                                           pairs, pair_cap);
     DeviceGuard g(ctx->device);
-    // rows of K elements: 16-byte aligned rows take the direct-to-LDS paths (K bytes a multiple of 128: the fast one),
-    // anything else is staged through registers with element-wise K bounds
-    HIP_TRY(laff::launch_gemm_nt(a, mode, ((long)K * esz) % 16 == 0, ctx->stream));
+    HIP_TRY(laff::launch_gemm_nt(a, sim_gemm_mode(precision), sim_gemm_aligned(K, precision), ctx->stream));
     return LAFF_OK;
 }
 
@@ -989,6 +1003,28 @@ int laff_sim_gemm_banded(laff_ctx* ctx, const void* T, const void* V, int Nt, in
     if (!gt_col || !s_gt64) return fail(LAFF_E_ARG, "laff_sim_gemm_banded: null gt_col / s_gt64");
     return sim_gemm_impl(ctx, "laff_sim_gemm_banded", T, V, Nt, Nv, K, scale, precision, S, lds, gt_col, col0, nullptr, count, s_gt64,
                          band_t, band_v, pairs, pair_cap);
+}
+
+int laff_sim_gemm_route(laff_ctx* ctx, int Nt, int Nv, int K, int precision, int lds, int count_mode, unsigned pair_cap, int* route) {
+    CHECK_CTX(ctx);
+    if (!route) return fail(LAFF_E_ARG, "laff_sim_gemm_route: null route");
+    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_sim_gemm_route: bad precision %d", precision);
+    if (count_mode < 0 || count_mode > 2) return fail(LAFF_E_ARG, "laff_sim_gemm_route: bad count_mode %d", count_mode);
+    const int esz = precision == LAFF_PREC_FP32 ? 4 : 2;
+    if (Nt < 1 || Nv < 1 || K < 1 || ((long)K * esz) % 4 || (lds && lds < Nv) || (!lds && !count_mode))
+        return fail(LAFF_E_SHAPE, "laff_sim_gemm_route: no launch for Nt=%d Nv=%d K=%d lds=%d count_mode=%d", Nt, Nv, K, lds, count_mode);
+    pair_cap &= ~3u;
+    if (count_mode == 2 && pair_cap < 4) return fail(LAFF_E_ARG, "laff_sim_gemm_route: the banded count needs a pair list of >= 4 slots");
+    // stand-ins for the caller's buffers: the choice looks at which are present and at the alignment of S, never at what they hold
+    alignas(16) static char stand_in[16];
+    void* p = stand_in;
+    const laff::GemmArgs a = sim_gemm_args(p, p, Nt, Nv, K, 1.0f, precision, lds ? (float*)p : nullptr, lds, count_mode ? (const int*)p : nullptr, 0,
+                                           count_mode == 1 ? (const float*)p : nullptr, count_mode ? (int*)p : nullptr,
+                                           count_mode == 2 ? (const double*)p : nullptr, count_mode == 2 ? (const float*)p : nullptr,
+                                           count_mode == 2 ? (const float*)p : nullptr, count_mode == 2 ? (unsigned*)p : nullptr,
+                                           count_mode == 2 ? pair_cap : 0);
+    *route = laff::gemm_route(a, sim_gemm_mode(precision), sim_gemm_aligned(K, precision));
+    return LAFF_OK;
 }
 
 int laff_rank_prepare(laff_ctx* ctx, const float* Et, const float* Ev, const void* T, const void* V, int Nt, int Nv, int H, int d,

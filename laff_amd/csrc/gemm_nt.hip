@@ -1537,26 +1537,43 @@ static hipError_t launch_x3(const GemmArgs& a, hipStream_t st);
 
 int g_num_cus = 256;       // set from the device properties when a ctx is created
 
-template <int MODE>
-static hipError_t launch_m(const GemmArgs& a, bool aligned, hipStream_t st) {
-    const int stg = staging_kind(a, ModeTraits<MODE>::ESZ, aligned);
-    if (stg == 0) return launch_t<MODE, 0, Cfg128>(a, st);
-    if (stg == 1) return launch_t<MODE, 1, Cfg128>(a, st);
-    if constexpr (MODE != GEMM_F32) {
+int gemm_route(const GemmArgs& a, int mode, bool aligned) {
+    if (sim_strip_eligible(a, mode, aligned)) return LAFF_ROUTE_STRIP;     // K = 512 similarity: the strip kernel
+    const int stg = staging_kind(a, mode == GEMM_F32 ? 4 : 2, aligned);
+    if (stg == 0) return LAFF_ROUTE_TILED128_REG;
+    if (stg == 1) return LAFF_ROUTE_TILED128_TAIL;
+    if (mode != GEMM_F32) {
         // big tiles when there are enough of them to fill 256 CUs a few times over
         const long tiles256 = (long)((a.nR + 255) / 256) * ((a.nC + 255) / 256);
         const bool big = tiles256 >= 512;
-        if (big && a.nseg == 3) return launch_x3<MODE>(a, st);
+        if (big && a.nseg == 3) return LAFF_ROUTE_X3;
         // long K, many tiles: 4 waves of 128x128 -- 1/3 fewer LDS fragment reads per MFMA and a K loop scheduled for a lone wave per
         // SIMD: 2,538 against 2,828 cycles per K-step at K = 4096 (tools/debug/trace_longk.py).  Its prologue and epilogue are longer
         // (4 waves do the work of 8; the banded epilogue reads its accumulators out of the AGPR half), so it pays where the K loop
         // dominates (tools/debug/time_shape.py, banded + S): 100k x 30k x 4096 bf16 23.5 -> 22.3 ms, count-only 21.7 -> 20.0 ms;
         // 59,800 x 2,990 x 4096 1.54 -> 1.59 ms (not taken: 2,808 tiles); 16384^2 x 2048 1.06 -> 1.07 ms (not taken).
-        const bool lone = a.nseg == 1 && tiles256 >= 4096 && (long long)a.K * ModeTraits<MODE>::ESZ >= 8192;
-        if (lone) return launch_t<MODE, 2, Cfg256L>(a, st);
-        if (big) return launch_t<MODE, 2, Cfg256>(a, st);
+        const bool lone = a.nseg == 1 && tiles256 >= 4096 && (long long)a.K * 2 >= 8192;
+        if (lone) return LAFF_ROUTE_TILED256_LONGK;
+        if (big) return LAFF_ROUTE_TILED256;
     }
-    return launch_t<MODE, 2, Cfg128>(a, st);
+    return LAFF_ROUTE_TILED128;
+}
+
+template <int MODE>
+static hipError_t launch_m(const GemmArgs& a, int route, hipStream_t st) {
+    switch (route) {
+        case LAFF_ROUTE_TILED128_REG: return launch_t<MODE, 0, Cfg128>(a, st);
+        case LAFF_ROUTE_TILED128_TAIL: return launch_t<MODE, 1, Cfg128>(a, st);
+        case LAFF_ROUTE_TILED128: return launch_t<MODE, 2, Cfg128>(a, st);
+    }
+    if constexpr (MODE != GEMM_F32) {
+        switch (route) {
+            case LAFF_ROUTE_X3: return launch_x3<MODE>(a, st);
+            case LAFF_ROUTE_TILED256_LONGK: return launch_t<MODE, 2, Cfg256L>(a, st);
+            case LAFF_ROUTE_TILED256: return launch_t<MODE, 2, Cfg256>(a, st);
+        }
+    }
+    return hipErrorInvalidValue;
 }
 
 // tile_start of a grouped launch in tiles of CF: each problem's first tile, and the total at [count]; returns the total, or 0 when
@@ -1646,11 +1663,12 @@ hipError_t launch_gemm_nt_grouped_f32(GroupedGemmArgs& g, int stg, hipStream_t s
 }
 
 hipError_t launch_gemm_nt(const GemmArgs& a, int mode, bool aligned, hipStream_t st) {
-    if (sim_strip_eligible(a, mode, aligned)) return launch_sim_strip(a, mode, st);     // K = 512 similarity: the strip kernel
+    const int route = gemm_route(a, mode, aligned);
+    if (route == LAFF_ROUTE_STRIP) return launch_sim_strip(a, mode, st);
     switch (mode) {
-        case GEMM_F32: return launch_m<GEMM_F32>(a, aligned, st);
-        case GEMM_F16: return launch_m<GEMM_F16>(a, aligned, st);
-        case GEMM_BF16: return launch_m<GEMM_BF16>(a, aligned, st);
+        case GEMM_F32: return launch_m<GEMM_F32>(a, route, st);
+        case GEMM_F16: return launch_m<GEMM_F16>(a, route, st);
+        case GEMM_BF16: return launch_m<GEMM_BF16>(a, route, st);
     }
     return hipErrorInvalidValue;
 }

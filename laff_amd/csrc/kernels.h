@@ -126,6 +126,8 @@ hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, cons
                                 void* img, hipStream_t st);
 hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st);
 
+// the kernel launch_gemm_nt runs for these arguments (LAFF_ROUTE_*, include/laff_hip.h); launches nothing
+int gemm_route(const GemmArgs& a, int mode, bool aligned);
 hipError_t launch_gemm_nt(const GemmArgs& a, int mode, bool aligned, hipStream_t st);
 hipError_t launch_gemm_nt_grouped_f32(GroupedGemmArgs& g, int staging, hipStream_t st);
 hipError_t launch_gemm_nt_grouped_f16(GroupedGemmArgs& g, hipStream_t st);

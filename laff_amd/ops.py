@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
 
-__all__ = ['clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -666,6 +666,26 @@ def sim_gemm(T, V, heads=1, out=None, want_scores=True, gt_col=None, s_gt=None, 
     _call('sim_gemm', lib.laff_sim_gemm, h, _ptr(T.buf), _ptr(V.buf), T.N, V.N, T.K, scale, PREC[T.precision], _ptr(S), lds,
                             _ptr(gt_col), col0, _ptr(s_gt), _ptr(count))
     return S
+
+
+#: the kernels laff_sim_gemm / laff_sim_gemm_banded choose between (LAFF_ROUTE_* of include/laff_hip.h, in that order)
+SIM_ROUTES = ('TILED128_REG', 'TILED128_TAIL', 'TILED128', 'TILED256', 'TILED256_LONGK', 'X3', 'STRIP')
+_COUNT_MODES = {None: 0, 'approx': 1, 'banded': 2}
+
+
+def sim_gemm_route(Nt, Nv, K, precision, lds=None, count=None, pair_cap=None, device=None):
+    """Name of the kernel (SIM_ROUTES) that sim_gemm (count None / 'approx') or sim_gemm_banded (count 'banded') runs for an Nt x Nv
+    problem of K packed elements, with scores of row pitch lds (None: count only) in a 16-byte aligned buffer; launches nothing.
+    Reads the LAFF_STRIP mode and CU count of the device's context (laff_sim_gemm_route)."""
+    if count not in _COUNT_MODES:
+        raise ValueError('count must be None, \'approx\' or \'banded\', got %r' % (count,))
+    if count == 'banded' and pair_cap is None:
+        pair_cap = default_pair_cap(Nt)
+    lib, h = _context(torch.device(device) if device is not None else torch.device('cuda'))
+    route = C.c_int(-1)
+    check(lib.laff_sim_gemm_route(h, int(Nt), int(Nv), int(K), PREC[precision], int(lds or 0), _COUNT_MODES[count], int(pair_cap or 0),
+                                  C.byref(route)))
+    return SIM_ROUTES[route.value]
 
 
 def row_dot_gt(T, V, gt_col, heads=1, col0=0, zero_count=None):

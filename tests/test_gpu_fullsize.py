@@ -57,6 +57,19 @@ def test_c4_40k_x_10k_properties():
     assert 5.0 < res.metrics[0] < 95.0          # the synthetic task is neither trivial nor chance
 
 
+def _fp64_max_err(S, E_t, E_v):
+    """max |S - float64 cosine| of fp32 embeddings (N, H, d) (l2norm per head as loss.l2norm, mean over heads), in row blocks."""
+    Nt, H = E_t.shape[0], E_t.shape[1]
+    v3 = E_v.double()
+    v3 = v3 / (v3.pow(2).sum(2, keepdim=True).sqrt() + (1e-13 + 1e-14))
+    err = 0.0
+    for a in range(0, Nt, 4096):
+        tb = E_t[a:a + 4096].double()
+        tb = tb / (tb.pow(2).sum(2, keepdim=True).sqrt() + (1e-13 + 1e-14))
+        err = max(err, float((S[a:a + 4096].double() - torch.einsum('thd,vhd->tv', tb, v3) / H).abs().max()))
+    return err
+
+
 def _fp64_ranks(E_t, E_v, gt, rows=None):
     """ranks of the float64 cosine scores of fp32 embeddings (N, H, d), computed with torch on the device in row blocks."""
     Nt, H = E_t.shape[0], E_t.shape[1]
@@ -89,6 +102,8 @@ def test_c4_precisions_agree_on_ranks():
     assert torch.equal(a.txt_emb, b.txt_emb)                  # same towers
     assert torch.equal(b.ranks, want) and a.metrics == b.metrics
     assert float((a.S - b.S).abs().max()) <= 1e-4
+    # the split pass predict() runs, at its own contract: every score within 2e-6 of the float64 cosine of its embeddings
+    assert _fp64_max_err(b.S, b.txt_emb, b.vis_emb) <= 2e-6
     c, _ = _c4('bf16')
     assert torch.equal(c.ranks, want)
     # FC on the fp32 MFMA instead of the split fp16 pipe: embeddings move by ~1e-6, so a rank can only move where two videos
@@ -444,7 +459,9 @@ def _oracle_sampled_parity(workload, precision, step_t, frames=False):
     S32 = O.txt2vis_matrix(te, ve)
     if res.S is not None:
         S_rows = res.S[rs]
-    else:       # C5: the 12 GB matrix is not materialised; the sampled rows through the same GEMM
+    else:       # C5: the 12 GB matrix is not materialised; the sampled rows recomputed by a GEMM of len(rows) rows, which takes
+                # another kernel than the full-size pass (TILED128, not TILED256_LONGK): test_gpu_sim_routes.py checks every route's
+                # scores element by element
         S_rows = ops.sim_gemm(ops.pack_rows(res.txt_emb[rs].contiguous(), True, 1e-13, precision),
                               ops.pack_rows(res.vis_emb, True, 1e-13, precision), heads=H)
     assert np.abs(S_rows.cpu().numpy() - S32).max() <= (2e-3 if precision == 'bf16' else 1e-4)
