@@ -472,13 +472,26 @@ def fc_act_bn_strip_grouped(problems):
     return outs
 
 
-def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=None, l2norm_planes=False, rank_side=None):
+def _out_buffer(t, shape, device, name):
+    """A caller-owned fp32 output of exactly `shape` (contiguous, on `device`), or a fresh one."""
+    if t is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    _dev(t, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError('%s must be a contiguous fp32 %s tensor on %s, got %s' % (name, tuple(shape), device, tuple(t.shape)))
+    return t
+
+
+def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=None, l2norm_planes=False, rank_side=None, out=None,
+         weights_out=None, packed_out=None):
     """planes: list of (src[N, ld-view], tile, scale, shift[, act]) -- act ('tanh' | 'relu' | 'sigmoid' | None) is applied to src
     before the affine (a projection that left its activation + BatchNorm to this kernel).  Returns E (N, H, d) [and softmax
     weights (N, H, L)].
     packed_precision ('fp16' | 'bf16'): also emit the similarity operand in the same launch; returned last.
     l2norm_planes: every plane row is first divided by its l2 norm over all H*d columns (`l2norm(local_embs, dim=2)` of the
-    expert-embedding branch, model/model.py:1866-1873): one extra launch computes the norms (laff_plane_row_norms)."""
+    expert-embedding branch, model/model.py:1866-1873): one extra launch computes the norms (laff_plane_row_norms).
+    out / weights_out / packed_out: caller-owned buffers the launch writes instead of fresh ones -- contiguous fp32 (N, H, d) /
+    (N, H, L), and uint8 of at least N * H * d * 2 bytes for the operand."""
     L = len(planes)
     arr = (Plane * L)()
     first = planes[0]
@@ -518,8 +531,8 @@ def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=N
         arr[i] = Plane(src.data_ptr(), ld, 1 if tile else 0, sp, tp, ACT[act], None, None, None, None, 0, 0, None)
         keep.append((src, scale, shift))
     dev = (first[5][1] if (len(first) > 5 and first[5] is not None) else first[0]).device
-    E = torch.empty((N, H, d), device=dev, dtype=torch.float32)
-    aw = torch.empty((N, H, L), device=dev, dtype=torch.float32) if return_weights else None
+    E = _out_buffer(out, (N, H, d), dev, 'out')
+    aw = _out_buffer(weights_out, (N, H, L), dev, 'weights_out') if return_weights else None
     for t, nm in ((w, 'w'), (b, 'b'), (gw, 'gw')):
         if t is not None:
             _dev(t, nm)
@@ -533,7 +546,12 @@ def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=N
     packed = None
     if packed_precision is not None:
         prescale = default_prescale(packed_precision)
-        buf = torch.empty((max(N * H * d * 2, 16),), device=dev, dtype=torch.uint8)
+        if packed_out is None:
+            buf = torch.empty((max(N * H * d * 2, 16),), device=dev, dtype=torch.uint8)
+        else:
+            buf = _dev(packed_out, 'packed_out', torch.uint8)
+            if buf.dim() != 1 or not buf.is_contiguous() or buf.numel() < N * H * d * 2:
+                raise ValueError('packed_out must be a contiguous uint8 vector of >= %d bytes' % (N * H * d * 2))
         rs = None
         if rank_side is not None:
             # FusedPrepare (below) for this side: laff_rank_prepare's work for these rows rides in this launch
@@ -551,8 +569,8 @@ def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=N
     return out if len(out) > 1 else out[0]
 
 
-def frame_fuse(frames, lens, w, b, gw, flags):
-    """frames (B, Fmax, d) zero padded, lens int32 (B,) or None -> (B, d)."""
+def frame_fuse(frames, lens, w, b, gw, flags, out=None):
+    """frames (B, Fmax, d) zero padded, lens int32 (B,) or None -> (B, d).  out: a contiguous fp32 (B, d) buffer to write instead."""
     _dev(frames, 'frames')
     if frames.dim() != 3 or not frames.is_contiguous():
         raise ValueError('frames must be contiguous (B, Fmax, d)')
@@ -561,17 +579,20 @@ def frame_fuse(frames, lens, w, b, gw, flags):
         _dev(lens, 'lens', torch.int32)
         if lens.numel() != B:
             raise ValueError('lens must have %d entries' % B)
-    V = torch.empty((B, d), device=frames.device, dtype=torch.float32)
+    V = _out_buffer(out, (B, d), frames.device, 'out')
     lib, h = _context(frames.device)
     _call('frame_fuse', lib.laff_frame_fuse, h, _ptr(frames), _ptr(lens), B, Fmax, d, _ptr(_dev(w, 'w')), _ptr(_dev(b, 'b')),
                               _ptr(gw), flags, _ptr(V))
     return V
 
 
-def frame_fuse_grouped(frames_list, lens, params, flags, mask=None):
+def frame_fuse_grouped(frames_list, lens, params, flags, mask=None, out=None):
     """frame_fuse for several frame features of the same shape in one launch.  frames_list: [(B, Fmax, d)], params: [(w, b, gw)].
-    mask (fp32 (B, >= Fmax) device tensor, rows of ones then zeros: the reference's mask_tensor) replaces lens: the launch sums it."""
+    mask (fp32 (B, >= Fmax) device tensor, rows of ones then zeros: the reference's mask_tensor) replaces lens: the launch sums it.
+    out: one contiguous fp32 (B, d) buffer per feature to write instead."""
     n = len(frames_list)
+    if out is not None and len(out) != n:
+        raise ValueError('out must hold one buffer per frame feature (%d)' % n)
     B, Fmax, d = frames_list[0].shape
     F, W, Bb, G, Vv = ((C.c_void_p * n)() for _ in range(5))
     outs, keep = [], []
@@ -579,7 +600,7 @@ def frame_fuse_grouped(frames_list, lens, params, flags, mask=None):
         _dev(fr, 'frames')
         if tuple(fr.shape) != (B, Fmax, d) or not fr.is_contiguous():
             raise ValueError('grouped frame features must share one contiguous (B, Fmax, d) shape')
-        V = torch.empty((B, d), device=fr.device, dtype=torch.float32)
+        V = _out_buffer(out[i] if out is not None else None, (B, d), fr.device, 'out[%d]' % i)
         F[i], W[i], Bb[i], G[i], Vv[i] = fr.data_ptr(), _dev(w, 'w').data_ptr(), _dev(b, 'b').data_ptr(), _ptr(gw), V.data_ptr()
         outs.append(V)
         keep.append((fr, w, b, gw))
