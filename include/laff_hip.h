@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 25
+#define LAFF_ABI_VERSION 26
 
 enum {
     LAFF_OK = 0,
@@ -232,6 +232,41 @@ int laff_clip_pack_weight(laff_ctx* ctx, const float* W, int rows, int cols, int
 int laff_clip_workspace_bytes(int R, int N, int width, int precision, size_t* out);
 int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_clip_text* model,
                      int precision, float* out, int ldo, void* workspace, size_t workspace_bytes);
+
+/* ---- video tower: the CLIP image encoder (clip.model.CLIP.encode_image: VisualTransformer, model/clip/model.py:153-243, 342-343) --
+ * Frames [F, 3, R, R] fp32 NCHW (preprocessed as the reference feeds them), g = R / patch_size, L = g^2 + 1 tokens per frame:
+ *   x = [class_embedding ; conv1(frame) as g^2 patch rows] + positional_embedding -> ln_pre
+ *   -> layers x the text encoder's block (laff_clip_block; full, non-causal attention) -> ln_post(x[class row]) . proj
+ * The last block computes queries, out_proj and the MLP for the class rows only (the only rows pooled): exact.
+ * Weights: conv1.weight [width, 3, p, p] viewed as [width, 3 p^2] is packed with laff_clip_pack_weight_padded into [width, Kp],
+ * Kp = laff_clip_image_kpad(patch_size, precision) (3 p^2 rounded up to 64 halves / 32 floats; the padding is zero and exact);
+ * the blocks as for the text encoder; proj [width, embed_dim] with laff_clip_pack_weight(transpose = 1).  Other pointers fp32.
+ * out_frames [F, ldo] fp32: frame f's feature in row f.  frame_off [V+1] int32 (frame_off[0] = 0, frame_off[V] = F, every video at
+ * least one frame) on the device, and the same values in HOST memory (frame_off_host) for the checks; out_mean [V, ldm] fp32: the mean
+ * of video v's frame features, summed in ascending frame order (out_mean may be NULL when V == 0).
+ * workspace: laff_clip_image_workspace_bytes(F, ...) bytes, 16-byte aligned.
+ * Limits (LAFF_E_UNSUPPORTED): width % 64 == 0, 64 <= width <= 1024, heads * 64 == width, layers >= 1, resolution % patch_size == 0,
+ * 2 <= L <= 257 (ViT-B/32, B/16, L/14; L/14@336 with L = 577 is refused); F L <= 4,194,304 token rows per call (LAFF_E_SHAPE).
+ * No allocation, no host synchronisation: capturable in a HIP graph.  A frame's feature does not depend on the rest of its batch
+ * (bitwise). */
+typedef struct laff_clip_visual {
+    int width, layers, heads, embed_dim, input_resolution, patch_size;
+    const void* conv1_weight;           /* packed [width, Kp] */
+    const float* class_embedding;       /* [width] */
+    const float* positional_embedding;  /* [L, width] */
+    const float* ln_pre_weight;
+    const float* ln_pre_bias;
+    const laff_clip_block* blocks;      /* HOST array of `layers` blocks (of device pointers) */
+    const float* ln_post_weight;
+    const float* ln_post_bias;
+    const void* proj;                   /* packed proj^T [embed_dim, width] */
+} laff_clip_visual;
+int laff_clip_pack_weight_padded(laff_ctx* ctx, const float* W, int rows, int cols, int padded_cols, int precision, void* packed);
+int laff_clip_image_kpad(int patch_size, int precision, int* out);
+int laff_clip_image_workspace_bytes(int F, int width, int input_resolution, int patch_size, int precision, size_t* out);
+int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int* frame_off, const int* frame_off_host, int V,
+                           const laff_clip_visual* model, int precision, float* out_frames, int ldo, float* out_mean, int ldm,
+                           void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

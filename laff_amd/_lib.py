@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class Plane(C.Structure):
@@ -58,6 +58,13 @@ class ClipText(C.Structure):
                 ('vocab_size', C.c_int), ('token_embedding', C.c_void_p), ('positional_embedding', C.c_void_p),
                 ('blocks', C.POINTER(ClipBlock)), ('ln_final_weight', C.c_void_p), ('ln_final_bias', C.c_void_p),
                 ('text_projection', C.c_void_p)]
+
+
+class ClipVisual(C.Structure):
+    _fields_ = [('width', C.c_int), ('layers', C.c_int), ('heads', C.c_int), ('embed_dim', C.c_int), ('input_resolution', C.c_int),
+                ('patch_size', C.c_int), ('conv1_weight', C.c_void_p), ('class_embedding', C.c_void_p),
+                ('positional_embedding', C.c_void_p), ('ln_pre_weight', C.c_void_p), ('ln_pre_bias', C.c_void_p),
+                ('blocks', C.POINTER(ClipBlock)), ('ln_post_weight', C.c_void_p), ('ln_post_bias', C.c_void_p), ('proj', C.c_void_p)]
 
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -129,6 +136,10 @@ SIGNATURES = {
     'laff_clip_pack_weight': (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     'laff_clip_workspace_bytes': (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_clip_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(ClipText), _I, _P, _I, _P, C.c_size_t]),
+    'laff_clip_pack_weight_padded': (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    'laff_clip_image_kpad': (C.c_int, [_I, _I, C.POINTER(_I)]),
+    'laff_clip_image_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_clip_image_encode': (C.c_int, [_P, _P, _I, _P, C.POINTER(_I), _I, C.POINTER(ClipVisual), _I, _P, _I, _P, _I, _P, C.c_size_t]),
 }
 
 _lib = None

@@ -544,6 +544,128 @@ int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     return LAFF_OK;
 }
 
+namespace {
+// the CLIP image encoder's workspace: X [F L, W] fp32 | A [F L, W] operand | big [F L, max(3W fp32, 4W operand)], at least the patch
+// operand [F g^2, Kp] + the patch GEMM output [F g^2, W] fp32 | q_cls [F, W] fp32 | a_cls [F, W] operand, each region on 256 bytes
+int vit_kpad(int patch, int fp16) {
+    const int step = fp16 ? 64 : 32;                     // the GEMM's K-step: 128 bytes of a row
+    return (3 * patch * patch + step - 1) / step * step;
+}
+int vit_check_dims(const char* fn, int width, int res, int patch) {
+    if (int rc = clip_check_width(fn, width)) return rc;
+    if (patch < 1 || res < patch || res % patch)
+        return fail(LAFF_E_UNSUPPORTED, "%s: input_resolution=%d patch_size=%d: the resolution must be a multiple of the patch size", fn,
+                    res, patch);
+    if (patch > 128) return fail(LAFF_E_UNSUPPORTED, "%s: patch_size=%d: at most 128", fn, patch);
+    const long g = res / patch, L = g * g + 1;
+    if (L < 2 || L > laff::VIT_MAX_TOKENS)
+        return fail(LAFF_E_UNSUPPORTED, "%s: %ld tokens per frame (input_resolution=%d patch_size=%d): the attention takes at most %d", fn, L,
+                    res, patch, laff::VIT_MAX_TOKENS);
+    return LAFF_OK;
+}
+struct VitWs {
+    size_t x, a, big, patch_out, q_cls, a_cls, total;
+};
+VitWs vit_ws(int F, int width, int res, int patch, int fp16) {
+    const size_t sz = fp16 ? 2 : 4, w = (size_t)width, g = (size_t)(res / patch), np = (size_t)F * g * g, r = (size_t)F * (g * g + 1);
+    VitWs s;
+    s.x = 0;
+    s.a = clip_round(r * w * 4);
+    s.big = s.a + clip_round(r * w * sz);
+    s.patch_out = clip_round(np * (size_t)vit_kpad(patch, fp16) * sz);
+    const size_t big = std::max(clip_round(r * std::max(3 * w * 4, 4 * w * sz)), s.patch_out + clip_round(np * w * 4));
+    s.q_cls = s.big + big;
+    s.a_cls = s.q_cls + clip_round((size_t)F * w * 4);
+    s.total = s.a_cls + clip_round((size_t)F * w * sz);
+    return s;
+}
+}  // namespace
+
+int laff_clip_pack_weight_padded(laff_ctx* ctx, const float* W, int rows, int cols, int padded_cols, int precision, void* packed) {
+    const char* fn = "laff_clip_pack_weight_padded";
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (rows < 1 || cols < 1 || padded_cols < cols)
+        return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d padded to %d columns", fn, rows, cols, padded_cols);
+    if (!W || !packed) return fail(LAFF_E_ARG, "%s: null argument", fn);
+    if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "%s: packed must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_vit_pack_padded(W, rows, cols, padded_cols, fp16, packed, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_clip_image_kpad(int patch_size, int precision, int* out) {
+    const char* fn = "laff_clip_image_kpad";
+    if (!out || patch_size < 1 || patch_size > 128) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    *out = vit_kpad(patch_size, fp16);
+    return LAFF_OK;
+}
+
+int laff_clip_image_workspace_bytes(int F, int width, int input_resolution, int patch_size, int precision, size_t* out) {
+    const char* fn = "laff_clip_image_workspace_bytes";
+    if (!out || F < 0) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = vit_check_dims(fn, width, input_resolution, patch_size)) return rc;
+    *out = vit_ws(F, width, input_resolution, patch_size, fp16).total;
+    return LAFF_OK;
+}
+
+int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int* frame_off, const int* frame_off_host, int V,
+                           const laff_clip_visual* m, int precision, float* out_frames, int ldo, float* out_mean, int ldm, void* workspace,
+                           size_t workspace_bytes) {
+    const char* fn = "laff_clip_image_encode";
+    // every argument is checked before any GPU work
+    if (!m) return fail(LAFF_E_ARG, "%s: null model", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = vit_check_dims(fn, m->width, m->input_resolution, m->patch_size)) return rc;
+    if (m->heads < 1 || m->heads * 64 != m->width)
+        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d heads=%d: only a head dim of 64 is supported", fn, m->width, m->heads);
+    if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
+    if (m->embed_dim < 1) return fail(LAFF_E_SHAPE, "%s: embed_dim=%d", fn, m->embed_dim);
+    if (F < 0 || V < 0 || V > F) return fail(LAFF_E_SHAPE, "%s: bad shape F=%d V=%d", fn, F, V);
+    const long L = (long)(m->input_resolution / m->patch_size) * (m->input_resolution / m->patch_size) + 1;
+    if ((long)F * L > (1L << 22))               /* the GEMMs' grid.y = rows / 128 stays well inside its limit */
+        return fail(LAFF_E_SHAPE, "%s: F=%d frames of %ld tokens: more than 4,194,304 token rows in one call", fn, F, L);
+    if (F == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
+    if (!pixels || !out_frames || !workspace || (V > 0 && (!frame_off || !frame_off_host || !out_mean)) || !m->conv1_weight ||
+        !m->class_embedding || !m->positional_embedding || !m->ln_pre_weight || !m->ln_pre_bias || !m->blocks || !m->ln_post_weight ||
+        !m->ln_post_bias || !m->proj)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    for (int l = 0; l < m->layers; ++l) {
+        const laff_clip_block& b = m->blocks[l];
+        if (!b.ln_1_weight || !b.ln_1_bias || !b.in_proj_weight || !b.in_proj_bias || !b.out_proj_weight || !b.out_proj_bias ||
+            !b.ln_2_weight || !b.ln_2_bias || !b.c_fc_weight || !b.c_fc_bias || !b.c_proj_weight || !b.c_proj_bias)
+            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
+        if (!aligned16(b.in_proj_weight) || !aligned16(b.out_proj_weight) || !aligned16(b.c_fc_weight) || !aligned16(b.c_proj_weight))
+            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
+    }
+    if (V > 0) {
+        if (frame_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: frame_off[0]=%d != 0", fn, frame_off_host[0]);
+        for (int v = 0; v < V; ++v)
+            if (frame_off_host[v + 1] - frame_off_host[v] < 1)
+                return fail(LAFF_E_ARG, "%s: frame_off: video %d has %d frames (at least 1)", fn, v, frame_off_host[v + 1] - frame_off_host[v]);
+        if (frame_off_host[V] != F) return fail(LAFF_E_ARG, "%s: frame_off[V]=%d != F=%d", fn, frame_off_host[V], F);
+        if (ldm < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldm=%d < embed_dim=%d", fn, ldm, m->embed_dim);
+    }
+    if (ldo < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldo=%d < embed_dim=%d", fn, ldo, m->embed_dim);
+    const VitWs ws = vit_ws(F, m->width, m->input_resolution, m->patch_size, fp16);
+    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
+    if (!aligned16(workspace) || !aligned16(m->proj) || !aligned16(m->conv1_weight))
+        return fail(LAFF_E_ALIGN, "%s: workspace / packed conv1 / packed proj must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* w = (char*)workspace;
+    laff::ClipImageArgs e{m, pixels, frame_off, F, V, vit_kpad(m->patch_size, fp16), (float*)(w + ws.x), w + ws.a, w + ws.big,
+                          ws.patch_out, (float*)(w + ws.q_cls), w + ws.a_cls, out_frames, ldo, out_mean, ldm};
+    HIP_TRY(laff::launch_clip_image_encode(e, fp16, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

@@ -337,4 +337,9 @@ hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st)
     return fp16 ? clip_encode_t<_Float16>(e, st) : clip_encode_t<float>(e, st);
 }
 
+hipError_t launch_clip_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi, int fp16,
+                            hipStream_t st) {
+    return fp16 ? clip_gemm<_Float16>(A, B, bias, C, M, N, K, ldc, epi, st) : clip_gemm<float>(A, B, bias, C, M, N, K, ldc, epi, st);
+}
+
 }  // namespace laff

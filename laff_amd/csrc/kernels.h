@@ -309,5 +309,29 @@ struct ClipEncodeArgs {
 };
 hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int fp16, void* out, hipStream_t st);
 hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st);
+// C[M, ldc] (+)= A[M, K] . B[N, K]^T + bias with epilogue epi (clip_gemm_kernel); K * operand size a multiple of 128 bytes
+hipError_t launch_clip_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi, int fp16,
+                            hipStream_t st);
+
+// clip_image.hip: the CLIP image encoder (laff_clip_image_encode)
+constexpr int VIT_MAX_TOKENS = 257;
+struct ClipImageArgs {
+    const laff_clip_visual* model;
+    const float* pixels;  // [F, 3, res, res]
+    const int* frame_off; // [V+1] device
+    int F, V, Kp;
+    float* X;             // workspace: [F L, W] fp32 residual stream
+    void* A;              // workspace: [F L, W] operand
+    void* big;            // workspace: QKV [F L, 3W] fp32 / MLP hidden [F L, 4W] operand / patch operand + patch GEMM output
+    size_t patch_out;     // byte offset of the patch GEMM output [F g^2, W] fp32 inside big
+    float* q_cls;         // workspace: [F, W] fp32 (the class rows' queries of the last block)
+    void* a_cls;          // workspace: [F, W] operand (the class rows' LayerNorm / attention output)
+    float* out;
+    int ldo;
+    float* out_mean;
+    int ldm;
+};
+hipError_t launch_vit_pack_padded(const float* W, int rows, int cols, int ldp, int fp16, void* out, hipStream_t st);
+hipError_t launch_clip_image_encode(const ClipImageArgs& e, int fp16, hipStream_t st);
 
 }  // namespace laff

@@ -323,6 +323,77 @@ def clip_encode(ids, row_off, row_off_host, model, precision='fp16', out=None, w
     return out
 
 
+def clip_image_kpad(patch_size, precision='fp16'):
+    """laff_clip_image_kpad: the padded K of the patch GEMM (3 p^2 rounded up to the GEMM's 128-byte K-step)."""
+    n = C.c_int()
+    check(_lib.load().laff_clip_image_kpad(int(patch_size), PREC[precision], C.byref(n)))
+    return n.value
+
+
+def clip_pack_weight_padded(w, padded_cols, precision='fp16'):
+    """laff_clip_pack_weight_padded: an fp32 weight [rows, cols] -> the CLIP GEMM operand [rows, padded_cols], zero past cols
+    (conv1.weight viewed as [width, 3 p^2])."""
+    w = _dev(w, 'w')
+    if w.dim() != 2:
+        raise ValueError('w must be 2-D, got %s' % (tuple(w.shape),))
+    w = w.contiguous()
+    rows, cols = w.shape
+    out = torch.empty((rows, int(padded_cols)), device=w.device, dtype=torch.float16 if precision == 'fp16' else torch.float32)
+    lib, h = _context(w.device)
+    _call('clip_pack_weight_padded', lib.laff_clip_pack_weight_padded, h, _ptr(w), int(rows), int(cols), int(padded_cols),
+          PREC[precision], _ptr(out))
+    return out
+
+
+def clip_image_workspace_bytes(F, width, input_resolution, patch_size, precision='fp16'):
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_clip_image_workspace_bytes(int(F), int(width), int(input_resolution), int(patch_size), PREC[precision], C.byref(n)))
+    return n.value
+
+
+def clip_image_encode(pixels, frame_off, frame_off_host, model, precision='fp16', out=None, out_mean=None, workspace=None):
+    """laff_clip_image_encode.  pixels [F, 3, R, R] fp32 (contiguous NCHW) on the device; frame_off [V+1] int32 on the device and
+    frame_off_host: the same offsets as a host int32 array (V = 0: both may be None, no means); model: a laff_amd._lib.ClipVisual of
+    device pointers (ClipImageEncoder builds it).  Returns (out [F, embed_dim], out_mean [V, embed_dim] or None), fp32.  workspace: a
+    uint8 device tensor of clip_image_workspace_bytes(F, ...) bytes, or None to allocate one here (pass one for HIP-graph capture)."""
+    pixels = _dev(pixels, 'pixels')
+    R = model.input_resolution
+    if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, R, R) or not pixels.is_contiguous():
+        raise ValueError('pixels must be a contiguous [F, 3, %d, %d] tensor, got %s' % (R, R, tuple(pixels.shape)))
+    F = pixels.shape[0]
+    if frame_off is None:
+        V, fo, roh = 0, None, np.zeros(1, np.int32)
+    else:
+        fo = _dev(frame_off, 'frame_off', torch.int32)
+        if fo.dim() != 1 or not fo.is_contiguous():
+            raise ValueError('frame_off must be a contiguous vector')
+        V = fo.numel() - 1
+        roh = np.ascontiguousarray(frame_off_host, dtype=np.int32)
+        if roh.shape != (V + 1,):
+            raise ValueError('frame_off_host has %d entries, frame_off %d' % (roh.size, V + 1))
+    E = model.embed_dim
+    if workspace is None:
+        workspace = torch.empty(max(clip_image_workspace_bytes(F, model.width, R, model.patch_size, precision), 16), dtype=torch.uint8,
+                                device=pixels.device)
+    if out is None:
+        out = torch.empty((F, E), device=pixels.device, dtype=torch.float32)
+    if tuple(out.shape) != (F, E):
+        raise ValueError('out must be (%d, %d), got %s' % (F, E, tuple(out.shape)))
+    o, ldo = _rows(out, 'out')
+    mo, ldm = None, E
+    if V > 0:
+        if out_mean is None:
+            out_mean = torch.empty((V, E), device=pixels.device, dtype=torch.float32)
+        if tuple(out_mean.shape) != (V, E):
+            raise ValueError('out_mean must be (%d, %d), got %s' % (V, E, tuple(out_mean.shape)))
+        mo, ldm = _rows(out_mean, 'out_mean')
+    lib, h = _context(pixels.device)
+    _call('clip_image_encode', lib.laff_clip_image_encode, h, _ptr(pixels), F, _ptr(fo), roh.ctypes.data_as(C.POINTER(C.c_int)), V,
+          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(mo), ldm, _ptr(workspace), workspace.numel())
+    return out, (out_mean if V > 0 else None)
+
+
 class SplitOperand:
     """fp16 hi/lo split of an fp32 matrix (laff_split_rows): buffer [2][N][Kp] + per-row reciprocal scales."""
 
