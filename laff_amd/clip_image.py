@@ -11,7 +11,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .clip_text import _Block
+from .clip_text import _Block, _Weights, _check_dims, _chunks, _init_blocks
 
 _PREFIXES = ('clip_model.ClipModel.', 'ClipModel.')
 
@@ -31,13 +31,7 @@ class _ClipVisual(nn.Module):
         self.transformer.resblocks = nn.Sequential(*[_Block(width) for _ in range(layers)])
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, embed_dim))
-        # CLIP.initialize_parameters' scales for the blocks (the visual tower's own are the ones above)
-        proj_std, attn_std, fc_std = width ** -0.5 * (2 * layers) ** -0.5, width ** -0.5, (2 * width) ** -0.5
-        for b in self.transformer.resblocks:
-            nn.init.normal_(b.attn.in_proj_weight, std=attn_std)
-            nn.init.normal_(b.attn.out_proj.weight, std=proj_std)
-            nn.init.normal_(b.mlp.c_fc.weight, std=fc_std)
-            nn.init.normal_(b.mlp.c_proj.weight, std=proj_std)
+        _init_blocks(self.transformer.resblocks, width, layers)    # (the visual tower's own scales are the ones above)
 
 
 class _ClipModel(nn.Module):
@@ -57,14 +51,7 @@ class ClipImageEncoder(nn.Module):
         super().__init__()
         width, layers, heads = int(width), int(layers), int(heads)
         patch_size, input_resolution = int(patch_size), int(input_resolution)
-        if precision not in ('fp16', 'fp32'):
-            raise NotImplementedError("ClipImageEncoder: precision %r; 'fp16' or 'fp32'" % (precision,))
-        if width % 64 or not 64 <= width <= 1024:
-            raise NotImplementedError('ClipImageEncoder: width=%d; the kernels take multiples of 64 up to 1024' % width)
-        if heads * 64 != width:
-            raise NotImplementedError('ClipImageEncoder: width=%d heads=%d; only a head dim of 64 is supported' % (width, heads))
-        if layers < 1:
-            raise NotImplementedError('ClipImageEncoder: layers=%d; at least one block' % layers)
+        _check_dims('ClipImageEncoder', precision, width, heads, layers)
         if patch_size < 1 or input_resolution % patch_size:
             raise NotImplementedError('ClipImageEncoder: input_resolution=%d is not a multiple of patch_size=%d'
                                       % (input_resolution, patch_size))
@@ -78,7 +65,7 @@ class ClipImageEncoder(nn.Module):
         self.max_frames = int(max_frames)
         self.ClipModel = _ClipModel(width, layers, patch_size, input_resolution, self.embed_dim)
         self.to(device)
-        self._cache_key, self._cache = None, None
+        self._weights = _Weights(self.ClipModel, precision)
 
     @staticmethod
     def visual_state_dict(sd):
@@ -120,35 +107,12 @@ class ClipImageEncoder(nn.Module):
     def _model(self):
         """The packed weights and the laff_clip_visual struct, rebuilt when any parameter has changed since the last build."""
         from . import _lib, ops
-        params = list(self.ClipModel.parameters())
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if key != self._cache_key:
-            m, prec, keep = self.ClipModel.visual, self.precision, []
-
-            def f32(t):
-                t = t.detach().float().contiguous()
-                keep.append(t)
-                return t.data_ptr()
-
-            def packed(t, transpose=False):
-                p = ops.clip_pack_weight(t.detach().float(), prec, transpose)
-                keep.append(p)
-                return p.data_ptr()
-            with torch.no_grad():
-                blocks = (_lib.ClipBlock * self.layers)()
-                for i, b in enumerate(m.transformer.resblocks):
-                    blocks[i] = _lib.ClipBlock(f32(b.ln_1.weight), f32(b.ln_1.bias), packed(b.attn.in_proj_weight),
-                                               f32(b.attn.in_proj_bias), packed(b.attn.out_proj.weight), f32(b.attn.out_proj.bias),
-                                               f32(b.ln_2.weight), f32(b.ln_2.bias), packed(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias),
-                                               packed(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))
-                conv = ops.clip_pack_weight_padded(m.conv1.weight.detach().float().reshape(self.width, -1),
-                                                   ops.clip_image_kpad(self.patch_size, prec), prec)
-                keep.append(conv)
-                st = _lib.ClipVisual(self.width, self.layers, self.heads, self.embed_dim, self.input_resolution, self.patch_size,
-                                     conv.data_ptr(), f32(m.class_embedding), f32(m.positional_embedding), f32(m.ln_pre.weight),
-                                     f32(m.ln_pre.bias), blocks, f32(m.ln_post.weight), f32(m.ln_post.bias), packed(m.proj, transpose=True))
-            self._cache, self._cache_key = (st, blocks, keep), key
-        return self._cache[0]
+        m = self.ClipModel.visual
+        return self._weights.get(lambda w: _lib.ClipVisual(
+            self.width, self.layers, self.heads, self.embed_dim, self.input_resolution, self.patch_size,
+            w.packed(m.conv1.weight.reshape(self.width, -1), padded_cols=ops.clip_image_kpad(self.patch_size, self.precision)),
+            w.f32(m.class_embedding), w.f32(m.positional_embedding), w.f32(m.ln_pre.weight), w.f32(m.ln_pre.bias),
+            w.blocks(m.transformer.resblocks), w.f32(m.ln_post.weight), w.f32(m.ln_post.bias), w.packed(m.proj, transpose=True)))
 
     def _pixels(self, frames):
         dev = self.ClipModel.visual.proj.device
@@ -180,17 +144,10 @@ class ClipImageEncoder(nn.Module):
         off = np.zeros(V + 1, np.int64)
         off[1:] = np.cumsum(counts)
         budget = max(int(max_frames or self.max_frames), 1)
-        ws, v0 = None, 0
-        while v0 < V:
-            v1 = int(np.searchsorted(off, off[v0] + budget, side='right')) - 1
-            v1 = min(max(v1, v0 + 1), V)
+        for v0, v1, ws in _chunks(off, budget, lambda v0, v1: self.workspace_bytes(int(off[v1] - off[v0])), dev):
             f0, f1 = int(off[v0]), int(off[v1])
             roh = (off[v0:v1 + 1] - f0).astype(np.int32)
-            need = self.workspace_bytes(f1 - f0)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
             self.encode_batch(pixels[f0:f1], torch.from_numpy(roh).to(dev), roh, out=out[f0:f1], out_mean=mean[v0:v1], workspace=ws)
-            v0 = v1
         return out, mean
 
     def encode_frames(self, frames, max_frames=None):

@@ -170,6 +170,84 @@ class _Block(nn.Module):
         self.ln_2 = nn.LayerNorm(width)
 
 
+def _init_blocks(resblocks, width, layers):
+    """CLIP.initialize_parameters' scales for the residual blocks."""
+    proj_std, attn_std, fc_std = width ** -0.5 * (2 * layers) ** -0.5, width ** -0.5, (2 * width) ** -0.5
+    for b in resblocks:
+        nn.init.normal_(b.attn.in_proj_weight, std=attn_std)
+        nn.init.normal_(b.attn.out_proj.weight, std=proj_std)
+        nn.init.normal_(b.mlp.c_fc.weight, std=fc_std)
+        nn.init.normal_(b.mlp.c_proj.weight, std=proj_std)
+
+
+def _check_dims(name, precision, width, heads, layers):
+    """The constructor refusals both encoders share; name: the class, for the message."""
+    if precision not in ('fp16', 'fp32'):
+        raise NotImplementedError("%s: precision %r; 'fp16' or 'fp32'" % (name, precision))
+    if width % 64 or not 64 <= width <= 1024:
+        raise NotImplementedError('%s: width=%d; the kernels take multiples of 64 up to 1024' % (name, width))
+    if heads * 64 != width:
+        raise NotImplementedError('%s: width=%d heads=%d; only a head dim of 64 is supported' % (name, width, heads))
+    if layers < 1:
+        raise NotImplementedError('%s: layers=%d; at least one block' % (name, layers))
+
+
+def _chunks(off, budget, workspace_bytes, device):
+    """The calls of a budgeted encode: (i0, i1, ws) for the consecutive items i0 .. i1 - 1 whose offsets off[i0] .. off[i1] span at
+    most budget (one item at least, so a longer item gets a call of its own), with a uint8 workspace of at least
+    workspace_bytes(i0, i1) bytes on the device, grown as needed."""
+    n, i0, ws = len(off) - 1, 0, None
+    while i0 < n:
+        i1 = int(np.searchsorted(off, off[i0] + budget, side='right')) - 1     # the items that end within the budget
+        i1 = min(max(i1, i0 + 1), n)
+        need = workspace_bytes(i0, i1)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+        yield i0, i1, ws
+        i0 = i1
+
+
+class _Weights(object):
+    """The device copies of a tower's parameters that its laff_* model struct points at, kept alive with it: f32 / packed return the
+    pointer of an fp32 / packed copy of a parameter, blocks the laff_clip_block array of a resblocks module.  get(build) returns the
+    struct build(self) makes, rebuilt whenever a parameter of `module` has changed since the last build (load_state_dict, copy_, ...)."""
+
+    def __init__(self, module, precision):
+        self.module, self.precision = module, precision
+        self._key, self._model, self._keep = None, None, []
+
+    def get(self, build):
+        key = tuple((p.data_ptr(), p._version, p.device) for p in self.module.parameters())
+        if key != self._key:
+            self._keep = []
+            with torch.no_grad():
+                self._model = build(self)
+            self._key = key
+        return self._model
+
+    def f32(self, t):
+        t = t.detach().float().contiguous()
+        self._keep.append(t)
+        return t.data_ptr()
+
+    def packed(self, t, transpose=False, padded_cols=None):
+        from . import ops
+        p = ops.clip_pack_weight(t.detach().float(), self.precision, transpose, padded_cols)
+        self._keep.append(p)
+        return p.data_ptr()
+
+    def blocks(self, resblocks):
+        from . import _lib
+        f32, packed = self.f32, self.packed
+        blocks = (_lib.ClipBlock * len(resblocks))()
+        for i, b in enumerate(resblocks):
+            blocks[i] = _lib.ClipBlock(f32(b.ln_1.weight), f32(b.ln_1.bias), packed(b.attn.in_proj_weight), f32(b.attn.in_proj_bias),
+                                       packed(b.attn.out_proj.weight), f32(b.attn.out_proj.bias), f32(b.ln_2.weight), f32(b.ln_2.bias),
+                                       packed(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias), packed(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))
+        self._keep.append(blocks)
+        return blocks
+
+
 class _ClipText(nn.Module):
     """The text parameters of clip.model.CLIP under their names there."""
 
@@ -184,12 +262,7 @@ class _ClipText(nn.Module):
         # CLIP.initialize_parameters' scales, so that an encoder that is never loaded still computes something sensible
         nn.init.normal_(self.token_embedding.weight, std=0.02)
         nn.init.normal_(self.positional_embedding, std=0.01)
-        proj_std, attn_std, fc_std = width ** -0.5 * (2 * layers) ** -0.5, width ** -0.5, (2 * width) ** -0.5
-        for b in self.transformer.resblocks:
-            nn.init.normal_(b.attn.in_proj_weight, std=attn_std)
-            nn.init.normal_(b.attn.out_proj.weight, std=proj_std)
-            nn.init.normal_(b.mlp.c_fc.weight, std=fc_std)
-            nn.init.normal_(b.mlp.c_proj.weight, std=proj_std)
+        _init_blocks(self.transformer.resblocks, width, layers)
         nn.init.normal_(self.text_projection, std=width ** -0.5)
 
 
@@ -211,22 +284,15 @@ class ClipTxtEncoder(nn.Module):
                  device='cuda', max_rows=1 << 16):
         super().__init__()
         width, layers, heads = int(width), int(layers), int(heads)
-        if precision not in ('fp16', 'fp32'):
-            raise NotImplementedError("ClipTxtEncoder: precision %r; 'fp16' or 'fp32'" % (precision,))
-        if width % 64 or not 64 <= width <= 1024:
-            raise NotImplementedError('ClipTxtEncoder: width=%d; the kernels take multiples of 64 up to 1024' % width)
-        if heads * 64 != width:
-            raise NotImplementedError('ClipTxtEncoder: width=%d heads=%d; only a head dim of 64 is supported' % (width, heads))
+        _check_dims('ClipTxtEncoder', precision, width, heads, layers)
         if not 1 <= int(context_length) <= 77:
             raise NotImplementedError('ClipTxtEncoder: context_length=%d; at most 77 positions' % context_length)
-        if layers < 1:
-            raise NotImplementedError('ClipTxtEncoder: layers=%d; at least one block' % layers)
         self.tokenizer, self.device, self.precision = tokenizer, device, precision
         self.width, self.layers, self.heads, self.embed_dim = width, layers, heads, int(embed_dim)
         self.context_length, self.vocab_size, self.max_rows = int(context_length), int(vocab_size), int(max_rows)
         self.ClipModel = _ClipText(width, layers, self.embed_dim, self.context_length, self.vocab_size)
         self.to(device)
-        self._cache_key, self._cache = None, None
+        self._weights = _Weights(self.ClipModel, precision)
 
     @staticmethod
     def text_state_dict(sd):
@@ -255,33 +321,12 @@ class ClipTxtEncoder(nn.Module):
 
     def _model(self):
         """The packed weights and the laff_clip_text struct, rebuilt when any parameter has changed since the last build."""
-        from . import _lib, ops
-        params = list(self.ClipModel.parameters())
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if key != self._cache_key:
-            m, prec, keep = self.ClipModel, self.precision, []
-
-            def f32(t):
-                t = t.detach().float().contiguous()
-                keep.append(t)
-                return t.data_ptr()
-
-            def packed(t, transpose=False):
-                p = ops.clip_pack_weight(t.detach().float(), prec, transpose)
-                keep.append(p)
-                return p.data_ptr()
-            with torch.no_grad():
-                blocks = (_lib.ClipBlock * self.layers)()
-                for i, b in enumerate(m.transformer.resblocks):
-                    blocks[i] = _lib.ClipBlock(f32(b.ln_1.weight), f32(b.ln_1.bias), packed(b.attn.in_proj_weight),
-                                               f32(b.attn.in_proj_bias), packed(b.attn.out_proj.weight), f32(b.attn.out_proj.bias),
-                                               f32(b.ln_2.weight), f32(b.ln_2.bias), packed(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias),
-                                               packed(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))
-                st = _lib.ClipText(self.width, self.layers, self.heads, self.embed_dim, self.context_length, self.vocab_size,
-                                   f32(m.token_embedding.weight), f32(m.positional_embedding), blocks, f32(m.ln_final.weight),
-                                   f32(m.ln_final.bias), packed(m.text_projection, transpose=True))
-            self._cache, self._cache_key = (st, blocks, keep), key
-        return self._cache[0]
+        from . import _lib
+        m = self.ClipModel
+        return self._weights.get(lambda w: _lib.ClipText(
+            self.width, self.layers, self.heads, self.embed_dim, self.context_length, self.vocab_size, w.f32(m.token_embedding.weight),
+            w.f32(m.positional_embedding), w.blocks(m.transformer.resblocks), w.f32(m.ln_final.weight), w.f32(m.ln_final.bias),
+            w.packed(m.text_projection, transpose=True)))
 
     def batch(self, captions):
         """ClipTokenizer.batch at this encoder's context length, with the ids checked against its vocabulary."""
@@ -313,18 +358,9 @@ class ClipTxtEncoder(nn.Module):
             return out
         budget = max(int(max_rows or self.max_rows), self.context_length)
         ids, ro = torch.from_numpy(b.ids).to(dev), torch.from_numpy(roh).to(dev)
-        ws = None
-        c0 = 0
-        while c0 < N:
-            c1 = int(np.searchsorted(roh, roh[c0] + budget, side='right')) - 1     # the captions whose rows end within the budget
-            c1 = min(max(c1, c0 + 1), N)
+        for c0, c1, ws in _chunks(roh, budget, lambda c0, c1: self.workspace_bytes(ClipBatch(None, None, roh[c0:c1 + 1] - roh[c0])), dev):
             r0, r1 = int(roh[c0]), int(roh[c1])
-            part = ClipBatch(ids[r0:r1], ro[c0:c1 + 1] - r0, roh[c0:c1 + 1] - r0)
-            need = self.workspace_bytes(part)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self.encode_batch(part, out=out[c0:c1], workspace=ws)
-            c0 = c1
+            self.encode_batch(ClipBatch(ids[r0:r1], ro[c0:c1 + 1] - r0, roh[c0:c1 + 1] - r0), out=out[c0:c1], workspace=ws)
         return out
 
     def forward(self, caption_feat_dict, task3=False):

@@ -459,12 +459,29 @@ int clip_check_width(const char* fn, int width) {
         return fail(LAFF_E_UNSUPPORTED, "%s: width=%d: the width must be a multiple of 64 in [64, 1024]", fn, width);
     return LAFF_OK;
 }
+int clip_check_heads(const char* fn, int width, int heads) {
+    if (heads < 1 || heads * 64 != width)
+        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d heads=%d: only a head dim of 64 is supported", fn, width, heads);
+    return LAFF_OK;
+}
+// every block's pointers, then the 16-byte alignment of its packed weights
+int clip_check_blocks(const char* fn, const laff_clip_block* blocks, int layers) {
+    for (int l = 0; l < layers; ++l) {
+        const laff_clip_block& b = blocks[l];
+        if (!b.ln_1_weight || !b.ln_1_bias || !b.in_proj_weight || !b.in_proj_bias || !b.out_proj_weight || !b.out_proj_bias ||
+            !b.ln_2_weight || !b.ln_2_bias || !b.c_fc_weight || !b.c_fc_bias || !b.c_proj_weight || !b.c_proj_bias)
+            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
+        if (!aligned16(b.in_proj_weight) || !aligned16(b.out_proj_weight) || !aligned16(b.c_fc_weight) || !aligned16(b.c_proj_weight))
+            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
+    }
+    return LAFF_OK;
+}
 size_t clip_round(size_t b) { return (b + 255) / 256 * 256; }
 struct ClipWs {
     size_t x, a, big, total;
 };
-ClipWs clip_ws(int R, int width, int fp16) {
-    const size_t sz = fp16 ? 2 : 4, r = (size_t)R, w = (size_t)width;
+ClipWs clip_ws(size_t R, int width, int fp16) {
+    const size_t sz = fp16 ? 2 : 4, r = R, w = (size_t)width;
     ClipWs s;
     s.x = 0;
     s.a = clip_round(r * w * 4);
@@ -472,19 +489,25 @@ ClipWs clip_ws(int R, int width, int fp16) {
     s.total = s.big + clip_round(r * std::max(3 * w * 4, 4 * w * sz));
     return s;
 }
-}  // namespace
-
-int laff_clip_pack_weight(laff_ctx* ctx, const float* W, int rows, int cols, int transpose, int precision, void* packed) {
-    const char* fn = "laff_clip_pack_weight";
+// laff_clip_pack_weight (padded = false, ldp = cols) and laff_clip_pack_weight_padded
+int clip_pack(const char* fn, laff_ctx* ctx, const float* W, int rows, int cols, int transpose, bool padded, int ldp, int precision,
+              void* packed) {
     int fp16 = 0;
     if (int rc = clip_precision(fn, precision, &fp16)) return rc;
-    if (rows < 1 || cols < 1) return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d", fn, rows, cols);
+    if (!padded && (rows < 1 || cols < 1)) return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d", fn, rows, cols);
+    if (padded && (rows < 1 || cols < 1 || ldp < cols))
+        return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d padded to %d columns", fn, rows, cols, ldp);
     if (!W || !packed) return fail(LAFF_E_ARG, "%s: null argument", fn);
     if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "%s: packed must be 16-byte aligned", fn);
     CHECK_CTX(ctx);
     DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_clip_pack(W, rows, cols, transpose != 0, fp16, packed, ctx->stream));
+    HIP_TRY(laff::launch_clip_pack(W, rows, cols, transpose, ldp, fp16, packed, ctx->stream));
     return LAFF_OK;
+}
+}  // namespace
+
+int laff_clip_pack_weight(laff_ctx* ctx, const float* W, int rows, int cols, int transpose, int precision, void* packed) {
+    return clip_pack("laff_clip_pack_weight", ctx, W, rows, cols, transpose != 0, false, cols, precision, packed);
 }
 
 int laff_clip_workspace_bytes(int R, int N, int width, int precision, size_t* out) {
@@ -505,8 +528,7 @@ int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     int fp16 = 0;
     if (int rc = clip_precision(fn, precision, &fp16)) return rc;
     if (int rc = clip_check_width(fn, m->width)) return rc;
-    if (m->heads < 1 || m->heads * 64 != m->width)
-        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d heads=%d: only a head dim of 64 is supported", fn, m->width, m->heads);
+    if (int rc = clip_check_heads(fn, m->width, m->heads)) return rc;
     if (m->context_length < 1 || m->context_length > 77)
         return fail(LAFF_E_UNSUPPORTED, "%s: context_length=%d: at most 77 positions are supported", fn, m->context_length);
     if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
@@ -516,14 +538,7 @@ int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     if (!ids || !row_off || !row_off_host || !out || !workspace || !m->token_embedding || !m->positional_embedding || !m->blocks ||
         !m->ln_final_weight || !m->ln_final_bias || !m->text_projection)
         return fail(LAFF_E_ARG, "%s: null argument", fn);
-    for (int l = 0; l < m->layers; ++l) {
-        const laff_clip_block& b = m->blocks[l];
-        if (!b.ln_1_weight || !b.ln_1_bias || !b.in_proj_weight || !b.in_proj_bias || !b.out_proj_weight || !b.out_proj_bias ||
-            !b.ln_2_weight || !b.ln_2_bias || !b.c_fc_weight || !b.c_fc_bias || !b.c_proj_weight || !b.c_proj_bias)
-            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
-        if (!aligned16(b.in_proj_weight) || !aligned16(b.out_proj_weight) || !aligned16(b.c_fc_weight) || !aligned16(b.c_proj_weight))
-            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
-    }
+    if (int rc = clip_check_blocks(fn, m->blocks, m->layers)) return rc;
     if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
     for (int i = 0; i < N; ++i) {
         const int L = row_off_host[i + 1] - row_off_host[i];
@@ -563,18 +578,15 @@ int vit_check_dims(const char* fn, int width, int res, int patch) {
                     res, patch, laff::VIT_MAX_TOKENS);
     return LAFF_OK;
 }
-struct VitWs {
-    size_t x, a, big, patch_out, q_cls, a_cls, total;
+struct VitWs : ClipWs {
+    size_t patch_out, q_cls, a_cls;
 };
 VitWs vit_ws(int F, int width, int res, int patch, int fp16) {
-    const size_t sz = fp16 ? 2 : 4, w = (size_t)width, g = (size_t)(res / patch), np = (size_t)F * g * g, r = (size_t)F * (g * g + 1);
+    const size_t sz = fp16 ? 2 : 4, w = (size_t)width, g = (size_t)(res / patch), np = (size_t)F * g * g;
     VitWs s;
-    s.x = 0;
-    s.a = clip_round(r * w * 4);
-    s.big = s.a + clip_round(r * w * sz);
+    static_cast<ClipWs&>(s) = clip_ws((size_t)F * (g * g + 1), width, fp16);
     s.patch_out = clip_round(np * (size_t)vit_kpad(patch, fp16) * sz);
-    const size_t big = std::max(clip_round(r * std::max(3 * w * 4, 4 * w * sz)), s.patch_out + clip_round(np * w * 4));
-    s.q_cls = s.big + big;
+    s.q_cls = std::max(s.total, s.big + s.patch_out + clip_round(np * w * 4));
     s.a_cls = s.q_cls + clip_round((size_t)F * w * 4);
     s.total = s.a_cls + clip_round((size_t)F * w * sz);
     return s;
@@ -582,17 +594,7 @@ VitWs vit_ws(int F, int width, int res, int patch, int fp16) {
 }  // namespace
 
 int laff_clip_pack_weight_padded(laff_ctx* ctx, const float* W, int rows, int cols, int padded_cols, int precision, void* packed) {
-    const char* fn = "laff_clip_pack_weight_padded";
-    int fp16 = 0;
-    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
-    if (rows < 1 || cols < 1 || padded_cols < cols)
-        return fail(LAFF_E_SHAPE, "%s: bad shape %d x %d padded to %d columns", fn, rows, cols, padded_cols);
-    if (!W || !packed) return fail(LAFF_E_ARG, "%s: null argument", fn);
-    if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "%s: packed must be 16-byte aligned", fn);
-    CHECK_CTX(ctx);
-    DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_vit_pack_padded(W, rows, cols, padded_cols, fp16, packed, ctx->stream));
-    return LAFF_OK;
+    return clip_pack("laff_clip_pack_weight_padded", ctx, W, rows, cols, 0, true, padded_cols, precision, packed);
 }
 
 int laff_clip_image_kpad(int patch_size, int precision, int* out) {
@@ -623,8 +625,7 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
     int fp16 = 0;
     if (int rc = clip_precision(fn, precision, &fp16)) return rc;
     if (int rc = vit_check_dims(fn, m->width, m->input_resolution, m->patch_size)) return rc;
-    if (m->heads < 1 || m->heads * 64 != m->width)
-        return fail(LAFF_E_UNSUPPORTED, "%s: width=%d heads=%d: only a head dim of 64 is supported", fn, m->width, m->heads);
+    if (int rc = clip_check_heads(fn, m->width, m->heads)) return rc;
     if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
     if (m->embed_dim < 1) return fail(LAFF_E_SHAPE, "%s: embed_dim=%d", fn, m->embed_dim);
     if (F < 0 || V < 0 || V > F) return fail(LAFF_E_SHAPE, "%s: bad shape F=%d V=%d", fn, F, V);
@@ -636,14 +637,7 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
         !m->class_embedding || !m->positional_embedding || !m->ln_pre_weight || !m->ln_pre_bias || !m->blocks || !m->ln_post_weight ||
         !m->ln_post_bias || !m->proj)
         return fail(LAFF_E_ARG, "%s: null argument", fn);
-    for (int l = 0; l < m->layers; ++l) {
-        const laff_clip_block& b = m->blocks[l];
-        if (!b.ln_1_weight || !b.ln_1_bias || !b.in_proj_weight || !b.in_proj_bias || !b.out_proj_weight || !b.out_proj_bias ||
-            !b.ln_2_weight || !b.ln_2_bias || !b.c_fc_weight || !b.c_fc_bias || !b.c_proj_weight || !b.c_proj_bias)
-            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
-        if (!aligned16(b.in_proj_weight) || !aligned16(b.out_proj_weight) || !aligned16(b.c_fc_weight) || !aligned16(b.c_proj_weight))
-            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
-    }
+    if (int rc = clip_check_blocks(fn, m->blocks, m->layers)) return rc;
     if (V > 0) {
         if (frame_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: frame_off[0]=%d != 0", fn, frame_off_host[0]);
         for (int v = 0; v < V; ++v)

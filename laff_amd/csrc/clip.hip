@@ -8,12 +8,15 @@
 // mask no later position can reach row p_i, so the rows after it are never computed.  The captions' rows are concatenated; row_off
 // [N+1] gives where each starts, and the pooled row of caption i is row_off[i+1] - 1.
 //
-// The residual stream x stays fp32 [R, W].  The matrix operands are the encoder's precision T (_Float16 or float):
-//   clip_ln_kernel     LayerNorm (fp32 statistics) of a row -> operand T; with the embedding gather for layer 0, or the pooled rows
+// The residual stream x stays fp32 [R, W].  The matrix operands are the encoder's precision T (_Float16 or float).  The kernels and the
+// block's launch sequence (launch_clip_block_qkv / _post) are shared with the image encoder (clip_image.hip):
+//   clip_ln_kernel     LayerNorm (fp32 statistics) of a row -> operand T; rows at a stride, the token embedding gather for layer 0,
+//                      the pooled rows, or the image's patch embedding + ln_pre
 //   clip_gemm_kernel   out[r][c] = sum_k A[r][k] * B[c][k] (B = a packed nn.Linear weight [out, in]) with three epilogues:
 //                      + bias -> fp32 (in_proj, text_projection), + bias, QuickGELU -> T (c_fc), + bias added in place to x
 //                      (out_proj, c_proj: every element has one owner, no atomics)
 //   clip_attn_kernel   softmax(q k^T / 8 + causal) v per (caption, head), fp32, from the fp32 QKV rows -> operand T
+//   clip_pack_kernel   an fp32 weight -> operand T: transposed (text_projection, proj), or zero-padded columns (conv1)
 //
 // Batch invariance: every reduction's split and order depends on the model's dimensions only.  A GEMM output is one full-K MFMA chain
 // in ascending K-steps from zero in one wave, the LayerNorm sums are one wave's butterfly over a fixed lane map, and attention reads
@@ -32,10 +35,6 @@
 #include "wave_reduce.h"
 
 namespace laff {
-
-typedef float clip_f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 clip_h8 __attribute__((ext_vector_type(8)));
-typedef unsigned clip_u4 __attribute__((ext_vector_type(4)));   // one 16-byte chunk (not HIP's clip_u4: a struct that stays in memory)
 
 constexpr int CLIP_BM = 128, CLIP_BN = 128, CLIP_THREADS = 256;
 constexpr int CLIP_CTX = 77;
@@ -145,17 +144,41 @@ __global__ __launch_bounds__(CLIP_THREADS) void clip_gemm_kernel(ClipGemmArgs g)
     }
 }
 
+// LayerNorm (gamma, beta) of one row held by a wave, element lane + 64 k in x[k]: put(k, y[k]) for each of the lane's elements
+template <typename Put>
+__device__ __forceinline__ void clip_layernorm(const float (&x)[16], int nv, int W, int lane, const float* gamma, const float* beta,
+                                               Put&& put) {
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) s += x[k];
+    const float mean = wave_allsum(s) / (float)W;
+    float q = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) q = fmaf(x[k] - mean, x[k] - mean, q);
+    const float rstd = 1.0f / sqrtf(wave_allsum(q) / (float)W + 1e-5f);
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < nv) {
+            const int e = lane + 64 * k;
+            put(k, fmaf((x[k] - mean) * rstd, gamma[e], beta[e]));
+        }
+}
+
 // One wave per row: x (fp32, width W <= 1024: W / 64 values per lane, element lane + 64 k) -> LayerNorm -> operand T.
-//   CLIP_LN_ROW    x = X[row]
+//   CLIP_LN_ROW    x = X[row * stride]          (stride 1: every row; stride L: the image's class rows)
 //   CLIP_LN_EMBED  x = token_embedding[ids[row]] + positional_embedding[row - row_off[caption]], also written to X[row]
 //   CLIP_LN_POOL   x = X[row_off[row + 1] - 1]        (row = caption)
-template <typename T, int MODE>
+//   CLIP_LN_PATCH  x = ln_pre((t == 0 ? class_embedding : patch[f g^2 + t - 1]) + pos[t]), also written to X[row]  (row = f L + t)
+// F32: the affine result is rounded to fp32 before the conversion to T (the image tower); otherwise fmaf rounds straight to T (the
+// text tower: one rounding, v_fma_mixlo_f16 for fp16).  The two differ in the last fp16 bit now and then; each tower keeps its own.
+template <typename T, int MODE, bool F32>
 __global__ __launch_bounds__(CLIP_THREADS) void clip_ln_kernel(ClipLnArgs a) {
     const int row = blockIdx.x * (CLIP_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= a.rows) return;                             // whole waves: the butterflies below see all 64 lanes
     const int W = a.W, nv = W >> 6;
     float x[16];
-    long src = row;
     if constexpr (MODE == CLIP_LN_EMBED) {
         int lo = 0, hi = a.N;                              // the caption: the last c with row_off[c] <= row
         while (hi - lo > 1) {
@@ -174,29 +197,26 @@ __global__ __launch_bounds__(CLIP_THREADS) void clip_ln_kernel(ClipLnArgs a) {
                 x[k] = ok ? te[e] + pe[e] : __builtin_nanf("");   // an id outside the table poisons its row instead of reading past it
                 a.X[(long)row * W + e] = x[k];
             }
+    } else if constexpr (MODE == CLIP_LN_PATCH) {
+        const int L = a.L, f = row / L, t = row - f * L;
+        const float* src = t == 0 ? a.cls : a.patch + ((long)f * (L - 1) + t - 1) * W;
+        const float* pe = a.pos_emb + (long)t * W;
+        float e[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < nv) e[k] = src[lane + 64 * k] + pe[lane + 64 * k];
+        clip_layernorm(e, nv, W, lane, a.pre_gamma, a.pre_beta, [&](int k, float v) { a.X[(long)row * W + lane + 64 * k] = x[k] = v; });
     } else {
-        if constexpr (MODE == CLIP_LN_POOL) src = a.row_off[row + 1] - 1;
+        const long src = MODE == CLIP_LN_POOL ? a.row_off[row + 1] - 1 : (long)row * a.stride;
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             if (k < nv) x[k] = a.X[src * W + lane + 64 * k];
     }
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) s += x[k];
-    const float mean = wave_allsum(s) / (float)W;
-    float q = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) q = fmaf(x[k] - mean, x[k] - mean, q);
-    const float rstd = 1.0f / sqrtf(wave_allsum(q) / (float)W + 1e-5f);
     T* out = reinterpret_cast<T*>(a.out) + (long)row * W;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) {
-            const int e = lane + 64 * k;
-            out[e] = (T)fmaf((x[k] - mean) * rstd, a.gamma[e], a.beta[e]);
-        }
+    clip_layernorm(x, nv, W, lane, a.gamma, a.beta, [&](int k, float v) {
+        if constexpr (F32) asm("" : "+v"(v));              // v stays an fp32 value: the conversion cannot fuse with the fmaf
+        out[lane + 64 * k] = (T)v;
+    });
 }
 
 // One workgroup per (caption, head): q, k, v of the caption's L <= 77 rows in LDS; wave w takes query rows w, w + 4, ...
@@ -247,21 +267,27 @@ __global__ __launch_bounds__(CLIP_THREADS) void clip_attn_kernel(ClipAttnArgs a)
     }
 }
 
+// out [rows, ldp]: out[r][c] = W[r][c], zero for c >= cols; transpose: out [cols, rows], out[c][r] = W[r][c]
 template <typename T>
-__global__ __launch_bounds__(256) void clip_pack_kernel(const float* __restrict__ W, int rows, int cols, int transpose, T* __restrict__ out) {
-    const long total = (long)rows * cols;
+__global__ __launch_bounds__(256) void clip_pack_kernel(const float* __restrict__ W, int rows, int cols, int transpose, int ldp,
+                                                        T* __restrict__ out) {
+    const long total = (long)rows * (transpose ? cols : ldp);
     for (long o = (long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long)gridDim.x * blockDim.x) {
-        // transpose: out [cols, rows], out[c][r] = W[r][c]
-        const long src = transpose ? (o % rows) * cols + o / rows : o;
-        out[o] = (T)W[src];
+        if (transpose) {
+            out[o] = (T)W[(o % rows) * cols + o / rows];
+        } else {
+            const long r = o / ldp;
+            const int c = (int)(o - r * ldp);
+            out[o] = c < cols ? (T)W[r * cols + c] : (T)0.0f;
+        }
     }
 }
 
-hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int fp16, void* out, hipStream_t st) {
-    const long total = (long)rows * cols;
+hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int ldp, int fp16, void* out, hipStream_t st) {
+    const long total = (long)rows * (transpose ? cols : ldp);
     const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-    if (fp16) clip_pack_kernel<_Float16><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, reinterpret_cast<_Float16*>(out));
-    else clip_pack_kernel<float><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, reinterpret_cast<float*>(out));
+    if (fp16) clip_pack_kernel<_Float16><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, ldp, reinterpret_cast<_Float16*>(out));
+    else clip_pack_kernel<float><<<blocks, 256, 0, st>>>(W, rows, cols, transpose, ldp, reinterpret_cast<float*>(out));
     return hipGetLastError();
 }
 
@@ -280,23 +306,25 @@ hipError_t clip_gemm(const void* A, const void* B, const float* bias, void* C, i
 template <typename T>
 hipError_t clip_ln(int mode, const ClipLnArgs& a, hipStream_t st) {
     const int blocks = (a.rows + 3) / 4;
-    if (mode == CLIP_LN_EMBED) clip_ln_kernel<T, CLIP_LN_EMBED><<<blocks, CLIP_THREADS, 0, st>>>(a);
-    else if (mode == CLIP_LN_POOL) clip_ln_kernel<T, CLIP_LN_POOL><<<blocks, CLIP_THREADS, 0, st>>>(a);
-    else clip_ln_kernel<T, CLIP_LN_ROW><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    if (mode == CLIP_LN_EMBED) clip_ln_kernel<T, CLIP_LN_EMBED, false><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else if (mode == CLIP_LN_POOL) clip_ln_kernel<T, CLIP_LN_POOL, false><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else if (mode == CLIP_LN_PATCH) clip_ln_kernel<T, CLIP_LN_PATCH, true><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else if (a.round_f32) clip_ln_kernel<T, CLIP_LN_ROW, true><<<blocks, CLIP_THREADS, 0, st>>>(a);
+    else clip_ln_kernel<T, CLIP_LN_ROW, false><<<blocks, CLIP_THREADS, 0, st>>>(a);
     return hipGetLastError();
 }
 
-#define CLIP_TRY(expr)                               \
-    do {                                             \
-        const hipError_t e_ = (expr);                \
-        if (e_ != hipSuccess) return e_;             \
-    } while (0)
-
 template <typename T>
 hipError_t clip_encode_t(const ClipEncodeArgs& e, hipStream_t st) {
+    constexpr int fp16 = sizeof(T) == 2;
     const laff_clip_text& m = *e.model;
     const int W = m.width, R = e.R, N = e.N;
     ClipLnArgs ln{};
+    ln.X = e.X;
+    ln.out = e.A;
+    ln.W = W;
+    ln.rows = R;
+    ln.stride = 1;
     ln.ids = e.ids;
     ln.row_off = e.row_off;
     ln.N = N;
@@ -304,25 +332,12 @@ hipError_t clip_encode_t(const ClipEncodeArgs& e, hipStream_t st) {
     ln.ctx = m.context_length;
     ln.tok_emb = m.token_embedding;
     ln.pos_emb = m.positional_embedding;
-    ln.X = e.X;
-    ln.out = e.A;
-    ln.W = W;
-    ln.rows = R;
     ClipAttnArgs at{reinterpret_cast<const float*>(e.big), e.row_off, e.A, W};
     for (int l = 0; l < m.layers; ++l) {
-        const laff_clip_block& b = m.blocks[l];
-        ln.gamma = b.ln_1_weight;
-        ln.beta = b.ln_1_bias;
-        CLIP_TRY(clip_ln<T>(l == 0 ? CLIP_LN_EMBED : CLIP_LN_ROW, ln, st));
-        CLIP_TRY(clip_gemm<T>(e.A, b.in_proj_weight, b.in_proj_bias, e.big, R, 3 * W, W, 3 * W, CLIP_EPI_F32, st));
+        CLIP_TRY(launch_clip_block_qkv(m.blocks[l], l == 0 ? CLIP_LN_EMBED : CLIP_LN_ROW, ln, e.big, fp16, st));
         clip_attn_kernel<T><<<dim3(N, m.heads), CLIP_THREADS, 0, st>>>(at);
         CLIP_TRY(hipGetLastError());
-        CLIP_TRY(clip_gemm<T>(e.A, b.out_proj_weight, b.out_proj_bias, e.X, R, W, W, W, CLIP_EPI_RESID, st));
-        ln.gamma = b.ln_2_weight;
-        ln.beta = b.ln_2_bias;
-        CLIP_TRY(clip_ln<T>(CLIP_LN_ROW, ln, st));
-        CLIP_TRY(clip_gemm<T>(e.A, b.c_fc_weight, b.c_fc_bias, e.big, R, 4 * W, W, 4 * W, CLIP_EPI_GELU, st));
-        CLIP_TRY(clip_gemm<T>(e.big, b.c_proj_weight, b.c_proj_bias, e.X, R, W, 4 * W, W, CLIP_EPI_RESID, st));
+        CLIP_TRY(launch_clip_block_post(m.blocks[l], ln, e.big, fp16, st));
     }
     ln.gamma = m.ln_final_weight;
     ln.beta = m.ln_final_bias;
@@ -340,6 +355,28 @@ hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st)
 hipError_t launch_clip_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi, int fp16,
                             hipStream_t st) {
     return fp16 ? clip_gemm<_Float16>(A, B, bias, C, M, N, K, ldc, epi, st) : clip_gemm<float>(A, B, bias, C, M, N, K, ldc, epi, st);
+}
+
+hipError_t launch_clip_ln(int mode, const ClipLnArgs& a, int fp16, hipStream_t st) {
+    return fp16 ? clip_ln<_Float16>(mode, a, st) : clip_ln<float>(mode, a, st);
+}
+
+hipError_t launch_clip_block_qkv(const laff_clip_block& b, int mode, ClipLnArgs ln, void* big, int fp16, hipStream_t st) {
+    const int W = ln.W;
+    ln.gamma = b.ln_1_weight;
+    ln.beta = b.ln_1_bias;
+    CLIP_TRY(launch_clip_ln(mode, ln, fp16, st));
+    return launch_clip_gemm(ln.out, b.in_proj_weight, b.in_proj_bias, big, ln.rows, 3 * W, W, 3 * W, CLIP_EPI_F32, fp16, st);
+}
+
+hipError_t launch_clip_block_post(const laff_clip_block& b, ClipLnArgs ln, void* big, int fp16, hipStream_t st) {
+    const int W = ln.W, M = ln.rows, ldx = ln.stride * W;
+    CLIP_TRY(launch_clip_gemm(ln.out, b.out_proj_weight, b.out_proj_bias, ln.X, M, W, W, ldx, CLIP_EPI_RESID, fp16, st));
+    ln.gamma = b.ln_2_weight;
+    ln.beta = b.ln_2_bias;
+    CLIP_TRY(launch_clip_ln(CLIP_LN_ROW, ln, fp16, st));
+    CLIP_TRY(launch_clip_gemm(ln.out, b.c_fc_weight, b.c_fc_bias, big, M, 4 * W, W, 4 * W, CLIP_EPI_GELU, fp16, st));
+    return launch_clip_gemm(big, b.c_proj_weight, b.c_proj_bias, ln.X, M, W, 4 * W, ldx, CLIP_EPI_RESID, fp16, st);
 }
 
 }  // namespace laff

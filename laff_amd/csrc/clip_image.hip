@@ -5,15 +5,14 @@
 //   layers x { x += out_proj(attn(ln_1(x)));  x += c_proj(QuickGELU(c_fc(ln_2(x)))) }   (pre-LN, full MHA, head dim 64)
 //   feature = ln_post(x[class row]) . proj
 //
-// The residual stream x stays fp32 [F L, W]; the matrix operands are the encoder's precision T (_Float16 or float).  The GEMMs are the
-// text encoder's clip_gemm_kernel (clip.hip, launch_clip_gemm) with its three epilogues.  The kernels of this file:
+// The residual stream x stays fp32 [F L, W]; the matrix operands are the encoder's precision T (_Float16 or float).  The transformer
+// core is the text encoder's (clip.hip): clip_gemm_kernel with its three epilogues, clip_ln_kernel (CLIP_LN_PATCH: class / patch row +
+// positional row -> ln_pre -> x (fp32), and ln_1 of layer 0 -> operand, in one pass; CLIP_LN_ROW at stride L: the class rows), the
+// weight packs and the block's launch sequence (launch_clip_block_qkv / _post).  The kernels of this file:
 //   vit_patch_kernel      pixels -> patch operand rows [F g^2, Kp] T in conv1.weight's (c, ky, kx) order, zero past 3 p^2
-//   vit_embed_ln_kernel   class / patch row + positional row -> ln_pre -> x (fp32), and ln_1 of layer 0 -> operand, in one pass
-//   vit_ln_kernel         LayerNorm of x rows s * stride (stride 1: every row; stride L: the class rows) -> operand rows s
 //   vit_attn_f16_kernel   softmax(q k^T / 8) v per (frame, head) on v_mfma_f32_16x16x32_f16, fp32 softmax (fp16 mode)
 //   vit_attn_f32_kernel   the same in fp32 on the vector ALU (fp32 mode)
 //   vit_mean_kernel       the per-video mean of the frame features, ascending frame order
-//   vit_pack_kernel       an fp32 weight [rows, cols] -> operand [rows, ldp], zero columns past cols (conv1)
 //
 // The last block: only the class rows are pooled, so its queries, out_proj, ln_2 and MLP run on the F class rows alone (the GEMMs
 // write the residual rows f L through ldc = L W); its K and V come from every row (in_proj rows W .. 3W).  Exact.
@@ -28,29 +27,11 @@
 
 namespace laff {
 
-typedef float vit_f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 vit_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 vit_h4 __attribute__((ext_vector_type(4)));
-
 constexpr int VIT_THREADS = 256;
 // the fp16 attention's key tiles of 16 (an even count: 32-key PV slices) by the token count: L <= 64 (ViT-B/32), 128, 224 (ViT-B/16),
 // 288 (ViT-L/14); the largest one covers VIT_MAX_TOKENS
 constexpr int VIT_NKT[4] = {4, 8, 14, 18};
 static_assert(VIT_NKT[3] * 16 >= VIT_MAX_TOKENS, "the largest key-tile class must cover VIT_MAX_TOKENS");
-
-struct VitLnArgs {
-    const float* X;        // [rows * stride, W] residual stream (ROW), or [F L, W] written (EMBED)
-    float* Xw;
-    const float* patch;    // EMBED: [F g^2, W] fp32 patch GEMM output
-    const float* cls;      // EMBED: [W]
-    const float* pos;      // EMBED: [L, W]
-    const float* g0;       // ln_pre (EMBED) / the LayerNorm (ROW)
-    const float* b0;
-    const float* g1;       // EMBED: ln_1 of layer 0
-    const float* b1;
-    void* out;             // [rows, W] operand
-    int W, rows, stride, L;
-};
 
 struct VitAttnArgs {
     const float* q;        // query row i of frame f at q + (f nq + i) ldq + 64 h
@@ -58,26 +39,6 @@ struct VitAttnArgs {
     void* out;             // [F nq, W] operand
     int W, L, nq, ldq;
 };
-
-__device__ __forceinline__ void vit_layernorm(const float (&x)[16], int nv, int W, int lane, const float* gamma, const float* beta,
-                                              float (&y)[16]) {
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) s += x[k];
-    const float mean = wave_allsum(s) / (float)W;
-    float q = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) q = fmaf(x[k] - mean, x[k] - mean, q);
-    const float rstd = 1.0f / sqrtf(wave_allsum(q) / (float)W + 1e-5f);
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) {
-            const int e = lane + 64 * k;
-            y[k] = fmaf((x[k] - mean) * rstd, gamma[e], beta[e]);
-        }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void vit_patch_kernel(const float* __restrict__ pix, int F, int res, int P, int g, int Kp,
@@ -98,59 +59,6 @@ __global__ __launch_bounds__(256) void vit_patch_kernel(const float* __restrict_
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void vit_pack_kernel(const float* __restrict__ W, int rows, int cols, int ldp, T* __restrict__ out) {
-    const long total = (long)rows * ldp;
-    for (long o = (long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long)gridDim.x * blockDim.x) {
-        const long r = o / ldp;
-        const int c = (int)(o - r * ldp);
-        out[o] = c < cols ? (T)W[r * cols + c] : (T)0.0f;
-    }
-}
-
-// One wave per row r = f L + t (width W <= 1024: W / 64 values per lane, element lane + 64 k):
-// x = (t == 0 ? class_embedding : patch[f g^2 + t - 1]) + pos[t] -> ln_pre -> Xw[r] (fp32) -> ln_1 of layer 0 -> out[r] (T)
-template <typename T>
-__global__ __launch_bounds__(VIT_THREADS) void vit_embed_ln_kernel(VitLnArgs a) {
-    const int row = blockIdx.x * (VIT_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= a.rows) return;                             // whole waves: the butterflies see all 64 lanes
-    const int W = a.W, nv = W >> 6, L = a.L;
-    const int f = row / L, t = row - f * L;
-    const float* src = t == 0 ? a.cls : a.patch + ((long)f * (L - 1) + t - 1) * W;
-    const float* pe = a.pos + (long)t * W;
-    float x[16], y[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) x[k] = src[lane + 64 * k] + pe[lane + 64 * k];
-    vit_layernorm(x, nv, W, lane, a.g0, a.b0, y);
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) a.Xw[(long)row * W + lane + 64 * k] = y[k];
-    vit_layernorm(y, nv, W, lane, a.g1, a.b1, x);
-    T* out = reinterpret_cast<T*>(a.out) + (long)row * W;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) out[lane + 64 * k] = (T)x[k];
-}
-
-// One wave per output row s: LayerNorm of X[s * stride] -> out[s]
-template <typename T>
-__global__ __launch_bounds__(VIT_THREADS) void vit_ln_kernel(VitLnArgs a) {
-    const int row = blockIdx.x * (VIT_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= a.rows) return;
-    const int W = a.W, nv = W >> 6;
-    const float* src = a.X + (long)row * a.stride * W;
-    float x[16], y[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) x[k] = src[lane + 64 * k];
-    vit_layernorm(x, nv, W, lane, a.g0, a.b0, y);
-    T* out = reinterpret_cast<T*>(a.out) + (long)row * W;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < nv) out[lane + 64 * k] = (T)y[k];
-}
-
 // fp16 attention.  One workgroup per (frame, head); K (fp16, [Lp][64], 16-byte chunk c of key j at chunk c ^ (j & 7)) and V^T (fp16,
 // [64][vld]) of the frame's L keys in LDS, zero for the padded keys L .. Lp - 1 (Lp = 16 NKT, the smallest class that holds L: every
 // loop over the tiles is unrolled at compile time and stays in registers).  Wave w takes the 16-query
@@ -166,18 +74,18 @@ __global__ __launch_bounds__(VIT_THREADS) void vit_attn_f16_kernel(VitAttnArgs a
     extern __shared__ __attribute__((aligned(16))) char vit_smem[];
     constexpr int Lp = NKT * 16, vld = Lp + 8;
     const int f = blockIdx.x, h = blockIdx.y, W = a.W, L = a.L, nq = a.nq;
-    vit_h8* ks = reinterpret_cast<vit_h8*>(vit_smem);                         // [Lp * 8] chunks
+    clip_h8* ks = reinterpret_cast<clip_h8*>(vit_smem);                         // [Lp * 8] chunks
     _Float16* vt = reinterpret_cast<_Float16*>(vit_smem + (size_t)Lp * 128);  // [64][vld]
-    vit_f4* kbias = reinterpret_cast<vit_f4*>(vit_smem + (size_t)Lp * 128 + 64 * vld * 2);   // [Lp / 4]: 0, or -inf past L
+    clip_f4* kbias = reinterpret_cast<clip_f4*>(vit_smem + (size_t)Lp * 128 + 64 * vld * 2);   // [Lp / 4]: 0, or -inf past L
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, ql = lane & 15, grp = lane >> 4;
     const float* kv = a.kv + (long)f * L * 3 * W + h * 64;
     for (int e = threadIdx.x; e < Lp * 8; e += VIT_THREADS) {
         const int j = e >> 3, c = e & 7;
-        vit_h8 kk, vv;
+        clip_h8 kk, vv;
         if (j < L) {
             const float* p = kv + (long)j * 3 * W + 8 * c;
-            const vit_f4 k0 = *reinterpret_cast<const vit_f4*>(p + W), k1 = *reinterpret_cast<const vit_f4*>(p + W + 4);
-            const vit_f4 v0 = *reinterpret_cast<const vit_f4*>(p + 2 * W), v1 = *reinterpret_cast<const vit_f4*>(p + 2 * W + 4);
+            const clip_f4 k0 = *reinterpret_cast<const clip_f4*>(p + W), k1 = *reinterpret_cast<const clip_f4*>(p + W + 4);
+            const clip_f4 v0 = *reinterpret_cast<const clip_f4*>(p + 2 * W), v1 = *reinterpret_cast<const clip_f4*>(p + 2 * W + 4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 kk[i] = (_Float16)k0[i];
@@ -191,7 +99,7 @@ __global__ __launch_bounds__(VIT_THREADS) void vit_attn_f16_kernel(VitAttnArgs a
         }
         ks[j * 8 + (c ^ (j & 7))] = kk;
         if (c == 0 && (j & 3) == 0)
-            kbias[j >> 2] = vit_f4{j < L ? 0.0f : -__builtin_inff(), j + 1 < L ? 0.0f : -__builtin_inff(),
+            kbias[j >> 2] = clip_f4{j < L ? 0.0f : -__builtin_inff(), j + 1 < L ? 0.0f : -__builtin_inff(),
                                    j + 2 < L ? 0.0f : -__builtin_inff(), j + 3 < L ? 0.0f : -__builtin_inff()};
 #pragma unroll
         for (int i = 0; i < 8; ++i) vt[(8 * c + i) * vld + j] = vv[i];
@@ -204,21 +112,21 @@ __global__ __launch_bounds__(VIT_THREADS) void vit_attn_f16_kernel(VitAttnArgs a
         // B operand: query min(16 qb + ql, nq - 1) (the rows past nq are computed and not stored), scaled by 1/8 (exact)
         const int qi = min(qb * 16 + ql, nq - 1);
         const float* qp = a.q + ((long)f * nq + qi) * a.ldq + h * 64 + 8 * grp;
-        vit_h8 qf[2];
+        clip_h8 qf[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const vit_f4 q0 = *reinterpret_cast<const vit_f4*>(qp + 32 * s), q1 = *reinterpret_cast<const vit_f4*>(qp + 32 * s + 4);
+            const clip_f4 q0 = *reinterpret_cast<const clip_f4*>(qp + 32 * s), q1 = *reinterpret_cast<const clip_f4*>(qp + 32 * s + 4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 qf[s][i] = (_Float16)(q0[i] * 0.125f);
                 qf[s][i + 4] = (_Float16)(q1[i] * 0.125f);
             }
         }
-        vit_f4 sc[NKT];
+        clip_f4 sc[NKT];
         float m = -__builtin_inff();
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
-            sc[kt] = vit_f4{0.0f, 0.0f, 0.0f, 0.0f};
+            sc[kt] = clip_f4{0.0f, 0.0f, 0.0f, 0.0f};
             const int j = kt * 16 + ql;
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -240,12 +148,12 @@ __global__ __launch_bounds__(VIT_THREADS) void vit_attn_f16_kernel(VitAttnArgs a
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
         const float inv = 1.0f / sum;
-        vit_f4 o[4];
+        clip_f4 o[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] = vit_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int dt = 0; dt < 4; ++dt) o[dt] = clip_f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int j = 0; j < NKT / 2; ++j) {
-            vit_h8 p;
+            clip_h8 p;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 p[r] = (_Float16)(sc[2 * j][r] * inv);
@@ -255,8 +163,8 @@ __global__ __launch_bounds__(VIT_THREADS) void vit_attn_f16_kernel(VitAttnArgs a
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const _Float16* vr = vt + (dt * 16 + ql) * vld + k0;
-                const vit_h4 lo = *reinterpret_cast<const vit_h4*>(vr), hi = *reinterpret_cast<const vit_h4*>(vr + 16);
-                const vit_h8 b = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const clip_h4 lo = *reinterpret_cast<const clip_h4*>(vr), hi = *reinterpret_cast<const clip_h4*>(vr + 16);
+                const clip_h8 b = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p, b, o[dt], 0, 0, 0);
             }
         }
@@ -346,21 +254,7 @@ __global__ __launch_bounds__(256) void vit_mean_kernel(const float* __restrict__
     mean[(long)v * ldm + e] = s / (float)(f1 - f0);
 }
 
-hipError_t launch_vit_pack_padded(const float* W, int rows, int cols, int ldp, int fp16, void* out, hipStream_t st) {
-    const long total = (long)rows * ldp;
-    const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-    if (fp16) vit_pack_kernel<_Float16><<<blocks, 256, 0, st>>>(W, rows, cols, ldp, reinterpret_cast<_Float16*>(out));
-    else vit_pack_kernel<float><<<blocks, 256, 0, st>>>(W, rows, cols, ldp, reinterpret_cast<float*>(out));
-    return hipGetLastError();
-}
-
 namespace {
-
-#define VIT_TRY(expr)                                \
-    do {                                             \
-        const hipError_t e_ = (expr);                \
-        if (e_ != hipSuccess) return e_;             \
-    } while (0)
 
 unsigned long long vit_attn_attr[5];
 
@@ -370,7 +264,7 @@ size_t vit_attn_f32_smem(int L) { return ((size_t)L * 129 + 4 * 64 * ((VIT_MAX_T
 template <int C>
 hipError_t vit_attn_f16(const VitAttnArgs& a, int F, int heads, hipStream_t st) {
     const int smem = (int)vit_attn_f16_smem(VIT_NKT[C]);
-    VIT_TRY(smem_attr_once(vit_attn_attr[1 + C], vit_attn_f16_kernel<VIT_NKT[C]>, smem));
+    CLIP_TRY(smem_attr_once(vit_attn_attr[1 + C], vit_attn_f16_kernel<VIT_NKT[C]>, smem));
     vit_attn_f16_kernel<VIT_NKT[C]><<<dim3(F, heads), VIT_THREADS, smem, st>>>(a);
     return hipGetLastError();
 }
@@ -383,16 +277,8 @@ hipError_t vit_attn(const VitAttnArgs& a, int F, int heads, int fp16, hipStream_
         return vit_attn_f16<3>(a, F, heads, st);
     }
     // the attribute once, at the largest size any call takes
-    VIT_TRY(smem_attr_once(vit_attn_attr[0], vit_attn_f32_kernel, (int)vit_attn_f32_smem(VIT_MAX_TOKENS)));
+    CLIP_TRY(smem_attr_once(vit_attn_attr[0], vit_attn_f32_kernel, (int)vit_attn_f32_smem(VIT_MAX_TOKENS)));
     vit_attn_f32_kernel<<<dim3(F, heads), VIT_THREADS, vit_attn_f32_smem(a.L), st>>>(a);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t vit_ln(const VitLnArgs& a, bool embed, hipStream_t st) {
-    const int blocks = (a.rows + 3) / 4;
-    if (embed) vit_embed_ln_kernel<T><<<blocks, VIT_THREADS, 0, st>>>(a);
-    else vit_ln_kernel<T><<<blocks, VIT_THREADS, 0, st>>>(a);
     return hipGetLastError();
 }
 
@@ -407,69 +293,58 @@ hipError_t vit_encode_t(const ClipImageArgs& e, hipStream_t st) {
         const long total = (long)F * gg * e.Kp;
         const int blocks = (int)std::min<long>((total + 255) / 256, 16384);
         vit_patch_kernel<T><<<blocks, 256, 0, st>>>(e.pixels, F, res, P, g, e.Kp, reinterpret_cast<T*>(big));
-        VIT_TRY(hipGetLastError());
+        CLIP_TRY(hipGetLastError());
     }
-    VIT_TRY(launch_clip_gemm(big, m.conv1_weight, nullptr, pout, F * gg, W, e.Kp, W, CLIP_EPI_F32, fp16, st));
-    VitLnArgs ln{};
+    CLIP_TRY(launch_clip_gemm(big, m.conv1_weight, nullptr, pout, F * gg, W, e.Kp, W, CLIP_EPI_F32, fp16, st));
+    ClipLnArgs ln{};                                       // every row; layer 0's ln_1 runs with ln_pre (CLIP_LN_PATCH)
     ln.X = e.X;
-    ln.Xw = e.X;
-    ln.patch = pout;
-    ln.cls = m.class_embedding;
-    ln.pos = m.positional_embedding;
-    ln.g0 = m.ln_pre_weight;
-    ln.b0 = m.ln_pre_bias;
-    ln.g1 = m.blocks[0].ln_1_weight;
-    ln.b1 = m.blocks[0].ln_1_bias;
     ln.out = e.A;
     ln.W = W;
     ln.rows = R;
     ln.stride = 1;
+    ln.round_f32 = 1;
+    ln.pos_emb = m.positional_embedding;
+    ln.patch = pout;
+    ln.cls = m.class_embedding;
+    ln.pre_gamma = m.ln_pre_weight;
+    ln.pre_beta = m.ln_pre_bias;
     ln.L = L;
-    VIT_TRY(vit_ln<T>(ln, true, st));
-
-    // LayerNorm (gamma, beta) of the rows s * stride of x into `out`
-    auto norm = [&](const float* gamma, const float* beta, int rows, int stride, void* out) {
-        VitLnArgs a = ln;
-        a.g0 = gamma;
-        a.b0 = beta;
-        a.rows = rows;
-        a.stride = stride;
-        a.out = out;
-        return vit_ln<T>(a, false, st);
-    };
+    ClipLnArgs cls = ln;                                   // the class rows x[f L] -> a_cls
+    cls.out = e.a_cls;
+    cls.rows = F;
+    cls.stride = L;
     const size_t sz = sizeof(T);
     for (int l = 0; l < m.layers; ++l) {
         const laff_clip_block& b = m.blocks[l];
-        if (l > 0) VIT_TRY(norm(b.ln_1_weight, b.ln_1_bias, R, 1, e.A));
+        const int mode = l == 0 ? CLIP_LN_PATCH : CLIP_LN_ROW;
         if (l + 1 < m.layers) {
-            VIT_TRY(launch_clip_gemm(e.A, b.in_proj_weight, b.in_proj_bias, e.big, R, 3 * W, W, 3 * W, CLIP_EPI_F32, fp16, st));
-            VIT_TRY(vit_attn(VitAttnArgs{reinterpret_cast<const float*>(e.big), reinterpret_cast<const float*>(e.big), e.A, W, L, L,
-                                         3 * W},
-                             F, m.heads, fp16, st));
-            VIT_TRY(launch_clip_gemm(e.A, b.out_proj_weight, b.out_proj_bias, e.X, R, W, W, W, CLIP_EPI_RESID, fp16, st));
-            VIT_TRY(norm(b.ln_2_weight, b.ln_2_bias, R, 1, e.A));
-            VIT_TRY(launch_clip_gemm(e.A, b.c_fc_weight, b.c_fc_bias, e.big, R, 4 * W, W, 4 * W, CLIP_EPI_GELU, fp16, st));
-            VIT_TRY(launch_clip_gemm(e.big, b.c_proj_weight, b.c_proj_bias, e.X, R, W, 4 * W, W, CLIP_EPI_RESID, fp16, st));
+            CLIP_TRY(launch_clip_block_qkv(b, mode, ln, e.big, fp16, st));
+            CLIP_TRY(vit_attn(VitAttnArgs{reinterpret_cast<const float*>(e.big), reinterpret_cast<const float*>(e.big), e.A, W, L, L,
+                                          3 * W},
+                              F, m.heads, fp16, st));
+            CLIP_TRY(launch_clip_block_post(b, ln, e.big, fp16, st));
         } else {
             // K and V of every row (in_proj rows W .. 3W into QKV columns W .. 3W); the rest on the class rows x[f L] alone
+            ln.gamma = cls.gamma = b.ln_1_weight;
+            ln.beta = cls.beta = b.ln_1_bias;
+            CLIP_TRY(launch_clip_ln(mode, ln, fp16, st));
             const char* kvw = reinterpret_cast<const char*>(b.in_proj_weight) + (size_t)W * W * sz;
-            VIT_TRY(launch_clip_gemm(e.A, kvw, b.in_proj_bias + W, reinterpret_cast<float*>(e.big) + W, R, 2 * W, W, 3 * W, CLIP_EPI_F32,
-                                     fp16, st));
-            VIT_TRY(norm(b.ln_1_weight, b.ln_1_bias, F, L, e.a_cls));
-            VIT_TRY(launch_clip_gemm(e.a_cls, b.in_proj_weight, b.in_proj_bias, e.q_cls, F, W, W, W, CLIP_EPI_F32, fp16, st));
-            VIT_TRY(vit_attn(VitAttnArgs{e.q_cls, reinterpret_cast<const float*>(e.big), e.a_cls, W, L, 1, W}, F, m.heads, fp16, st));
-            VIT_TRY(launch_clip_gemm(e.a_cls, b.out_proj_weight, b.out_proj_bias, e.X, F, W, W, L * W, CLIP_EPI_RESID, fp16, st));
-            VIT_TRY(norm(b.ln_2_weight, b.ln_2_bias, F, L, e.a_cls));
-            VIT_TRY(launch_clip_gemm(e.a_cls, b.c_fc_weight, b.c_fc_bias, e.big, F, 4 * W, W, 4 * W, CLIP_EPI_GELU, fp16, st));
-            VIT_TRY(launch_clip_gemm(e.big, b.c_proj_weight, b.c_proj_bias, e.X, F, W, 4 * W, L * W, CLIP_EPI_RESID, fp16, st));
+            CLIP_TRY(launch_clip_gemm(e.A, kvw, b.in_proj_bias + W, reinterpret_cast<float*>(e.big) + W, R, 2 * W, W, 3 * W, CLIP_EPI_F32,
+                                      fp16, st));
+            CLIP_TRY(launch_clip_ln(CLIP_LN_ROW, cls, fp16, st));
+            CLIP_TRY(launch_clip_gemm(e.a_cls, b.in_proj_weight, b.in_proj_bias, e.q_cls, F, W, W, W, CLIP_EPI_F32, fp16, st));
+            CLIP_TRY(vit_attn(VitAttnArgs{e.q_cls, reinterpret_cast<const float*>(e.big), e.a_cls, W, L, 1, W}, F, m.heads, fp16, st));
+            CLIP_TRY(launch_clip_block_post(b, cls, e.big, fp16, st));
         }
     }
-    VIT_TRY(norm(m.ln_post_weight, m.ln_post_bias, F, L, e.a_cls));
-    VIT_TRY(launch_clip_gemm(e.a_cls, m.proj, nullptr, e.out, F, m.embed_dim, W, e.ldo, CLIP_EPI_F32, fp16, st));
+    cls.gamma = m.ln_post_weight;
+    cls.beta = m.ln_post_bias;
+    CLIP_TRY(launch_clip_ln(CLIP_LN_ROW, cls, fp16, st));
+    CLIP_TRY(launch_clip_gemm(e.a_cls, m.proj, nullptr, e.out, F, m.embed_dim, W, e.ldo, CLIP_EPI_F32, fp16, st));
     if (e.V > 0) {
         const long n = (long)e.V * m.embed_dim;
         vit_mean_kernel<<<(int)((n + 255) / 256), 256, 0, st>>>(e.out, e.ldo, e.frame_off, e.V, m.embed_dim, e.out_mean, e.ldm);
-        VIT_TRY(hipGetLastError());
+        CLIP_TRY(hipGetLastError());
     }
     return hipSuccess;
 }

@@ -268,9 +268,18 @@ struct GruStepArgs {
 hipError_t launch_gru_pack_whh(const float* W, int H, float* Wp, hipStream_t st);
 hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st);
 
-// clip.hip: the CLIP text encoder (laff_clip_encode)
+// clip.hip: the CLIP text encoder (laff_clip_encode) and the transformer core it shares with the image encoder (clip_image.hip)
+typedef float clip_f4 __attribute__((ext_vector_type(4)));
+typedef _Float16 clip_h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 clip_h8 __attribute__((ext_vector_type(8)));
+typedef unsigned clip_u4 __attribute__((ext_vector_type(4)));   // one 16-byte chunk (not HIP's uint4: a struct that stays in memory)
+#define CLIP_TRY(expr)                               \
+    do {                                             \
+        const hipError_t e_ = (expr);                \
+        if (e_ != hipSuccess) return e_;             \
+    } while (0)
 enum { CLIP_EPI_F32 = 0, CLIP_EPI_GELU = 1, CLIP_EPI_RESID = 2 };
-enum { CLIP_LN_ROW = 0, CLIP_LN_EMBED = 1, CLIP_LN_POOL = 2 };
+enum { CLIP_LN_ROW = 0, CLIP_LN_EMBED = 1, CLIP_LN_POOL = 2, CLIP_LN_PATCH = 3 };
 struct ClipGemmArgs {
     const void* A;        // [M, K] operand rows
     const void* B;        // [N, K] packed weight (nn.Linear layout)
@@ -279,16 +288,22 @@ struct ClipGemmArgs {
     int M, N, K, ldc;
 };
 struct ClipLnArgs {
-    const int* ids;       // [R] token ids (EMBED)
-    const int* row_off;   // [N+1] (EMBED, POOL)
-    int N, V, ctx;
-    const float* tok_emb; // [V, W]
-    const float* pos_emb; // [ctx, W]
-    float* X;             // [R, W] residual stream
-    const float* gamma;
+    float* X;             // residual stream [*, W]: read (ROW: rows s * stride; POOL), written (EMBED, PATCH)
+    const float* gamma;   // the LayerNorm into out
     const float* beta;
     void* out;            // [rows, W] operand
-    int W, rows;
+    int W, rows, stride;
+    int round_f32;        // ROW: round to fp32 before the operand conversion, as the image tower does (clip_ln_kernel's F32)
+    const int* ids;       // EMBED: [R] token ids
+    const int* row_off;   // EMBED, POOL: [N+1]
+    int N, V, ctx;        // EMBED
+    const float* tok_emb; // EMBED: [V, W]
+    const float* pos_emb; // EMBED: [ctx, W]; PATCH: [L, W]
+    const float* patch;   // PATCH: [F g^2, W] fp32 patch GEMM output
+    const float* cls;     // PATCH: [W] class embedding
+    const float* pre_gamma;   // PATCH: ln_pre, its output written to X
+    const float* pre_beta;
+    int L;                // PATCH: tokens per frame
 };
 struct ClipAttnArgs {
     const float* qkv;     // [R, 3W]
@@ -307,11 +322,19 @@ struct ClipEncodeArgs {
     float* out;
     int ldo;
 };
-hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int fp16, void* out, hipStream_t st);
+// an fp32 weight [rows, cols] -> operand [rows, ldp], zero columns past cols; transpose: [cols, rows] (ldp unused)
+hipError_t launch_clip_pack(const float* W, int rows, int cols, int transpose, int ldp, int fp16, void* out, hipStream_t st);
 hipError_t launch_clip_encode(const ClipEncodeArgs& e, int fp16, hipStream_t st);
 // C[M, ldc] (+)= A[M, K] . B[N, K]^T + bias with epilogue epi (clip_gemm_kernel); K * operand size a multiple of 128 bytes
 hipError_t launch_clip_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi, int fp16,
                             hipStream_t st);
+// LayerNorm of a.rows rows into the operand a.out in mode CLIP_LN_* (clip_ln_kernel)
+hipError_t launch_clip_ln(int mode, const ClipLnArgs& a, int fp16, hipStream_t st);
+// One pre-LN residual block around its attention, which each encoder launches itself (ln: X, out = the operand A, W, rows, stride):
+//   launch_clip_block_qkv    A = ln_1(x) (LayerNorm mode `mode`, stride 1);  big = in_proj(A) [rows, 3W] fp32
+//   launch_clip_block_post   x += out_proj(A);  A = ln_2(x);  x += c_proj(QuickGELU(c_fc(A)))  on x rows s * stride (ldc = stride W)
+hipError_t launch_clip_block_qkv(const laff_clip_block& b, int mode, ClipLnArgs ln, void* big, int fp16, hipStream_t st);
+hipError_t launch_clip_block_post(const laff_clip_block& b, ClipLnArgs ln, void* big, int fp16, hipStream_t st);
 
 // clip_image.hip: the CLIP image encoder (laff_clip_image_encode)
 constexpr int VIT_MAX_TOKENS = 257;
@@ -331,7 +354,6 @@ struct ClipImageArgs {
     float* out_mean;
     int ldm;
 };
-hipError_t launch_vit_pack_padded(const float* W, int rows, int cols, int ldp, int fp16, void* out, hipStream_t st);
 hipError_t launch_clip_image_encode(const ClipImageArgs& e, int fp16, hipStream_t st);
 
 }  // namespace laff

@@ -274,17 +274,23 @@ def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean'
     return out
 
 
-def clip_pack_weight(w, precision='fp16', transpose=False):
+def clip_pack_weight(w, precision='fp16', transpose=False, padded_cols=None):
     """laff_clip_pack_weight: an fp32 weight [rows, cols] -> the CLIP GEMM operand in the encoder's precision (fp16 or fp32),
-    [rows, cols], or [cols, rows] with transpose (text_projection)."""
+    [rows, cols], or [cols, rows] with transpose (text_projection).  padded_cols: laff_clip_pack_weight_padded, [rows, padded_cols]
+    zero past cols (conv1.weight viewed as [width, 3 p^2])."""
     w = _dev(w, 'w')
     if w.dim() != 2:
         raise ValueError('w must be 2-D, got %s' % (tuple(w.shape),))
     w = w.contiguous()
     rows, cols = w.shape
     dt = torch.float16 if precision == 'fp16' else torch.float32
-    out = torch.empty((cols, rows) if transpose else (rows, cols), device=w.device, dtype=dt)
     lib, h = _context(w.device)
+    if padded_cols is not None:
+        out = torch.empty((rows, int(padded_cols)), device=w.device, dtype=dt)
+        _call('clip_pack_weight_padded', lib.laff_clip_pack_weight_padded, h, _ptr(w), int(rows), int(cols), int(padded_cols),
+              PREC[precision], _ptr(out))
+        return out
+    out = torch.empty((cols, rows) if transpose else (rows, cols), device=w.device, dtype=dt)
     _call('clip_pack_weight', lib.laff_clip_pack_weight, h, _ptr(w), int(rows), int(cols), int(bool(transpose)), PREC[precision],
           _ptr(out))
     return out
@@ -328,21 +334,6 @@ def clip_image_kpad(patch_size, precision='fp16'):
     n = C.c_int()
     check(_lib.load().laff_clip_image_kpad(int(patch_size), PREC[precision], C.byref(n)))
     return n.value
-
-
-def clip_pack_weight_padded(w, padded_cols, precision='fp16'):
-    """laff_clip_pack_weight_padded: an fp32 weight [rows, cols] -> the CLIP GEMM operand [rows, padded_cols], zero past cols
-    (conv1.weight viewed as [width, 3 p^2])."""
-    w = _dev(w, 'w')
-    if w.dim() != 2:
-        raise ValueError('w must be 2-D, got %s' % (tuple(w.shape),))
-    w = w.contiguous()
-    rows, cols = w.shape
-    out = torch.empty((rows, int(padded_cols)), device=w.device, dtype=torch.float16 if precision == 'fp16' else torch.float32)
-    lib, h = _context(w.device)
-    _call('clip_pack_weight_padded', lib.laff_clip_pack_weight_padded, h, _ptr(w), int(rows), int(cols), int(padded_cols),
-          PREC[precision], _ptr(out))
-    return out
 
 
 def clip_image_workspace_bytes(F, width, input_resolution, patch_size, precision='fp16'):

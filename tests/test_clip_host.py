@@ -181,9 +181,9 @@ def test_clip_entry_points_in_header_library_and_binding_at_the_header_abi():
     assert C.sizeof(_lib.ClipBlock) == 12 * 8 and C.sizeof(_lib.ClipText) == 6 * 4 + 6 * 8
 
 
-def test_clip_kernels_have_no_spills_and_no_scratch(tmp_path):
-    """Every clip_* kernel of clip.hip: 0 VGPR / SGPR spills and no scratch (the GEMM's staging registers and accumulators stay in
-    registers; a struct-typed vector there once sent them to scratch and LDS)."""
+def test_clip_hip_kernels_have_no_spills_and_no_scratch(tmp_path):
+    """Every clip_* kernel of clip.hip, the transformer core both CLIP encoders share: 0 VGPR / SGPR spills and no scratch (the
+    GEMM's staging registers and accumulators stay in registers; a struct-typed vector there once sent them to scratch and LDS)."""
     import subprocess
     import sys
     from laff_amd import build
@@ -196,7 +196,11 @@ def test_clip_kernels_have_no_spills_and_no_scratch(tmp_path):
     asm = [str(tmp_path / f) for f in os.listdir(tmp_path) if f.endswith('gfx950.s')]
     assert len(asm) == 1
     stats = isa_audit.audit(asm[0], 'clip_', quiet=True)
-    assert len(stats) == 16, sorted(stats)                        # 6 GEMMs, 6 LayerNorms, 2 attention, 2 packs
+    # 6 GEMMs, 10 LayerNorms (x2 precisions: ROW, EMBED, POOL, and from clip_image.hip the image's ROW with its fp32 rounding and its
+    # PATCH embed LayerNorm), 2 attention, 2 packs (the image's padded pack merged into clip_pack_kernel)
+    assert len(stats) == 20, sorted(stats)
+    per_family = {f: sum(f in name for name in stats) for f in ('gemm_kernel', 'ln_kernel', 'attn_kernel', 'pack_kernel')}
+    assert per_family == {'gemm_kernel': 6, 'ln_kernel': 10, 'attn_kernel': 2, 'pack_kernel': 2}, per_family
     text = open(asm[0]).read()
     for name, st in stats.items():
         assert st['scratch'] == 0, (name, st)
