@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 26
+#define LAFF_ABI_VERSION 27
 
 enum {
     LAFF_OK = 0,
@@ -267,6 +267,56 @@ int laff_clip_image_workspace_bytes(int F, int width, int input_resolution, int 
 int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int* frame_off, const int* frame_off_host, int V,
                            const laff_clip_visual* model, int precision, float* out_frames, int ldo, float* out_mean, int ldm,
                            void* workspace, size_t workspace_bytes);
+
+/* ---- text tower: the BERT text encoder (BertTxtEncoder.forward: transformers' BertModel pooler_output, model/model.py:437-466) ----
+ * Post-LN encoder, inference, eps = layer_norm_eps:
+ *   x = LN_emb(word[id] + type[0] + pos[t])
+ *   layers x { h = LN_1(x + attention.output.dense(MHA(x)));  x = LN_2(h + output.dense(GELU_erf(intermediate.dense(h)))) }
+ *   out = tanh(pooler.dense(x[CLS row]))        (bidirectional MHA with head dim 64, scale 1/8)
+ * Captions come RAGGED: caption i is its wordpiece ids [CLS] ... [SEP] without padding.  The reference pads with a key mask that gives
+ * padded keys a weight of exactly 0, so each caption's rows equal the unpadded computation.  ids [R] int32 concatenates the captions;
+ * row_off [N+1] int32 (row_off[0] = 0, row_off[N] = R, every caption 1 .. max_position rows, at most 512) is passed TWICE: on the
+ * device for the kernels and in HOST memory for the checks (the same values).  Caption i's CLS row is row_off[i].
+ * The last layer runs its queries, attention output, LayerNorms and feed-forward on the N CLS rows only (K and V from every row).
+ * Weights: per layer the query / key / value weights stacked into one [3 width, width] matrix (rows: query, key, value) with its
+ * [3 width] bias, attention.output.dense [width, width], intermediate.dense [intermediate, width], output.dense [width, intermediate]
+ * and pooler.dense [width, width], each packed once with laff_clip_pack_weight (transpose = 0) into the encoder's precision
+ * (LAFF_PREC_FP32, or LAFF_PREC_FP16: fp16 operands, fp32 accumulation, LayerNorm, softmax and residual stream).  Every other
+ * pointer is fp32 on the device; token_type_embedding is row 0 of the token-type table.
+ * out [N, ldo] fp32: caption i's pooler_output in row i.  workspace: laff_bert_workspace_bytes(R, N, ...) bytes, 16-byte aligned.
+ * Limits (LAFF_E_UNSUPPORTED): width % 64 == 0, 64 <= width <= 1024, heads * 64 == width, intermediate % 64 == 0,
+ * 1 <= max_position <= 512, layers >= 1; R <= 4,194,304 token rows per call (LAFF_E_SHAPE).
+ * No allocation, no host synchronisation: capturable in a HIP graph (one stream, no branches).  A caption's feature does not depend on
+ * the rest of its batch (bitwise), so any split of a batch into calls gives the same features. */
+typedef struct laff_bert_block {
+    const void* qkv_weight;             /* packed [3 width, width]: attention.self.query / key / value weights, stacked */
+    const float* qkv_bias;              /* [3 width] */
+    const void* attn_out_weight;        /* packed [width, width]: attention.output.dense */
+    const float* attn_out_bias;
+    const float* ln_1_weight;           /* attention.output.LayerNorm */
+    const float* ln_1_bias;
+    const void* inter_weight;           /* packed [intermediate, width]: intermediate.dense */
+    const float* inter_bias;
+    const void* out_weight;             /* packed [width, intermediate]: output.dense */
+    const float* out_bias;
+    const float* ln_2_weight;           /* output.LayerNorm */
+    const float* ln_2_bias;
+} laff_bert_block;
+typedef struct laff_bert_text {
+    int width, layers, heads, intermediate, max_position, vocab_size;
+    float layer_norm_eps;
+    const float* word_embeddings;       /* [vocab_size, width] */
+    const float* position_embeddings;   /* [max_position, width] */
+    const float* token_type_embedding;  /* [width]: row 0 of embeddings.token_type_embeddings */
+    const float* emb_ln_weight;         /* embeddings.LayerNorm */
+    const float* emb_ln_bias;
+    const laff_bert_block* blocks;      /* HOST array of `layers` blocks (of device pointers) */
+    const void* pooler_weight;          /* packed [width, width] */
+    const float* pooler_bias;
+} laff_bert_text;
+int laff_bert_workspace_bytes(int R, int N, int width, int intermediate, int precision, size_t* out);
+int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_bert_text* model,
+                     int precision, float* out, int ldo, void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

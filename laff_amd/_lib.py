@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class Plane(C.Structure):
@@ -65,6 +65,19 @@ class ClipVisual(C.Structure):
                 ('patch_size', C.c_int), ('conv1_weight', C.c_void_p), ('class_embedding', C.c_void_p),
                 ('positional_embedding', C.c_void_p), ('ln_pre_weight', C.c_void_p), ('ln_pre_bias', C.c_void_p),
                 ('blocks', C.POINTER(ClipBlock)), ('ln_post_weight', C.c_void_p), ('ln_post_bias', C.c_void_p), ('proj', C.c_void_p)]
+
+
+class BertBlock(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('qkv_weight', 'qkv_bias', 'attn_out_weight', 'attn_out_bias', 'ln_1_weight', 'ln_1_bias',
+                                          'inter_weight', 'inter_bias', 'out_weight', 'out_bias', 'ln_2_weight', 'ln_2_bias')]
+
+
+class BertText(C.Structure):
+    _fields_ = [('width', C.c_int), ('layers', C.c_int), ('heads', C.c_int), ('intermediate', C.c_int), ('max_position', C.c_int),
+                ('vocab_size', C.c_int), ('layer_norm_eps', C.c_float), ('word_embeddings', C.c_void_p),
+                ('position_embeddings', C.c_void_p), ('token_type_embedding', C.c_void_p), ('emb_ln_weight', C.c_void_p),
+                ('emb_ln_bias', C.c_void_p), ('blocks', C.POINTER(BertBlock)), ('pooler_weight', C.c_void_p),
+                ('pooler_bias', C.c_void_p)]
 
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -140,6 +153,8 @@ SIGNATURES = {
     'laff_clip_image_kpad': (C.c_int, [_I, _I, C.POINTER(_I)]),
     'laff_clip_image_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_clip_image_encode': (C.c_int, [_P, _P, _I, _P, C.POINTER(_I), _I, C.POINTER(ClipVisual), _I, _P, _I, _P, _I, _P, C.c_size_t]),
+    'laff_bert_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_bert_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(BertText), _I, _P, _I, _P, C.c_size_t]),
 }
 
 _lib = None

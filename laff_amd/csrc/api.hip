@@ -660,6 +660,94 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
     return LAFF_OK;
 }
 
+namespace {
+// the BERT text encoder's workspace: X [R, W] fp32 | A [R, W] operand | big [R, max(3W fp32, I operand)] | Xc [N, W] fp32 |
+// Qc [N, W] fp32 | Ac [N, W] operand, each region on 256 bytes
+int bert_check_dims(const char* fn, int width, int intermediate) {
+    if (int rc = clip_check_width(fn, width)) return rc;
+    if (intermediate < 64 || intermediate % 64)
+        return fail(LAFF_E_UNSUPPORTED, "%s: intermediate=%d: the GEMM takes a positive multiple of 64", fn, intermediate);
+    return LAFF_OK;
+}
+struct BertWs {
+    size_t x, a, big, xc, qc, ac, total;
+};
+BertWs bert_ws(size_t R, size_t N, int width, int intermediate, int fp16) {
+    const size_t sz = fp16 ? 2 : 4, w = (size_t)width;
+    BertWs s;
+    s.x = 0;
+    s.a = clip_round(R * w * 4);
+    s.big = s.a + clip_round(R * w * sz);
+    s.xc = s.big + clip_round(R * std::max(3 * w * 4, (size_t)intermediate * sz));
+    s.qc = s.xc + clip_round(N * w * 4);
+    s.ac = s.qc + clip_round(N * w * 4);
+    s.total = s.ac + clip_round(N * w * sz);
+    return s;
+}
+}  // namespace
+
+int laff_bert_workspace_bytes(int R, int N, int width, int intermediate, int precision, size_t* out) {
+    const char* fn = "laff_bert_workspace_bytes";
+    if (!out || R < 0 || N < 0 || N > R) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = bert_check_dims(fn, width, intermediate)) return rc;
+    *out = bert_ws(R, N, width, intermediate, fp16).total;
+    return LAFF_OK;
+}
+
+int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_bert_text* m,
+                     int precision, float* out, int ldo, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_bert_encode";
+    // every argument is checked before any GPU work
+    if (!m) return fail(LAFF_E_ARG, "%s: null model", fn);
+    int fp16 = 0;
+    if (int rc = clip_precision(fn, precision, &fp16)) return rc;
+    if (int rc = bert_check_dims(fn, m->width, m->intermediate)) return rc;
+    if (int rc = clip_check_heads(fn, m->width, m->heads)) return rc;
+    if (m->max_position < 1 || m->max_position > laff::BERT_MAX_POSITION)
+        return fail(LAFF_E_UNSUPPORTED, "%s: max_position=%d: at most %d positions are supported", fn, m->max_position,
+                    laff::BERT_MAX_POSITION);
+    if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
+    if (m->vocab_size < 1) return fail(LAFF_E_SHAPE, "%s: vocab_size=%d", fn, m->vocab_size);
+    if (!(m->layer_norm_eps >= 0.0f) || m->layer_norm_eps > 1.0f)
+        return fail(LAFF_E_ARG, "%s: layer_norm_eps=%g: expected a value in [0, 1]", fn, (double)m->layer_norm_eps);
+    if (N < 0 || R < N) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d", fn, N, R);
+    if (R > (1 << 22))                          /* the GEMMs' grid.y = rows / 128 stays well inside its limit */
+        return fail(LAFF_E_SHAPE, "%s: R=%d: more than 4,194,304 token rows in one call", fn, R);
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
+    if (!ids || !row_off || !row_off_host || !out || !workspace || !m->word_embeddings || !m->position_embeddings ||
+        !m->token_type_embedding || !m->emb_ln_weight || !m->emb_ln_bias || !m->blocks || !m->pooler_weight || !m->pooler_bias)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    for (int l = 0; l < m->layers; ++l) {
+        const laff_bert_block& b = m->blocks[l];
+        if (!b.qkv_weight || !b.qkv_bias || !b.attn_out_weight || !b.attn_out_bias || !b.ln_1_weight || !b.ln_1_bias ||
+            !b.inter_weight || !b.inter_bias || !b.out_weight || !b.out_bias || !b.ln_2_weight || !b.ln_2_bias)
+            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
+        if (!aligned16(b.qkv_weight) || !aligned16(b.attn_out_weight) || !aligned16(b.inter_weight) || !aligned16(b.out_weight))
+            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
+    }
+    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
+    for (int i = 0; i < N; ++i) {
+        const int L = row_off_host[i + 1] - row_off_host[i];
+        if (L < 1 || L > m->max_position)
+            return fail(LAFF_E_ARG, "%s: row_off: caption %d has %d rows (1 .. max_position=%d)", fn, i, L, m->max_position);
+    }
+    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (ldo < m->width) return fail(LAFF_E_SHAPE, "%s: ldo=%d < width=%d", fn, ldo, m->width);
+    const BertWs ws = bert_ws(R, N, m->width, m->intermediate, fp16);
+    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
+    if (!aligned16(workspace) || !aligned16(m->pooler_weight))
+        return fail(LAFF_E_ALIGN, "%s: workspace / packed pooler weight must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* w = (char*)workspace;
+    laff::BertEncodeArgs e{m, ids, row_off, N, R, (float*)(w + ws.x), w + ws.a, w + ws.big, (float*)(w + ws.xc), (float*)(w + ws.qc),
+                           w + ws.ac, out, ldo};
+    HIP_TRY(laff::launch_bert_encode(e, fp16, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

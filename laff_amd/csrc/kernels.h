@@ -278,7 +278,9 @@ typedef unsigned clip_u4 __attribute__((ext_vector_type(4)));   // one 16-byte c
         const hipError_t e_ = (expr);                \
         if (e_ != hipSuccess) return e_;             \
     } while (0)
-enum { CLIP_EPI_F32 = 0, CLIP_EPI_GELU = 1, CLIP_EPI_RESID = 2 };
+// epilogues of clip_gemm_tile (clip_core.h): + bias -> fp32, + bias QuickGELU -> operand, + bias added in place to fp32 C; and BERT's
+// + bias erf-GELU -> operand, + bias tanh -> fp32
+enum { CLIP_EPI_F32 = 0, CLIP_EPI_GELU = 1, CLIP_EPI_RESID = 2, CLIP_EPI_GELU_ERF = 3, CLIP_EPI_TANH = 4 };
 enum { CLIP_LN_ROW = 0, CLIP_LN_EMBED = 1, CLIP_LN_POOL = 2, CLIP_LN_PATCH = 3 };
 struct ClipGemmArgs {
     const void* A;        // [M, K] operand rows
@@ -355,5 +357,24 @@ struct ClipImageArgs {
     int ldm;
 };
 hipError_t launch_clip_image_encode(const ClipImageArgs& e, int fp16, hipStream_t st);
+
+// bert.hip: the BERT text encoder (laff_bert_encode) on the transformer core of clip_core.h
+constexpr int BERT_MAX_POSITION = 512;
+enum { BERT_LN_EMBED = 0, BERT_LN_ROW = 1, BERT_LN_CLS = 2 };
+struct BertEncodeArgs {
+    const laff_bert_text* model;
+    const int* ids;
+    const int* row_off;
+    int N, R;
+    float* X;             // workspace: [R, W] fp32 residual stream
+    void* A;              // workspace: [R, W] operand
+    void* big;            // workspace: [R, 3W] fp32 (QKV) / [R, I] operand (intermediate)
+    float* Xc;            // workspace: [N, W] fp32, the CLS rows' residual stream in the last layer
+    float* Qc;            // workspace: [N, W] fp32, their queries
+    void* Ac;             // workspace: [N, W] operand
+    float* out;
+    int ldo;
+};
+hipError_t launch_bert_encode(const BertEncodeArgs& e, int fp16, hipStream_t st);
 
 }  // namespace laff

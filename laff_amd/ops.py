@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
 
-__all__ = ['clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -325,6 +325,40 @@ def clip_encode(ids, row_off, row_off_host, model, precision='fp16', out=None, w
     o, ldo = _rows(out, 'out')
     lib, h = _context(ids.device)
     _call('clip_encode', lib.laff_clip_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
+          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
+    return out
+
+
+def bert_workspace_bytes(R, N, width, intermediate, precision='fp32'):
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_bert_workspace_bytes(int(R), int(N), int(width), int(intermediate), PREC[precision], C.byref(n)))
+    return n.value
+
+
+def bert_encode(ids, row_off, row_off_host, model, precision='fp32', out=None, workspace=None):
+    """laff_bert_encode.  ids [R] int32 (the captions' wordpiece rows concatenated) and row_off [N+1] int32 on the device,
+    row_off_host: the same offsets as a host int32 array; model: a laff_amd._lib.BertText of device pointers (BertTxtEncoder builds
+    it).  Returns out [N, width] fp32 (pooler_output).  workspace: a uint8 device tensor of bert_workspace_bytes(R, N, ...) bytes, or
+    None to allocate one here (pass one for HIP-graph capture)."""
+    ids = _dev(ids, 'ids', torch.int32)
+    row_off = _dev(row_off, 'row_off', torch.int32)
+    if not ids.is_contiguous() or not row_off.is_contiguous() or ids.dim() != 1 or row_off.dim() != 1:
+        raise ValueError('ids and row_off must be contiguous vectors')
+    R, N = ids.numel(), row_off.numel() - 1
+    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
+    if roh.shape != (N + 1,):
+        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
+    if workspace is None:
+        workspace = torch.empty(max(bert_workspace_bytes(R, N, model.width, model.intermediate, precision), 16), dtype=torch.uint8,
+                                device=ids.device)
+    if out is None:
+        out = torch.empty((N, model.width), device=ids.device, dtype=torch.float32)
+    if tuple(out.shape) != (N, model.width):
+        raise ValueError('out must be (%d, %d), got %s' % (N, model.width, tuple(out.shape)))
+    o, ldo = _rows(out, 'out')
+    lib, h = _context(ids.device)
+    _call('bert_encode', lib.laff_bert_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
           C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
     return out
 
