@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 27
+#define LAFF_ABI_VERSION 28
 
 enum {
     LAFF_OK = 0,
@@ -317,6 +317,25 @@ typedef struct laff_bert_text {
 int laff_bert_workspace_bytes(int R, int N, int width, int intermediate, int precision, size_t* out);
 int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const int* row_off_host, int N, int R, const laff_bert_text* model,
                      int precision, float* out, int ldo, void* workspace, size_t workspace_bytes);
+
+/* ---- text tower: the NetVLAD text encoder (NetVLADTxtEncoder, model/model.py:529-549; NetVLAD.forward, model/Attention.py:862-918) --
+ * Per caption, over its word2vec rows x_m: xh_m = x_m / max(|x_m|, 1e-12), a_m = softmax_k(xh_m . fc1_weight[k]) (no bias),
+ * u_k = sum_m a_mk xh_m - (sum_m a_mk) centroids[k]; each u_k / max(|u_k|, 1e-12), flattened k-major to K*D values, then the row
+ * / max(|row|, 1e-12).
+ * Captions come RAGGED: ids [R] int32 (rows of table [V, D]) concatenates the captions' distinct known words; row_off [N+1] int32
+ * (row_off[0] = 0, non-decreasing, row_off[N] = R) is passed TWICE: on the device for the kernels and in HOST memory for the checks
+ * (the same values).  zero_rows [N] int32 on the device: for a caption without ids, the number of all-zero rows it stands for (the
+ * reference's caption whose words are all unknown); ignored for a caption with ids.  A caption with no ids and no zero rows gives a
+ * zero row.  fc1_weight and centroids are [K, D] contiguous, read as they are (nothing to pack).
+ * out [N, ldo]: caption i's K*D values in row i.  workspace: laff_netvlad_workspace_bytes(R, K) bytes, 16-byte aligned.
+ * Limits: 1 <= K <= 64 (LAFF_E_UNSUPPORTED); D % 4 == 0, 4 <= D <= 1024 (LAFF_E_UNSUPPORTED); ldo % 4 == 0; table, centroids, out
+ * 16-byte aligned.  An id outside [0, V) makes its caption's row NaN instead of reading past the table.
+ * No allocation, no host synchronisation: capturable in a HIP graph.  A caption's row does not depend on the rest of its batch
+ * (bitwise). */
+int laff_netvlad_workspace_bytes(int R, int K, size_t* out);
+int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off, const int* row_off_host,
+                        const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, float* out, int ldo,
+                        void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

@@ -64,7 +64,8 @@ class config(object):
 
 def make_config(vid_dims, txt_dims, D=4096, heads=8, model_name='LAFF', vis_no_transform=(), txt_no_transform=(),
                 frame_feats=None, **overrides):
-    """vid_dims: {feature name: dim} in fusion order; txt_dims: subset of {'rnn','bert','bow','w2v','CLIP'} -> dim."""
+    """vid_dims: {feature name: dim} in fusion order; txt_dims: subset of {'rnn','bert','bow','w2v','CLIP'} -> dim, and optionally
+    'NetVLAD' -> number of clusters (its width is that times the w2v dim)."""
     c = config()
     c.model_name = model_name
     c.text_encoding = copy.deepcopy(config.text_encoding)
@@ -79,6 +80,9 @@ def make_config(vid_dims, txt_dims, D=4096, heads=8, model_name='LAFF', vis_no_t
     c.t2v_bow = T2V(txt_dims.get('bow', 0))
     c.t2v_w2v = T2V(txt_dims.get('w2v', 0))
     c.clip_opt = dict(config.clip_opt, size=txt_dims.get('CLIP', 512))
+    if 'NetVLAD' in txt_dims:
+        te['NetVLAD_encoding']['name'] = 'NetVLAD'
+        c.NetVLAD_opt = dict(config.NetVLAD_opt, num_clusters=int(txt_dims['NetVLAD']))
     fc0 = dict(vid_dims)
     c.vid_feats = list(vid_dims.keys())
     if frame_feats:

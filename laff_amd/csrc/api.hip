@@ -748,6 +748,55 @@ int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     return LAFF_OK;
 }
 
+namespace {
+// the NetVLAD encoder's workspace: soft assignments [R, K] fp32 | 1 / max(|x|, eps) [R] fp32, each region on 256 bytes
+size_t netvlad_rnorm_offset(int R, int K) { return ((size_t)R * K * sizeof(float) + 255) / 256 * 256; }
+size_t netvlad_ws_bytes(int R, int K) { return netvlad_rnorm_offset(R, K) + ((size_t)R * sizeof(float) + 255) / 256 * 256; }
+int netvlad_check_k(const char* fn, int K) {
+    if (K < 1 || K > laff::NETVLAD_MAX_K)
+        return fail(LAFF_E_UNSUPPORTED, "%s: K=%d: the number of clusters must be in [1, %d]", fn, K, laff::NETVLAD_MAX_K);
+    return LAFF_OK;
+}
+}  // namespace
+
+int laff_netvlad_workspace_bytes(int R, int K, size_t* out) {
+    if (!out || R < 0) return fail(LAFF_E_ARG, "laff_netvlad_workspace_bytes: bad args");
+    if (int rc = netvlad_check_k("laff_netvlad_workspace_bytes", K)) return rc;
+    *out = netvlad_ws_bytes(R, K);
+    return LAFF_OK;
+}
+
+int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off, const int* row_off_host,
+                        const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, float* out, int ldo,
+                        void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_netvlad_encode";
+    // every argument is checked before any GPU work
+    if (int rc = netvlad_check_k(fn, K)) return rc;
+    if (D < 4 || D > laff::NETVLAD_MAX_D || D % 4)
+        return fail(LAFF_E_UNSUPPORTED, "%s: D=%d: the word-vector width must be a multiple of 4 in [4, %d]", fn, D, laff::NETVLAD_MAX_D);
+    if (N < 0 || R < 0 || V < 1) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d V=%d", fn, N, R, V);
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
+    if (!table || (R && !ids) || !row_off || !row_off_host || !zero_rows || !fc1_weight || !centroids || !out || (R && !workspace))
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
+    for (int i = 0; i < N; ++i)
+        if (row_off_host[i + 1] < row_off_host[i])
+            return fail(LAFF_E_ARG, "%s: row_off decreases at caption %d (%d -> %d)", fn, i, row_off_host[i], row_off_host[i + 1]);
+    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (ldo < K * D || ldo % 4) return fail(LAFF_E_SHAPE, "%s: ldo=%d: at least K*D=%d and a multiple of 4", fn, ldo, K * D);
+    const size_t need = netvlad_ws_bytes(R, K);
+    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
+    if (!aligned16(table) || !aligned16(centroids) || !aligned16(fc1_weight) || !aligned16(out) || !aligned16(workspace))
+        return fail(LAFF_E_ALIGN, "%s: table / fc1_weight / centroids / out / workspace must be 16-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    float* ws = (float*)workspace;
+    laff::NetvladArgs a{table, V, D, K, ids, row_off, zero_rows, N, R, fc1_weight, centroids, ws,
+                        (float*)((char*)workspace + netvlad_rnorm_offset(R, K)), out, ldo};
+    HIP_TRY(laff::launch_netvlad_encode(a, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

@@ -377,4 +377,23 @@ struct BertEncodeArgs {
 };
 hipError_t launch_bert_encode(const BertEncodeArgs& e, int fp16, hipStream_t st);
 
+// netvlad.hip: the NetVLAD text encoder (laff_netvlad_encode)
+constexpr int NETVLAD_MAX_K = 64;
+constexpr int NETVLAD_MAX_D = 1024;
+struct NetvladArgs {
+    const float* table;       // [V, D] word2vec rows
+    int V, D, K;
+    const int* ids;           // [R] table rows, caption i's are ids[row_off[i] .. row_off[i+1])
+    const int* row_off;       // [N+1]
+    const int* zero_rows;     // [N] zero rows of a caption without known words
+    int N, R;
+    const float* fc1;         // [K, D]
+    const float* centroids;   // [K, D]
+    float* assign;            // workspace: [R, K] soft assignments
+    float* rnorm;             // workspace: [R] 1 / max(|x|, eps)
+    float* out;
+    long ldo;
+};
+hipError_t launch_netvlad_encode(const NetvladArgs& a, hipStream_t st);
+
 }  // namespace laff

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
 
-__all__ = ['bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -360,6 +360,52 @@ def bert_encode(ids, row_off, row_off_host, model, precision='fp32', out=None, w
     lib, h = _context(ids.device)
     _call('bert_encode', lib.laff_bert_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
           C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
+    return out
+
+
+def netvlad_workspace_bytes(R, K):
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_netvlad_workspace_bytes(int(R), int(K), C.byref(n)))
+    return n.value
+
+
+def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, out=None, workspace=None):
+    """laff_netvlad_encode.  table [V, D] fp32 (word2vec rows), ids [R] int32, row_off [N+1] int32 and zero_rows [N] int32 on the
+    device, row_off_host: the same offsets as a host int32 array; fc1_weight / centroids [K, D] fp32.  Returns out [N, K*D] fp32.
+    workspace: a uint8 device tensor of netvlad_workspace_bytes(R, K) bytes, or None to allocate one here (pass one for HIP-graph
+    capture)."""
+    table, fc1_weight, centroids = _dev(table, 'table'), _dev(fc1_weight, 'fc1_weight'), _dev(centroids, 'centroids')
+    ids, row_off = _dev(ids, 'ids', torch.int32), _dev(row_off, 'row_off', torch.int32)
+    zero_rows = _dev(zero_rows, 'zero_rows', torch.int32)
+    for t, nm in ((table, 'table'), (fc1_weight, 'fc1_weight'), (centroids, 'centroids'), (ids, 'ids'), (row_off, 'row_off'),
+                  (zero_rows, 'zero_rows')):
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % nm)
+    if table.dim() != 2 or ids.dim() != 1 or row_off.dim() != 1:
+        raise ValueError('table must be [V, D], ids and row_off vectors')
+    V, D = table.shape
+    K = fc1_weight.shape[0]
+    if tuple(fc1_weight.shape) != (K, D) or tuple(centroids.shape) != (K, D):
+        raise ValueError('fc1_weight and centroids must both be [K, %d], got %s and %s' % (D, tuple(fc1_weight.shape),
+                                                                                           tuple(centroids.shape)))
+    R, N = ids.numel(), row_off.numel() - 1
+    if zero_rows.numel() != N:
+        raise ValueError('zero_rows has %d entries for %d captions' % (zero_rows.numel(), N))
+    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
+    if roh.shape != (N + 1,):
+        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
+    if workspace is None:
+        workspace = torch.empty(max(netvlad_workspace_bytes(R, K), 16), dtype=torch.uint8, device=table.device)
+    if out is None:
+        out = torch.empty((N, K * D), device=table.device, dtype=torch.float32)
+    if tuple(out.shape) != (N, K * D):
+        raise ValueError('out must be (%d, %d), got %s' % (N, K * D, tuple(out.shape)))
+    o, ldo = _rows(out, 'out')
+    lib, h = _context(table.device)
+    _call('netvlad_encode', lib.laff_netvlad_encode, h, _ptr(table), V, D, _ptr(ids), _ptr(row_off),
+          roh.ctypes.data_as(C.POINTER(C.c_int)), _ptr(zero_rows), N, R, _ptr(fc1_weight), _ptr(centroids), K, _ptr(o), ldo,
+          _ptr(workspace), workspace.numel())
     return out
 
 

@@ -10,6 +10,9 @@ gather-sum on the GPU (`laff_fc_gather_act_bn`): bow -> a CSR count matrix that 
 Stop words are DATA of the deployment (the reference ships `stopwords_en.txt`); pass them in (`stopwords=`), e.g.
 `set(open('stopwords_en.txt').read().split())`.
 
+The NetVLAD encoder (`NetVLADTxtEncoder`) shares the W2Vec object and its device table: the host maps captions to table rows
+(`W2Vec.ragged`), the soft assignment and the residual pooling run on the GPU (`laff_netvlad_encode`).
+
 The GRU encoder (`GruTxtEncoder`) keeps the same split: the host maps captions to token ids and lays the batch out the way the
 step kernel walks it (`IdxVec.batch`); the recurrence runs on the GPU (`laff_gru_encode`).
 """
@@ -152,10 +155,25 @@ class W2Vec(object):
         mat = np.fromfile(bf.binary_file, dtype=np.float32).reshape(bf.nr_of_images, bf.ndims)
         return cls(list(bf.names), mat, stopwords)
 
-    def _ids(self, caption):
+    def raw_ids(self, caption):
+        """The row set of the reference's W2Vec.raw_encoding (txt2vec.py:106-114): (the distinct known words' table rows in row
+        order, the number of tokens).  With no known word the reference returns that many zero rows instead."""
         words = tokenize(caption, self.clean, self.stopwords is not None, self.stopwords or ())
-        ids = sorted({self.index[w] for w in words if w in self.index})       # BigFile.read dedups and drops unknown names
+        return sorted({self.index[w] for w in words if w in self.index}), len(words)   # BigFile.read dedups, drops unknown names
+
+    def _ids(self, caption):
+        ids, _ = self.raw_ids(caption)
         return ids, [1.0 / max(1, len(ids))] * len(ids)
+
+    def ragged(self, captions):
+        """The captions as laff_netvlad_encode takes them: ids [R] int32 (raw_ids concatenated), row_off [N+1] int32 and zero_rows
+        [N] int32 (the token count of a caption without known words, else 0)."""
+        rows = [self.raw_ids(c) for c in captions]
+        row_off = np.zeros(len(rows) + 1, np.int32)
+        row_off[1:] = np.cumsum([len(ids) for ids, _ in rows])
+        ids = np.fromiter((i for r, _ in rows for i in r), np.int32, int(row_off[-1]))
+        zero_rows = np.array([0 if r else n for r, n in rows], np.int32)
+        return ids, row_off, zero_rows
 
     def encoding(self, caption):
         ids, _ = self._ids(caption)
@@ -201,6 +219,52 @@ class W2VTxtEncoder(nn.Module):
 
     def forward(self, caption_feat_dict, task3=False):
         return {'text_features': self.t2v_w2v.encode(caption_feat_dict['caption'], self.device)}
+
+
+class _NetVLAD(nn.Module):
+    """The parameters of model/Attention.py:862-884 NetVLAD under its names (fc1.weight [K, D], no bias; centeroids [K, D]) and its
+    initialisation.  alpha is kept as the reference keeps it: its forward does not use it."""
+
+    def __init__(self, feature_dim, num_clusters=32, alpha=100):
+        super().__init__()
+        self.num_clusters, self.dim, self.alpha = int(num_clusters), int(feature_dim), alpha
+        init_sc = 1.0 / np.sqrt(feature_dim)
+        self.fc1 = nn.Linear(self.dim, self.num_clusters, bias=False)
+        self.centeroids = nn.Parameter(init_sc * torch.randn(self.num_clusters, self.dim))
+        self.fc1.weight = nn.Parameter(init_sc * torch.randn(self.num_clusters, self.dim))
+
+
+class NetVLADTxtEncoder(nn.Module):
+    """Drop-in for model.model.NetVLADTxtEncoder (model/model.py:529-549), inference:
+    `txt_net.encoder.NetVLAD_encoder = NetVLADTxtEncoder(t2v_w2v, num_clusters, alpha)`, sharing the W2Vec (and its device table)
+    with W2VTxtEncoder.  State-dict keys are the reference's (netvlad.fc1.weight, netvlad.centeroids), so its checkpoints load with
+    strict=True.  Output: {'text_features': (N, K * D)}.  The kernel reads the parameters as they are, so every change of them
+    (load_state_dict, copy_, a new Parameter) is seen by the next call."""
+
+    def __init__(self, t2v_w2v, num_clusters=32, alpha=100, device='cuda'):
+        super().__init__()
+        K, D = int(num_clusters), int(t2v_w2v.ndims)
+        if not 1 <= K <= 64:
+            raise NotImplementedError('NetVLADTxtEncoder: num_clusters=%d; the kernel takes 1 to 64 clusters' % K)
+        if D % 4 or not 4 <= D <= 1024:
+            raise NotImplementedError('NetVLADTxtEncoder: word-vector width %d; the kernel takes multiples of 4 up to 1024' % D)
+        self.t2v_w2v, self.device = t2v_w2v, device
+        self.netvlad = _NetVLAD(D, K, alpha).to(device)
+
+    def to_device(self, ids, row_off, zero_rows):
+        dev = self.netvlad.centeroids.device
+        return (torch.from_numpy(ids).to(dev), torch.from_numpy(row_off).to(dev), row_off, torch.from_numpy(zero_rows).to(dev))
+
+    def encode_batch(self, ids, row_off, row_off_host, zero_rows, out=None, workspace=None):
+        """The device half of forward(): W2Vec.ragged's arrays, ids / row_off / zero_rows already on the device."""
+        from . import ops
+        v = self.netvlad
+        return ops.netvlad_encode(self.t2v_w2v.device_table(self.device), ids, row_off, row_off_host, zero_rows,
+                                  v.fc1.weight.detach(), v.centeroids.detach(), out=out, workspace=workspace)
+
+    def forward(self, caption_feat_dict, task3=False):
+        b = self.to_device(*self.t2v_w2v.ragged(caption_feat_dict['caption']))
+        return {'text_features': self.encode_batch(*b)}
 
 
 GruBatch = collections.namedtuple('GruBatch', ['tokens', 'lengths', 'perm', 'batch_sizes'])
