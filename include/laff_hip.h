@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 28
+#define LAFF_ABI_VERSION 29
 
 enum {
     LAFF_OK = 0,
@@ -98,6 +98,39 @@ typedef struct {
     float* Y; int ldy;
 } laff_fc_problem;
 int laff_fc_act_bn_grouped(laff_ctx* ctx, const laff_fc_problem* problems /*host array*/, int count);
+
+/* ---- the W2VV++ "concat" towers (VisTransformNet model/model.py:279-308, MultiScaleTxtEncoder + MultiScaleTxtNet :683-726) --------
+ * Y[N,D] = (act(sum_s X_s . W[:, col_s : col_s + Dk_s]^T + bias)) * bn_scale + bn_shift          in ONE launch
+ * i.e. a1 on torch.cat(X_0 .. X_{n-1}, dim 1) without the concatenated matrix ever existing.  W is [D, K] with rows ldw apart and is
+ * read in place at each segment's column window.  A segment is
+ *   dense  (X != NULL):  X [N, Dk] fp32, rows ldx >= Dk apart; fp32 MFMA.  16-byte aligned rows (X, ldx, Dk and, for W's window,
+ *                        W, ldw, col multiples of 4 floats) take the direct-to-LDS loads, anything else goes through registers;
+ *   sparse (X == NULL):  CSR (indptr [N + 1], indices, values | NULL = ones) over Dk columns + Wt = the TRANSPOSED window
+ *                        [Dk, ldwt >= D] (one vocabulary entry = one contiguous row, as laff_fc_gather_act_bn takes it); added to the
+ *                        same accumulators with fp32 FMAs before bias / activation / BatchNorm.  `indices` are not validated (ids
+ *                        outside [0, Dk) contribute nothing); rows may be empty and may repeat a column.
+ * fp32-class arithmetic only: there is no 16-bit operand route.  Rows are bitwise independent of the batch they arrive in.
+ * Limits: 1 <= nseg <= 8, Dk >= 1, D % 4 == 0, 4 <= D <= 8192, ldy % 4 == 0 and Y / Wt 16-byte aligned, ldwt % 4 == 0, windows inside
+ * [0, K) and pairwise disjoint, ldw >= K (LAFF_E_ARG / LAFF_E_SHAPE / LAFF_E_ALIGN before any GPU work).  W may be NULL when every
+ * segment is sparse.  N == 0 is a successful no-op.  Allocates nothing, does not synchronise, can be captured in a graph. */
+typedef struct {
+    const float* X; int ldx;                                      /* dense segment (X == NULL: sparse) */
+    const int* indptr; const int* indices; const float* values;   /* sparse segment */
+    const float* Wt; int ldwt;
+    int Dk;                                                       /* width of the segment */
+    int col;                                                      /* first column of its window in W */
+} laff_fc_concat_segment;
+typedef struct {
+    const laff_fc_concat_segment* segments /*host array*/; int nseg;
+    int N;
+    const float* W; int K, ldw;                                   /* K: columns of W (sum of the widths, or more) */
+    const float* bias; const float* bn_scale; const float* bn_shift;
+    int D, act;
+    float* Y; int ldy;
+} laff_fc_concat_problem;
+int laff_fc_concat_act_bn(laff_ctx* ctx, const laff_fc_concat_problem* problem);
+/* up to 4 problems per launch (both sides' towers of a retrieval run as one launch); more are launched four at a time */
+int laff_fc_concat_act_bn_grouped(laff_ctx* ctx, const laff_fc_concat_problem* problems /*host array*/, int count);
 
 /* a1 on the 16-bit matrix pipe with fp32-class accuracy ("fp16x3"): both operands are split once into exact fp16
  * hi + lo parts with a per-row power-of-two scale (laff_split_rows); the GEMM accumulates lo*hi + hi*lo + hi*hi in fp32

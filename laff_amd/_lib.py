@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class Plane(C.Structure):
@@ -40,6 +40,17 @@ class FcProblem(C.Structure):
     _fields_ = [('X', C.c_void_p), ('N', C.c_int), ('Dk', C.c_int), ('ldx', C.c_int), ('W', C.c_void_p), ('ldw', C.c_int),
                 ('bias', C.c_void_p), ('bn_scale', C.c_void_p), ('bn_shift', C.c_void_p), ('D', C.c_int), ('act', C.c_int),
                 ('Y', C.c_void_p), ('ldy', C.c_int)]
+
+
+class FcConcatSegment(C.Structure):
+    _fields_ = [('X', C.c_void_p), ('ldx', C.c_int), ('indptr', C.c_void_p), ('indices', C.c_void_p), ('values', C.c_void_p),
+                ('Wt', C.c_void_p), ('ldwt', C.c_int), ('Dk', C.c_int), ('col', C.c_int)]
+
+
+class FcConcatProblem(C.Structure):
+    _fields_ = [('segments', C.POINTER(FcConcatSegment)), ('nseg', C.c_int), ('N', C.c_int), ('W', C.c_void_p), ('K', C.c_int),
+                ('ldw', C.c_int), ('bias', C.c_void_p), ('bn_scale', C.c_void_p), ('bn_shift', C.c_void_p), ('D', C.c_int),
+                ('act', C.c_int), ('Y', C.c_void_p), ('ldy', C.c_int)]
 
 
 class FcSplitProblem(C.Structure):
@@ -93,6 +104,8 @@ SIGNATURES = {
     'laff_fc_act_bn': (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _P, _I]),
     'laff_fc_act_bn_grouped': (C.c_int, [_P, C.POINTER(FcProblem), _I]),
     'laff_fc_gather_act_bn': (C.c_int, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _P, _I]),
+    'laff_fc_concat_act_bn': (C.c_int, [_P, C.POINTER(FcConcatProblem)]),
+    'laff_fc_concat_act_bn_grouped': (C.c_int, [_P, C.POINTER(FcConcatProblem), _I]),
     'laff_margin_loss_workspace_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_margin_loss': (C.c_int, [_P, _P, _P, _I, _I, _I, C.c_float, C.c_uint, _P, _P, _P, _P, C.c_size_t]),
     'laff_row_scales_grouped': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),

@@ -47,6 +47,7 @@ class config(object):
     txt_expert_embedding = {'expert': False, 'l2norm': False}
     vis_expert_embedding = {'expert': False, 'l2norm': False}
     vis_feat_add_concat = False
+    txt_fc_same_with_vis_fc = False
     multi_head_attention = {'dropout': 0.0, 'heads': 8, 'embed_dim_qkv': 512}
     attention_param_each_head = {'with_ave': False, 'mul': False, 'split_head': True}
     txt_attention_global_decay_rate = 0.8

@@ -253,6 +253,79 @@ int laff_fc_act_bn_grouped(laff_ctx* ctx, const laff_fc_problem* problems, int c
     return LAFF_OK;
 }
 
+/* checks problem i of a concat launch and, when it is not empty, turns it into the kernel's form */
+static int fc_concat_problem_args(const laff_fc_concat_problem& q, laff::ConcatProblem& a, const char* who, int i) {
+    if (q.N < 0) return fail(LAFF_E_ARG, "%s: problem %d: negative N=%d", who, i, q.N);
+    if (q.N == 0) { a = laff::ConcatProblem{}; return LAFF_OK; }              /* empty problem (skipped): pointers may be null */
+    if (!q.segments || q.nseg < 1 || q.nseg > laff::CONCAT_MAX_SEG)
+        return fail(LAFF_E_ARG, "%s: problem %d: need 1 <= nseg <= %d segments (nseg=%d)", who, i, laff::CONCAT_MAX_SEG, q.nseg);
+    if (q.D < 4 || (q.D & 3) || q.D > 8192 || q.ldy < q.D || (q.ldy & 3) || q.K < 1)
+        return fail(LAFF_E_SHAPE, "%s: problem %d: need D %% 4 == 0, 4 <= D <= 8192, ldy >= D, ldy %% 4 == 0, K >= 1 (D=%d ldy=%d K=%d)", who,
+                    i, q.D, q.ldy, q.K);
+    if (int rc = check_epilogue(who, i, q.act, q.bias, q.bn_scale, q.bn_shift, false)) return rc;
+    a = laff::ConcatProblem{};
+    bool dense = false;
+    for (int s = 0; s < q.nseg; ++s) {
+        const laff_fc_concat_segment& g = q.segments[s];
+        if (g.Dk < 1) return fail(LAFF_E_SHAPE, "%s: problem %d: segment %d has width Dk=%d", who, i, s, g.Dk);
+        if (g.col < 0 || (long long)g.col + g.Dk > q.K)
+            return fail(LAFF_E_SHAPE, "%s: problem %d: segment %d: columns [%d, %lld) are outside W's K=%d", who, i, s, g.col,
+                        (long long)g.col + g.Dk, q.K);
+        for (int t = 0; t < s; ++t) {
+            const laff_fc_concat_segment& h = q.segments[t];
+            if (g.col < h.col + h.Dk && h.col < g.col + g.Dk)
+                return fail(LAFF_E_SHAPE, "%s: problem %d: segments %d and %d overlap in W's columns", who, i, t, s);
+        }
+        if (g.X) {
+            if (g.ldx < g.Dk) return fail(LAFF_E_SHAPE, "%s: problem %d: segment %d: ldx=%d < Dk=%d", who, i, s, g.ldx, g.Dk);
+            dense = true;
+            laff::ConcatDense& d = a.d[a.nd++];
+            d.X = g.X; d.ldx = g.ldx; d.dk = g.Dk; d.c0 = g.col;
+            d.fast = ((aligned16(g.X) && g.ldx % 4 == 0 && g.Dk % 4 == 0) ? 1 : 0) |
+                     ((q.W && aligned16(q.W) && q.ldw % 4 == 0 && g.col % 4 == 0 && g.Dk % 4 == 0) ? 2 : 0);
+        } else {
+            if (!g.indptr || !g.indices || !g.Wt)
+                return fail(LAFF_E_ARG, "%s: problem %d: segment %d: null X and null indptr / indices / Wt", who, i, s);
+            if (g.ldwt < q.D || (g.ldwt & 3))
+                return fail(LAFF_E_SHAPE, "%s: problem %d: segment %d: need ldwt >= D, ldwt %% 4 == 0 (ldwt=%d D=%d)", who, i, s, g.ldwt, q.D);
+            if (!aligned16(g.Wt)) return fail(LAFF_E_ALIGN, "%s: problem %d: segment %d: Wt must be 16-byte aligned", who, i, s);
+            laff::ConcatSparse& p = a.s[a.ns++];
+            p.indptr = g.indptr; p.indices = g.indices; p.values = g.values; p.wt = g.Wt; p.ldwt = g.ldwt; p.dk = g.Dk;
+        }
+    }
+    if (dense && (q.ldw < q.K)) return fail(LAFF_E_SHAPE, "%s: problem %d: ldw=%d < K=%d", who, i, q.ldw, q.K);
+    if ((dense && !q.W) || !q.Y) return fail(LAFF_E_ARG, "%s: problem %d: null W / Y", who, i);
+    if (!aligned16(q.Y)) return fail(LAFF_E_ALIGN, "%s: problem %d: Y must be 16-byte aligned", who, i);
+    a.W = q.W; a.bias = q.bias; a.bn_scale = q.bn_scale; a.bn_shift = q.bn_shift; a.Y = q.Y;
+    a.N = q.N; a.D = q.D; a.ldw = q.ldw; a.ldy = q.ldy; a.act = q.act;
+    return LAFF_OK;
+}
+
+int laff_fc_concat_act_bn_grouped(laff_ctx* ctx, const laff_fc_concat_problem* problems, int count) {
+    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_concat_act_bn_grouped: bad problem list");
+    std::vector<laff::ConcatProblem> live;
+    for (int i = 0; i < count; ++i) {               /* every problem is checked before anything is launched */
+        laff::ConcatProblem a;
+        if (int rc = fc_concat_problem_args(problems[i], a, "laff_fc_concat_act_bn_grouped", i)) return rc;
+        if (problems[i].N > 0) live.push_back(a);
+    }
+    CHECK_CTX(ctx);
+    if (live.empty()) return LAFF_OK;
+    DeviceGuard g(ctx->device);
+    for (size_t i0 = 0; i0 < live.size(); i0 += laff::CONCAT_MAX_GROUP) {
+        laff::ConcatArgs ca{};
+        ca.count = (int)std::min(live.size() - i0, (size_t)laff::CONCAT_MAX_GROUP);
+        for (int j = 0; j < ca.count; ++j) ca.p[j] = live[i0 + j];
+        HIP_TRY(laff::launch_fc_concat(ca, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
+int laff_fc_concat_act_bn(laff_ctx* ctx, const laff_fc_concat_problem* problem) {
+    if (!problem) return fail(LAFF_E_ARG, "laff_fc_concat_act_bn: null problem");
+    return laff_fc_concat_act_bn_grouped(ctx, problem, 1);
+}
+
 int laff_fc_gather_act_bn(laff_ctx* ctx, const int* indptr, const int* indices, const float* values, int N, int Dk,
                           const float* Wt, int ldwt, const float* bias, const float* bn_scale, const float* bn_shift, int D,
                           int act, float* Y, int ldy) {

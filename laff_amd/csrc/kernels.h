@@ -126,6 +126,39 @@ hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, cons
                                 void* img, hipStream_t st);
 hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st);
 
+// ---- concat tower (fc_concat.hip): Y = bn(act(sum_s X_s . W[:, c_s : c_s + Dk_s]^T + bias)), dense + CSR segments, one launch ------
+constexpr int CONCAT_MAX_SEG = 8;        // segments per problem, dense and sparse together
+constexpr int CONCAT_MAX_GROUP = 4;      // problems per launch (the launch arguments stay below the 4 KiB kernel-argument limit)
+struct ConcatDense {
+    const float* X;           // [N][ldx] fp32
+    int ldx, dk, c0;          // c0: first column of W's window
+    int fast;                 // bit 0: X rows take the LDS-DMA path, bit 1: W's window does
+};
+struct ConcatSparse {
+    const int* indptr;        // CSR over dk columns
+    const int* indices;
+    const float* values;      // null = ones
+    const float* wt;          // [dk][ldwt >= D]: the transposed column block
+    int ldwt, dk;
+};
+struct ConcatProblem {
+    const float* W;           // [D][ldw], read in place at every dense segment's column offset
+    const float* bias;
+    const float* bn_scale;
+    const float* bn_shift;
+    float* Y;                 // [N][ldy]
+    int N, D, ldw, ldy, act;
+    int nd, ns;               // dense / sparse segments, each in list order
+    ConcatDense d[CONCAT_MAX_SEG];
+    ConcatSparse s[CONCAT_MAX_SEG];
+};
+struct ConcatArgs {
+    int count;
+    int tile_start[CONCAT_MAX_GROUP + 1];     // filled by launch_fc_concat
+    ConcatProblem p[CONCAT_MAX_GROUP];
+};
+hipError_t launch_fc_concat(ConcatArgs& a, hipStream_t st);
+
 // the kernel launch_gemm_nt runs for these arguments (LAFF_ROUTE_*, include/laff_hip.h); launches nothing
 int gemm_route(const GemmArgs& a, int mode, bool aligned);
 hipError_t launch_gemm_nt(const GemmArgs& a, int mode, bool aligned, hipStream_t st);

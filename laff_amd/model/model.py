@@ -10,6 +10,8 @@ as /root/reference/model/model.py for the symbols on the hot path (SURVEY.md sec
   VisMutiTransformNetPlusFrameFeat     :2101-2194   -> laff_frame_fuse instead of the per-sample Python loop
   W2VVPP.get_txt2vis_matrix / predict  :1003-1128   -> one laff_sim_gemm over all pairs instead of the
                                                        (Nt/bs)x(Nv/bs) block loop; embeddings stay in HBM
+  VisTransformNet                      :279-308     -> laff_fc_concat_act_bn: the W2VV++ concat towers, one segmented-K launch,
+  MultiScaleTxtEncoder / MultiScaleTxtNet :552-726     the concatenated input never formed
   get_model                            :2501-2519
 
 Inference only: training (forward(), losses, optimisers) is out of scope and raises.
@@ -88,9 +90,21 @@ def coalesce_batches(batches):
 
 
 def run_fc(pending):
-    """Launch every queued FC projection; returns their outputs in the order of `pending`.  fp32: one grouped GEMM.  fp16x3: oversized
-    problems are cut into row chunks, then each problem goes to the strip form, the fused split or the materialised split: one launch
-    per form that has problems."""
+    """Launch every queued FC projection; returns their outputs in the order of `pending`.  Concat-tower problems (a 'segments' list:
+    VisTransformNet / MultiScaleTxtNet) run as ONE segmented-K launch, in fp32 arithmetic whatever FC_PRECISION says (that kernel has
+    no 16-bit operand route); the per-feature projections as before."""
+    concat = [q for q in pending if 'segments' in q]
+    if not concat:
+        return _run_fc_features(pending)
+    ops.fc_concat_act_bn_grouped(concat)
+    rest = [q for q in pending if 'segments' not in q]
+    done = dict(zip(map(id, rest), _run_fc_features(rest))) if rest else {}
+    return [q['out'] if 'segments' in q else done[id(q)] for q in pending]
+
+
+def _run_fc_features(pending):
+    """fp32: one grouped GEMM.  fp16x3: oversized problems are cut into row chunks, then each problem goes to the strip form, the fused
+    split or the materialised split: one launch per form that has problems."""
     if FC_PRECISION == 'fp32':
         return ops.fc_act_bn_grouped(pending)
     if FC_PRECISION != 'fp16x3':
@@ -210,6 +224,45 @@ class TransformNet(nn.Module):
             self._w_t = (key, w.detach().t().contiguous())
         return self._w_t[1]
 
+    def weight_t_block(self, col, width):
+        """Columns [col, col + width) of fc1.weight transposed ([width, D]): the block a sparse segment of a concat tower gathers from,
+        cached until the weight changes."""
+        w = self.fc1.weight
+        key = (w.data_ptr(), w._version)
+        if getattr(self, '_w_t_blocks', None) is None or self._w_t_blocks[0] != key:
+            self._w_t_blocks = (key, {})
+        blocks = self._w_t_blocks[1]
+        if (col, width) not in blocks:
+            blocks[(col, width)] = w.detach()[:, col:col + width].t().contiguous()
+        return blocks[(col, width)]
+
+    def concat_problem(self, segments, pending=None):
+        """This layer applied to torch.cat(segments, dim=1) without forming it (laff_fc_concat_act_bn): queued on `pending` for the
+        caller's run_fc(), or run now.  segments: dense fp32 matrices and / or torch.sparse_csr ones, in column order.  Always fp32
+        arithmetic, also with FC_PRECISION == 'fp16x3'.  Returns the (N, D) output (filled once the launch has run)."""
+        _eval_only(self)
+        segs, wt, col = [], {}, 0
+        for j, x in enumerate(segments):
+            if x.layout == torch.sparse_csr:
+                x = x.to(device)
+                wt[j] = self.weight_t_block(col, x.shape[1])
+            else:
+                x = to_device_and_float16(x)
+            segs.append(x)
+            col += x.shape[1]
+        if col != self.fc1.in_features:
+            raise ValueError('the concatenated input has %d columns, fc1 takes %d' % (col, self.fc1.in_features))
+        scale, shift = self.bn_affine(None)
+        out = torch.empty((segs[0].shape[0], self.out_features), device=segs[0].device, dtype=torch.float32)
+        prob = dict(segments=segs, weight=self.fc1.weight.detach(), weight_t=wt,
+                    bias=self.fc1.bias.detach() if self.fc1.bias is not None else None,
+                    bn_scale=scale, bn_shift=shift, activation=self.activation_name, out=out)
+        if pending is None:
+            run_fc([prob])
+        else:
+            pending.append(prob)
+        return out
+
     def weight_split(self):
         """fp16 hi/lo split of fc1.weight for FC_PRECISION == 'fp16x3', cached until the weight changes."""
         if FC_PRECISION != 'fp16x3':
@@ -268,6 +321,23 @@ class TransformNet(nn.Module):
         out = ops.fuse([(src, tile, scale, shift)], 1, src.shape[1], None, None, None,
                        ops.attention_flags(just_average=True))
         return out.view(out.shape[0], -1)
+
+
+class VisTransformNet(TransformNet):
+    """The W2VV++ video tower (model/model.py:279-308): one TransformNet over the concatenated video features.  The features stay
+    where they are: each is a segment of the K loop of one laff_fc_concat_act_bn launch."""
+
+    def __init__(self, opt):
+        super().__init__((int(np.sum(list(opt.vis_fc_layers[0].values()))), opt.vis_fc_layers[1]), opt)
+
+    def prepare(self, vis_input, vis_frame_feat_dict_input=None, pending=None):
+        """Queue the projection on `pending`; returns the closure that hands the embeddings over once run_fc() has run."""
+        segments = list(vis_input.values()) if isinstance(vis_input, dict) else [vis_input]     # dict order, as torch.cat(list(...))
+        out = self.concat_problem(segments, pending)
+        return lambda: out
+
+    def forward(self, vis_input, txt_emb=None, vis_frame_feat_dict_input=None):
+        return self.prepare(vis_input)()
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -401,9 +471,79 @@ class PreExtractedEncoder(nn.Module):
         return {'text_features': caption_feat_dict[self.key]}
 
 
+ENCODER_KEYS = {'rnn_encoder': 'rnn_encoding', 'bert_encoder': 'bert_encoding', 'bow_encoder': 'bow_encoding',
+                'w2v_encoder': 'w2v_encoding', 'CLIP_encoder': 'CLIP_encoding', 'NetVLAD_encoder': 'NetVLAD_encoding'}
+
+
+class MultiScaleTxtEncoder(nn.Module):
+    """The text encoders of the W2VV++ tower (model/model.py:552-700) under `encoder.<name>`, in the reference's fixed order rnn,
+    bert, bow, w2v, CLIP, NetVLAD: PreExtractedEncoder placeholders, replaced by plugging a module that returns
+    {'text_features': tensor} (laff_amd.txt2vec, clip_text, bert_text) into `encoder.<name>`.  A sparse-CSR bow feature stays sparse.
+    (NetVLAD: the width is w2v dims x clusters, what the encoder emits; the reference's space_dict entry lacks the cluster factor.)"""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        te = opt.text_encoding
+        rnn = te['rnn_encoding']['name'].split('_', 1)[0]
+        self.space_dict = {}
+        if rnn == 'gru':
+            self.space_dict['rnn_encoder'] = opt.rnn_size
+        elif rnn == 'bigru':
+            self.space_dict['rnn_encoder'] = opt.rnn_size * 2
+        if te['bert_encoding']['name'] != 'noBert':
+            self.space_dict['bert_encoder'] = opt.bert_size
+        if 'no' not in te['bow_encoding']['name']:
+            self.space_dict['bow_encoder'] = opt.t2v_bow.ndims
+        if 'no' not in te['w2v_encoding']['name']:
+            self.space_dict['w2v_encoder'] = opt.t2v_w2v.ndims
+        if 'no' not in te['CLIP_encoding']['name']:
+            self.space_dict['CLIP_encoder'] = opt.clip_opt['size']
+        if 'no' not in te['NetVLAD_encoding']['name']:
+            self.space_dict['NetVLAD_encoder'] = opt.t2v_w2v.ndims * opt.NetVLAD_opt['num_clusters']
+        self.encoder = nn.Module()
+        for name in self.space_dict:
+            self.encoder.add_module(name, PreExtractedEncoder(ENCODER_KEYS[name]))
+        self.encoder_name_list = list(self.space_dict.keys())
+        self.txt_encoder_num = len(self.encoder_name_list)
+
+    def segments(self, caption_feat_dict, task3=False):
+        """The encoders' outputs in encoder order: the segments of the concatenated text feature."""
+        out = []
+        for name in self.encoder_name_list:
+            feats = getattr(self.encoder, name)(caption_feat_dict, task3=task3)['text_features']
+            if feats.shape[1] != self.space_dict[name]:
+                raise ValueError("text feature '%s' has %d columns, the config says %d" % (name, feats.shape[1], self.space_dict[name]))
+            out.append(feats)
+        return out
+
+    def forward(self, caption_feat_dict, task3=False):
+        """The concatenated feature itself, as the reference returns it (the tower does not go through this: MultiScaleTxtNet)."""
+        return torch.cat([to_device_and_float16(f.to_dense() if f.layout == torch.sparse_csr else f)
+                          for f in self.segments(caption_feat_dict, task3)], dim=1)
+
+
+class MultiScaleTxtNet(nn.Module):
+    """The W2VV++ text tower (model/model.py:703-726): `encoder` + one TransformNet `transformer` over the concatenated features,
+    run as one segmented launch (laff_fc_concat_act_bn).  Sets opt.txt_fc_layers[0] to the summed width like the reference."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.encoder = MultiScaleTxtEncoder(opt)
+        self.opt.txt_fc_layers[0] = int(sum(self.encoder.space_dict.values()))
+        self.transformer = TransformNet(opt.txt_fc_layers, opt, opt.dropout, opt.batch_norm, opt.activation)
+
+    def prepare(self, caption_feat_dict, pending=None, task3=False):
+        out = self.transformer.concat_problem(self.encoder.segments(caption_feat_dict, task3), pending)
+        return lambda: out
+
+    def forward(self, caption_feat_dict, visual_emb=None, task3=False):
+        return self.prepare(caption_feat_dict, task3=task3)()
+
+
 class MultiScaleTxtEncoderAttention(nn.Module):
-    ENCODER_KEYS = {'rnn_encoder': 'rnn_encoding', 'bert_encoder': 'bert_encoding', 'bow_encoder': 'bow_encoding',
-                    'w2v_encoder': 'w2v_encoding', 'CLIP_encoder': 'CLIP_encoding', 'NetVLAD_encoder': 'NetVLAD_encoding'}
+    ENCODER_KEYS = ENCODER_KEYS
 
     def __init__(self, opt):
         super().__init__()
@@ -601,10 +741,12 @@ class W2VVPP(nn.Module):
     sim_precision = None
 
     def _init_vis_net(self, opt):
-        raise NotImplementedError
+        self.vis_net = VisTransformNet(opt)
 
     def _init_txt_net(self, opt):
-        raise NotImplementedError
+        if getattr(opt, 'txt_fc_same_with_vis_fc', False):
+            raise NotImplementedError('txt_fc_same_with_vis_fc (one FC shared by both towers, model/model.py:764-768) is not supported')
+        self.txt_net = MultiScaleTxtNet(opt)
 
     def __init__(self, opt):
         super().__init__()
@@ -737,6 +879,8 @@ class W2VVPP(nn.Module):
             identity = np.array_equal(cols, np.arange(len(cols)))
             if not identity:   # the reference indexes the cached embeddings BY dataset index (:1066)
                 vis_used = self.video_all_embs[torch.as_tensor(cols, device=self.video_all_embs.device)]
+            if txt_all.dim() != vis_used.dim():      # a concat (2-D) side against a multi-head (3-D) one: as get_txt2vis_matrix
+                raise ValueError('txt_embs %s / vis_embs %s' % (tuple(txt_all.shape), tuple(vis_used.shape)))
             self.last_t2v_ranks = None
             self.last_rank_state = None          # ops.RankState of the exact-rank pass: predictor.retrieval_metrics(S, ..., state=) ranks V2T exactly with it
             owner = None
@@ -814,12 +958,12 @@ class W2VVPP(nn.Module):
 class W2VVPP_MutiVis(W2VVPP):
     def _init_txt_net(self, opt):
         if opt.txt_attention == 'concat':
-            raise NotImplementedError("txt_attention 'concat' (MultiScaleTxtNet) is outside the LAFF hot path")
+            return super()._init_txt_net(opt)
         self.txt_net = MultiScaleTxtEncoderAttention(opt)
 
     def _init_vis_net(self, opt):
         if opt.vis_attention == 'concat':
-            raise NotImplementedError("vis_attention 'concat' (VisTransformNet) is outside the LAFF hot path")
+            return super()._init_vis_net(opt)
         self.vis_net = VisMutiTransformNetAddAttnetion(opt, opt.vis_fc_layers[0])
 
     def change_raw_global_emb_weight(self):
@@ -862,11 +1006,12 @@ def get_model(name, device_, config):
     device = torch.device(device_)
     float16 = config.float16
     NAME_TO_MODELS = {
+        'W2VVPP': W2VVPP,
         'FrameLAFF': W2VVPP_MutiVisFrameFeat,
         'w2vpp_mutivis_attention': W2VVPP_MutiVis,
         'LAFF': W2VVPP_MultiHeadAttention,
     }
-    if name in ('W2VVPP', 'End2EndClip'):
+    if name == 'End2EndClip':
         raise NotImplementedError("model '%s' is outside the LAFF hot path (SURVEY.md section 2)" % name)
     assert name in NAME_TO_MODELS, '%s not supported.' % name
     model_ = NAME_TO_MODELS[name](config)

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
-                   FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide)
+                   FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment)
 
 __all__ = ['netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
@@ -178,6 +178,70 @@ def fc_gather_act_bn(x_csr, weight_t, bias=None, bn_scale=None, bn_shift=None, a
     _call('fc_gather', lib.laff_fc_gather_act_bn, h, _ptr(crow), _ptr(col), _ptr(val), N, Dk, _ptr(wt), ldwt, _ptr(bias),
           _ptr(bn_scale), _ptr(bn_shift), D, ACT[activation], _ptr(out), D)
     return out
+
+
+def fc_concat_act_bn(segments, weight, bias=None, bn_scale=None, bn_shift=None, activation=None, out=None, weight_t=None):
+    """Y = act(cat(segments, dim 1) @ weight.T + bias) * bn_scale + bn_shift without forming the concatenation (the W2VV++ towers)."""
+    return fc_concat_act_bn_grouped([dict(segments=segments, weight=weight, bias=bias, bn_scale=bn_scale, bn_shift=bn_shift,
+                                          activation=activation, out=out, weight_t=weight_t)])[0]
+
+
+def fc_concat_act_bn_grouped(problems):
+    """Several concat projections (both towers of a retrieval) in one launch.  problems: dicts with
+        segments  list of 2-D fp32 CUDA matrices (contiguous rows, any row stride) and / or torch.sparse_csr matrices, all of N rows,
+                  in the order their columns have in `weight`
+        weight    (D, sum of the segment widths) fp32, read in place
+        weight_t  optional {segment index: (width, ld >= D) transposed column block} for the sparse segments; a missing one is
+                  made here (callers that keep the model cache it)
+      and optional bias, bn_scale, bn_shift, activation, out.  fp32 arithmetic whatever FC_PRECISION says.  Returns the outputs."""
+    if not problems:
+        return []
+    arr = (FcConcatProblem * len(problems))()
+    outs, keep = [], []
+    dev = None
+    for i, q in enumerate(problems):
+        segs = list(q['segments'])
+        w, ldw = _rows(q['weight'], 'weight')
+        D, K = w.shape
+        dev = w.device
+        if not segs:
+            raise ValueError('problem %d: no segments' % i)
+        N = segs[0].shape[0]
+        sarr = (FcConcatSegment * len(segs))()
+        col = 0
+        for j, x in enumerate(segs):
+            if x.dim() != 2 or x.shape[0] != N:
+                raise ValueError('problem %d: segment %d is %s, expected %d rows' % (i, j, tuple(x.shape), N))
+            Dk = x.shape[1]
+            if x.layout == torch.sparse_csr:
+                if not x.is_cuda:
+                    raise RuntimeError('problem %d: segment %d must be a CUDA torch.sparse_csr tensor' % (i, j))
+                wt = (q.get('weight_t') or {}).get(j)
+                if wt is None:
+                    wt = w[:, col:col + Dk].t().contiguous()
+                wt, ldwt = _rows(wt, 'weight_t')
+                if wt.shape[0] != Dk or wt.shape[1] != D:
+                    raise ValueError('problem %d: weight_t of segment %d is %s, expected (%d, %d)' % (i, j, tuple(wt.shape), Dk, D))
+                crow = x.crow_indices().to(torch.int32).contiguous()
+                cidx = x.col_indices().to(torch.int32).contiguous()
+                val = x.values().to(torch.float32).contiguous()
+                keep += [wt, crow, cidx, val]
+                sarr[j] = FcConcatSegment(None, 0, crow.data_ptr(), cidx.data_ptr(), val.data_ptr(), wt.data_ptr(), ldwt, Dk, col)
+            else:
+                x, ldx = _rows(x, 'segment')
+                sarr[j] = FcConcatSegment(x.data_ptr(), ldx, None, None, None, None, 0, Dk, col)
+            col += Dk
+        if col != K:
+            raise ValueError('problem %d: weight is %s but the segments have %d columns' % (i, tuple(w.shape), col))
+        vecs, out, ldy = _fc_epilogue(q, N, D, dev)
+        if tuple(out.shape) != (N, D):
+            raise ValueError('problem %d: out is %s, expected (%d, %d)' % (i, tuple(out.shape), N, D))
+        arr[i] = FcConcatProblem(sarr, len(segs), N, w.data_ptr(), K, ldw, *vecs, D, ACT[q.get('activation')], out.data_ptr(), ldy)
+        keep.append(sarr)
+        outs.append(out)
+    lib, h = _context(dev)
+    _call('fc_concat', lib.laff_fc_concat_act_bn_grouped, h, arr, len(problems))
+    return outs
 
 
 LOSS_FLAGS = {'max_violation': 1, 'mean': 2, 'i2t': 4, 't2i': 8}
