@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 29
+#define LAFF_ABI_VERSION 30
 
 enum {
     LAFF_OK = 0,
@@ -300,6 +300,41 @@ int laff_clip_image_workspace_bytes(int F, int width, int input_resolution, int 
 int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int* frame_off, const int* frame_off_host, int V,
                            const laff_clip_visual* model, int precision, float* out_frames, int ldo, float* out_mean, int ldm,
                            void* workspace, size_t workspace_bytes);
+
+/* ---- video tower: frame preprocessing, decoded frames -> the image encoder's pixels (clip._transform, model/clip/clip.py:58-65:
+ * Resize(R, BICUBIC), CenterCrop(R), ToTensor, Normalize through torchvision on Pillow; data_provider.py:274-281 the bilinear variant) --
+ * frames: F ragged frames as packed HWC uint8 RGB in one buffer of frames_bytes bytes; frame f is `height x width x 3` bytes at byte
+ * `offset` of its descriptor (ANY byte offset: the kernel reads bytes).  desc [F] is passed TWICE: on the device for the kernel and in
+ * HOST memory (desc_host, the same values) for the checks, like frame_off / frame_off_host above.
+ * The resize is Pillow's 8-bit resample bit for bit: horizontal pass -> uint8 -> vertical pass, each
+ *   out = clip8((sum_i k_i p_i + 2^21) >> 22)     int32 taps k_i, int32 accumulation, arithmetic shift
+ * -- integer multiply-adds only on the device.  The taps come from the caller (laff_amd/frame_prep.py derives them in float64 once
+ * per distinct (in, out, filter)), so the filter (bicubic, bilinear, ...) is the caller's choice.  A tap table describes ONE axis of
+ * the cropped window, R outputs, as int32 words { K, xmin[R], count[R], taps[K][R] }: output j of the window is
+ * sum_{i < count[j]} taps[i][j] * p[xmin[j] + i], 1 <= count[j] <= K, taps[i][j] for i >= count[j] unused.  An axis that is not resized
+ * is the identity table (K = 1, xmin[j] = crop + j, taps = 2^22).  htab / vtab of a descriptor are the word indices of the frame's
+ * horizontal / vertical table in `taps` (taps_len words; on the device and the same words in HOST memory, taps_host).
+ * out_pixels [F, 3, R, R] fp32 = (float(u) / 255.0f - mean[c]) / stdv[c] with true fp32 divides (mean, stdv: host arrays of 3);
+ * out_u8 [F, R, R, 3] uint8 (nullable): the resized, cropped image u itself.
+ * One launch over (frame, row tile); the uint8 intermediate stays in LDS, so laff_frame_preprocess_workspace_bytes is 0 today and
+ * workspace may be NULL (the arguments are kept so that a plan with a workspace does not change the ABI).
+ * Limits (LAFF_E_UNSUPPORTED): 1 <= height, width <= 4096; 1 <= R <= 512; F <= 65535 per call; one output row's LDS image,
+ * (taps of the row) x R x 3 bytes, at most 65,536 bytes, i.e. a vertical tap count of at most floor(65536 / (3 R)) (97 at R = 224,
+ * 42 at R = 512: every short-side resize of a frame up to 4096 px fits, bicubic included).  Every table entry is checked against
+ * its frame (xmin >= 0, xmin + count <= width / height; LAFF_E_ARG) before anything is launched.
+ * No allocation, no host synchronisation: capturable in a HIP graph.  A frame's output does not depend on the rest of its batch
+ * (bitwise). */
+typedef struct laff_frame_desc {
+    int64_t offset;        /* byte offset of the frame in `frames` */
+    int32_t height, width;
+    int32_t htab, vtab;    /* word index of the horizontal / vertical tap table in `taps` */
+    int32_t reserved[2];   /* 0 */
+} laff_frame_desc;
+int laff_frame_preprocess_workspace_bytes(int F, int R, size_t* out);
+int laff_frame_preprocess(laff_ctx* ctx, const uint8_t* frames, size_t frames_bytes, const laff_frame_desc* desc,
+                          const laff_frame_desc* desc_host, int F, int R, const int32_t* taps, const int32_t* taps_host, size_t taps_len,
+                          const float* mean, const float* stdv, float* out_pixels, uint8_t* out_u8, void* workspace,
+                          size_t workspace_bytes);
 
 /* ---- text tower: the BERT text encoder (BertTxtEncoder.forward: transformers' BertModel pooler_output, model/model.py:437-466) ----
  * Post-LN encoder, inference, eps = layer_norm_eps:

@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class Plane(C.Structure):
@@ -91,6 +91,11 @@ class BertText(C.Structure):
                 ('pooler_bias', C.c_void_p)]
 
 
+class FrameDesc(C.Structure):
+    _fields_ = [('offset', C.c_int64), ('height', C.c_int32), ('width', C.c_int32), ('htab', C.c_int32), ('vtab', C.c_int32),
+                ('reserved', C.c_int32 * 2)]
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
     'laff_abi_version': (C.c_int, []),
@@ -166,6 +171,9 @@ SIGNATURES = {
     'laff_clip_image_kpad': (C.c_int, [_I, _I, C.POINTER(_I)]),
     'laff_clip_image_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_clip_image_encode': (C.c_int, [_P, _P, _I, _P, C.POINTER(_I), _I, C.POINTER(ClipVisual), _I, _P, _I, _P, _I, _P, C.c_size_t]),
+    'laff_frame_preprocess_workspace_bytes': (C.c_int, [_I, _I, C.POINTER(C.c_size_t)]),
+    'laff_frame_preprocess': (C.c_int, [_P, _P, C.c_size_t, _P, _P, _I, _I, _P, _P, C.c_size_t, C.POINTER(_F), C.POINTER(_F), _P, _P, _P,
+                                        C.c_size_t]),
     'laff_bert_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_bert_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(BertText), _I, _P, _I, _P, C.c_size_t]),
     'laff_netvlad_workspace_bytes': (C.c_int, [_I, _I, C.POINTER(C.c_size_t)]),

@@ -3,9 +3,12 @@ the reference's `CLIPEncoder` (model/model.py:485-525) over `clip.model.CLIP.enc
 153-243, 342-343).  The ViT towers only (ViT-B/32, ViT-B/16, ViT-L/14); the transformer runs on the GPU (`laff_clip_image_encode`,
 laff_amd/csrc/clip_image.hip).
 
-Frames come as the reference's data provider leaves them: `vis_origin_frame_tuple`, one [F_v, 3, R, R] fp32 tensor per video, already
-resized and normalised (decoding and preprocessing stay with the caller).  `ClipFrameLoader` wraps a loader of `collate_vision`
-batches and fills the per-video mean and the zero-padded per-frame features, so a LAFF / FrameLAFF model's predict() runs from frames.
+Frames come either as the reference's data provider leaves them -- `vis_origin_frame_tuple`, one [F_v, 3, R, R] fp32 tensor per video,
+already resized and normalised -- or as decoded RGB uint8 frames of any size (`encode_raw_frames`, `video_features_raw`): those are
+resized, cropped and normalised on the device too, bit for bit as the reference's torchvision-on-Pillow transform does it
+(laff_amd/frame_prep.py, `laff_frame_preprocess`).  Only decoding stays with the caller.  `ClipFrameLoader` wraps a loader of
+`collate_vision` batches and fills the per-video mean and the zero-padded per-frame features, so a LAFF / FrameLAFF model's predict()
+runs from frames of either form.
 """
 import numpy as np
 import torch
@@ -173,6 +176,30 @@ class ClipImageEncoder(nn.Module):
         frames[mask.bool()] = feats
         return mean, frames, mask
 
+    def preprocessor(self, kind='clip'):
+        """The FramePreprocessor of this encoder's input_resolution and device (one per kind, kept: its tap tables are cached)."""
+        from .frame_prep import FramePreprocessor
+        pre = self.__dict__.setdefault('_preprocessors', {})
+        if kind not in pre:
+            pre[kind] = FramePreprocessor(self.input_resolution, kind=kind, device=self.ClipModel.visual.proj.device)
+        return pre[kind]
+
+    def encode_raw_frames(self, frames, kind='clip', max_frames=None):
+        """Decoded RGB uint8 frames of any size (a list of [H, W, 3] arrays / tensors or one [F, H, W, 3] tensor) -> (F, embed_dim) fp32:
+        the preprocessing of `kind` ('clip' / 'slip', laff_amd/frame_prep.py) on the device, then encode_frames."""
+        return self.encode_frames(self.preprocessor(kind)(frames), max_frames)
+
+    def video_features_raw(self, list_of_videos, kind='clip', max_frames=None):
+        """video_features of videos given as decoded uint8 frames: one list of [H, W, 3] frames (or one [F_v, H, W, 3] tensor) per
+        video."""
+        pre = self.preprocessor(kind)
+        vids = [pre._frame_list(v) for v in list_of_videos]
+        if any(len(v) < 1 for v in vids):
+            raise ValueError('every video needs at least one frame')
+        pix = pre([f for v in vids for f in v])
+        off = np.concatenate([[0], np.cumsum([len(v) for v in vids])])
+        return self.video_features(tuple(pix[off[i]:off[i + 1]] for i in range(len(vids))), max_frames)
+
     def forward(self, caption_feat_dict=None, vis_origin_frame_tuple=None, frame_agg_method='mean'):
         """The visual half of CLIPEncoder.forward: {'visual_features': [V, E]}, the mean of each video's frame features (the text
         half is clip_text.ClipTxtEncoder; caption_feat_dict is not read here)."""
@@ -185,14 +212,25 @@ class ClipImageEncoder(nn.Module):
         return output
 
 
+def _is_raw(vis_origin_frame_tuple):
+    """True when the tuple holds decoded uint8 frames (every video: a uint8 array / tensor or a list of them)."""
+    def raw(v):
+        if isinstance(v, (list, tuple)):
+            return len(v) > 0 and all(raw(f) for f in v)
+        return isinstance(v, (np.ndarray, torch.Tensor)) and v.dtype in (np.uint8, torch.uint8)
+    return len(vis_origin_frame_tuple) > 0 and all(raw(v) for v in vis_origin_frame_tuple)
+
+
 class ClipFrameLoader(object):
     """Wraps a loader of collate_vision batches (dicts with 'vis_feat_dict', 'vis_frame_feat_dict', 'vis_origin_frame_tuple', ...):
     encodes each batch's frames and puts the per-video mean into vis_feat_dict[mean_name] and the zero-padded per-frame features into
-    vis_frame_feat_dict[frame_name] (+ 'mask_tensor'), all on the device.  mean_name / frame_name None: that entry is not filled."""
+    vis_frame_feat_dict[frame_name] (+ 'mask_tensor'), all on the device.  mean_name / frame_name None: that entry is not filled.
+    A batch whose vis_origin_frame_tuple holds decoded uint8 frames (per video a [F_v, H, W, 3] tensor / array or a list of [H, W, 3]
+    frames) goes through `preprocessor` first (None: the encoder's own 'clip' one); fp32 tuples are encoded as they are."""
 
     def __init__(self, vis_loader, encoder, mean_name='mean_clip_frame_feat_ViT-B_32,os', frame_name='clip_frame_feat_ViT-B_32,os',
-                 max_frames=None):
-        self.vis_loader, self.encoder = vis_loader, encoder
+                 max_frames=None, preprocessor=None):
+        self.vis_loader, self.encoder, self.preprocessor = vis_loader, encoder, preprocessor
         self.mean_name, self.frame_name, self.max_frames = mean_name, frame_name, max_frames
         for a in ('batch_size', 'dataset'):
             if hasattr(vis_loader, a):
@@ -207,6 +245,12 @@ class ClipFrameLoader(object):
             frames = batch.get('vis_origin_frame_tuple')
             if frames is None or any(f is None for f in frames):
                 raise ValueError('ClipFrameLoader: the batch carries no vis_origin_frame_tuple')
+            if _is_raw(frames):
+                pre = self.preprocessor if self.preprocessor is not None else self.encoder.preprocessor()
+                vids = [pre._frame_list(v) for v in frames]
+                off = np.concatenate([[0], np.cumsum([len(v) for v in vids])])
+                pix = pre([f for v in vids for f in v])
+                frames = tuple(pix[off[i]:off[i + 1]] for i in range(len(vids)))
             mean, feats, mask = self.encoder.video_features(frames, self.max_frames)
             if self.mean_name is not None:
                 batch['vis_feat_dict'] = dict(batch.get('vis_feat_dict') or {}, **{self.mean_name: mean})

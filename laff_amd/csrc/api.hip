@@ -733,6 +733,94 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
     return LAFF_OK;
 }
 
+int laff_frame_preprocess_workspace_bytes(int F, int R, size_t* out) {
+    const char* fn = "laff_frame_preprocess_workspace_bytes";
+    if (!out || F < 0) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    if (R < 1 || R > 512) return fail(LAFF_E_UNSUPPORTED, "%s: R=%d: 1 .. 512", fn, R);
+    *out = 0;                                   /* the intermediate of the two passes stays in LDS */
+    return LAFF_OK;
+}
+
+namespace {
+// one axis' tap table { K, xmin[R], count[R], taps[K][R] } at word `at` of the host copy, checked against the axis' source size
+int frame_prep_check_table(const char* fn, int f, const char* axis, const int32_t* taps, size_t taps_len, long at, int R, int in) {
+    if (at < 0 || (size_t)at + 1 + 2 * (size_t)R > taps_len)
+        return fail(LAFF_E_ARG, "%s: frame %d: %s table at word %ld is outside the %zu words of taps", fn, f, axis, at, taps_len);
+    const int32_t* t = taps + at;
+    const int K = t[0];
+    if (K < 1 || (size_t)at + 1 + (2 + (size_t)K) * R > taps_len)
+        return fail(LAFF_E_ARG, "%s: frame %d: %s table with K=%d runs past the %zu words of taps", fn, f, axis, K, taps_len);
+    for (int j = 0; j < R; ++j) {
+        const int xmin = t[1 + j], n = t[1 + R + j];
+        if (xmin < 0 || n < 1 || n > K || (long)xmin + n > in)
+            return fail(LAFF_E_ARG, "%s: frame %d: %s table entry %d reads [%d, %d + %d) of %d", fn, f, axis, j, xmin, xmin, n, in);
+    }
+    return LAFF_OK;
+}
+}  // namespace
+
+int laff_frame_preprocess(laff_ctx* ctx, const uint8_t* frames, size_t frames_bytes, const laff_frame_desc* desc,
+                          const laff_frame_desc* desc_host, int F, int R, const int32_t* taps, const int32_t* taps_host, size_t taps_len,
+                          const float* mean, const float* stdv, float* out_pixels, uint8_t* out_u8, void* workspace,
+                          size_t workspace_bytes) {
+    const char* fn = "laff_frame_preprocess";
+    (void)workspace;
+    (void)workspace_bytes;
+    // every argument is checked before any GPU work
+    if (F < 0) return fail(LAFF_E_SHAPE, "%s: F=%d", fn, F);
+    if (R < 1 || R > 512) return fail(LAFF_E_UNSUPPORTED, "%s: R=%d: 1 .. 512", fn, R);
+    if (F > 65535) return fail(LAFF_E_UNSUPPORTED, "%s: F=%d: at most 65535 frames per call", fn, F);
+    if (F == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
+    if (!frames || !desc || !desc_host || !taps || !taps_host || !mean || !stdv || !out_pixels)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f) || !std::isfinite(stdv[c]) || !std::isfinite(mean[c]))
+            return fail(LAFF_E_ARG, "%s: mean[%d]=%g std[%d]=%g: finite, std > 0", fn, c, (double)mean[c], c, (double)stdv[c]);
+    // the tallest LDS image over the frames at every tile height: rows [min xmin, max xmin + count) of the tile x R x 3 bytes
+    constexpr int NT = 5;                       /* tile heights 16, 8, 4, 2, 1 */
+    int need[NT] = {0, 0, 0, 0, 0};
+    long last_h = -1, last_v = -1;
+    int last_w = -1, last_hh = -1;
+    for (int f = 0; f < F; ++f) {
+        const laff_frame_desc& d = desc_host[f];
+        if (d.height < 1 || d.height > 4096 || d.width < 1 || d.width > 4096)
+            return fail(LAFF_E_UNSUPPORTED, "%s: frame %d is %d x %d: each side 1 .. 4096", fn, f, d.height, d.width);
+        const size_t bytes = (size_t)d.height * d.width * 3;
+        if (d.offset < 0 || (size_t)d.offset > frames_bytes || bytes > frames_bytes - (size_t)d.offset)
+            return fail(LAFF_E_ARG, "%s: frame %d at byte %lld with %zu bytes is outside the %zu bytes of frames", fn, f,
+                        (long long)d.offset, bytes, frames_bytes);
+        if (d.htab != last_h || d.width != last_w) {
+            if (int rc = frame_prep_check_table(fn, f, "horizontal", taps_host, taps_len, d.htab, R, d.width)) return rc;
+            last_h = d.htab, last_w = d.width;
+        }
+        if (d.vtab == last_v && d.height == last_hh) continue;      /* the same vertical table: already in `need` */
+        if (int rc = frame_prep_check_table(fn, f, "vertical", taps_host, taps_len, d.vtab, R, d.height)) return rc;
+        last_v = d.vtab, last_hh = d.height;
+        const int32_t* xmin = taps_host + d.vtab + 1;
+        const int32_t* cnt = xmin + R;
+        for (int t = 0; t < NT; ++t) {
+            const int tile = laff::FRAME_PREP_MAX_TILE >> t;
+            for (int y0 = 0; y0 < R; y0 += tile) {
+                int s0 = xmin[y0], s1 = s0;
+                for (int y = y0; y < std::min(R, y0 + tile); ++y) s0 = std::min(s0, xmin[y]), s1 = std::max(s1, xmin[y] + cnt[y]);
+                need[t] = std::max(need[t], s1 - s0);
+            }
+        }
+    }
+    int pick = -1;
+    for (int t = 0; t < NT && pick < 0; ++t)
+        if ((size_t)need[t] * R * 3 <= (size_t)laff::FRAME_PREP_LDS_BYTES) pick = t;
+    if (pick < 0)
+        return fail(LAFF_E_UNSUPPORTED, "%s: %d vertical taps at R=%d need %zu bytes of LDS for one output row (at most %d)", fn,
+                    need[NT - 1], R, (size_t)need[NT - 1] * R * 3, laff::FRAME_PREP_LDS_BYTES);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    laff::FramePrepArgs a{frames, desc, taps, F, R, laff::FRAME_PREP_MAX_TILE >> pick, {mean[0], mean[1], mean[2]},
+                          {stdv[0], stdv[1], stdv[2]}, out_pixels, out_u8};
+    HIP_TRY(laff::launch_frame_prep(a, (size_t)need[pick] * R * 3, ctx->stream));
+    return LAFF_OK;
+}
+
 namespace {
 // the BERT text encoder's workspace: X [R, W] fp32 | A [R, W] operand | big [R, max(3W fp32, I operand)] | Xc [N, W] fp32 |
 // Qc [N, W] fp32 | Ac [N, W] operand, each region on 256 bytes

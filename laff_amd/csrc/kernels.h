@@ -391,6 +391,20 @@ struct ClipImageArgs {
 };
 hipError_t launch_clip_image_encode(const ClipImageArgs& e, int fp16, hipStream_t st);
 
+// frame_prep.hip: frame preprocessing (laff_frame_preprocess)
+constexpr int FRAME_PREP_LDS_BYTES = 64 * 1024;   // the LDS image of one row tile: two blocks per CU
+constexpr int FRAME_PREP_MAX_TILE = 16;
+struct FramePrepArgs {
+    const unsigned char* frames;   // packed HWC uint8 frames
+    const laff_frame_desc* desc;   // [F] device
+    const int* taps;               // the tap tables, device
+    int F, R, tile;                // tile: output rows per block
+    float mean[3], stdv[3];
+    float* out_pixels;             // [F, 3, R, R] fp32
+    unsigned char* out_u8;         // [F, R, R, 3] uint8 or null
+};
+hipError_t launch_frame_prep(const FramePrepArgs& a, size_t lds_bytes, hipStream_t st);
+
 // bert.hip: the BERT text encoder (laff_bert_encode) on the transformer core of clip_core.h
 constexpr int BERT_MAX_POSITION = 512;
 enum { BERT_LN_EMBED = 0, BERT_LN_ROW = 1, BERT_LN_CLS = 2 };

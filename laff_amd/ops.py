@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment)
 
-__all__ = ['netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -527,6 +527,48 @@ def clip_image_encode(pixels, frame_off, frame_off_host, model, precision='fp16'
     _call('clip_image_encode', lib.laff_clip_image_encode, h, _ptr(pixels), F, _ptr(fo), roh.ctypes.data_as(C.POINTER(C.c_int)), V,
           C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(mo), ldm, _ptr(workspace), workspace.numel())
     return out, (out_mean if V > 0 else None)
+
+
+#: frames per laff_frame_preprocess call (the kernel's grid.y)
+FRAME_PREP_MAX_FRAMES = 65535
+
+
+def frame_desc_device(desc, F, device):
+    """A _lib.FrameDesc array's first F descriptors as a uint8 device tensor."""
+    raw = np.frombuffer(memoryview(desc), dtype=np.uint8)[:F * C.sizeof(_lib.FrameDesc)].copy()
+    return torch.from_numpy(raw).to(device)
+
+
+def frame_preprocess(frames, desc, F, R, taps, taps_host, mean, std, out=None, out_u8=None, desc_dev=None):
+    """laff_frame_preprocess.  frames: uint8 device buffer of packed HWC frames; desc: a _lib.FrameDesc array of F descriptors (host;
+    desc_dev: the same bytes on the device, or None to copy them here -- pass one for HIP-graph capture); taps: the int32 tap tables on
+    the device and taps_host the same words as a host int32 array; mean, std: 3 floats each.  Returns out [F, 3, R, R] fp32; out_u8
+    [F, R, R, 3] uint8, when given, receives the resized, cropped image."""
+    frames = _dev(frames, 'frames', torch.uint8)
+    taps = _dev(taps, 'taps', torch.int32)
+    F, R = int(F), int(R)
+    th = np.ascontiguousarray(taps_host, dtype=np.int32)
+    if not frames.is_contiguous() or not taps.is_contiguous() or taps.numel() != th.size:
+        raise ValueError('frames / taps must be contiguous and taps_host must hold the words of taps')
+    if len(desc) < F:
+        raise ValueError('desc holds %d descriptors, F = %d' % (len(desc), F))
+    if out is None:
+        out = torch.empty((F, 3, R, R), device=frames.device, dtype=torch.float32)
+    _dev(out, 'out')
+    if tuple(out.shape) != (F, 3, R, R) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous (%d, 3, %d, %d) tensor, got %s' % (F, R, R, tuple(out.shape)))
+    if out_u8 is not None:
+        _dev(out_u8, 'out_u8', torch.uint8)
+        if tuple(out_u8.shape) != (F, R, R, 3) or not out_u8.is_contiguous():
+            raise ValueError('out_u8 must be a contiguous (%d, %d, %d, 3) tensor, got %s' % (F, R, R, tuple(out_u8.shape)))
+    if desc_dev is None and F:
+        desc_dev = frame_desc_device(desc, F, frames.device)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    sd = (C.c_float * 3)(*[float(v) for v in std])
+    lib, h = _context(frames.device)
+    _call('frame_preprocess', lib.laff_frame_preprocess, h, _ptr(frames), frames.numel(), _ptr(desc_dev), C.cast(desc, C.c_void_p), F, R,
+          _ptr(taps), C.c_void_p(th.ctypes.data), th.size, m, sd, _ptr(out), _ptr(out_u8), None, 0)
+    return out
 
 
 class SplitOperand:
