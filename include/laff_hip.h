@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 30
+#define LAFF_ABI_VERSION 31
 
 enum {
     LAFF_OK = 0,
@@ -165,6 +165,37 @@ typedef struct {
     float* Y; int ldy;
 } laff_fc_fused_problem;
 int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* problems /*host array*/, int count);
+
+/* Which kernels the three grouped FC entry points above run for a list of problems, in launch order: the answer of the very
+ * functions the launches go through (the staging kind of each problem, the grouping by kind and by eight, the 512-big-tile test
+ * and the tail split of the split tile, which reads this process's CU count).  Launches nothing, reads no device memory.
+ *   family   LAFF_FC_FAMILY_F32 (laff_fc_act_bn_grouped), _SPLIT (laff_fc_act_bn_split_grouped), _FUSED (laff_fc_act_bn_fused_grouped)
+ *   shapes   host array; x_aligned / w_aligned stand for 16-byte aligned X / W base pointers (the split operands of the SPLIT
+ *            family and Ws of the FUSED one are always aligned; ldx is ignored by SPLIT, ldw by SPLIT and FUSED)
+ *   kind     [count] host out: F32: the staging kind 0 / 1 / 2 (registers, LDS-DMA with a K tail, fast LDS-DMA); SPLIT / FUSED:
+ *            the tile edge, 128 or 256; -1 for an empty problem (N = 0: in no launch)
+ *   launch_of[count] host out: index of the launch that computes the problem, -1 for an empty one
+ *   launches [cap] host out, *n_launches of them: the kernel, its problems, its tiles (128 x 128 for F32_* and F16_128, 256 x 256
+ *            otherwise) and, for LAFF_FC_KERNEL_X3, the tail split: nbig whole tiles + `quarters` 128 x 128 workgroups (4 per
+ *            remaining tile)
+ * A problem list the entry point would refuse is refused here with the same code; more than cap launches: LAFF_E_ARG. */
+enum { LAFF_FC_FAMILY_F32 = 0, LAFF_FC_FAMILY_SPLIT = 1, LAFF_FC_FAMILY_FUSED = 2 };
+enum {
+    LAFF_FC_KERNEL_F32_REG = 0,      /* fp32 MFMA, 128 x 128 tiles, operands through registers: unaligned rows / Dk % 4 != 0 */
+    LAFF_FC_KERNEL_F32_TAIL = 1,     /* fp32 MFMA, LDS-DMA with a K tail: Dk * 4 % 128 != 0, or an operand span >= 4 GiB     */
+    LAFF_FC_KERNEL_F32_GLDS = 2,     /* fp32 MFMA, fast LDS-DMA                                                            */
+    LAFF_FC_KERNEL_F16_128 = 3,      /* split operands, 128 x 128 tiles: a launch of < 512 tiles of 256 x 256              */
+    LAFF_FC_KERNEL_X3 = 4,           /* split operands, the 256 x 256 hi/lo tile (+ quarter tiles of a sparse last round)   */
+    LAFF_FC_KERNEL_X3_FUSED = 5,     /* the same tile with the input split on its way into LDS (any launch size)            */
+    LAFF_FC_KERNEL_STRIP = 6,        /* laff_fc_act_bn_strip_grouped, laff_fc_gather_act_bn, laff_fc_concat_act_bn*: one     */
+    LAFF_FC_KERNEL_GATHER = 7,       /*   kernel family each; never an answer of laff_fc_route (named for the bindings'      */
+    LAFF_FC_KERNEL_CONCAT = 8,       /*   route tables)                                                                      */
+    LAFF_FC_KERNEL_F16_256 = 9       /* 16-bit one-plane operands on 256 x 256 tiles: no FC entry point builds such a group   */
+};
+typedef struct { int N, Dk, D, ldx, ldw; int x_aligned, w_aligned; } laff_fc_shape;
+typedef struct { int kernel, count; long long tiles; int nbig; long long quarters; } laff_fc_launch;
+int laff_fc_route(laff_ctx* ctx, int family, const laff_fc_shape* shapes /*host*/, int count, int* kind, int* launch_of,
+                  laff_fc_launch* launches, int cap, int* n_launches);
 
 /* a1 / a3 in STRIP form for Dk == 512 inputs (TransformNet.forward, model/model.py:257-276; the per-feature loops :1807-1827 and
  * :1673-1681): same arithmetic as the fused-split form above (fp16 hi/lo, three products, fp32 accumulation) with X STATIONARY --

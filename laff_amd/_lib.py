@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 class Plane(C.Structure):
@@ -40,6 +40,15 @@ class FcProblem(C.Structure):
     _fields_ = [('X', C.c_void_p), ('N', C.c_int), ('Dk', C.c_int), ('ldx', C.c_int), ('W', C.c_void_p), ('ldw', C.c_int),
                 ('bias', C.c_void_p), ('bn_scale', C.c_void_p), ('bn_shift', C.c_void_p), ('D', C.c_int), ('act', C.c_int),
                 ('Y', C.c_void_p), ('ldy', C.c_int)]
+
+
+class FcShape(C.Structure):
+    _fields_ = [('N', C.c_int), ('Dk', C.c_int), ('D', C.c_int), ('ldx', C.c_int), ('ldw', C.c_int), ('x_aligned', C.c_int),
+                ('w_aligned', C.c_int)]
+
+
+class FcLaunch(C.Structure):
+    _fields_ = [('kernel', C.c_int), ('count', C.c_int), ('tiles', C.c_longlong), ('nbig', C.c_int), ('quarters', C.c_longlong)]
 
 
 class FcConcatSegment(C.Structure):
@@ -116,6 +125,7 @@ SIGNATURES = {
     'laff_row_scales_grouped': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),
                                           C.POINTER(C.c_void_p)]),
     'laff_fc_act_bn_fused_grouped': (C.c_int, [_P, C.POINTER(FcFusedProblem), _I]),
+    'laff_fc_route': (C.c_int, [_P, _I, C.POINTER(FcShape), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(FcLaunch), _I, C.POINTER(_I)]),
     'laff_fc_strip_pack_bytes': (C.c_int, [_I, _I, C.POINTER(C.c_size_t)]),
     'laff_fc_strip_pack': (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'laff_fc_act_bn_strip_grouped': (C.c_int, [_P, C.POINTER(FcStripProblem), _I]),

@@ -92,13 +92,20 @@ int check_epilogue(const char* who, int i, int act, const float* bias, const flo
     return LAFF_OK;
 }
 
+// a grouped GEMM launch being assembled, with the index each of its problems has in the caller's list
+struct FcGroup {
+    laff::GroupedGemmArgs ga{};
+    int idx[laff::MAX_GROUP];
+};
+
 // adds a problem to a grouped GEMM launch and issues the launch once MAX_GROUP are in; the caller launches the rest
 template <typename Launch>
-hipError_t group_add(laff::GroupedGemmArgs& ga, const laff::GemmArgs& a, Launch launch) {
-    ga.p[ga.count++] = a;
-    if (ga.count < laff::MAX_GROUP) return hipSuccess;
-    const hipError_t e = launch(ga);
-    ga.count = 0;
+hipError_t group_add(FcGroup& g, const laff::GemmArgs& a, int i, Launch launch) {
+    g.idx[g.ga.count] = i;
+    g.ga.p[g.ga.count++] = a;
+    if (g.ga.count < laff::MAX_GROUP) return hipSuccess;
+    const hipError_t e = launch(g);
+    g.ga.count = 0;
     return e;
 }
 
@@ -233,24 +240,36 @@ int laff_fc_act_bn(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, const 
     return laff_fc_act_bn_grouped(ctx, &q, 1);
 }
 
-int laff_fc_act_bn_grouped(laff_ctx* ctx, const laff_fc_problem* problems, int count) {
-    CHECK_CTX(ctx);
-    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_grouped: bad problem list");
-    DeviceGuard g(ctx->device);
-    // problems are grouped by staging kind (see staging_kind), at most MAX_GROUP per launch
+// laff_fc_act_bn_grouped's walk over its problems: launch(group, kind) gets each launch in order (laff_fc_route passes a recorder).
+// Problems are grouped by staging kind (see staging_kind), at most MAX_GROUP per launch; kinds (nullable) receives every kind.
+extern "C++" {
+template <typename Launch>
+static int fc_f32_walk(const laff_fc_problem* problems, int count, int* kinds, Launch launch_kind) {
     for (int kind = 2; kind >= 0; --kind) {
-        auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_grouped_f32(ga, kind, ctx->stream); };
-        laff::GroupedGemmArgs ga{};
+        auto launch = [&](FcGroup& g) { return launch_kind(g, kind); };
+        FcGroup g;
         for (int i = 0; i < count; ++i) {
             laff::GemmArgs a;
             bool aligned;
             if (int rc = fc_problem_args(problems[i], a, aligned, "laff_fc_act_bn_grouped", i)) return rc;
-            if (problems[i].N == 0 || laff::staging_kind(a, 4, aligned) != kind) continue;
-            HIP_TRY(group_add(ga, a, launch));
+            if (problems[i].N == 0) continue;
+            const int k = laff::staging_kind(a, 4, aligned);
+            if (kinds) kinds[i] = k;
+            if (k != kind) continue;
+            HIP_TRY(group_add(g, a, i, launch));
         }
-        if (ga.count) HIP_TRY(launch(ga));
+        if (g.ga.count) HIP_TRY(launch(g));
     }
     return LAFF_OK;
+}
+}  // extern "C++"
+
+int laff_fc_act_bn_grouped(laff_ctx* ctx, const laff_fc_problem* problems, int count) {
+    CHECK_CTX(ctx);
+    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_grouped: bad problem list");
+    DeviceGuard g(ctx->device);
+    return fc_f32_walk(problems, count, nullptr,
+                       [&](FcGroup& fg, int kind) { return laff::launch_gemm_nt_grouped_f32(fg.ga, kind, ctx->stream); });
 }
 
 /* checks problem i of a concat launch and, when it is not empty, turns it into the kernel's form */
@@ -978,12 +997,11 @@ int laff_split_rows_grouped(laff_ctx* ctx, int count, const float* const* X, con
     return split_rows_by_eight(ctx, "laff_split_rows_grouped", count, X, N, K, ldx, out, rscale);
 }
 
-int laff_fc_act_bn_split_grouped(laff_ctx* ctx, const laff_fc_split_problem* problems, int count) {
-    CHECK_CTX(ctx);
-    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: bad problem list");
-    DeviceGuard g(ctx->device);
-    auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_grouped_f16(ga, ctx->stream); };
-    laff::GroupedGemmArgs ga{};
+// laff_fc_act_bn_split_grouped's walk over its problems: launch(group) gets each launch in order (laff_fc_route passes a recorder)
+extern "C++" {
+template <typename Launch>
+static int fc_split_walk(const laff_fc_split_problem* problems, int count, Launch launch) {
+    FcGroup g;
     for (int i = 0; i < count; ++i) {
         const laff_fc_split_problem& q = problems[i];
         if (!q.Xs || !q.Ws || !q.x_rscale || !q.w_rscale || !q.Y) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: problem %d has a null operand", i);
@@ -1003,10 +1021,18 @@ int laff_fc_act_bn_split_grouped(laff_ctx* ctx, const laff_fc_split_problem* pro
         a.out = q.Y; a.ldo = q.ldy; a.scale = 1.0f;
         a.row_scale = q.x_rscale; a.col_scale = q.w_rscale;
         a.bias = q.bias; a.bn_scale = q.bn_scale; a.bn_shift = q.bn_shift; a.act = q.act;
-        HIP_TRY(group_add(ga, a, launch));
+        HIP_TRY(group_add(g, a, i, launch));
     }
-    if (ga.count) HIP_TRY(launch(ga));
+    if (g.ga.count) HIP_TRY(launch(g));
     return LAFF_OK;
+}
+}  // extern "C++"
+
+int laff_fc_act_bn_split_grouped(laff_ctx* ctx, const laff_fc_split_problem* problems, int count) {
+    CHECK_CTX(ctx);
+    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_split_grouped: bad problem list");
+    DeviceGuard g(ctx->device);
+    return fc_split_walk(problems, count, [&](FcGroup& fg) { return laff::launch_gemm_nt_grouped_f16(fg.ga, ctx->stream); });
 }
 
 int laff_row_scales_grouped(laff_ctx* ctx, int count, const float* const* X, const int* N, const int* K, const int* ldx,
@@ -1016,12 +1042,11 @@ int laff_row_scales_grouped(laff_ctx* ctx, int count, const float* const* X, con
     return split_rows_by_eight(ctx, "laff_row_scales_grouped", count, X, N, K, ldx, nullptr, rscale);
 }
 
-int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* problems, int count) {
-    CHECK_CTX(ctx);
-    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_fused_grouped: bad problem list");
-    DeviceGuard g(ctx->device);
-    auto launch = [&](laff::GroupedGemmArgs& ga) { return laff::launch_gemm_nt_x3_fused_grouped(ga, ctx->stream); };
-    laff::GroupedGemmArgs ga{};
+// laff_fc_act_bn_fused_grouped's walk over its problems: launch(group) gets each launch in order (laff_fc_route passes a recorder)
+extern "C++" {
+template <typename Launch>
+static int fc_fused_walk(const laff_fc_fused_problem* problems, int count, Launch launch) {
+    FcGroup g;
     for (int i = 0; i < count; ++i) {
         const laff_fc_fused_problem& q = problems[i];
         if (q.N == 0) continue;
@@ -1045,9 +1070,77 @@ int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* pro
 #ifdef LAFF_GEMM_TRACE
         if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-        HIP_TRY(group_add(ga, a, launch));
+        HIP_TRY(group_add(g, a, i, launch));
     }
-    if (ga.count) HIP_TRY(launch(ga));
+    if (g.ga.count) HIP_TRY(launch(g));
+    return LAFF_OK;
+}
+}  // extern "C++"
+
+int laff_fc_act_bn_fused_grouped(laff_ctx* ctx, const laff_fc_fused_problem* problems, int count) {
+    CHECK_CTX(ctx);
+    if (!problems || count < 0) return fail(LAFF_E_ARG, "laff_fc_act_bn_fused_grouped: bad problem list");
+    DeviceGuard g(ctx->device);
+    return fc_fused_walk(problems, count, [&](FcGroup& fg) { return laff::launch_gemm_nt_x3_fused_grouped(fg.ga, ctx->stream); });
+}
+
+int laff_fc_route(laff_ctx* ctx, int family, const laff_fc_shape* shapes, int count, int* kind, int* launch_of, laff_fc_launch* launches,
+                  int cap, int* n_launches) {
+    CHECK_CTX(ctx);
+    if (family < LAFF_FC_FAMILY_F32 || family > LAFF_FC_FAMILY_FUSED) return fail(LAFF_E_ARG, "laff_fc_route: bad family %d", family);
+    if (count < 0 || cap < 0 || !n_launches || (count && (!shapes || !kind || !launch_of)) || (cap && !launches))
+        return fail(LAFF_E_ARG, "laff_fc_route: bad argument list");
+    // stand-ins for the caller's buffers: the choice looks at their alignment and at which are present, never at what they hold
+    alignas(16) static char stand_in[32];
+    float* const al = (float*)stand_in;
+    float* const off = (float*)(stand_in + 4);
+    for (int i = 0; i < count; ++i) kind[i] = launch_of[i] = -1;
+    int n = 0;
+    bool over = false;
+    // records one launch the way the launcher of the family plans it
+    auto record = [&](FcGroup& g, int stg) {
+        laff::GroupedPlan pl;
+        const bool ok = family == LAFF_FC_FAMILY_F32     ? laff::plan_gemm_nt_grouped_f32(g.ga, stg, pl)
+                        : family == LAFF_FC_FAMILY_SPLIT ? laff::plan_gemm_nt_grouped_f16(g.ga, pl)
+                                                         : laff::plan_gemm_nt_x3_fused_grouped(g.ga, pl);
+        if (!ok) return hipErrorInvalidValue;
+        if (n >= cap) { over = true; return hipSuccess; }
+        const bool tile128 = pl.kernel <= LAFF_FC_KERNEL_F16_128;
+        for (int j = 0; j < g.ga.count; ++j) {
+            launch_of[g.idx[j]] = n;
+            if (family != LAFF_FC_FAMILY_F32) kind[g.idx[j]] = tile128 ? 128 : 256;
+        }
+        launches[n++] = laff_fc_launch{pl.kernel, g.ga.count, pl.tiles, pl.nbig, pl.quarters};
+        return hipSuccess;
+    };
+    int rc = LAFF_OK;
+    if (family == LAFF_FC_FAMILY_F32) {
+        std::vector<laff_fc_problem> ps((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const laff_fc_shape& q = shapes[i];
+            ps[i] = laff_fc_problem{q.x_aligned ? al : off, q.N, q.Dk, q.ldx, q.w_aligned ? al : off, q.ldw, nullptr, nullptr, nullptr,
+                                    q.D, LAFF_ACT_NONE, al, q.D};
+        }
+        rc = fc_f32_walk(ps.data(), count, kind, record);
+    } else if (family == LAFF_FC_FAMILY_SPLIT) {
+        std::vector<laff_fc_split_problem> ps((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const laff_fc_shape& q = shapes[i];
+            ps[i] = laff_fc_split_problem{al, al, q.N, q.Dk, al, al, nullptr, nullptr, nullptr, q.D, LAFF_ACT_NONE, al, q.D};
+        }
+        rc = fc_split_walk(ps.data(), count, [&](FcGroup& g) { return record(g, 2); });
+    } else {
+        std::vector<laff_fc_fused_problem> ps((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const laff_fc_shape& q = shapes[i];
+            ps[i] = laff_fc_fused_problem{q.x_aligned ? al : off, q.ldx, al, q.N, q.Dk, al, al, nullptr, nullptr, nullptr, q.D,
+                                          LAFF_ACT_NONE, al, q.D};
+        }
+        rc = fc_fused_walk(ps.data(), count, [&](FcGroup& g) { return record(g, 2); });
+    }
+    if (rc) return rc;
+    if (over) return fail(LAFF_E_ARG, "laff_fc_route: more than cap=%d launches", cap);
+    *n_launches = n;
     return LAFF_OK;
 }
 

@@ -265,7 +265,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[CF::WM
                         for (int e = 0; e < 4; ++e) v[e] = fast_tanh(v[e]);
                     } else if (a.act == 2) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+                        for (int e = 0; e < 4; ++e) v[e] = v[e] != v[e] ? v[e] : fmaxf(v[e], 0.0f);     // a NaN stays one, as in torch.relu
                     } else if (a.act == 3) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = fast_sigmoid(v[e]);
@@ -395,7 +395,7 @@ __device__ __forceinline__ void epilogue_fc(const GemmArgs& a, f32x16 (&acc)[CF:
                     for (int e = 0; e < 4; ++e) v[e] = fast_tanh(v[e]);
                 } else if (a.act == 2) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+                    for (int e = 0; e < 4; ++e) v[e] = v[e] != v[e] ? v[e] : fmaxf(v[e], 0.0f);     // a NaN stays one, as in torch.relu
                 } else if (a.act == 3) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fast_sigmoid(v[e]);
@@ -1590,32 +1590,69 @@ static long group_tiles(GroupedGemmArgs& g) {
     return nb;
 }
 
+// ---- what a grouped FC launch is going to run: decided here, reported by laff_fc_route, acted on by the launchers below -----------
+// Each plan_* fills g.tile_start (and g.nbig for the split tile) and pl; false when the group is empty or does not fit a 1-D grid.
+bool plan_gemm_nt_grouped_f32(GroupedGemmArgs& g, int stg, GroupedPlan& pl) {
+    pl = GroupedPlan{};
+    pl.kernel = stg == 0 ? LAFF_FC_KERNEL_F32_REG : (stg == 1 ? LAFF_FC_KERNEL_F32_TAIL : LAFF_FC_KERNEL_F32_GLDS);
+    pl.tiles = group_tiles<Cfg128>(g);
+    return pl.tiles != 0;
+}
+
+bool plan_gemm_nt_grouped_f16(GroupedGemmArgs& g, GroupedPlan& pl) {
+    pl = GroupedPlan{};
+    long t256 = 0;
+    bool split = true;
+    for (int i = 0; i < g.count; ++i) {
+        t256 += (long)((g.p[i].nR + 255) / 256) * ((g.p[i].nC + 255) / 256);
+        split = split && g.p[i].nseg == 3;
+    }
+    const bool big = t256 >= 512;
+    if (big && split) {
+        pl.kernel = LAFF_FC_KERNEL_X3;
+        const long nb = group_tiles<CfgX3>(g);
+        if (nb == 0) return false;
+        // tail split: the big tiles of a last round that would fill at most 3/4 of the CUs become 4 small tiles each
+        const long rem = nb % g_num_cus;
+        g.nbig = (int)nb;
+        if (nb > g_num_cus && rem > 0 && rem * 4 <= 3L * g_num_cus) g.nbig = (int)(nb - rem);
+        pl.tiles = nb;
+        pl.nbig = g.nbig;
+        pl.quarters = 4L * (nb - g.nbig);
+        return true;
+    }
+    pl.kernel = big ? LAFF_FC_KERNEL_F16_256 : LAFF_FC_KERNEL_F16_128;
+    pl.tiles = big ? group_tiles<Cfg256>(g) : group_tiles<Cfg128>(g);
+    return pl.tiles != 0;
+}
+
+bool plan_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, GroupedPlan& pl) {
+    pl = GroupedPlan{};
+    pl.kernel = LAFF_FC_KERNEL_X3_FUSED;
+    const long nb = group_tiles<CfgX3>(g);
+    if (nb == 0) return false;
+    g.nbig = (int)nb;
+    pl.tiles = nb;
+    pl.nbig = g.nbig;
+    return true;
+}
+
 template <int STG>
-static hipError_t launch_grouped_t(GroupedGemmArgs& g, hipStream_t st) {
-    const long nb = group_tiles<Cfg128>(g);
-    if (nb == 0) return hipErrorInvalidValue;
+static hipError_t launch_grouped_t(const GroupedGemmArgs& g, long nb, hipStream_t st) {
     hipLaunchKernelGGL((gemm_nt_grouped_kernel<GEMM_F32, STG, Cfg128>), dim3((unsigned)nb), dim3(Cfg128::THREADS), Cfg128::SMEM, st, g);
     return hipGetLastError();
 }
 
 template <typename CF>
-static hipError_t launch_grouped_f16_t(GroupedGemmArgs& g, hipStream_t st) {
-    const long nb = group_tiles<CF>(g);
-    if (nb == 0) return hipErrorInvalidValue;
+static hipError_t launch_grouped_f16_t(const GroupedGemmArgs& g, long nb, hipStream_t st) {
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_grouped_kernel<GEMM_F16, 2, CF>, CF::SMEM); e != hipSuccess) return e;
     hipLaunchKernelGGL((gemm_nt_grouped_kernel<GEMM_F16, 2, CF>), dim3((unsigned)nb), dim3(CF::THREADS), CF::SMEM, st, g);
     return hipGetLastError();
 }
 
-static hipError_t launch_grouped_x3(GroupedGemmArgs& g, hipStream_t st) {
-    const long nb = group_tiles<CfgX3>(g);
-    if (nb == 0) return hipErrorInvalidValue;
-    // tail split: the big tiles of a last round that would fill at most 3/4 of the CUs become 4 small tiles each
-    const long rem = nb % g_num_cus;
-    g.nbig = (int)nb;
-    if (nb > g_num_cus && rem > 0 && rem * 4 <= 3L * g_num_cus) g.nbig = (int)(nb - rem);
-    const long grid = g.nbig + 4L * (nb - g.nbig);
+static hipError_t launch_grouped_x3(const GroupedGemmArgs& g, const GroupedPlan& pl, hipStream_t st) {
+    const long grid = pl.nbig + pl.quarters;
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_x3_grouped_kernel<GEMM_F16>, CfgX3::SMEM); e != hipSuccess) return e;
     hipLaunchKernelGGL((gemm_nt_x3_grouped_kernel<GEMM_F16>), dim3((unsigned)grid), dim3(CfgX3::THREADS), CfgX3::SMEM, st, g);
@@ -1623,12 +1660,11 @@ static hipError_t launch_grouped_x3(GroupedGemmArgs& g, hipStream_t st) {
 }
 
 hipError_t launch_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, hipStream_t st) {
-    const long nb = group_tiles<CfgX3>(g);
-    if (nb == 0) return hipErrorInvalidValue;
-    g.nbig = (int)nb;
+    GroupedPlan pl;
+    if (!plan_gemm_nt_x3_fused_grouped(g, pl)) return hipErrorInvalidValue;
     static unsigned long long attr_done = 0;     // per device; also keeps the call out of HIP-graph captures
     if (hipError_t e = smem_attr_once(attr_done, gemm_nt_x3_fused_grouped_kernel<GEMM_F16>, CfgX3::SMEM); e != hipSuccess) return e;
-    hipLaunchKernelGGL((gemm_nt_x3_fused_grouped_kernel<GEMM_F16>), dim3((unsigned)nb), dim3(CfgX3::THREADS), CfgX3::SMEM, st, g);
+    hipLaunchKernelGGL((gemm_nt_x3_fused_grouped_kernel<GEMM_F16>), dim3((unsigned)pl.tiles), dim3(CfgX3::THREADS), CfgX3::SMEM, st, g);
     return hipGetLastError();
 }
 
@@ -1643,22 +1679,22 @@ static hipError_t launch_x3(const GemmArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_gemm_nt_grouped_f16(GroupedGemmArgs& g, hipStream_t st) {
-    long t256 = 0;
-    bool split = true;
-    for (int i = 0; i < g.count; ++i) {
-        t256 += (long)((g.p[i].nR + 255) / 256) * ((g.p[i].nC + 255) / 256);
-        split = split && g.p[i].nseg == 3;
+    GroupedPlan pl;
+    if (!plan_gemm_nt_grouped_f16(g, pl)) return hipErrorInvalidValue;
+    switch (pl.kernel) {
+        case LAFF_FC_KERNEL_X3: return launch_grouped_x3(g, pl, st);
+        case LAFF_FC_KERNEL_F16_256: return launch_grouped_f16_t<Cfg256>(g, pl.tiles, st);
+        default: return launch_grouped_f16_t<Cfg128>(g, pl.tiles, st);
     }
-    const bool big = t256 >= 512;
-    if (big && split) return launch_grouped_x3(g, st);
-    return big ? launch_grouped_f16_t<Cfg256>(g, st) : launch_grouped_f16_t<Cfg128>(g, st);
 }
 
 hipError_t launch_gemm_nt_grouped_f32(GroupedGemmArgs& g, int stg, hipStream_t st) {
-    switch (stg) {
-        case 0: return launch_grouped_t<0>(g, st);
-        case 1: return launch_grouped_t<1>(g, st);
-        default: return launch_grouped_t<2>(g, st);
+    GroupedPlan pl;
+    if (!plan_gemm_nt_grouped_f32(g, stg, pl)) return hipErrorInvalidValue;
+    switch (pl.kernel) {
+        case LAFF_FC_KERNEL_F32_REG: return launch_grouped_t<0>(g, pl.tiles, st);
+        case LAFF_FC_KERNEL_F32_TAIL: return launch_grouped_t<1>(g, pl.tiles, st);
+        default: return launch_grouped_t<2>(g, pl.tiles, st);
     }
 }
 

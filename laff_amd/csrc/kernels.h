@@ -162,6 +162,12 @@ hipError_t launch_fc_concat(ConcatArgs& a, hipStream_t st);
 // the kernel launch_gemm_nt runs for these arguments (LAFF_ROUTE_*, include/laff_hip.h); launches nothing
 int gemm_route(const GemmArgs& a, int mode, bool aligned);
 hipError_t launch_gemm_nt(const GemmArgs& a, int mode, bool aligned, hipStream_t st);
+// what a grouped FC launch runs (laff_fc_route reports it, the launchers below act on it): kernel = LAFF_FC_KERNEL_*, tiles in that
+// kernel's own tile; the split tile's tail split leaves nbig whole 256 x 256 tiles and `quarters` 128 x 128 workgroups
+struct GroupedPlan { int kernel; long tiles; int nbig; long quarters; };
+bool plan_gemm_nt_grouped_f32(GroupedGemmArgs& g, int staging, GroupedPlan& pl);
+bool plan_gemm_nt_grouped_f16(GroupedGemmArgs& g, GroupedPlan& pl);
+bool plan_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, GroupedPlan& pl);
 hipError_t launch_gemm_nt_grouped_f32(GroupedGemmArgs& g, int staging, hipStream_t st);
 hipError_t launch_gemm_nt_grouped_f16(GroupedGemmArgs& g, hipStream_t st);
 hipError_t launch_gemm_nt_x3_fused_grouped(GroupedGemmArgs& g, hipStream_t st);   // fp32 row operand split in the kernel   // fast staging only (packed operands)

@@ -11,9 +11,10 @@ import torch
 
 from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
-                   FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment)
+                   FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
+                   FcLaunch, FcShape)
 
-__all__ = ['frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -665,6 +666,77 @@ def fc_act_bn_fused_grouped(problems):
     _call('row_scales', lib.laff_row_scales_grouped, h, n, X, N, K, LD, R)
     _call('fc_act_bn', lib.laff_fc_act_bn_fused_grouped, h, arr, n)
     return outs
+
+
+#: the kernels behind the FC projections (LAFF_FC_KERNEL_* of include/laff_hip.h, in that order).  The first six are what
+#: fc_act_bn_grouped / fc_act_bn_split_grouped / fc_act_bn_fused_grouped choose between; fc_act_bn_strip_grouped, fc_gather_act_bn and
+#: fc_concat_act_bn_grouped each have a kernel family of their own.
+FC_ROUTES = ('F32_REG', 'F32_TAIL', 'F32_GLDS', 'F16_128', 'X3', 'X3_FUSED', 'STRIP', 'GATHER', 'CONCAT')
+_FC_FAMILIES = {'fp32': 0, 'split': 1, 'fused': 2}
+_FC_OWN_KERNEL = {'strip': 'STRIP', 'gather': 'GATHER', 'concat': 'CONCAT'}
+
+
+class FcRoute:
+    """What fc_route reports.  kinds: per problem, the staging kind 0 / 1 / 2 (family 'fp32') or the tile edge 128 / 256 ('split',
+    'fused'), None for an empty problem; launch_of: per problem, the index of its launch (None: empty); launches: in launch order,
+    dicts with kernel (FC_ROUTES), problems (indices), tiles, nbig and quarters (the split tile's tail split, 0 elsewhere)."""
+
+    def __init__(self, kinds, launch_of, launches):
+        self.kinds, self.launch_of, self.launches = kinds, launch_of, launches
+
+    @property
+    def kernels(self):
+        return [l['kernel'] for l in self.launches]
+
+
+def fc_route(family, shapes, device=None):
+    """Which kernels an FC entry point runs for a list of problems, in launch order; launches nothing (laff_fc_route: the answer of the
+    functions the launches themselves go through, with the CU count of the device's context).
+    family: 'fp32' (fc_act_bn_grouped), 'split' (fc_act_bn_split_grouped), 'fused' (fc_act_bn_fused_grouped); 'strip', 'gather' and
+    'concat' (fc_act_bn_strip_grouped, fc_gather_act_bn, fc_concat_act_bn_grouped) have one kernel family each and are only named.
+    shapes: dicts with N, Dk, D and optional ldx, ldw (default Dk), x_aligned, w_aligned (16-byte aligned bases, default True) --
+    or with x and weight, the tensors themselves (weight may be a SplitOperand)."""
+    if family in _FC_OWN_KERNEL:
+        k = _FC_OWN_KERNEL[family]
+        return FcRoute([None] * len(shapes), [None] * len(shapes), [dict(kernel=k, problems=list(range(len(shapes))), tiles=0, nbig=0,
+                                                                         quarters=0)])
+    if family not in _FC_FAMILIES:
+        raise ValueError('family must be one of %s, got %r' % (sorted(list(_FC_FAMILIES) + list(_FC_OWN_KERNEL)), family))
+    n = len(shapes)
+    arr = (FcShape * max(n, 1))()
+    for i, q in enumerate(shapes):
+        if 'x' in q:
+            x, w = q['x'], q.get('weight', q.get('weight_split'))
+            if isinstance(x, SplitOperand):
+                N, Dk, ldx, xa = x.N, x.K, x.K, True
+            else:
+                N, Dk, ldx, xa = x.shape[0], x.shape[1], _rows(x, 'x')[1], x.data_ptr() % 16 == 0
+            if isinstance(w, SplitOperand):
+                D, ldw, wa = w.N, w.K, True
+            else:
+                D, ldw, wa = w.shape[0], _rows(w, 'weight')[1], w.data_ptr() % 16 == 0
+            if device is None:
+                device = (x.buf if isinstance(x, SplitOperand) else x).device
+        else:
+            N, Dk, D = int(q['N']), int(q['Dk']), int(q['D'])
+            ldx, ldw = int(q.get('ldx', Dk)), int(q.get('ldw', Dk))
+            xa, wa = bool(q.get('x_aligned', True)), bool(q.get('w_aligned', True))
+        arr[i] = FcShape(N, Dk, D, ldx, ldw, int(xa), int(wa))
+    lib, h = _context(torch.device(device) if device is not None else torch.device('cuda'))
+    kind, launch_of = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+    cap = 3 * (n // 8 + 1)
+    launches, nl = (FcLaunch * cap)(), C.c_int(0)
+    check(lib.laff_fc_route(h, _FC_FAMILIES[family], arr, n, kind, launch_of, launches, cap, C.byref(nl)))
+    out = []
+    for j in range(nl.value):
+        l = launches[j]
+        if l.kernel >= len(FC_ROUTES):
+            raise RuntimeError('laff_fc_route: kernel %d is not an FC route' % l.kernel)
+        out.append(dict(kernel=FC_ROUTES[l.kernel], problems=[i for i in range(n) if launch_of[i] == j], tiles=int(l.tiles),
+                        nbig=int(l.nbig), quarters=int(l.quarters)))
+        assert len(out[-1]['problems']) == l.count
+    return FcRoute([kind[i] if kind[i] >= 0 else None for i in range(n)], [launch_of[i] if launch_of[i] >= 0 else None for i in range(n)],
+                   out)
 
 
 class StripWeights:
