@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 31
+#define LAFF_ABI_VERSION 32
 
 enum {
     LAFF_OK = 0,
@@ -685,6 +685,37 @@ int laff_v2t_count_exact(laff_ctx* ctx, const float* S, int Nt, int Nv, int lds,
  * 64 / 512 / 2048 / 4096 / 8192) must fit 160 KiB of LDS: wider collections are split by columns and the per-block lists merged with a
  * second call (laff_amd.ops.topk_rows does; LAFF_E_UNSUPPORTED says how many columns fit). */
 int laff_topk_rows(laff_ctx* ctx, const float* S, int Nt, int Nv, int lds, int K, int* idx_out, float* val_out);
+
+/* ---- retrieval post-processing: k-reciprocal re-ranking (model/ReRank.py:19-104, Zhong et al., CVPR 2017) -------------------------
+ * P independent problems per call; a problem is one candidate set given as three SIMILARITY blocks by pointer and pitch: qq [Q, Q],
+ * qg [Q, G], gg [G, G] (gg need not be symmetric), N = Q + G items.  The N x N matrix is never concatenated.  All arithmetic fp32:
+ *   orig = 2 - 2 [[qq, qg], [qg^T, gg]];  D[i, j] = orig[j, i] / max_k orig[k, i]  (IEEE division)
+ *   rank[i] = the k1 + 1 smallest entries of D[i, :], ascending (ties: lower index)
+ *   R(i, k) = { j in rank[i][0..k] : i in rank[j][0..k] };  kh = round_half_even(k1 / 2)
+ *   E(i) = R(i, k1) + every R(c, kh), c in R(i, k1), with |R(c, kh) & R(i, k1)| > 2/3 |R(c, kh)|  (a set, ascending)
+ *   V[i, e] = exp(-D[i, e]) / sum over E(i);  k2 != 1: V[i] <- mean of V[rank[i][0..k2)]
+ *   m[i, j] = sum_k min(V[i, k], V[j, k]);  out[i, g] = (1 - m / (2 - m)) (1 - lambda) + D[i, Q + g] lambda   for i < Q, j = Q + g
+ * out [Q, ldo] of every problem receives its Q x G block.  workspace: laff_rerank_workspace_bytes(problems, P, k1, k2) bytes, 256-byte
+ * aligned; per problem it holds the neighbour lists and the sparse rows of V before and after the query expansion, about
+ * 8 N (min(cap, N) + min(k2 cap, N)) bytes with cap = (k1 + 1)(kh + 2) -- 42 MB at N = 3001, k1 = 20, k2 = 6.
+ * Limits (LAFF_E_UNSUPPORTED): 1 <= k1 <= 32, 1 <= k2 <= min(8, k1 + 1), Q >= 1, G >= 1, k1 + 1 <= N <= 4096.
+ * No allocation, no host synchronisation; problems run 16 to a launch set of four kernels.  A problem's result does not depend on
+ * the problems it is batched with (bitwise). */
+typedef struct laff_rerank_problem {
+    const float* qq; long long ldqq;
+    const float* qg; long long ldqg;
+    const float* gg; long long ldgg;
+    float* out;      long long ldo;
+    int Q, G;
+} laff_rerank_problem;
+int laff_rerank_workspace_bytes(const laff_rerank_problem* problems /*host array; Q and G are read*/, int P, int k1, int k2, size_t* out);
+int laff_rerank_run(laff_ctx* ctx, const laff_rerank_problem* problems /*host array*/, int P, int k1, int k2, float lambda_value,
+                    void* workspace, size_t workspace_bytes);
+/* re_ranking_tkb_simple (model/ReRank.py:107-159) after the two top-K passes (laff_topk_rows): nn [G, k1] int32 = the k1 best columns
+ * of every gg row, cand [Q, K] int32 = the K best columns of every qg row.  count [G] int32 receives 1 + the number of rows of nn
+ * that hold the column (a histogram pass); out [Q, ldo] receives log(count + 1) at each row's candidate columns and 0 in its other
+ * G - K columns.  The caller L2-normalises the rows (loss.l2norm).  An index outside [0, G) is skipped. */
+int laff_rerank_tkb(laff_ctx* ctx, const int* nn, int G, int k1, const int* cand, int Q, int K, int* count, float* out, int ldo);
 
 /* ---- a13: evaluation.eval (evaluation.py:92-109) for single-GT rows ---------------------------------------
  * rank[i] = r[i] + base must be >= 1: pass 1-based ranks with base = 0, or the counts of better-scoring videos that

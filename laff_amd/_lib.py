@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 class Plane(C.Structure):
@@ -105,6 +105,11 @@ class FrameDesc(C.Structure):
                 ('reserved', C.c_int32 * 2)]
 
 
+class RerankProblem(C.Structure):
+    _fields_ = [('qq', C.c_void_p), ('ldqq', C.c_longlong), ('qg', C.c_void_p), ('ldqg', C.c_longlong), ('gg', C.c_void_p),
+                ('ldgg', C.c_longlong), ('out', C.c_void_p), ('ldo', C.c_longlong), ('Q', C.c_int), ('G', C.c_int)]
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
     'laff_abi_version': (C.c_int, []),
@@ -188,6 +193,9 @@ SIGNATURES = {
     'laff_bert_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(BertText), _I, _P, _I, _P, C.c_size_t]),
     'laff_netvlad_workspace_bytes': (C.c_int, [_I, _I, C.POINTER(C.c_size_t)]),
     'laff_netvlad_encode': (C.c_int, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _I, _I, _P, _P, _I, _P, _I, _P, C.c_size_t]),
+    'laff_rerank_workspace_bytes': (C.c_int, [C.POINTER(RerankProblem), _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_rerank_run': (C.c_int, [_P, C.POINTER(RerankProblem), _I, _I, _I, _F, _P, C.c_size_t]),
+    'laff_rerank_tkb': (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I]),
 }
 
 _lib = None

@@ -977,6 +977,113 @@ int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const i
     return LAFF_OK;
 }
 
+namespace {
+size_t rr_pad(size_t b) { return (b + 255) / 256 * 256; }
+int rr_round_half_even(int k1) { return (k1 & 1) ? ((k1 / 2) & 1 ? k1 / 2 + 1 : k1 / 2) : k1 / 2; }
+// checks k1 / k2 and one problem's sizes; lays the problem's workspace out from `base` (may be null: sizes only); returns the bytes
+int rerank_layout(const char* fn, int i, int Q, int G, int k1, int k2, char* base, laff::RerankProblem* d, size_t* bytes) {
+    if (k1 < 1 || k1 > laff::RERANK_MAX_K1) return fail(LAFF_E_UNSUPPORTED, "%s: k1=%d: supported 1 <= k1 <= %d", fn, k1, laff::RERANK_MAX_K1);
+    if (k2 < 1 || k2 > laff::RERANK_MAX_K2 || k2 > k1 + 1)
+        return fail(LAFF_E_UNSUPPORTED, "%s: k2=%d: supported 1 <= k2 <= min(%d, k1 + 1)", fn, k2, laff::RERANK_MAX_K2);
+    if (Q < 1 || G < 1) return fail(LAFF_E_UNSUPPORTED, "%s: problem %d: Q=%d G=%d: both at least 1", fn, i, Q, G);
+    const long N = (long)Q + G;
+    if (N < k1 + 1 || N > laff::RERANK_MAX_N)
+        return fail(LAFF_E_UNSUPPORTED, "%s: problem %d: N=Q+G=%ld: supported k1 + 1 = %d <= N <= %d", fn, i, N, k1 + 1, laff::RERANK_MAX_N);
+    const int cap = (k1 + 1) * (rr_round_half_even(k1) + 2);
+    const int L1 = (int)std::min<long>(cap, N), L2 = k2 == 1 ? L1 : (int)std::min<long>((long)k2 * cap, N);
+    size_t o = 0;
+    auto take = [&](size_t b) { char* r = base ? base + o : nullptr; o += rr_pad(b); return r; };
+    char* rank = take((size_t)N * (k1 + 1) * 4);
+    char* colmax = take((size_t)N * 4);
+    char* cnt1 = take((size_t)N * 4);
+    char* idx1 = take((size_t)N * L1 * 4);
+    char* val1 = take((size_t)N * L1 * 4);
+    char *cnt2 = cnt1, *idx2 = idx1, *val2 = val1;
+    if (k2 != 1) {
+        cnt2 = take((size_t)N * 4);
+        idx2 = take((size_t)N * L2 * 4);
+        val2 = take((size_t)N * L2 * 4);
+    }
+    if (d) {
+        d->L1 = L1; d->L2 = L2;
+        d->rank = (int*)rank; d->colmax = (float*)colmax;
+        d->cnt1 = (int*)cnt1; d->idx1 = (int*)idx1; d->val1 = (float*)val1;
+        d->cnt2 = (int*)cnt2; d->idx2 = (int*)idx2; d->val2 = (float*)val2;
+    }
+    *bytes = o;
+    return LAFF_OK;
+}
+}  // namespace
+
+int laff_rerank_workspace_bytes(const laff_rerank_problem* problems, int P, int k1, int k2, size_t* out) {
+    const char* fn = "laff_rerank_workspace_bytes";
+    if (!out || P < 0 || (P && !problems)) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    size_t total = 0;
+    for (int i = 0; i < P; ++i) {
+        size_t b;
+        if (int rc = rerank_layout(fn, i, problems[i].Q, problems[i].G, k1, k2, nullptr, nullptr, &b)) return rc;
+        total += b;
+    }
+    *out = total;
+    return LAFF_OK;
+}
+
+int laff_rerank_run(laff_ctx* ctx, const laff_rerank_problem* problems, int P, int k1, int k2, float lambda_value, void* workspace,
+                    size_t workspace_bytes) {
+    const char* fn = "laff_rerank_run";
+    // every argument is checked before any GPU work
+    if (P < 0 || (P && !problems)) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    if (!(lambda_value >= 0.0f && lambda_value <= 1.0f)) return fail(LAFF_E_ARG, "%s: lambda_value=%g outside [0, 1]", fn, (double)lambda_value);
+    size_t need = 0;
+    if (int rc = laff_rerank_workspace_bytes(problems, P, k1, k2, &need)) {
+        g_err.replace(0, strlen("laff_rerank_workspace_bytes"), fn);
+        return rc;
+    }
+    if (P == 0) return LAFF_OK;
+    for (int i = 0; i < P; ++i) {
+        const laff_rerank_problem& q = problems[i];
+        if (!q.qq || !q.qg || !q.gg || !q.out) return fail(LAFF_E_ARG, "%s: problem %d has a null pointer", fn, i);
+        if (q.ldqq < q.Q || q.ldqg < q.G || q.ldgg < q.G || q.ldo < q.G)
+            return fail(LAFF_E_SHAPE, "%s: problem %d: a pitch is shorter than its row (Q=%d G=%d)", fn, i, q.Q, q.G);
+    }
+    if (!workspace || workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace ? workspace_bytes : (size_t)0, need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(LAFF_E_ALIGN, "%s: workspace must be 256-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* base = (char*)workspace;
+    for (int i0 = 0; i0 < P; i0 += laff::RERANK_GROUP) {
+        laff::RerankArgs a{};
+        a.count = std::min(P - i0, laff::RERANK_GROUP);
+        a.k1 = k1; a.k2 = k2; a.kh = rr_round_half_even(k1); a.lambda = lambda_value;
+        int maxQ = 0, maxG = 0, maxN = 0;
+        for (int i = 0; i < a.count; ++i) {
+            const laff_rerank_problem& q = problems[i0 + i];
+            laff::RerankProblem& d = a.p[i];
+            d.qq = q.qq; d.qg = q.qg; d.gg = q.gg; d.out = q.out;
+            d.ldqq = (long)q.ldqq; d.ldqg = (long)q.ldqg; d.ldgg = (long)q.ldgg; d.ldo = (long)q.ldo;
+            d.Q = q.Q; d.G = q.G;
+            size_t b;
+            (void)rerank_layout(fn, i0 + i, q.Q, q.G, k1, k2, base, &d, &b);
+            base += b;
+            maxQ = std::max(maxQ, q.Q); maxG = std::max(maxG, q.G); maxN = std::max(maxN, q.Q + q.G);
+        }
+        // the grids and the LDS rows are sized for the largest Q, G and N = Q + G of the set (each possibly of another problem)
+        HIP_TRY(laff::launch_rerank(a, maxQ, maxG, maxN, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
+int laff_rerank_tkb(laff_ctx* ctx, const int* nn, int G, int k1, const int* cand, int Q, int K, int* count, float* out, int ldo) {
+    const char* fn = "laff_rerank_tkb";
+    if (G < 1 || Q < 0 || k1 < 1 || k1 > G || K < 0 || K > G || ldo < G)
+        return fail(LAFF_E_SHAPE, "%s: need 1 <= k1 <= G, 0 <= K <= G, ldo >= G (G=%d Q=%d k1=%d K=%d ldo=%d)", fn, G, Q, k1, K, ldo);
+    if (!nn || !count || (Q && (!out || (K && !cand)))) return fail(LAFF_E_ARG, "%s: null argument", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_rerank_tkb(nn, G, k1, cand, Q, K, count, out, ldo, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

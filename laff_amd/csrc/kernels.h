@@ -449,4 +449,33 @@ struct NetvladArgs {
 };
 hipError_t launch_netvlad_encode(const NetvladArgs& a, hipStream_t st);
 
+// rerank.hip: k-reciprocal re-ranking (laff_rerank_run) and the neighbour-count re-ranking (laff_rerank_tkb)
+constexpr int RERANK_MAX_K1 = 32;
+constexpr int RERANK_MAX_K2 = 8;
+constexpr int RERANK_MAX_N = 4096;        // items of one problem: four N-float rows in 64 KiB of LDS
+constexpr int RERANK_MAX_CAP = 608;       // >= (k1 + 1) * (round(k1 / 2) + 2) at k1 = 32 (594): the expansion set's bound
+constexpr int RERANK_GROUP = 16;          // problems per launch (the descriptors travel as kernel arguments)
+struct RerankProblem {
+    const float *qq, *qg, *gg;            // [Q, Q], [Q, G], [G, G] similarities
+    float* out;                           // [Q, G]
+    long ldqq, ldqg, ldgg, ldo;
+    int Q, G;
+    int L1, L2;                           // row pitch of the sparse rows: min(cap, N), min(k2 cap, N)
+    int* rank;                            // workspace: [N, k1 + 1] neighbour lists, ascending distance
+    float* colmax;                        // workspace: [N] column maxima of 2 - 2 x
+    int *cnt1, *idx1;                     // workspace: V before query expansion, [N] entries per row, [N, L1] columns (ascending)
+    float* val1;                          //            [N, L1] weights
+    int *cnt2, *idx2;                     // workspace: V after query expansion, [N, L2] (the same buffers as *1 when k2 == 1)
+    float* val2;
+};
+struct RerankArgs {
+    RerankProblem p[RERANK_GROUP];
+    int count, k1, k2, kh;                // kh = round_half_even(k1 / 2)
+    float lambda;
+};
+size_t rerank_lds_bytes(int maxN);
+hipError_t launch_rerank(const RerankArgs& a, int maxQ, int maxG, int maxN, hipStream_t st);   // the largest Q, G and Q + G of the set
+hipError_t launch_rerank_tkb(const int* nn, int G, int k1, const int* cand, int Q, int K, int* count, float* out, long ldo,
+                             hipStream_t st);
+
 }  // namespace laff

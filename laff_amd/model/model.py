@@ -954,6 +954,75 @@ class W2VVPP(nn.Module):
         with 288 GB of HBM the single-pass path covers it, results are identical."""
         return self.predict(txt_loader, vis_loader, measure, False)
 
+    # -- re-ranked predict ----------------------------------------------------------------------------------
+    #: queries whose candidate blocks (K x K similarities + re-ranking workspace) are alive at once
+    rerank_chunk_bytes = 1 << 30
+
+    def _rerank_predict(self, rerank_rows, txt_loader, vis_loader, measure, t2i_matrix, topK, reranking_weight, return_blocks):
+        if measure != 'cosine':
+            raise NotImplementedError("measure '%s'" % measure)
+        self.eval()
+        precision = self.sim_precision or self.predict_precision
+        with torch.no_grad():
+            Ev, idxs_list, _ = self._embed_videos(vis_loader)
+            cols = np.concatenate([np.asarray(i, dtype=np.int64) for i in idxs_list])
+            Et = torch.cat([self.txt_net(caption_feat_dict) for caption_feat_dict, _, _ in txt_loader], dim=0)
+            out = torch.as_tensor(np.asarray(t2i_matrix), dtype=torch.float32).to(Ev.device).contiguous().clone()
+            Nt, Nv = out.shape
+            if Et.shape[0] != Nt or len(cols) != Nv or not np.array_equal(np.sort(cols), np.arange(Nv)):
+                raise ValueError('t2i_matrix is %d x %d; the loaders give %d captions and %d videos' % (Nt, Nv, Et.shape[0], len(cols)))
+            if not np.array_equal(cols, np.arange(Nv)):               # embeddings by t2i_matrix column (= dataset index)
+                by_col = torch.empty_like(Ev)
+                by_col[torch.as_tensor(cols, device=Ev.device)] = Ev
+                Ev = by_col
+            K = min(int(topK), Nv)
+            cand, _ = ops.topk_rows(out, K)
+            cand = cand.long()
+            per_query = 4 * K * K + 8 * K * min(K + 1, 2048)
+            step = max(1, int(self.rerank_chunk_bytes // per_query))
+            one = torch.ones((1, 1), device=Ev.device, dtype=torch.float32)
+            blocks = ([], [])
+            for r0 in range(0, Nt, step):
+                problems = []
+                for r in range(r0, min(Nt, r0 + step)):
+                    Ec = Ev[cand[r]].contiguous()
+                    s = self.get_txt2vis_matrix(Et[r:r + 1].contiguous(), Ec, measure, precision)
+                    gg = self.get_txt2vis_matrix(Ec, Ec, measure, precision)
+                    problems.append((s.contiguous(), one, gg.contiguous()))
+                for r, (s, _, gg), rr in zip(range(r0, r0 + len(problems)), problems, rerank_rows(problems)):
+                    out[r, cand[r]] = (s + reranking_weight * rr)[0]
+                    if return_blocks:
+                        blocks[0].append(s[0].cpu().numpy())
+                        blocks[1].append(gg.cpu().numpy())
+            res = _loss.l2norm(out).cpu().numpy()
+        if return_blocks:
+            return res, cand.cpu().numpy(), np.stack(blocks[0]), np.stack(blocks[1])
+        return res
+
+    def predict_rerank(self, txt_loader, vis_loader, measure, t2i_matrix, topK=3000, k1=20, reranking_weight=2, return_blocks=False):
+        """The reference's predict_rerank (model/model.py:1131-1201) on the device.  For every query row r of t2i_matrix: cand = its
+        K = min(topK, Nv) best columns (descending), s = the similarity of text r to the candidates, gg = the candidates against
+        themselves (both by get_txt2vis_matrix's route at predict()'s precision), and
+        out[r, cand] = s + reranking_weight * ReRank.re_ranking(s, [[1]], gg, k1=k1); the other columns keep t2i_matrix's values; rows
+        are then L2-normalised.  Returns np.float32 [Nt, Nv]; with return_blocks=True (our addition, for small shapes) also
+        cand [Nt, K], s [Nt, K] and gg [Nt, K, K] as consumed.
+
+        Two deliberate deviations from the reference: it addresses the query as `i * j + j` (batch i, row j), which is the intended
+        row only within the first text batch -- the global row index is used here; and its per-query subset loader does not run
+        against its own current loader format -- the video embeddings are computed once, as predict() does, and the candidates'
+        rows gathered on the device."""
+        from . import ReRank
+        return self._rerank_predict(lambda ps: ReRank.re_ranking_batched(ps, k1=k1), txt_loader, vis_loader, measure, t2i_matrix, topK,
+                                    reranking_weight, return_blocks)
+
+    def predict_rerank_tkb_simple(self, txt_loader, vis_loader, measure, t2i_matrix, topK=3000, k1=20, reranking_weight=2,
+                                  return_blocks=False):
+        """The reference's predict_rerank_tkb_simple (model/model.py:1203-1275): as predict_rerank, with
+        ReRank.re_ranking_tkb_simple(s, [[1]], gg, topK=topK, k1=k1) as the re-ranking term (same two deviations)."""
+        from . import ReRank
+        return self._rerank_predict(lambda ps: [ReRank.re_ranking_tkb_simple(s, qq, gg, topK=topK, k1=k1) for s, qq, gg in ps],
+                                    txt_loader, vis_loader, measure, t2i_matrix, topK, reranking_weight, return_blocks)
+
 
 class W2VVPP_MutiVis(W2VVPP):
     def _init_txt_net(self, opt):

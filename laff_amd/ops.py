@@ -12,9 +12,9 @@ import torch
 from . import _lib
 from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT_MUL, ATT_NO_SPLIT_HEAD, ATT_WITH_AVE, PREC,
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
-                   FcLaunch, FcShape)
+                   FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1486,6 +1486,64 @@ def topk_from_operands(T, V, K, heads=1, block_rows=None, scratch_bytes=192 << 2
         i, v = topk_rows(S, K)
         idx[r0:r1], val[r0:r1] = i, v
     return idx, val
+
+
+def _rerank_array(sizes):
+    arr = (RerankProblem * max(len(sizes), 1))()
+    for a, (Q, G) in zip(arr, sizes):
+        a.Q, a.G = int(Q), int(G)
+    return arr
+
+
+def rerank_workspace_bytes(sizes, k1=20, k2=6):
+    """laff_rerank_workspace_bytes for problems of the given (Q, G) sizes; raises on sizes or k1 / k2 outside the kernels' limits."""
+    lib = _lib.load()
+    n = C.c_size_t()
+    check(lib.laff_rerank_workspace_bytes(_rerank_array(sizes), len(sizes), int(k1), int(k2), C.byref(n)))
+    return n.value
+
+
+def rerank_run(problems, k1=20, k2=6, lambda_value=0.3, workspace=None):
+    """laff_rerank_run: k-reciprocal re-ranking of P independent problems in one call.  problems: a list of (qg [Q, G], qq [Q, Q],
+    gg [G, G]) fp32 device SIMILARITY matrices with contiguous rows (views with a pitch are taken as they are).  Returns the list of
+    [Q, G] fp32 results.  workspace: a uint8 device tensor of rerank_workspace_bytes(...) bytes, or None to allocate one here."""
+    if not problems:
+        return []
+    arr = (RerankProblem * len(problems))()
+    outs = []
+    dev = problems[0][0].device
+    for a, (qg, qq, gg) in zip(arr, problems):
+        (qg, ldqg), (qq, ldqq), (gg, ldgg) = _rows(qg, 'q_g_dist'), _rows(qq, 'q_q_dist'), _rows(gg, 'g_g_dist')
+        Q, G = qg.shape
+        if tuple(qq.shape) != (Q, Q) or tuple(gg.shape) != (G, G):
+            raise ValueError('re-ranking blocks must be q_g [Q, G], q_q [Q, Q], g_g [G, G]; got %s, %s, %s'
+                             % (tuple(qg.shape), tuple(qq.shape), tuple(gg.shape)))
+        out = torch.empty((Q, G), device=dev, dtype=torch.float32)
+        a.qq, a.ldqq, a.qg, a.ldqg, a.gg, a.ldgg = qq.data_ptr(), ldqq, qg.data_ptr(), ldqg, gg.data_ptr(), ldgg
+        a.out, a.ldo, a.Q, a.G = out.data_ptr(), max(G, 1), Q, G
+        outs.append(out)
+    lib, h = _context(dev)
+    n = C.c_size_t()
+    check(lib.laff_rerank_workspace_bytes(arr, len(problems), int(k1), int(k2), C.byref(n)))
+    if workspace is None:
+        workspace = torch.empty(max(n.value, 256), dtype=torch.uint8, device=dev)
+    _call('rerank_run', lib.laff_rerank_run, h, arr, len(problems), int(k1), int(k2), float(lambda_value), _ptr(workspace),
+          workspace.numel())
+    return outs
+
+
+def rerank_tkb(nn, cand, G):
+    """laff_rerank_tkb: nn [G, k1] int32 (the k1 best columns of every g_g row), cand [Q, K] int32 (the K best columns of every q_g
+    row).  Returns (out [Q, G] fp32: log(count + 1) at the candidate columns, 0 elsewhere; count [G] int32)."""
+    nn, cand = _dev(nn, 'nn', torch.int32), _dev(cand, 'cand', torch.int32)
+    if nn.dim() != 2 or cand.dim() != 2 or nn.shape[0] != G or not nn.is_contiguous() or not cand.is_contiguous():
+        raise ValueError('nn must be [G, k1] and cand [Q, K], contiguous')
+    Q, K = cand.shape
+    count = torch.empty((G,), device=nn.device, dtype=torch.int32)
+    out = torch.empty((Q, G), device=nn.device, dtype=torch.float32)
+    lib, h = _context(nn.device)
+    _call('rerank_tkb', lib.laff_rerank_tkb, h, _ptr(nn), int(G), nn.shape[1], _ptr(cand), Q, K, _ptr(count), _ptr(out), int(G))
+    return out, count
 
 
 def v2t_count(S, grp_off, grp_idx, max_group):
