@@ -11,7 +11,6 @@ keys a weight of exactly 0: each caption's rows are its unpadded computation, so
 The vocabulary (`vocab.txt` of a BERT checkpoint) is an input of the deployment: pass its path, or load a local checkpoint directory
 with `BertTxtEncoder.from_pretrained`.  Nothing is ever fetched.
 """
-import collections
 import json
 import os
 import re
@@ -21,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .clip_text import _chunks, _Weights
+from .ragged import RaggedBatch as BertBatch, _TextEncoder, _Weights, ragged_batch
 
 SPECIALS = ('[UNK]', '[SEP]', '[PAD]', '[CLS]', '[MASK]')
 MAX_POSITION = 512                                        # what bert.hip's limits take (BertConfig's default as well)
@@ -45,12 +44,6 @@ def _is_punctuation(ch):
 def _is_cjk(cp):
     return (0x4E00 <= cp <= 0x9FFF or 0x3400 <= cp <= 0x4DBF or 0x20000 <= cp <= 0x2A6DF or 0x2A700 <= cp <= 0x2B73F or
             0x2B740 <= cp <= 0x2B81F or 0x2B820 <= cp <= 0x2CEAF or 0xF900 <= cp <= 0xFAFF or 0x2F800 <= cp <= 0x2FA1F)
-
-
-BertBatch = collections.namedtuple('BertBatch', ['ids', 'row_off', 'row_off_host'])
-BertBatch.__doc__ = """Captions as laff_bert_encode takes them: ids [R] int32 (each caption's wordpiece ids [CLS] ... [SEP], the captions
-concatenated), row_off [N+1] int32 (caption i is rows row_off[i] .. row_off[i+1] - 1; its CLS row is row_off[i]), row_off_host: the
-same offsets on the host.  ids / row_off are numpy arrays from BertTokenizer.batch and device tensors after BertTxtEncoder.to_device."""
 
 
 class BertTokenizer(object):
@@ -141,11 +134,7 @@ class BertTokenizer(object):
         return [self.cls] + self.encode(text)[:self.max_length - 2] + [self.sep]
 
     def batch(self, texts):
-        rows = [self.tokens(t) for t in texts]
-        row_off = np.zeros(len(rows) + 1, dtype=np.int32)
-        row_off[1:] = np.cumsum([len(r) for r in rows])
-        ids = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
-        return BertBatch(ids, row_off, row_off)
+        return ragged_batch([self.tokens(t) for t in texts])
 
 
 class _Layer(nn.Module):
@@ -218,7 +207,7 @@ def _check_config(cfg):
         raise NotImplementedError('%s: num_hidden_layers=%d; at least one layer' % (name, cfg['num_hidden_layers']))
 
 
-class BertTxtEncoder(nn.Module):
+class BertTxtEncoder(_TextEncoder):
     """Drop-in for model.model.BertTxtEncoder (frozen, inference):
     `model.txt_net.encoder.bert_encoder = BertTxtEncoder.from_pretrained(local_dir)` (or from_state_dict(sd, BertTokenizer(vocab))).
     Parameters keep transformers' names under `BertModel.` (BertModel.embeddings.word_embeddings.weight, BertModel.encoder.layer.3.
@@ -229,6 +218,8 @@ class BertTxtEncoder(nn.Module):
     caption_feat_dict['caption']: {'text_features': (N, hidden) fp32}.  A caption's feature is bitwise the same in any batch.
     The packed weights are cached and rebuilt whenever a parameter changes (load_state_dict, copy_, ...).  max_rows bounds the
     token rows per device call (and so the workspace); it does not change any result."""
+
+    feature_key = 'bert_encoding'
 
     def __init__(self, tokenizer, config, precision='fp32', device='cuda', max_rows=1 << 16):
         super().__init__()
@@ -242,6 +233,7 @@ class BertTxtEncoder(nn.Module):
         self.max_position, self.vocab_size = int(cfg['max_position_embeddings']), int(cfg['vocab_size'])
         self.type_vocab_size = int(cfg.get('type_vocab_size', 2))
         self.layer_norm_eps = float(cfg.get('layer_norm_eps', 1e-12))
+        self.out_width, self.max_len = self.width, self.max_position
         self.BertModel = _BertModel(self.width, self.layers, self.intermediate, self.max_position, self.vocab_size, self.type_vocab_size)
         self.to(device)
         self._weights = _Weights(self.BertModel, precision)
@@ -333,19 +325,13 @@ class BertTxtEncoder(nn.Module):
                                  packed(m.pooler.dense.weight), f32(m.pooler.dense.bias))
         return self._weights.get(build)
 
-    def batch(self, captions):
-        """BertTokenizer.batch, cut at this encoder's positions, with the ids checked against its vocabulary."""
+    def _tokenize(self, captions):
+        """BertTokenizer.batch, cut at this encoder's positions."""
         b = self.tokenizer.batch(captions)
         if len(b.row_off) > 1 and int(np.diff(b.row_off).max()) > self.max_position:
             raise ValueError('a caption of %d tokens: the encoder has %d positions (tokenizer max_length)'
                              % (int(np.diff(b.row_off).max()), self.max_position))
-        if b.ids.size and (int(b.ids.max()) >= self.vocab_size or int(b.ids.min()) < 0):
-            raise ValueError('token id %d outside the vocabulary of %d' % (int(b.ids.max()), self.vocab_size))
         return b
-
-    def to_device(self, b):
-        dev = self.BertModel.embeddings.word_embeddings.weight.device
-        return BertBatch(torch.from_numpy(b.ids).to(dev), torch.from_numpy(b.row_off).to(dev), b.row_off_host)
 
     def workspace_bytes(self, b):
         from . import ops
@@ -355,23 +341,3 @@ class BertTxtEncoder(nn.Module):
         """The device half of forward(): a BertBatch on the device, in one call (allocates nothing when out and workspace are given)."""
         from . import ops
         return ops.bert_encode(b.ids, b.row_off, b.row_off_host, self._model(), self.precision, out=out, workspace=workspace)
-
-    def encode(self, captions, max_rows=None):
-        """Caption strings -> (N, hidden), in calls of at most max_rows token rows (one caption never spans two calls)."""
-        b = self.batch(captions)
-        dev = self.BertModel.embeddings.word_embeddings.weight.device
-        N, roh = len(captions), b.row_off_host
-        out = torch.empty((N, self.width), device=dev, dtype=torch.float32)
-        if N == 0:
-            return out
-        budget = max(int(max_rows or self.max_rows), self.max_position)
-        ids, ro = torch.from_numpy(b.ids).to(dev), torch.from_numpy(roh).to(dev)
-        for c0, c1, ws in _chunks(roh, budget, lambda c0, c1: self.workspace_bytes(BertBatch(None, None, roh[c0:c1 + 1] - roh[c0])), dev):
-            r0, r1 = int(roh[c0]), int(roh[c1])
-            self.encode_batch(BertBatch(ids[r0:r1], ro[c0:c1 + 1] - r0, roh[c0:c1 + 1] - r0), out=out[c0:c1], workspace=ws)
-        return out
-
-    def forward(self, caption_feat_dict, task3=False):
-        if 'bert_encoding' in caption_feat_dict:
-            return {'text_features': caption_feat_dict['bert_encoding']}
-        return {'text_features': self.encode(caption_feat_dict['caption'])}

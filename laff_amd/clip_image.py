@@ -14,7 +14,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .clip_text import _Block, _Weights, _check_dims, _chunks, _init_blocks
+from .clip_text import _Block, _check_dims, _init_blocks
+from .ragged import _Weights, _chunks
 
 _PREFIXES = ('clip_model.ClipModel.', 'ClipModel.')
 

@@ -14,13 +14,14 @@ Two documented approximations of the host side, both exact in the cases stated:
   * `ftfy.fix_text` is applied when ftfy is importable, otherwise the identity: exact for text that ftfy leaves alone.
   * the split pattern uses the `regex` module (\\p{L}, \\p{N}); without it a stdlib pattern is used that is exact for ASCII text.
 """
-import collections
 import gzip
 import html
 
 import numpy as np
 import torch
 import torch.nn as nn
+
+from .ragged import RaggedBatch as ClipBatch, _TextEncoder, _Weights, _chunks, ragged_batch   # noqa: F401 (_chunks: re-export)
 
 try:
     import ftfy
@@ -54,12 +55,6 @@ def byte_symbols():
             table[b] = chr(256 + n)
             n += 1
     return table
-
-
-ClipBatch = collections.namedtuple('ClipBatch', ['ids', 'row_off', 'row_off_host'])
-ClipBatch.__doc__ = """Captions as laff_clip_encode takes them: ids [R] int32 (caption i's ids up to and including p_i, the captions
-concatenated), row_off [N+1] int32 (caption i is rows row_off[i] .. row_off[i+1] - 1), row_off_host: the same offsets on the host.
-ids / row_off are numpy arrays from ClipTokenizer.batch and device tensors after ClipTxtEncoder.to_device."""
 
 
 class ClipTokenizer(object):
@@ -143,10 +138,7 @@ class ClipTokenizer(object):
         for t in texts:
             ids = self.tokens(t, context_length)
             rows.append(ids[:int(np.argmax(ids)) + 1])
-        row_off = np.zeros(len(rows) + 1, dtype=np.int32)
-        row_off[1:] = np.cumsum([len(r) for r in rows])
-        ids = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
-        return ClipBatch(ids, row_off, row_off)
+        return ragged_batch(rows)
 
 
 class _Attn(nn.Module):
@@ -192,62 +184,6 @@ def _check_dims(name, precision, width, heads, layers):
         raise NotImplementedError('%s: layers=%d; at least one block' % (name, layers))
 
 
-def _chunks(off, budget, workspace_bytes, device):
-    """The calls of a budgeted encode: (i0, i1, ws) for the consecutive items i0 .. i1 - 1 whose offsets off[i0] .. off[i1] span at
-    most budget (one item at least, so a longer item gets a call of its own), with a uint8 workspace of at least
-    workspace_bytes(i0, i1) bytes on the device, grown as needed."""
-    n, i0, ws = len(off) - 1, 0, None
-    while i0 < n:
-        i1 = int(np.searchsorted(off, off[i0] + budget, side='right')) - 1     # the items that end within the budget
-        i1 = min(max(i1, i0 + 1), n)
-        need = workspace_bytes(i0, i1)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-        yield i0, i1, ws
-        i0 = i1
-
-
-class _Weights(object):
-    """The device copies of a tower's parameters that its laff_* model struct points at, kept alive with it: f32 / packed return the
-    pointer of an fp32 / packed copy of a parameter, blocks the laff_clip_block array of a resblocks module.  get(build) returns the
-    struct build(self) makes, rebuilt whenever a parameter of `module` has changed since the last build (load_state_dict, copy_, ...)."""
-
-    def __init__(self, module, precision):
-        self.module, self.precision = module, precision
-        self._key, self._model, self._keep = None, None, []
-
-    def get(self, build):
-        key = tuple((p.data_ptr(), p._version, p.device) for p in self.module.parameters())
-        if key != self._key:
-            self._keep = []
-            with torch.no_grad():
-                self._model = build(self)
-            self._key = key
-        return self._model
-
-    def f32(self, t):
-        t = t.detach().float().contiguous()
-        self._keep.append(t)
-        return t.data_ptr()
-
-    def packed(self, t, transpose=False, padded_cols=None):
-        from . import ops
-        p = ops.clip_pack_weight(t.detach().float(), self.precision, transpose, padded_cols)
-        self._keep.append(p)
-        return p.data_ptr()
-
-    def blocks(self, resblocks):
-        from . import _lib
-        f32, packed = self.f32, self.packed
-        blocks = (_lib.ClipBlock * len(resblocks))()
-        for i, b in enumerate(resblocks):
-            blocks[i] = _lib.ClipBlock(f32(b.ln_1.weight), f32(b.ln_1.bias), packed(b.attn.in_proj_weight), f32(b.attn.in_proj_bias),
-                                       packed(b.attn.out_proj.weight), f32(b.attn.out_proj.bias), f32(b.ln_2.weight), f32(b.ln_2.bias),
-                                       packed(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias), packed(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))
-        self._keep.append(blocks)
-        return blocks
-
-
 class _ClipText(nn.Module):
     """The text parameters of clip.model.CLIP under their names there."""
 
@@ -269,7 +205,7 @@ class _ClipText(nn.Module):
 _IGNORED = ('visual.', 'logit_scale', 'input_resolution', 'context_length', 'vocab_size')
 
 
-class ClipTxtEncoder(nn.Module):
+class ClipTxtEncoder(_TextEncoder):
     """Drop-in for the text half of model.model.CLIPEncoder (frozen, inference):
     `model.txt_net.encoder.CLIP_encoder = ClipTxtEncoder.from_state_dict(sd, ClipTokenizer(bpe_path))`.
     Parameters keep the reference's names under `ClipModel.` (ClipModel.token_embedding.weight, ClipModel.transformer.resblocks.0.
@@ -279,6 +215,8 @@ class ClipTxtEncoder(nn.Module):
     caption_feat_dict['caption']: {'text_features': (N, embed_dim) fp32}.  A caption's feature is bitwise the same in any batch.
     The packed weights are cached and rebuilt whenever a parameter changes (load_state_dict, copy_, ...).  max_rows bounds the
     token rows per device call (and so the workspace); it does not change any result."""
+
+    feature_key = 'CLIP_encoding'
 
     def __init__(self, tokenizer, width, layers, heads, embed_dim, context_length=77, vocab_size=49408, precision='fp16',
                  device='cuda', max_rows=1 << 16):
@@ -290,6 +228,7 @@ class ClipTxtEncoder(nn.Module):
         self.tokenizer, self.device, self.precision = tokenizer, device, precision
         self.width, self.layers, self.heads, self.embed_dim = width, layers, heads, int(embed_dim)
         self.context_length, self.vocab_size, self.max_rows = int(context_length), int(vocab_size), int(max_rows)
+        self.out_width, self.max_len = self.embed_dim, self.context_length
         self.ClipModel = _ClipText(width, layers, self.embed_dim, self.context_length, self.vocab_size)
         self.to(device)
         self._weights = _Weights(self.ClipModel, precision)
@@ -328,16 +267,9 @@ class ClipTxtEncoder(nn.Module):
             w.f32(m.positional_embedding), w.blocks(m.transformer.resblocks), w.f32(m.ln_final.weight), w.f32(m.ln_final.bias),
             w.packed(m.text_projection, transpose=True)))
 
-    def batch(self, captions):
-        """ClipTokenizer.batch at this encoder's context length, with the ids checked against its vocabulary."""
-        b = self.tokenizer.batch(captions, self.context_length)
-        if b.ids.size and (int(b.ids.max()) >= self.vocab_size or int(b.ids.min()) < 0):
-            raise ValueError('token id %d outside the vocabulary of %d' % (int(b.ids.max()), self.vocab_size))
-        return b
-
-    def to_device(self, b):
-        dev = self.ClipModel.token_embedding.weight.device
-        return ClipBatch(torch.from_numpy(b.ids).to(dev), torch.from_numpy(b.row_off).to(dev), b.row_off_host)
+    def _tokenize(self, captions):
+        """ClipTokenizer.batch at this encoder's context length."""
+        return self.tokenizer.batch(captions, self.context_length)
 
     def workspace_bytes(self, b):
         from . import ops
@@ -347,23 +279,3 @@ class ClipTxtEncoder(nn.Module):
         """The device half of forward(): a ClipBatch on the device, in one call (allocates nothing when out and workspace are given)."""
         from . import ops
         return ops.clip_encode(b.ids, b.row_off, b.row_off_host, self._model(), self.precision, out=out, workspace=workspace)
-
-    def encode(self, captions, max_rows=None):
-        """Caption strings -> (N, embed_dim), in calls of at most max_rows token rows (one caption never spans two calls)."""
-        b = self.batch(captions)
-        dev = self.ClipModel.token_embedding.weight.device
-        N, roh = len(captions), b.row_off_host
-        out = torch.empty((N, self.embed_dim), device=dev, dtype=torch.float32)
-        if N == 0:
-            return out
-        budget = max(int(max_rows or self.max_rows), self.context_length)
-        ids, ro = torch.from_numpy(b.ids).to(dev), torch.from_numpy(roh).to(dev)
-        for c0, c1, ws in _chunks(roh, budget, lambda c0, c1: self.workspace_bytes(ClipBatch(None, None, roh[c0:c1 + 1] - roh[c0])), dev):
-            r0, r1 = int(roh[c0]), int(roh[c1])
-            self.encode_batch(ClipBatch(ids[r0:r1], ro[c0:c1 + 1] - r0, roh[c0:c1 + 1] - r0), out=out[c0:c1], workspace=ws)
-        return out
-
-    def forward(self, caption_feat_dict, task3=False):
-        if 'CLIP_encoding' in caption_feat_dict:
-            return {'text_features': caption_feat_dict['CLIP_encoding']}
-        return {'text_features': self.encode(caption_feat_dict['caption'])}

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -537,8 +538,54 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
 }
 
 namespace {
-// the CLIP text encoder's limits and workspace: X [R, W] fp32 | A [R, W] operand | big [R, max(3W fp32, 4W operand)], each region on
-// 256 bytes
+// what the ragged entry points share (laff_clip_encode, laff_bert_encode, laff_netvlad_encode, laff_clip_image_encode: items
+// concatenated without padding, their [N+1] offsets on the device and on the host, out with a pitch, a byte workspace)
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }                 // every workspace region starts on 256 bytes
+// the token rows one transformer call takes at most: the GEMMs' grid.y = rows / 128 stays well inside its limit
+constexpr long MAX_TOKEN_ROWS = 1L << 22;
+int check_token_rows(const char* fn, int items, long rows_per_item) {
+    if (items * rows_per_item <= MAX_TOKEN_ROWS) return LAFF_OK;
+    if (rows_per_item == 1) return fail(LAFF_E_SHAPE, "%s: R=%d: more than 4,194,304 token rows in one call", fn, items);
+    return fail(LAFF_E_SHAPE, "%s: F=%d frames of %ld tokens: more than 4,194,304 token rows in one call", fn, items, rows_per_item);
+}
+// the host copy off[0 .. N] of the offsets `name` ("row_off": rows, "frame_off": frames) of N `item`s in R rows, N and R under the
+// letters dims[0] and dims[1]: off[0] = 0, every length in [lo, hi] (hi = INT_MAX: no upper limit, otherwise `limit` names it),
+// off[N] = R -- in that order
+int check_offsets(const char* fn, const char* name, const char* item, const char* dims, const int* off, int N, int R, int lo, int hi,
+                  const char* limit) {
+    const int unit = (int)strlen(name) - 4;     /* "row" / "frame" */
+    if (off[0] != 0) return fail(LAFF_E_ARG, "%s: %s[0]=%d != 0", fn, name, off[0]);
+    for (int i = 0; i < N; ++i) {
+        const int L = off[i + 1] - off[i];
+        if (L >= lo && L <= hi) continue;
+        if (lo == 0 && L < 0) return fail(LAFF_E_ARG, "%s: %s decreases at %s %d (%d -> %d)", fn, name, item, i, off[i], off[i + 1]);
+        if (hi == INT_MAX) return fail(LAFF_E_ARG, "%s: %s: %s %d has %d %.*ss (at least %d)", fn, name, item, i, L, unit, name, lo);
+        return fail(LAFF_E_ARG, "%s: %s: %s %d has %d %.*ss (%d .. %s=%d)", fn, name, item, i, L, unit, name, lo, limit, hi);
+    }
+    if (off[N] != R) return fail(LAFF_E_ARG, "%s: %s[%c]=%d != %c=%d", fn, name, dims[0], off[N], dims[1], R);
+    return LAFF_OK;
+}
+// the workspace holds `need` bytes; then it and the packed operands named with it in `what` (others_aligned) sit on 16 bytes
+int check_workspace(const char* fn, const void* workspace, size_t workspace_bytes, size_t need, bool others_aligned, const char* what) {
+    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
+    if (!aligned16(workspace) || !others_aligned) return fail(LAFF_E_ALIGN, "%s: %s must be 16-byte aligned", fn, what);
+    return LAFF_OK;
+}
+// the workspace prefix of the transformer encoders: X [rows, W] fp32 | A [rows, W] operand (sz bytes an element) |
+// big [rows, max(3W fp32, big_cols operand)], each region on 256 bytes; total: where an encoder's own regions start.  The CLIP text
+// encoder's workspace is this prefix with big_cols = 4W
+struct ClipWs {
+    size_t x, a, big, total;
+};
+ClipWs clip_ws(size_t rows, int width, size_t sz, size_t big_cols) {
+    const size_t w = (size_t)width;
+    ClipWs s;
+    s.x = 0;
+    s.a = round256(rows * w * 4);
+    s.big = s.a + round256(rows * w * sz);
+    s.total = s.big + round256(rows * std::max(3 * w * 4, big_cols * sz));
+    return s;
+}
 int clip_precision(const char* fn, int precision, int* fp16) {
     if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "%s: unknown precision %d", fn, precision);
     if (precision != LAFF_PREC_FP32 && precision != LAFF_PREC_FP16)
@@ -568,18 +615,16 @@ int clip_check_blocks(const char* fn, const laff_clip_block* blocks, int layers)
     }
     return LAFF_OK;
 }
-size_t clip_round(size_t b) { return (b + 255) / 256 * 256; }
-struct ClipWs {
-    size_t x, a, big, total;
-};
-ClipWs clip_ws(size_t R, int width, int fp16) {
-    const size_t sz = fp16 ? 2 : 4, r = R, w = (size_t)width;
-    ClipWs s;
-    s.x = 0;
-    s.a = clip_round(r * w * 4);
-    s.big = s.a + clip_round(r * w * sz);
-    s.total = s.big + clip_round(r * std::max(3 * w * 4, 4 * w * sz));
-    return s;
+int bert_check_blocks(const char* fn, const laff_bert_block* blocks, int layers) {
+    for (int l = 0; l < layers; ++l) {
+        const laff_bert_block& b = blocks[l];
+        if (!b.qkv_weight || !b.qkv_bias || !b.attn_out_weight || !b.attn_out_bias || !b.ln_1_weight || !b.ln_1_bias ||
+            !b.inter_weight || !b.inter_bias || !b.out_weight || !b.out_bias || !b.ln_2_weight || !b.ln_2_bias)
+            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
+        if (!aligned16(b.qkv_weight) || !aligned16(b.attn_out_weight) || !aligned16(b.inter_weight) || !aligned16(b.out_weight))
+            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
+    }
+    return LAFF_OK;
 }
 // laff_clip_pack_weight (padded = false, ldp = cols) and laff_clip_pack_weight_padded
 int clip_pack(const char* fn, laff_ctx* ctx, const float* W, int rows, int cols, int transpose, bool padded, int ldp, int precision,
@@ -608,7 +653,7 @@ int laff_clip_workspace_bytes(int R, int N, int width, int precision, size_t* ou
     int fp16 = 0;
     if (int rc = clip_precision(fn, precision, &fp16)) return rc;
     if (int rc = clip_check_width(fn, width)) return rc;
-    *out = clip_ws(R, width, fp16).total;
+    *out = clip_ws(R, width, fp16 ? 2 : 4, 4 * (size_t)width).total;
     return LAFF_OK;
 }
 
@@ -626,23 +671,18 @@ int laff_clip_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     if (m->layers < 1) return fail(LAFF_E_UNSUPPORTED, "%s: layers=%d: at least one block", fn, m->layers);
     if (m->embed_dim < 1 || m->vocab_size < 1) return fail(LAFF_E_SHAPE, "%s: embed_dim=%d vocab_size=%d", fn, m->embed_dim, m->vocab_size);
     if (N < 0 || R < N) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d", fn, N, R);
+    if (int rc = check_token_rows(fn, R, 1)) return rc;
     if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
     if (!ids || !row_off || !row_off_host || !out || !workspace || !m->token_embedding || !m->positional_embedding || !m->blocks ||
         !m->ln_final_weight || !m->ln_final_bias || !m->text_projection)
         return fail(LAFF_E_ARG, "%s: null argument", fn);
     if (int rc = clip_check_blocks(fn, m->blocks, m->layers)) return rc;
-    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
-    for (int i = 0; i < N; ++i) {
-        const int L = row_off_host[i + 1] - row_off_host[i];
-        if (L < 1 || L > m->context_length)
-            return fail(LAFF_E_ARG, "%s: row_off: caption %d has %d rows (1 .. context_length=%d)", fn, i, L, m->context_length);
-    }
-    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (int rc = check_offsets(fn, "row_off", "caption", "NR", row_off_host, N, R, 1, m->context_length, "context_length")) return rc;
     if (ldo < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldo=%d < embed_dim=%d", fn, ldo, m->embed_dim);
-    const ClipWs ws = clip_ws(R, m->width, fp16);
-    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
-    if (!aligned16(workspace) || !aligned16(m->text_projection))
-        return fail(LAFF_E_ALIGN, "%s: workspace / packed text_projection must be 16-byte aligned", fn);
+    const ClipWs ws = clip_ws(R, m->width, fp16 ? 2 : 4, 4 * (size_t)m->width);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, ws.total, aligned16(m->text_projection),
+                                 "workspace / packed text_projection"))
+        return rc;
     CHECK_CTX(ctx);
     DeviceGuard g(ctx->device);
     char* w = (char*)workspace;
@@ -676,11 +716,11 @@ struct VitWs : ClipWs {
 VitWs vit_ws(int F, int width, int res, int patch, int fp16) {
     const size_t sz = fp16 ? 2 : 4, w = (size_t)width, g = (size_t)(res / patch), np = (size_t)F * g * g;
     VitWs s;
-    static_cast<ClipWs&>(s) = clip_ws((size_t)F * (g * g + 1), width, fp16);
-    s.patch_out = clip_round(np * (size_t)vit_kpad(patch, fp16) * sz);
-    s.q_cls = std::max(s.total, s.big + s.patch_out + clip_round(np * w * 4));
-    s.a_cls = s.q_cls + clip_round((size_t)F * w * 4);
-    s.total = s.a_cls + clip_round((size_t)F * w * sz);
+    static_cast<ClipWs&>(s) = clip_ws((size_t)F * (g * g + 1), width, sz, 4 * w);
+    s.patch_out = round256(np * (size_t)vit_kpad(patch, fp16) * sz);
+    s.q_cls = std::max(s.total, s.big + s.patch_out + round256(np * w * 4));
+    s.a_cls = s.q_cls + round256((size_t)F * w * 4);
+    s.total = s.a_cls + round256((size_t)F * w * sz);
     return s;
 }
 }  // namespace
@@ -722,8 +762,7 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
     if (m->embed_dim < 1) return fail(LAFF_E_SHAPE, "%s: embed_dim=%d", fn, m->embed_dim);
     if (F < 0 || V < 0 || V > F) return fail(LAFF_E_SHAPE, "%s: bad shape F=%d V=%d", fn, F, V);
     const long L = (long)(m->input_resolution / m->patch_size) * (m->input_resolution / m->patch_size) + 1;
-    if ((long)F * L > (1L << 22))               /* the GEMMs' grid.y = rows / 128 stays well inside its limit */
-        return fail(LAFF_E_SHAPE, "%s: F=%d frames of %ld tokens: more than 4,194,304 token rows in one call", fn, F, L);
+    if (int rc = check_token_rows(fn, F, L)) return rc;
     if (F == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
     if (!pixels || !out_frames || !workspace || (V > 0 && (!frame_off || !frame_off_host || !out_mean)) || !m->conv1_weight ||
         !m->class_embedding || !m->positional_embedding || !m->ln_pre_weight || !m->ln_pre_bias || !m->blocks || !m->ln_post_weight ||
@@ -731,18 +770,14 @@ int laff_clip_image_encode(laff_ctx* ctx, const float* pixels, int F, const int*
         return fail(LAFF_E_ARG, "%s: null argument", fn);
     if (int rc = clip_check_blocks(fn, m->blocks, m->layers)) return rc;
     if (V > 0) {
-        if (frame_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: frame_off[0]=%d != 0", fn, frame_off_host[0]);
-        for (int v = 0; v < V; ++v)
-            if (frame_off_host[v + 1] - frame_off_host[v] < 1)
-                return fail(LAFF_E_ARG, "%s: frame_off: video %d has %d frames (at least 1)", fn, v, frame_off_host[v + 1] - frame_off_host[v]);
-        if (frame_off_host[V] != F) return fail(LAFF_E_ARG, "%s: frame_off[V]=%d != F=%d", fn, frame_off_host[V], F);
+        if (int rc = check_offsets(fn, "frame_off", "video", "VF", frame_off_host, V, F, 1, INT_MAX, nullptr)) return rc;
         if (ldm < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldm=%d < embed_dim=%d", fn, ldm, m->embed_dim);
     }
     if (ldo < m->embed_dim) return fail(LAFF_E_SHAPE, "%s: ldo=%d < embed_dim=%d", fn, ldo, m->embed_dim);
     const VitWs ws = vit_ws(F, m->width, m->input_resolution, m->patch_size, fp16);
-    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
-    if (!aligned16(workspace) || !aligned16(m->proj) || !aligned16(m->conv1_weight))
-        return fail(LAFF_E_ALIGN, "%s: workspace / packed conv1 / packed proj must be 16-byte aligned", fn);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, ws.total, aligned16(m->proj) && aligned16(m->conv1_weight),
+                                 "workspace / packed conv1 / packed proj"))
+        return rc;
     CHECK_CTX(ctx);
     DeviceGuard g(ctx->device);
     char* w = (char*)workspace;
@@ -849,19 +884,17 @@ int bert_check_dims(const char* fn, int width, int intermediate) {
         return fail(LAFF_E_UNSUPPORTED, "%s: intermediate=%d: the GEMM takes a positive multiple of 64", fn, intermediate);
     return LAFF_OK;
 }
-struct BertWs {
-    size_t x, a, big, xc, qc, ac, total;
+struct BertWs : ClipWs {
+    size_t xc, qc, ac;
 };
 BertWs bert_ws(size_t R, size_t N, int width, int intermediate, int fp16) {
     const size_t sz = fp16 ? 2 : 4, w = (size_t)width;
     BertWs s;
-    s.x = 0;
-    s.a = clip_round(R * w * 4);
-    s.big = s.a + clip_round(R * w * sz);
-    s.xc = s.big + clip_round(R * std::max(3 * w * 4, (size_t)intermediate * sz));
-    s.qc = s.xc + clip_round(N * w * 4);
-    s.ac = s.qc + clip_round(N * w * 4);
-    s.total = s.ac + clip_round(N * w * sz);
+    static_cast<ClipWs&>(s) = clip_ws(R, width, sz, (size_t)intermediate);
+    s.xc = s.total;
+    s.qc = s.xc + round256(N * w * 4);
+    s.ac = s.qc + round256(N * w * 4);
+    s.total = s.ac + round256(N * w * sz);
     return s;
 }
 }  // namespace
@@ -893,32 +926,18 @@ int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
     if (!(m->layer_norm_eps >= 0.0f) || m->layer_norm_eps > 1.0f)
         return fail(LAFF_E_ARG, "%s: layer_norm_eps=%g: expected a value in [0, 1]", fn, (double)m->layer_norm_eps);
     if (N < 0 || R < N) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d", fn, N, R);
-    if (R > (1 << 22))                          /* the GEMMs' grid.y = rows / 128 stays well inside its limit */
-        return fail(LAFF_E_SHAPE, "%s: R=%d: more than 4,194,304 token rows in one call", fn, R);
+    if (int rc = check_token_rows(fn, R, 1)) return rc;
     if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
     if (!ids || !row_off || !row_off_host || !out || !workspace || !m->word_embeddings || !m->position_embeddings ||
         !m->token_type_embedding || !m->emb_ln_weight || !m->emb_ln_bias || !m->blocks || !m->pooler_weight || !m->pooler_bias)
         return fail(LAFF_E_ARG, "%s: null argument", fn);
-    for (int l = 0; l < m->layers; ++l) {
-        const laff_bert_block& b = m->blocks[l];
-        if (!b.qkv_weight || !b.qkv_bias || !b.attn_out_weight || !b.attn_out_bias || !b.ln_1_weight || !b.ln_1_bias ||
-            !b.inter_weight || !b.inter_bias || !b.out_weight || !b.out_bias || !b.ln_2_weight || !b.ln_2_bias)
-            return fail(LAFF_E_ARG, "%s: null pointer in block %d", fn, l);
-        if (!aligned16(b.qkv_weight) || !aligned16(b.attn_out_weight) || !aligned16(b.inter_weight) || !aligned16(b.out_weight))
-            return fail(LAFF_E_ALIGN, "%s: packed weights of block %d must be 16-byte aligned", fn, l);
-    }
-    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
-    for (int i = 0; i < N; ++i) {
-        const int L = row_off_host[i + 1] - row_off_host[i];
-        if (L < 1 || L > m->max_position)
-            return fail(LAFF_E_ARG, "%s: row_off: caption %d has %d rows (1 .. max_position=%d)", fn, i, L, m->max_position);
-    }
-    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (int rc = bert_check_blocks(fn, m->blocks, m->layers)) return rc;
+    if (int rc = check_offsets(fn, "row_off", "caption", "NR", row_off_host, N, R, 1, m->max_position, "max_position")) return rc;
     if (ldo < m->width) return fail(LAFF_E_SHAPE, "%s: ldo=%d < width=%d", fn, ldo, m->width);
     const BertWs ws = bert_ws(R, N, m->width, m->intermediate, fp16);
-    if (workspace_bytes < ws.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, ws.total);
-    if (!aligned16(workspace) || !aligned16(m->pooler_weight))
-        return fail(LAFF_E_ALIGN, "%s: workspace / packed pooler weight must be 16-byte aligned", fn);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, ws.total, aligned16(m->pooler_weight),
+                                 "workspace / packed pooler weight"))
+        return rc;
     CHECK_CTX(ctx);
     DeviceGuard g(ctx->device);
     char* w = (char*)workspace;
@@ -930,8 +949,8 @@ int laff_bert_encode(laff_ctx* ctx, const int* ids, const int* row_off, const in
 
 namespace {
 // the NetVLAD encoder's workspace: soft assignments [R, K] fp32 | 1 / max(|x|, eps) [R] fp32, each region on 256 bytes
-size_t netvlad_rnorm_offset(int R, int K) { return ((size_t)R * K * sizeof(float) + 255) / 256 * 256; }
-size_t netvlad_ws_bytes(int R, int K) { return netvlad_rnorm_offset(R, K) + ((size_t)R * sizeof(float) + 255) / 256 * 256; }
+size_t netvlad_rnorm_offset(int R, int K) { return round256((size_t)R * K * sizeof(float)); }
+size_t netvlad_ws_bytes(int R, int K) { return netvlad_rnorm_offset(R, K) + round256((size_t)R * sizeof(float)); }
 int netvlad_check_k(const char* fn, int K) {
     if (K < 1 || K > laff::NETVLAD_MAX_K)
         return fail(LAFF_E_UNSUPPORTED, "%s: K=%d: the number of clusters must be in [1, %d]", fn, K, laff::NETVLAD_MAX_K);
@@ -958,16 +977,12 @@ int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const i
     if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
     if (!table || (R && !ids) || !row_off || !row_off_host || !zero_rows || !fc1_weight || !centroids || !out || (R && !workspace))
         return fail(LAFF_E_ARG, "%s: null argument", fn);
-    if (row_off_host[0] != 0) return fail(LAFF_E_ARG, "%s: row_off[0]=%d != 0", fn, row_off_host[0]);
-    for (int i = 0; i < N; ++i)
-        if (row_off_host[i + 1] < row_off_host[i])
-            return fail(LAFF_E_ARG, "%s: row_off decreases at caption %d (%d -> %d)", fn, i, row_off_host[i], row_off_host[i + 1]);
-    if (row_off_host[N] != R) return fail(LAFF_E_ARG, "%s: row_off[N]=%d != R=%d", fn, row_off_host[N], R);
+    if (int rc = check_offsets(fn, "row_off", "caption", "NR", row_off_host, N, R, 0, INT_MAX, nullptr)) return rc;
     if (ldo < K * D || ldo % 4) return fail(LAFF_E_SHAPE, "%s: ldo=%d: at least K*D=%d and a multiple of 4", fn, ldo, K * D);
-    const size_t need = netvlad_ws_bytes(R, K);
-    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
-    if (!aligned16(table) || !aligned16(centroids) || !aligned16(fc1_weight) || !aligned16(out) || !aligned16(workspace))
-        return fail(LAFF_E_ALIGN, "%s: table / fc1_weight / centroids / out / workspace must be 16-byte aligned", fn);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, netvlad_ws_bytes(R, K),
+                                 aligned16(table) && aligned16(centroids) && aligned16(fc1_weight) && aligned16(out),
+                                 "table / fc1_weight / centroids / out / workspace"))
+        return rc;
     CHECK_CTX(ctx);
     DeviceGuard g(ctx->device);
     float* ws = (float*)workspace;
@@ -978,7 +993,6 @@ int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const i
 }
 
 namespace {
-size_t rr_pad(size_t b) { return (b + 255) / 256 * 256; }
 int rr_round_half_even(int k1) { return (k1 & 1) ? ((k1 / 2) & 1 ? k1 / 2 + 1 : k1 / 2) : k1 / 2; }
 // checks k1 / k2 and one problem's sizes; lays the problem's workspace out from `base` (may be null: sizes only); returns the bytes
 int rerank_layout(const char* fn, int i, int Q, int G, int k1, int k2, char* base, laff::RerankProblem* d, size_t* bytes) {
@@ -992,7 +1006,7 @@ int rerank_layout(const char* fn, int i, int Q, int G, int k1, int k2, char* bas
     const int cap = (k1 + 1) * (rr_round_half_even(k1) + 2);
     const int L1 = (int)std::min<long>(cap, N), L2 = k2 == 1 ? L1 : (int)std::min<long>((long)k2 * cap, N);
     size_t o = 0;
-    auto take = [&](size_t b) { char* r = base ? base + o : nullptr; o += rr_pad(b); return r; };
+    auto take = [&](size_t b) { char* r = base ? base + o : nullptr; o += round256(b); return r; };
     char* rank = take((size_t)N * (k1 + 1) * 4);
     char* colmax = take((size_t)N * 4);
     char* cnt1 = take((size_t)N * 4);

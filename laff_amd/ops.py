@@ -92,6 +92,44 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _size_query(symbol_name, *ints):
+    """A laff_*_workspace_bytes style query: symbol(ints..., size_t* out) -> out."""
+    n = C.c_size_t()
+    check(getattr(_lib.load(), symbol_name)(*[int(i) for i in ints], C.byref(n)))
+    return n.value
+
+
+def _offsets(off, off_host, name):
+    """The offsets of a ragged batch (laff_amd/ragged.py): off [N+1] int32 on the device and off_host, the same on the host.
+    Returns (off, off_host as a contiguous int32 array, N)."""
+    off = _dev(off, name, torch.int32)
+    if off.dim() != 1 or not off.is_contiguous():
+        raise ValueError('%s must be a contiguous vector' % name)
+    N = off.numel() - 1
+    host = np.ascontiguousarray(off_host, dtype=np.int32)
+    if host.shape != (N + 1,):
+        raise ValueError('%s_host has %d entries, %s %d' % (name, host.size, name, N + 1))
+    return off, host, N
+
+
+def _out_rows(out, shape, device, name='out'):
+    """An fp32 output of `shape` with a row pitch, allocated here when None: (out, its pointer, its pitch)."""
+    if out is None:
+        out = torch.empty(shape, device=device, dtype=torch.float32)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError('%s must be (%d, %d), got %s' % (name, shape[0], shape[1], tuple(out.shape)))
+    o, ld = _rows(out, name)
+    return out, _ptr(o), ld
+
+
+def _ws_out(workspace, nbytes, out, shape, device):
+    """A ragged entry point's workspace (allocated here from nbytes(), 16 bytes at least, when None) and its out through _out_rows:
+    (workspace, out, out's pointer, out's pitch).  Allocates nothing when both are given."""
+    if workspace is None:
+        workspace = torch.empty(max(nbytes(), 16), dtype=torch.uint8, device=device)
+    return (workspace,) + _out_rows(out, shape, device)
+
+
 def alloc_scores(Nt, Nv, device):
     """(Nt, Nv) fp32 score matrix whose rows start on 128-byte lines (row pitch = Nv rounded up to 32 floats; a view when Nv is not
     a multiple of 32): the GEMM stores whole lines, which the memory system takes ~25 % faster than rows that straddle them
@@ -289,10 +327,7 @@ def gru_pack_whh(w_hh):
 
 
 def gru_workspace_bytes(N, H, num_layers=1, bidirectional=False, pooling='mean'):
-    lib = _lib.load()
-    n = C.c_size_t()
-    check(lib.laff_gru_workspace_bytes(int(N), int(H), int(num_layers), int(bool(bidirectional)), GRU_POOLING[pooling], C.byref(n)))
-    return n.value
+    return _size_query('laff_gru_workspace_bytes', N, H, num_layers, bool(bidirectional), GRU_POOLING[pooling])
 
 
 def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean', num_layers=1, out=None, workspace=None):
@@ -361,11 +396,22 @@ def clip_pack_weight(w, precision='fp16', transpose=False, padded_cols=None):
     return out
 
 
+def _text_encode(name, ids, row_off, row_off_host, model, precision, out, workspace, nbytes, width):
+    """clip_encode / bert_encode (laff_<name>): nbytes(R, N) is the workspace query, width the columns of out."""
+    ids = _dev(ids, 'ids', torch.int32)
+    if ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError('ids and row_off must be contiguous vectors')
+    row_off, roh, N = _offsets(row_off, row_off_host, 'row_off')
+    R = ids.numel()
+    workspace, out, o, ldo = _ws_out(workspace, lambda: nbytes(R, N), out, (N, width), ids.device)
+    lib, h = _context(ids.device)
+    _call(name, getattr(lib, 'laff_' + name), h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R, C.byref(model),
+          PREC[precision], o, ldo, _ptr(workspace), workspace.numel())
+    return out
+
+
 def clip_workspace_bytes(R, N, width, precision='fp16'):
-    lib = _lib.load()
-    n = C.c_size_t()
-    check(lib.laff_clip_workspace_bytes(int(R), int(N), int(width), PREC[precision], C.byref(n)))
-    return n.value
+    return _size_query('laff_clip_workspace_bytes', R, N, width, PREC[precision])
 
 
 def clip_encode(ids, row_off, row_off_host, model, precision='fp16', out=None, workspace=None):
@@ -373,32 +419,12 @@ def clip_encode(ids, row_off, row_off_host, model, precision='fp16', out=None, w
     same offsets as a host int32 array; model: a laff_amd._lib.ClipText of device pointers (ClipTxtEncoder builds it).  Returns out
     [N, embed_dim] fp32.  workspace: a uint8 device tensor of clip_workspace_bytes(R, N, width, precision) bytes, or None to
     allocate one here (pass one for HIP-graph capture)."""
-    ids = _dev(ids, 'ids', torch.int32)
-    row_off = _dev(row_off, 'row_off', torch.int32)
-    if not ids.is_contiguous() or not row_off.is_contiguous() or ids.dim() != 1 or row_off.dim() != 1:
-        raise ValueError('ids and row_off must be contiguous vectors')
-    R, N = ids.numel(), row_off.numel() - 1
-    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
-    if roh.shape != (N + 1,):
-        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
-    if workspace is None:
-        workspace = torch.empty(max(clip_workspace_bytes(R, N, model.width, precision), 16), dtype=torch.uint8, device=ids.device)
-    if out is None:
-        out = torch.empty((N, model.embed_dim), device=ids.device, dtype=torch.float32)
-    if tuple(out.shape) != (N, model.embed_dim):
-        raise ValueError('out must be (%d, %d), got %s' % (N, model.embed_dim, tuple(out.shape)))
-    o, ldo = _rows(out, 'out')
-    lib, h = _context(ids.device)
-    _call('clip_encode', lib.laff_clip_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
-          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
-    return out
+    return _text_encode('clip_encode', ids, row_off, row_off_host, model, precision, out, workspace,
+                        lambda R, N: clip_workspace_bytes(R, N, model.width, precision), model.embed_dim)
 
 
 def bert_workspace_bytes(R, N, width, intermediate, precision='fp32'):
-    lib = _lib.load()
-    n = C.c_size_t()
-    check(lib.laff_bert_workspace_bytes(int(R), int(N), int(width), int(intermediate), PREC[precision], C.byref(n)))
-    return n.value
+    return _size_query('laff_bert_workspace_bytes', R, N, width, intermediate, PREC[precision])
 
 
 def bert_encode(ids, row_off, row_off_host, model, precision='fp32', out=None, workspace=None):
@@ -406,33 +432,12 @@ def bert_encode(ids, row_off, row_off_host, model, precision='fp32', out=None, w
     row_off_host: the same offsets as a host int32 array; model: a laff_amd._lib.BertText of device pointers (BertTxtEncoder builds
     it).  Returns out [N, width] fp32 (pooler_output).  workspace: a uint8 device tensor of bert_workspace_bytes(R, N, ...) bytes, or
     None to allocate one here (pass one for HIP-graph capture)."""
-    ids = _dev(ids, 'ids', torch.int32)
-    row_off = _dev(row_off, 'row_off', torch.int32)
-    if not ids.is_contiguous() or not row_off.is_contiguous() or ids.dim() != 1 or row_off.dim() != 1:
-        raise ValueError('ids and row_off must be contiguous vectors')
-    R, N = ids.numel(), row_off.numel() - 1
-    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
-    if roh.shape != (N + 1,):
-        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
-    if workspace is None:
-        workspace = torch.empty(max(bert_workspace_bytes(R, N, model.width, model.intermediate, precision), 16), dtype=torch.uint8,
-                                device=ids.device)
-    if out is None:
-        out = torch.empty((N, model.width), device=ids.device, dtype=torch.float32)
-    if tuple(out.shape) != (N, model.width):
-        raise ValueError('out must be (%d, %d), got %s' % (N, model.width, tuple(out.shape)))
-    o, ldo = _rows(out, 'out')
-    lib, h = _context(ids.device)
-    _call('bert_encode', lib.laff_bert_encode, h, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), N, R,
-          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(workspace), workspace.numel())
-    return out
+    return _text_encode('bert_encode', ids, row_off, row_off_host, model, precision, out, workspace,
+                        lambda R, N: bert_workspace_bytes(R, N, model.width, model.intermediate, precision), model.width)
 
 
 def netvlad_workspace_bytes(R, K):
-    lib = _lib.load()
-    n = C.c_size_t()
-    check(lib.laff_netvlad_workspace_bytes(int(R), int(K), C.byref(n)))
-    return n.value
+    return _size_query('laff_netvlad_workspace_bytes', R, K)
 
 
 def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, out=None, workspace=None):
@@ -457,19 +462,11 @@ def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, cen
     R, N = ids.numel(), row_off.numel() - 1
     if zero_rows.numel() != N:
         raise ValueError('zero_rows has %d entries for %d captions' % (zero_rows.numel(), N))
-    roh = np.ascontiguousarray(row_off_host, dtype=np.int32)
-    if roh.shape != (N + 1,):
-        raise ValueError('row_off_host has %d entries, row_off %d' % (roh.size, N + 1))
-    if workspace is None:
-        workspace = torch.empty(max(netvlad_workspace_bytes(R, K), 16), dtype=torch.uint8, device=table.device)
-    if out is None:
-        out = torch.empty((N, K * D), device=table.device, dtype=torch.float32)
-    if tuple(out.shape) != (N, K * D):
-        raise ValueError('out must be (%d, %d), got %s' % (N, K * D, tuple(out.shape)))
-    o, ldo = _rows(out, 'out')
+    row_off, roh, N = _offsets(row_off, row_off_host, 'row_off')
+    workspace, out, o, ldo = _ws_out(workspace, lambda: netvlad_workspace_bytes(R, K), out, (N, K * D), table.device)
     lib, h = _context(table.device)
     _call('netvlad_encode', lib.laff_netvlad_encode, h, _ptr(table), V, D, _ptr(ids), _ptr(row_off),
-          roh.ctypes.data_as(C.POINTER(C.c_int)), _ptr(zero_rows), N, R, _ptr(fc1_weight), _ptr(centroids), K, _ptr(o), ldo,
+          roh.ctypes.data_as(C.POINTER(C.c_int)), _ptr(zero_rows), N, R, _ptr(fc1_weight), _ptr(centroids), K, o, ldo,
           _ptr(workspace), workspace.numel())
     return out
 
@@ -482,10 +479,7 @@ def clip_image_kpad(patch_size, precision='fp16'):
 
 
 def clip_image_workspace_bytes(F, width, input_resolution, patch_size, precision='fp16'):
-    lib = _lib.load()
-    n = C.c_size_t()
-    check(lib.laff_clip_image_workspace_bytes(int(F), int(width), int(input_resolution), int(patch_size), PREC[precision], C.byref(n)))
-    return n.value
+    return _size_query('laff_clip_image_workspace_bytes', F, width, input_resolution, patch_size, PREC[precision])
 
 
 def clip_image_encode(pixels, frame_off, frame_off_host, model, precision='fp16', out=None, out_mean=None, workspace=None):
@@ -501,32 +495,16 @@ def clip_image_encode(pixels, frame_off, frame_off_host, model, precision='fp16'
     if frame_off is None:
         V, fo, roh = 0, None, np.zeros(1, np.int32)
     else:
-        fo = _dev(frame_off, 'frame_off', torch.int32)
-        if fo.dim() != 1 or not fo.is_contiguous():
-            raise ValueError('frame_off must be a contiguous vector')
-        V = fo.numel() - 1
-        roh = np.ascontiguousarray(frame_off_host, dtype=np.int32)
-        if roh.shape != (V + 1,):
-            raise ValueError('frame_off_host has %d entries, frame_off %d' % (roh.size, V + 1))
+        fo, roh, V = _offsets(frame_off, frame_off_host, 'frame_off')
     E = model.embed_dim
-    if workspace is None:
-        workspace = torch.empty(max(clip_image_workspace_bytes(F, model.width, R, model.patch_size, precision), 16), dtype=torch.uint8,
-                                device=pixels.device)
-    if out is None:
-        out = torch.empty((F, E), device=pixels.device, dtype=torch.float32)
-    if tuple(out.shape) != (F, E):
-        raise ValueError('out must be (%d, %d), got %s' % (F, E, tuple(out.shape)))
-    o, ldo = _rows(out, 'out')
+    workspace, out, o, ldo = _ws_out(workspace, lambda: clip_image_workspace_bytes(F, model.width, R, model.patch_size, precision), out,
+                                     (F, E), pixels.device)
     mo, ldm = None, E
     if V > 0:
-        if out_mean is None:
-            out_mean = torch.empty((V, E), device=pixels.device, dtype=torch.float32)
-        if tuple(out_mean.shape) != (V, E):
-            raise ValueError('out_mean must be (%d, %d), got %s' % (V, E, tuple(out_mean.shape)))
-        mo, ldm = _rows(out_mean, 'out_mean')
+        out_mean, mo, ldm = _out_rows(out_mean, (V, E), pixels.device, 'out_mean')
     lib, h = _context(pixels.device)
     _call('clip_image_encode', lib.laff_clip_image_encode, h, _ptr(pixels), F, _ptr(fo), roh.ctypes.data_as(C.POINTER(C.c_int)), V,
-          C.byref(model), PREC[precision], _ptr(o), ldo, _ptr(mo), ldm, _ptr(workspace), workspace.numel())
+          C.byref(model), PREC[precision], o, ldo, mo, ldm, _ptr(workspace), workspace.numel())
     return out, (out_mean if V > 0 else None)
 
 

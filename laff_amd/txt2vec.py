@@ -24,6 +24,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .ragged import _Weights, ragged_batch
+
 _NON_ALNUM = re.compile(r"[^A-Za-z0-9]")
 
 
@@ -169,11 +171,8 @@ class W2Vec(object):
         """The captions as laff_netvlad_encode takes them: ids [R] int32 (raw_ids concatenated), row_off [N+1] int32 and zero_rows
         [N] int32 (the token count of a caption without known words, else 0)."""
         rows = [self.raw_ids(c) for c in captions]
-        row_off = np.zeros(len(rows) + 1, np.int32)
-        row_off[1:] = np.cumsum([len(ids) for ids, _ in rows])
-        ids = np.fromiter((i for r, _ in rows for i in r), np.int32, int(row_off[-1]))
-        zero_rows = np.array([0 if r else n for r, n in rows], np.int32)
-        return ids, row_off, zero_rows
+        b = ragged_batch([r for r, _ in rows])
+        return b.ids, b.row_off, np.array([0 if r else n for r, n in rows], np.int32)
 
     def encoding(self, caption):
         ids, _ = self._ids(caption)
@@ -337,22 +336,20 @@ class GruTxtEncoder(nn.Module):
         self.we = nn.Embedding(len(t2v_idx.vocab), int(we_dim))
         self.rnn = _GruWeights(int(we_dim), H, self.bigru)
         self.to(device)
-        self._cache_key, self._cache = None, None
+        self._weights = _Weights(self, None)
 
     def _tables(self):
         """(P, packed W_hh, b_hh) per direction, rebuilt when any parameter has changed since the last build."""
         from . import ops
-        params = [self.we.weight] + list(self.rnn.parameters())
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if key != self._cache_key:
-            with torch.no_grad():
-                r, sets = self.rnn, []
-                for sfx in ('_l0', '_l0_reverse') if self.bigru else ('_l0',):
-                    w_ih, w_hh = getattr(r, 'weight_ih' + sfx), getattr(r, 'weight_hh' + sfx)
-                    P = ops.fc_act_bn(self.we.weight.detach(), w_ih.detach(), getattr(r, 'bias_ih' + sfx).detach())
-                    sets.append((P, ops.gru_pack_whh(w_hh.detach()), getattr(r, 'bias_hh' + sfx).detach().contiguous()))
-            self._cache, self._cache_key = sets, key
-        return self._cache
+
+        def build(_):
+            r, sets = self.rnn, []
+            for sfx in ('_l0', '_l0_reverse') if self.bigru else ('_l0',):
+                w_ih, w_hh = getattr(r, 'weight_ih' + sfx), getattr(r, 'weight_hh' + sfx)
+                P = ops.fc_act_bn(self.we.weight.detach(), w_ih.detach(), getattr(r, 'bias_ih' + sfx).detach())
+                sets.append((P, ops.gru_pack_whh(w_hh.detach()), getattr(r, 'bias_hh' + sfx).detach().contiguous()))
+            return sets
+        return self._weights.get(build)
 
     def encode_batch(self, b, out=None, workspace=None):
         """The device half of forward(): a GruBatch (IdxVec.batch) whose arrays are already device tensors."""
