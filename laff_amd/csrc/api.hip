@@ -62,6 +62,27 @@ int metrics_buffers(laff_ctx* ctx) {
     return LAFF_OK;
 }
 
+// slot 0 serves the synchronous calls; every asynchronous one takes the next of the others
+size_t next_metrics_slot(laff_ctx* ctx) { return 1 + ctx->metrics_slot++ % (METRIC_SLOTS - 1); }
+
+// A pinned (hipHostMalloc'ed / registered) result buffer is addressable from the device: the finishing workgroup stores the 64 bytes
+// there itself and no copy node follows the launch.  Returns that alias, or null (anything else gets the copy).
+double* pinned_alias(double* host8) {
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, host8, 0) == hipSuccess && dp) return (double*)dp;
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// the synchronous result: slot 0 back to the host, refused with `flagged` when the kernel saw a rank < 1
+int metrics_read_back(laff_ctx* ctx, double out7[7], const char* flagged) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_metrics, ctx->d_metrics, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->h_metrics[7] != 0.0) return fail(LAFF_E_ARG, "%s", flagged);
+    for (int i = 0; i < 7; ++i) out7[i] = ctx->h_metrics[i];
+    return LAFF_OK;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct DeviceGuard {
@@ -79,6 +100,9 @@ struct DeviceGuard {
 
 bool is_x3(int p) { return p == LAFF_PREC_FP16X3 || p == LAFF_PREC_BF16X3; }
 int elem_size(int p) { return p == LAFF_PREC_FP32 ? 4 : 2; }
+int bad_precision(const char* who, int p) {
+    return p < LAFF_PREC_FP32 || p > LAFF_PREC_BF16X3 ? fail(LAFF_E_ARG, "%s: bad precision %d", who, p) : LAFF_OK;
+}
 
 // the FC epilogue of `who` (problem i, or the only one when i < 0): the activation code, bn_scale / bn_shift given together and, with
 // `align`, bias / bn_scale / bn_shift 16-byte aligned -- in that order
@@ -1466,9 +1490,7 @@ int laff_fuse_packed_rank(laff_ctx* ctx, const laff_plane* planes, int L, int N,
         a.rp_side = rs->side; a.rp_gt = rs->gt_col; a.rp_col0 = rs->col0; a.rp_Nv = rs->Nv; a.rp_Ev = rs->Ev; a.rp_sgt = rs->s_gt64;
         a.rp_band = rs->band; a.rp_band_v = rs->band_v; a.rp_count = rs->count; a.rp_pairs = rs->pairs;
         a.rp_part = rs->partials; a.rp_ticket = rs->tickets;
-        // the same constants as laff_rank_prepare (rank.hip: launch_rank_prepare) for a single-plane operand
-        a.rp_unit = precision == LAFF_PREC_BF16 ? 3.90625e-3f : 4.8828125e-4f;
-        a.rp_cacc = (float)((double)H * d * 1.1920929e-7 + 9.5367432e-7);
+        laff::rank_band_constants(precision, H, d, &a.rp_unit, &a.rp_cacc);
     }
     DeviceGuard g(ctx->device);
     if (rs && H > 1) HIP_TRY(hipMemsetAsync(rs->tickets, 0, (size_t)N * sizeof(unsigned), ctx->stream));
@@ -1534,7 +1556,7 @@ int laff_frame_fuse(laff_ctx* ctx, const float* frames, const int* lens, int B, 
 
 int laff_packed_bytes(int N, int K, int precision, size_t* out) {
     if (!out || N < 0 || K < 0) return fail(LAFF_E_ARG, "laff_packed_bytes: bad args");
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_packed_bytes: bad precision %d", precision);
+    if (int rc = bad_precision("laff_packed_bytes", precision)) return rc;
     *out = (size_t)N * K * elem_size(precision) * (is_x3(precision) ? 2 : 1);
     return LAFF_OK;
 }
@@ -1546,11 +1568,10 @@ int laff_pack_rows(laff_ctx* ctx, const float* E, int N, int H, int d, int lde, 
     if (!E || !out) return fail(LAFF_E_ARG, "laff_pack_rows: null E/out");
     if (N < 0 || H < 1 || d < 1 || lde < H * d)
         return fail(LAFF_E_SHAPE, "laff_pack_rows: bad shape N=%d H=%d d=%d lde=%d", N, H, d, lde);
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_pack_rows: bad precision %d", precision);
+    if (int rc = bad_precision("laff_pack_rows", precision)) return rc;
     const bool vec = !(d & 3) && !(lde & 3) && aligned16(E) && aligned16(out);
     if (!vec && precision != LAFF_PREC_FP32)
         return fail(LAFF_E_ALIGN, "laff_pack_rows: 16-bit output needs d%%4==0, lde%%4==0 and 16-byte aligned buffers (d=%d lde=%d)", d, lde);
-    if (N == 0) return LAFF_OK;
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_pack_rows(E, N, H, d, lde, normalize, eps, prescale, precision, out, ctx->stream));
     return LAFF_OK;
@@ -1589,7 +1610,7 @@ static int sim_gemm_mode(int precision) {
 
 // rows of K elements: 16-byte aligned rows take the direct-to-LDS paths (K bytes a multiple of 128: the fast one),
 // anything else is staged through registers with element-wise K bounds
-static bool sim_gemm_aligned(int K, int precision) { return ((long)K * (precision == LAFF_PREC_FP32 ? 4 : 2)) % 16 == 0; }
+static bool sim_gemm_aligned(int K, int precision) { return ((long)K * elem_size(precision)) % 16 == 0; }
 
 static int sim_gemm_impl(laff_ctx* ctx, const char* who, const void* T, const void* V, int Nt, int Nv, int K, float scale,
                          int precision, float* S, int lds, const int* gt_col, int col0, const float* s_gt, int* count,
@@ -1597,9 +1618,8 @@ static int sim_gemm_impl(laff_ctx* ctx, const char* who, const void* T, const vo
     CHECK_CTX(ctx);
     if (Nt == 0 || Nv == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
     if (!T || !V) return fail(LAFF_E_ARG, "%s: null T/V", who);
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "%s: bad precision %d", who, precision);
-    const int esz = precision == LAFF_PREC_FP32 ? 4 : 2;
-    if (Nt < 0 || Nv < 0 || K < 1 || ((long)K * esz) % 4)
+    if (int rc = bad_precision(who, precision)) return rc;
+    if (Nt < 0 || Nv < 0 || K < 1 || ((long)K * elem_size(precision)) % 4)
         return fail(LAFF_E_SHAPE, "%s: K must be positive (and even for 16-bit operands) (Nt=%d Nv=%d K=%d)", who, Nt, Nv, K);
     if (!S && !gt_col) return fail(LAFF_E_ARG, "%s: nothing to produce (S and gt_col both null)", who);
     if (S && lds < Nv) return fail(LAFF_E_SHAPE, "%s: lds=%d < Nv=%d", who, lds, Nv);
@@ -1636,10 +1656,9 @@ int laff_sim_gemm_banded(laff_ctx* ctx, const void* T, const void* V, int Nt, in
 int laff_sim_gemm_route(laff_ctx* ctx, int Nt, int Nv, int K, int precision, int lds, int count_mode, unsigned pair_cap, int* route) {
     CHECK_CTX(ctx);
     if (!route) return fail(LAFF_E_ARG, "laff_sim_gemm_route: null route");
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_sim_gemm_route: bad precision %d", precision);
+    if (int rc = bad_precision("laff_sim_gemm_route", precision)) return rc;
     if (count_mode < 0 || count_mode > 2) return fail(LAFF_E_ARG, "laff_sim_gemm_route: bad count_mode %d", count_mode);
-    const int esz = precision == LAFF_PREC_FP32 ? 4 : 2;
-    if (Nt < 1 || Nv < 1 || K < 1 || ((long)K * esz) % 4 || (lds && lds < Nv) || (!lds && !count_mode))
+    if (Nt < 1 || Nv < 1 || K < 1 || ((long)K * elem_size(precision)) % 4 || (lds && lds < Nv) || (!lds && !count_mode))
         return fail(LAFF_E_SHAPE, "laff_sim_gemm_route: no launch for Nt=%d Nv=%d K=%d lds=%d count_mode=%d", Nt, Nv, K, lds, count_mode);
     pair_cap &= ~3u;
     if (count_mode == 2 && pair_cap < 4) return fail(LAFF_E_ARG, "laff_sim_gemm_route: the banded count needs a pair list of >= 4 slots");
@@ -1655,6 +1674,21 @@ int laff_sim_gemm_route(laff_ctx* ctx, int Nt, int Nv, int K, int precision, int
     return LAFF_OK;
 }
 
+// what the three laff_rank_prepare* entry points share behind their own null / empty-problem rules
+static int rank_prepare_impl(laff_ctx* ctx, const char* who, int sides, int emit, const float* Et, const float* Ev, const void* T,
+                             const void* V, int Nt, int Nv, int H, int d, int precision, float prescale, const int* gt_col, int col0,
+                             double* s_gt64, float* band_t, float* band_v, int* zero_count, unsigned* pairs) {
+    if (int rc = bad_precision(who, precision)) return rc;
+    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3)) return fail(LAFF_E_SHAPE, "%s: need H >= 1, d %% 4 == 0 (Nt=%d Nv=%d H=%d d=%d)", who, Nt, Nv, H, d);
+    if (!(prescale > 0.0f)) return fail(LAFF_E_ARG, "%s: prescale must be positive", who);
+    if ((Et && !aligned16(Et)) || (Ev && !aligned16(Ev)) || (T && !aligned16(T)) || (V && !aligned16(V)))
+        return fail(LAFF_E_ALIGN, "%s: embeddings and operands must be 16-byte aligned", who);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_rank_prepare(Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64, band_t, band_v, zero_count,
+                                      pairs, sides, ctx->stream, emit));
+    return LAFF_OK;
+}
+
 int laff_rank_prepare(laff_ctx* ctx, const float* Et, const float* Ev, const void* T, const void* V, int Nt, int Nv, int H, int d,
                       int precision, float prescale, const int* gt_col, int col0, double* s_gt64, float* band_t, float* band_v,
                       int* zero_count, unsigned* pairs) {
@@ -1662,15 +1696,8 @@ int laff_rank_prepare(laff_ctx* ctx, const float* Et, const float* Ev, const voi
     if (Nt == 0 && Nv == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
     if ((Nt > 0 && (!Et || !T || !gt_col || !s_gt64 || !band_t)) || (Nv > 0 && (!Ev || !V || !band_v)))
         return fail(LAFF_E_ARG, "laff_rank_prepare: null argument");
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_rank_prepare: bad precision %d", precision);
-    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3)) return fail(LAFF_E_SHAPE, "laff_rank_prepare: need H >= 1, d %% 4 == 0 (Nt=%d Nv=%d H=%d d=%d)", Nt, Nv, H, d);
-    if (!(prescale > 0.0f)) return fail(LAFF_E_ARG, "laff_rank_prepare: prescale must be positive");
-    if ((Et && !aligned16(Et)) || (Ev && !aligned16(Ev)) || (T && !aligned16(T)) || (V && !aligned16(V)))
-        return fail(LAFF_E_ALIGN, "laff_rank_prepare: embeddings and operands must be 16-byte aligned");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_rank_prepare(Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64, band_t, band_v, zero_count,
-                                      pairs, 3, ctx->stream));
-    return LAFF_OK;
+    return rank_prepare_impl(ctx, "laff_rank_prepare", 3, 0, Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64, band_t,
+                             band_v, zero_count, pairs);
 }
 
 int laff_rank_prepare_part(laff_ctx* ctx, int sides, const float* Et, const float* Ev, const void* T, const void* V, int Nt, int Nv, int H,
@@ -1681,15 +1708,8 @@ int laff_rank_prepare_part(laff_ctx* ctx, int sides, const float* Et, const floa
     if ((sides == 1 && Nt == 0) || (sides == 2 && Nv == 0)) return LAFF_OK;
     if (sides == 1 && (!Et || !T || !gt_col || !s_gt64 || !band_t || (Nv > 0 && !Ev))) return fail(LAFF_E_ARG, "laff_rank_prepare_part: null argument (text side)");
     if (sides == 2 && (!Ev || !V || !band_v)) return fail(LAFF_E_ARG, "laff_rank_prepare_part: null argument (video side)");
-    if (precision < LAFF_PREC_FP32 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_ARG, "laff_rank_prepare_part: bad precision %d", precision);
-    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3)) return fail(LAFF_E_SHAPE, "laff_rank_prepare_part: need H >= 1, d %% 4 == 0 (Nt=%d Nv=%d H=%d d=%d)", Nt, Nv, H, d);
-    if (!(prescale > 0.0f)) return fail(LAFF_E_ARG, "laff_rank_prepare_part: prescale must be positive");
-    if ((Et && !aligned16(Et)) || (Ev && !aligned16(Ev)) || (T && !aligned16(T)) || (V && !aligned16(V)))
-        return fail(LAFF_E_ALIGN, "laff_rank_prepare_part: embeddings and operands must be 16-byte aligned");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_rank_prepare(Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64, band_t, band_v, zero_count,
-                                      pairs, sides, ctx->stream));
-    return LAFF_OK;
+    return rank_prepare_impl(ctx, "laff_rank_prepare_part", sides, 0, Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64,
+                             band_t, band_v, zero_count, pairs);
 }
 
 int laff_rank_prepare_emit(laff_ctx* ctx, int emit, const float* Et, const float* Ev, void* T, void* V, int Nt, int Nv, int H, int d,
@@ -1701,14 +1721,8 @@ int laff_rank_prepare_emit(laff_ctx* ctx, int emit, const float* Et, const float
         return fail(LAFF_E_UNSUPPORTED, "laff_rank_prepare_emit: single-plane 16-bit operands only (precision %d): call laff_pack_rows + laff_rank_prepare", precision);
     if (Nt == 0 || Nv == 0) return LAFF_OK;
     if (!Et || !Ev || !T || !V || !gt_col || !s_gt64 || !band_t || !band_v) return fail(LAFF_E_ARG, "laff_rank_prepare_emit: null argument");
-    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3)) return fail(LAFF_E_SHAPE, "laff_rank_prepare_emit: need H >= 1, d %% 4 == 0 (Nt=%d Nv=%d H=%d d=%d)", Nt, Nv, H, d);
-    if (!(prescale > 0.0f)) return fail(LAFF_E_ARG, "laff_rank_prepare_emit: prescale must be positive");
-    if (!aligned16(Et) || !aligned16(Ev) || !aligned16(T) || !aligned16(V))
-        return fail(LAFF_E_ALIGN, "laff_rank_prepare_emit: embeddings and operands must be 16-byte aligned");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(laff::launch_rank_prepare(Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64, band_t, band_v, zero_count,
-                                      pairs, 3, ctx->stream, emit));
-    return LAFF_OK;
+    return rank_prepare_impl(ctx, "laff_rank_prepare_emit", 3, emit, Et, Ev, T, V, Nt, Nv, H, d, precision, prescale, gt_col, col0, s_gt64,
+                             band_t, band_v, zero_count, pairs);
 }
 
 int laff_rank_export_pairs(laff_ctx* ctx, const double* s_gt64, int* count, float* S, int lds, int Nv, unsigned* pairs, unsigned pair_cap,
@@ -1724,15 +1738,23 @@ int laff_rank_export_pairs(laff_ctx* ctx, const double* s_gt64, int* count, floa
     return LAFF_OK;
 }
 
+// the arguments laff_rank_resolve and laff_rank_resolve_metrics share; pair_cap comes back as whole groups of four slots (as
+// laff_sim_gemm_banded uses the list)
+static int rank_resolve_checks(const char* who, const float* Et, const float* Ev, int Nt, int Nv, int H, int d, const double* s_gt64,
+                               const int* count, const float* S, int lds, const unsigned* pairs, unsigned& pair_cap) {
+    if (!Et || !Ev || !s_gt64 || !count || !pairs) return fail(LAFF_E_ARG, "%s: null argument", who);
+    pair_cap &= ~3u;
+    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3) || pair_cap < 4) return fail(LAFF_E_SHAPE, "%s: bad shape", who);
+    if (S && lds < Nv) return fail(LAFF_E_SHAPE, "%s: lds=%d < Nv=%d", who, lds, Nv);
+    if (!aligned16(Et) || !aligned16(Ev)) return fail(LAFF_E_ALIGN, "%s: embeddings must be 16-byte aligned", who);
+    return LAFF_OK;
+}
+
 int laff_rank_resolve(laff_ctx* ctx, const float* Et, const float* Ev, int Nt, int Nv, int H, int d, const double* s_gt64,
                       int* count, float* S, int lds, unsigned* pairs, unsigned pair_cap) {
     CHECK_CTX(ctx);
     if (Nt == 0 || Nv == 0) return LAFF_OK;                 /* empty problem: nothing was listed */
-    if (!Et || !Ev || !s_gt64 || !count || !pairs) return fail(LAFF_E_ARG, "laff_rank_resolve: null argument");
-    pair_cap &= ~3u;            /* as laff_sim_gemm_banded: whole groups of four slots */
-    if (Nt < 0 || Nv < 0 || H < 1 || d < 4 || (d & 3) || pair_cap < 4) return fail(LAFF_E_SHAPE, "laff_rank_resolve: bad shape");
-    if (S && lds < Nv) return fail(LAFF_E_SHAPE, "laff_rank_resolve: lds=%d < Nv=%d", lds, Nv);
-    if (!aligned16(Et) || !aligned16(Ev)) return fail(LAFF_E_ALIGN, "laff_rank_resolve: embeddings must be 16-byte aligned");
+    if (int rc = rank_resolve_checks("laff_rank_resolve", Et, Ev, Nt, Nv, H, d, s_gt64, count, S, lds, pairs, pair_cap)) return rc;
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_rank_resolve(Et, Ev, Nt, Nv, H, d, s_gt64, count, S, lds, pairs, pair_cap, ctx->stream));
     return LAFF_OK;
@@ -1744,37 +1766,23 @@ int laff_rank_resolve_metrics(laff_ctx* ctx, const float* Et, const float* Ev, i
     CHECK_CTX(ctx);
     if (!out8) return fail(LAFF_E_ARG, "laff_rank_resolve_metrics: null out8");
     if (Nt < 1 || Nv < 1) return fail(LAFF_E_SHAPE, "laff_rank_resolve_metrics: Nt=%d Nv=%d (the metrics of an empty query set are undefined)", Nt, Nv);
-    if (!Et || !Ev || !s_gt64 || !count || !pairs) return fail(LAFF_E_ARG, "laff_rank_resolve_metrics: null argument");
-    pair_cap &= ~3u;
-    if (H < 1 || d < 4 || (d & 3) || pair_cap < 4) return fail(LAFF_E_SHAPE, "laff_rank_resolve_metrics: bad shape");
-    if (S && lds < Nv) return fail(LAFF_E_SHAPE, "laff_rank_resolve_metrics: lds=%d < Nv=%d", lds, Nv);
-    if (!aligned16(Et) || !aligned16(Ev)) return fail(LAFF_E_ALIGN, "laff_rank_resolve_metrics: embeddings must be 16-byte aligned");
+    if (int rc = rank_resolve_checks("laff_rank_resolve_metrics", Et, Ev, Nt, Nv, H, d, s_gt64, count, S, lds, pairs, pair_cap)) return rc;
     DeviceGuard g(ctx->device);
     if (int rc = metrics_buffers(ctx)) return rc;
-    const size_t si = synchronous ? 0 : 1 + ctx->metrics_slot++ % (METRIC_SLOTS - 1);
+    const size_t si = synchronous ? 0 : next_metrics_slot(ctx);
     double* slot = ctx->d_metrics + 8 * si;
     unsigned* ticket = (unsigned*)(ctx->d_mscratch + si * laff::rank_metrics_scratch_bytes() + laff::rank_resolve_ticket_offset());
-    // Pinned (hipHostMalloc'ed / registered) result buffers are addressable from the device: the finishing workgroup stores the 64 bytes
-    // there itself and no copy node follows the launch.  Anything else gets the copy.
-    double* host8 = nullptr;
-    if (!synchronous) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, out8, 0) == hipSuccess && dp) host8 = (double*)dp;
-        else (void)hipGetLastError();
-    }
+    double* host8 = synchronous ? nullptr : pinned_alias(out8);
     HIP_TRY(laff::launch_rank_resolve(Et, Ev, Nt, Nv, H, d, s_gt64, count, S, lds, pairs, pair_cap, ctx->stream, Nt, base, ranks_out, slot,
                                       host8, ticket));
     if (synchronous) {
-        HIP_TRY(hipMemcpyAsync(ctx->h_metrics, slot, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->h_metrics[7] != 0.0)
-            return fail(LAFF_E_ARG, "laff_rank_resolve_metrics: a rank < 1 was found (the pair list of laff_sim_gemm_banded overflowed, or the "
-                                    "counts are corrupt)");
-        for (int i = 0; i < 7; ++i) out8[i] = ctx->h_metrics[i];
+        if (int rc = metrics_read_back(ctx, out8, "laff_rank_resolve_metrics: a rank < 1 was found (the pair list of laff_sim_gemm_banded "
+                                                  "overflowed, or the counts are corrupt)"))
+            return rc;
         out8[7] = 0.0;
-    } else if (!host8) {
-        HIP_TRY(hipMemcpyAsync(out8, slot, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        return LAFF_OK;
     }
+    if (!host8) HIP_TRY(hipMemcpyAsync(out8, slot, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return LAFF_OK;
 }
 
@@ -1783,7 +1791,6 @@ int laff_gather_gt(laff_ctx* ctx, const float* S, int Nt, int Nv, int lds, const
     if (Nt == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
     if (!S || !gt_col || !s_gt) return fail(LAFF_E_ARG, "laff_gather_gt: null argument");
     if (Nt < 0 || Nv < 0 || lds < Nv) return fail(LAFF_E_SHAPE, "laff_gather_gt: bad shape");
-    if (Nt == 0) return LAFF_OK;
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_gather_gt(S, Nt, Nv, lds, gt_col, col0, s_gt, ctx->stream));
     return LAFF_OK;
@@ -1795,7 +1802,6 @@ int laff_rank_count(laff_ctx* ctx, const float* S, int Nt, int Nv, int lds, cons
     if (Nt == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
     if (!S || !gt_col || !s_gt || !count) return fail(LAFF_E_ARG, "laff_rank_count: null argument");
     if (Nt < 0 || Nv < 0 || lds < Nv) return fail(LAFF_E_SHAPE, "laff_rank_count: bad shape");
-    if (Nt == 0) return LAFF_OK;
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_rank_count(S, Nt, Nv, lds, gt_col, col0, s_gt, count, accumulate, ctx->stream));
     return LAFF_OK;
@@ -1812,7 +1818,6 @@ int laff_topk_rows(laff_ctx* ctx, const float* S, int Nt, int Nv, int lds, int K
             return fail(LAFF_E_UNSUPPORTED, "laff_topk_rows: Nv=%d with K=%d does not fit the LDS-resident row (%zu columns at most: split the "
                         "columns and merge the per-block lists, as laff_amd.ops.topk_rows does)", Nv, K, (160 * 1024 - kp * 8 - 1040) / 4);
     }
-    if (Nt == 0) return LAFF_OK;
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_topk_rows(S, Nt, Nv, lds, K, idx_out, val_out, ctx->stream));
     return LAFF_OK;
@@ -1860,7 +1865,6 @@ int laff_row_dot_gt(laff_ctx* ctx, const void* T, const void* V, int Nt, int Nv,
     if (precision < LAFF_PREC_FP16 || precision > LAFF_PREC_BF16X3) return fail(LAFF_E_UNSUPPORTED, "laff_row_dot_gt: 16-bit precisions only (got %d)", precision);
     if (Nt < 0 || Nv < 0 || K < 2 || (K & 1)) return fail(LAFF_E_SHAPE, "laff_row_dot_gt: K must be positive and even (K=%d)", K);
     if (!aligned16(T) || !aligned16(V)) return fail(LAFF_E_ALIGN, "laff_row_dot_gt: operands must be 16-byte aligned");
-    if (Nt == 0) return LAFF_OK;
     const int bf16 = (precision == LAFF_PREC_BF16 || precision == LAFF_PREC_BF16X3);
     DeviceGuard g(ctx->device);
     HIP_TRY(laff::launch_row_dot_gt(T, V, Nt, Nv, K, bf16, is_x3(precision) ? 1 : 0, scale, gt_col, col0, s_gt, zero_count, ctx->stream));
@@ -1873,13 +1877,9 @@ int laff_rank_metrics_async(laff_ctx* ctx, const int* rank1, int Nq, int base, i
     if (Nq < 1) return fail(LAFF_E_SHAPE, "laff_rank_metrics_async: Nq=%d", Nq);
     DeviceGuard g(ctx->device);
     if (int rc = metrics_buffers(ctx)) return rc;
-    const size_t si = 1 + ctx->metrics_slot++ % (METRIC_SLOTS - 1);                                  // (slot 0: the synchronous call)
+    const size_t si = next_metrics_slot(ctx);
     double* slot = ctx->d_metrics + 8 * si;
-    // a pinned result buffer is addressable from the device: the finishing workgroup stores the 64 bytes there itself, no copy node
-    double* host8 = nullptr;
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, out8, 0) == hipSuccess && dp) host8 = (double*)dp;
-    else (void)hipGetLastError();
+    double* host8 = pinned_alias(out8);
     HIP_TRY(laff::launch_rank_metrics(rank1, Nq, base, ranks_out, slot, slot + 7,
                                       (unsigned*)(ctx->d_mscratch + si * laff::rank_metrics_scratch_bytes()), ctx->stream, host8));
     if (!host8) HIP_TRY(hipMemcpyAsync(out8, slot, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1893,13 +1893,8 @@ int laff_rank_metrics(laff_ctx* ctx, const int* rank1, int Nq, int base, int* ra
     DeviceGuard g(ctx->device);
     if (int rc = metrics_buffers(ctx)) return rc;
     HIP_TRY(laff::launch_rank_metrics(rank1, Nq, base, ranks_out, ctx->d_metrics, ctx->d_metrics + 7, (unsigned*)ctx->d_mscratch, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_metrics, ctx->d_metrics, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_metrics[7] != 0.0)
-        return fail(LAFF_E_ARG, "laff_rank_metrics: a rank < 1 was found (ranks must be 1-based; a poisoned count also means the pair "
-                                "list of laff_sim_gemm_banded overflowed)");
-    for (int i = 0; i < 7; ++i) out7[i] = ctx->h_metrics[i];
-    return LAFF_OK;
+    return metrics_read_back(ctx, out7, "laff_rank_metrics: a rank < 1 was found (ranks must be 1-based; a poisoned count also means the "
+                                        "pair list of laff_sim_gemm_banded overflowed)");
 }
 
 }  // extern "C"

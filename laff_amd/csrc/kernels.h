@@ -256,6 +256,16 @@ hipError_t launch_pack_rows(const float* E, int N, int H, int d, int lde, int no
 
 hipError_t launch_row_dot_gt(const void* T, const void* V, int Nt, int Nv, int K, int bf16, int x3, float scale,
                              const int* gt_col, int col0, float* s_gt, int* zero_count, hipStream_t st);
+// The constants of the exact-rank error band (rank_prepare_kernel, and fuse_kernel's rp_* rows): the unit roundoff of the operand format,
+// and the fp32 accumulation of the exact products: K = H * d terms (3K for a hi/lo split, plus its dropped lo*lo term <= 2^-22), 2^-23
+// each (covers round-to-nearest and truncating accumulators), + 2^-20 for the fp32 copy of s_gt64, the scaling and the rounding of the
+// accumulator-unit thresholds the GEMM epilogue compares against.
+static inline void rank_band_constants(int precision, int H, int d, float* unit, float* c_acc) {
+    const bool x3 = precision == LAFF_PREC_FP16X3 || precision == LAFF_PREC_BF16X3;
+    const bool bf16 = precision == LAFF_PREC_BF16 || precision == LAFF_PREC_BF16X3;
+    *unit = precision == LAFF_PREC_FP32 ? 5.9604645e-8f : (bf16 ? 3.90625e-3f : 4.8828125e-4f);
+    *c_acc = (float)((double)H * d * (x3 ? 3.0 : 1.0) * 1.1920929e-7 + 9.5367432e-7 + (x3 ? 2.3841858e-7 : 0.0));
+}
 hipError_t launch_rank_prepare(const float* Et, const float* Ev, const void* T, const void* V, int Nt, int Nv, int H, int d,
                                int precision, float prescale, const int* gt_col, int col0, double* s_gt64, float* band_t,
                                float* band_v, int* zero_count, unsigned* pairs, int sides, hipStream_t st, int emit = 0);

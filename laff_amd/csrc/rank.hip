@@ -403,20 +403,17 @@ hipError_t launch_rank_prepare(const float* Et, const float* Ev, const void* T, 
     if (grid == 0) return hipSuccess;
     if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
     const float inv = 1.0f / prescale;
-    // fp32 accumulation of the exact products: K terms (3K for a hi/lo split, plus its dropped lo*lo term <= 2^-22), 2^-23 each
-    // (covers round-to-nearest and truncating accumulators), + 2^-20 for the fp32 copy of s_gt64, the scaling and the rounding of the
-    // accumulator-unit thresholds the GEMM epilogue compares against
-    const bool x3 = precision == LAFF_PREC_FP16X3 || precision == LAFF_PREC_BF16X3;
-    const float c_acc = (float)((double)H * d * (x3 ? 3.0 : 1.0) * 1.1920929e-7 + 9.5367432e-7 + (x3 ? 2.3841858e-7 : 0.0));
-#define LAFF_PREP(P, U)                                                                                                          \
-    hipLaunchKernelGGL((rank_prepare_kernel<P>), dim3((unsigned)grid), dim3(256), 0, st, Et, Ev, T, V, Nt, Nv, H, d, inv, U, c_acc, gt_col, \
+    float unit, c_acc;
+    rank_band_constants(precision, H, d, &unit, &c_acc);
+#define LAFF_PREP(P)                                                                                                                \
+    hipLaunchKernelGGL((rank_prepare_kernel<P>), dim3((unsigned)grid), dim3(256), 0, st, Et, Ev, T, V, Nt, Nv, H, d, inv, unit, c_acc, gt_col, \
                        col0, s_gt64, band_t, band_v, zero_count, pairs, vblocks, emit, prescale)
     switch (precision) {
-        case LAFF_PREC_FP32: LAFF_PREP(LAFF_PREC_FP32, 5.9604645e-8f); break;
-        case LAFF_PREC_FP16: LAFF_PREP(LAFF_PREC_FP16, 4.8828125e-4f); break;
-        case LAFF_PREC_BF16: LAFF_PREP(LAFF_PREC_BF16, 3.90625e-3f); break;
-        case LAFF_PREC_FP16X3: LAFF_PREP(LAFF_PREC_FP16X3, 4.8828125e-4f); break;
-        case LAFF_PREC_BF16X3: LAFF_PREP(LAFF_PREC_BF16X3, 3.90625e-3f); break;
+        case LAFF_PREC_FP32: LAFF_PREP(LAFF_PREC_FP32); break;
+        case LAFF_PREC_FP16: LAFF_PREP(LAFF_PREC_FP16); break;
+        case LAFF_PREC_BF16: LAFF_PREP(LAFF_PREC_BF16); break;
+        case LAFF_PREC_FP16X3: LAFF_PREP(LAFF_PREC_FP16X3); break;
+        case LAFF_PREC_BF16X3: LAFF_PREP(LAFF_PREC_BF16X3); break;
         default: return hipErrorInvalidValue;
     }
 #undef LAFF_PREP

@@ -964,24 +964,27 @@ def pack_rows(E, normalize=True, eps=1e-13, precision='fp16', prescale=None):
     return Packed(buf, N, H * d, precision, prescale)
 
 
+def _sim_out(T, V, heads, want_scores, out):
+    """What sim_gemm and sim_gemm_banded share: the (Nt, Nv) score output (`out`, or allocated here; None with the pitch of a dense
+    matrix when only counts are wanted) and the scale that undoes the operands' prescale.  Returns (S, lds, scale)."""
+    S, lds = None, V.N
+    if want_scores:
+        S, lds = _rows(out if out is not None else alloc_scores(T.N, V.N, T.buf.device), 'out')
+        if tuple(S.shape) != (T.N, V.N):
+            raise ValueError('out must be (%d, %d)' % (T.N, V.N))
+    return S, lds, 1.0 / (heads * T.prescale * V.prescale)
+
+
 def sim_gemm(T, V, heads=1, out=None, want_scores=True, gt_col=None, s_gt=None, count=None, col0=0):
     """S = T.V^T / (heads * prescale^2) on Packed operands; optional fused ground-truth rank count."""
     if T.precision != V.precision or T.K != V.K:
         raise ValueError('operands differ in precision or K')
-    dev = T.buf.device
-    S = None
-    lds = V.N
-    if want_scores:
-        S = out if out is not None else alloc_scores(T.N, V.N, dev)
-        S, lds = _rows(S, 'out')
-        if tuple(S.shape) != (T.N, V.N):
-            raise ValueError('out must be (%d, %d)' % (T.N, V.N))
+    S, lds, scale = _sim_out(T, V, heads, want_scores, out)
     if gt_col is not None:
         _dev(gt_col, 'gt_col', torch.int32)
         _dev(s_gt, 's_gt')
         _dev(count, 'count', torch.int32)
-    scale = 1.0 / (heads * T.prescale * V.prescale)
-    lib, h = _context(dev)
+    lib, h = _context(T.buf.device)
     _call('sim_gemm', lib.laff_sim_gemm, h, _ptr(T.buf), _ptr(V.buf), T.N, V.N, T.K, scale, PREC[T.precision], _ptr(S), lds,
                             _ptr(gt_col), col0, _ptr(s_gt), _ptr(count))
     return S
@@ -1093,6 +1096,41 @@ def default_pair_cap(Nt):
     return max(1 << 20, 128 * int(Nt))
 
 
+def _gt_col(gt_col, Nt=None):
+    """gt_col as the rank kernels take it: int32 (with Nt: a contiguous vector of Nt), cloned when it does not start on 16 bytes
+    (the banded GEMM fetches it in 16-byte groups)."""
+    _dev(gt_col, 'gt_col', torch.int32)
+    if Nt is not None and (gt_col.numel() != Nt or not gt_col.is_contiguous()):
+        raise ValueError('gt_col must be a contiguous int32 vector of %d' % Nt)
+    return gt_col.clone() if gt_col.data_ptr() % 16 else gt_col
+
+
+# The rank-state buffers.  The slack is what the banded GEMM may read past the end: it fetches these vectors in 16-byte groups.
+def _alloc_text_bands(Nt, dev):
+    """(s_gt64: Nt float64 of Nt + 2, band_t: Nt + 4 float32)."""
+    return torch.empty((Nt + 2,), device=dev, dtype=torch.float64)[:Nt], torch.empty((Nt + 4,), device=dev, dtype=torch.float32)
+
+
+def _alloc_band_v(Nv, dev):
+    """band_v in the layout the banded GEMM reads: one float per column, then -- from a 16-byte aligned offset -- the maximum of
+    every 64-column block, + 4 of slack."""
+    return torch.empty((((Nv + 3) & ~3) + (Nv + 63) // 64 + 4,), device=dev, dtype=torch.float32)
+
+
+def _alloc_list(Nt, pair_cap, dev):
+    """The in-band list of pair_cap slots (None: default_pair_cap) in the whole groups of four the kernels use, one at least:
+    (count: Nt int32, pairs: a header of 4 int32 then cap slots of {row, col}, cap)."""
+    cap = (int(pair_cap) if pair_cap is not None else default_pair_cap(Nt)) & ~3
+    if cap < 4:
+        raise ValueError('pair_cap must be >= 4')
+    return torch.empty((Nt,), device=dev, dtype=torch.int32), torch.empty((4 + 2 * cap,), device=dev, dtype=torch.int32), cap
+
+
+def _opt_scores(S):
+    """An optional score matrix argument: (S, its row pitch), or (None, 0)."""
+    return _rows(S, 'S') if S is not None else (None, 0)
+
+
 def fused_prepare_eligible(Nt, Nv, H, d, precision):
     """laff_fuse_packed_rank covers split heads of d <= 512 with a single-plane 16-bit operand; the text launch finishes the videos'
     64-column block maxima (it needs ceil(Nv / 64) workgroups of 4 (row, head) items)."""
@@ -1135,21 +1173,12 @@ class FusedPrepare:
                 self.owner.Et, self.owner.T = E, packed
 
     def __init__(self, Nt, Nv, gt_col, col0=0, pair_cap=None, heads=1):
-        _dev(gt_col, 'gt_col', torch.int32)
-        if gt_col.numel() != Nt or not gt_col.is_contiguous():
-            raise ValueError('gt_col must be a contiguous int32 vector of %d' % Nt)
-        if gt_col.data_ptr() % 16:
-            gt_col = gt_col.clone()
+        gt_col = _gt_col(gt_col, Nt)
         dev = gt_col.device
-        cap = (int(pair_cap) if pair_cap is not None else default_pair_cap(Nt)) & ~3
-        if cap < 4:
-            raise ValueError('pair_cap must be >= 4')
-        self.Nt, self.Nv, self.gt_col, self.col0, self.pair_cap, self.heads = Nt, Nv, gt_col, int(col0), cap, int(heads)
-        self.s_gt64 = torch.empty((Nt + 2,), device=dev, dtype=torch.float64)[:Nt]
-        self.band_t = torch.empty((Nt + 4,), device=dev, dtype=torch.float32)
-        self.band_v = torch.empty((((Nv + 3) & ~3) + (Nv + 63) // 64 + 4,), device=dev, dtype=torch.float32)
-        self.count = torch.empty((Nt,), device=dev, dtype=torch.int32)
-        self.pairs = torch.empty((4 + 2 * cap,), device=dev, dtype=torch.int32)
+        self.Nt, self.Nv, self.gt_col, self.col0, self.heads = Nt, Nv, gt_col, int(col0), int(heads)
+        self.s_gt64, self.band_t = _alloc_text_bands(Nt, dev)
+        self.band_v = _alloc_band_v(Nv, dev)
+        self.count, self.pairs, self.pair_cap = _alloc_list(Nt, pair_cap, dev)
         self.Et = self.Ev = self.T = self.V = None
         self._scratch = []
         self.video, self.text = self._Side(self, 2), self._Side(self, 1)
@@ -1186,27 +1215,15 @@ def rank_prepare(Et, Ev, T, V, gt_col, col0=0, pair_cap=None, emit_precision=Non
         raise ValueError('embeddings %s / %s do not match the operands (%d x %d, %d x %d)' % (tuple(Et.shape), tuple(Ev.shape), T.N, T.K, V.N, V.K))
     if T.precision != V.precision or T.prescale != V.prescale:
         raise ValueError('operands differ in precision or prescale')
-    _dev(gt_col, 'gt_col', torch.int32)
-    if gt_col.numel() != Nt or not gt_col.is_contiguous():
-        raise ValueError('gt_col must be a contiguous int32 vector of %d' % Nt)
-    if gt_col.data_ptr() % 16:          # the GEMM fetches gt_col in 16-byte groups
-        gt_col = gt_col.clone()
+    gt_col = _gt_col(gt_col, Nt)
     dev = Et.device
-    cap = (int(pair_cap) if pair_cap is not None else default_pair_cap(Nt)) & ~3      # the list is used in groups of four slots
-    if cap < 4:
-        raise ValueError('pair_cap must be >= 4')
-    s_gt64 = torch.empty((Nt + 2,), device=dev, dtype=torch.float64)[:Nt]
-    band_t = torch.empty((Nt + 4,), device=dev, dtype=torch.float32)          # (+ slack: the GEMM fetches 16-byte groups)
-    band_v = torch.empty((((Nv + 3) & ~3) + (Nv + 63) // 64 + 4,), device=dev, dtype=torch.float32)     # per column, then (16-byte aligned) per 64-column block
-    count = torch.empty((Nt,), device=dev, dtype=torch.int32)
-    pairs = torch.empty((4 + 2 * cap,), device=dev, dtype=torch.int32)
+    s_gt64, band_t = _alloc_text_bands(Nt, dev)
+    band_v = _alloc_band_v(Nv, dev)
+    count, pairs, cap = _alloc_list(Nt, pair_cap, dev)
     lib, h = _context(dev)
-    if emit:
-        _call('rank_prepare', lib.laff_rank_prepare_emit, h, emit, _ptr(Et), _ptr(Ev), _ptr(T.buf), _ptr(V.buf), Nt, Nv, H, d, PREC[T.precision],
-              float(T.prescale), _ptr(gt_col), int(col0), _ptr(s_gt64), _ptr(band_t), _ptr(band_v), _ptr(count), _ptr(pairs))
-    else:
-        _call('rank_prepare', lib.laff_rank_prepare, h, _ptr(Et), _ptr(Ev), _ptr(T.buf), _ptr(V.buf), Nt, Nv, H, d, PREC[T.precision],
-              float(T.prescale), _ptr(gt_col), int(col0), _ptr(s_gt64), _ptr(band_t), _ptr(band_v), _ptr(count), _ptr(pairs))
+    entry = (lib.laff_rank_prepare_emit, h, emit) if emit else (lib.laff_rank_prepare, h)
+    _call('rank_prepare', *entry, _ptr(Et), _ptr(Ev), _ptr(T.buf), _ptr(V.buf), Nt, Nv, H, d, PREC[T.precision], float(T.prescale),
+          _ptr(gt_col), int(col0), _ptr(s_gt64), _ptr(band_t), _ptr(band_v), _ptr(count), _ptr(pairs))
     return RankState(Et, Ev, T, V, H, gt_col, int(col0), s_gt64, band_t, band_v, count, pairs, cap)
 
 
@@ -1217,13 +1234,9 @@ def rank_prepare_text(Et, Ev, T, gt_col, col0=0, prescale=None):
     Nt, H, d = Et.shape
     if tuple(Ev.shape[1:]) != (H, d) or T.N != Nt or T.K != H * d:
         raise ValueError('embeddings %s / %s do not match the operand (%d x %d)' % (tuple(Et.shape), tuple(Ev.shape), T.N, T.K))
-    _dev(gt_col, 'gt_col', torch.int32)
-    if gt_col.numel() != Nt or not gt_col.is_contiguous():
-        raise ValueError('gt_col must be a contiguous int32 vector of %d' % Nt)
-    dev = Et.device
-    s_gt64 = torch.empty((Nt + 2,), device=dev, dtype=torch.float64)[:Nt]
-    band_t = torch.empty((Nt + 4,), device=dev, dtype=torch.float32)
-    lib, h = _context(dev)
+    gt_col = _gt_col(gt_col, Nt)
+    s_gt64, band_t = _alloc_text_bands(Nt, Et.device)
+    lib, h = _context(Et.device)
     _call('rank_prepare', lib.laff_rank_prepare_part, h, 1, _ptr(Et), _ptr(Ev), _ptr(T.buf), None, Nt, Ev.shape[0], H, d, PREC[T.precision],
           float(T.prescale), _ptr(gt_col), int(col0), _ptr(s_gt64), _ptr(band_t), None, None, None)
     return s_gt64, band_t
@@ -1236,7 +1249,7 @@ def rank_band_video(Ev, V):
     Nv, H, d = Ev.shape
     if V.N != Nv or V.K != H * d:
         raise ValueError('embeddings %s do not match the operand (%d x %d)' % (tuple(Ev.shape), V.N, V.K))
-    band_v = torch.empty((((Nv + 3) & ~3) + (Nv + 63) // 64 + 4,), device=Ev.device, dtype=torch.float32)
+    band_v = _alloc_band_v(Nv, Ev.device)
     lib, h = _context(Ev.device)
     _call('rank_prepare', lib.laff_rank_prepare_part, h, 2, None, _ptr(Ev), None, _ptr(V.buf), 0, Nv, H, d, PREC[V.precision], float(V.prescale),
           None, 0, None, None, _ptr(band_v), None, None)
@@ -1245,13 +1258,9 @@ def rank_band_video(Ev, V):
 
 def banded_state(T, V, heads, gt_col, col0, s_gt64, band_t, band_v, pair_cap=None):
     """A RankState for laff_sim_gemm_banded assembled from parts (no fp32 rows: its list is exported, not resolved here)."""
-    _dev(gt_col, 'gt_col', torch.int32)
-    if gt_col.data_ptr() % 16:
-        gt_col = gt_col.clone()
-    dev = T.buf.device
-    cap = (int(pair_cap) if pair_cap is not None else default_pair_cap(T.N)) & ~3
-    count = torch.zeros((T.N,), device=dev, dtype=torch.int32)
-    pairs = torch.empty((4 + 2 * cap,), device=dev, dtype=torch.int32)
+    gt_col = _gt_col(gt_col)
+    count, pairs, cap = _alloc_list(T.N, pair_cap, T.buf.device)
+    count.zero_()
     pairs[:4].zero_()
     return RankState(None, None, T, V, heads, gt_col, int(col0), s_gt64, band_t, band_v, count, pairs, cap)
 
@@ -1264,9 +1273,7 @@ def rank_export_pairs(st, S, bounds, col0, cap):
     dev = st.pairs.device
     out = torch.empty((world, cap, 2), device=dev, dtype=torch.int32)
     fill = torch.empty((world + 1,), device=dev, dtype=torch.int32)
-    lds = 0
-    if S is not None:
-        S, lds = _rows(S, 'S')
+    S, lds = _opt_scores(S)
     lib, h = _context(dev)
     _call('rank_export', lib.laff_rank_export_pairs, h, _ptr(st.s_gt64), _ptr(st.count), _ptr(S), lds, st.V.N, _ptr(st.pairs), st.pair_cap,
           _ptr(bounds), world, int(col0), _ptr(out), cap, _ptr(fill))
@@ -1276,26 +1283,15 @@ def rank_export_pairs(st, S, bounds, col0, cap):
 def rank_resolve_list(Et, Ev, s_gt64, count, lst):
     """laff_rank_resolve on a plain list: lst int32 (4 + 2 n), header {0, 0, n, 4} then n slots {row, col} with unused slots -1 and
     the valid pairs first in every group of four (what concatenated laff_rank_export_pairs buckets are).  count += wins."""
-    Et, Ev = _emb3(Et, 'Et'), _emb3(Ev, 'Ev')
-    Nt, H, d = Et.shape
-    n = (lst.numel() - 4) // 2
-    lib, h = _context(Et.device)
-    _call('rank_resolve', lib.laff_rank_resolve, h, _ptr(Et), _ptr(Ev), Nt, Ev.shape[0], H, d, _ptr(s_gt64), _ptr(count), None, 0, _ptr(lst), n)
-    return count
+    return rank_resolve(RankState(_emb3(Et, 'Et'), _emb3(Ev, 'Ev'), None, None, None, None, 0, s_gt64, None, None, count, lst,
+                                  (lst.numel() - 4) // 2))
 
 
 def sim_gemm_banded(st, want_scores=True, out=None):
     """Second launch: the similarity GEMM with the banded count (state.count, state.pairs are filled).  Returns S or None."""
     T, V = st.T, st.V
-    dev = T.buf.device
-    S, lds = None, V.N
-    if want_scores:
-        S = out if out is not None else alloc_scores(T.N, V.N, dev)
-        S, lds = _rows(S, 'out')
-        if tuple(S.shape) != (T.N, V.N):
-            raise ValueError('out must be (%d, %d)' % (T.N, V.N))
-    scale = 1.0 / (st.heads * T.prescale * V.prescale)
-    lib, h = _context(dev)
+    S, lds, scale = _sim_out(T, V, st.heads, want_scores, out)
+    lib, h = _context(T.buf.device)
     _call('sim_gemm', lib.laff_sim_gemm_banded, h, _ptr(T.buf), _ptr(V.buf), T.N, V.N, T.K, scale, PREC[T.precision], _ptr(S), lds,
           _ptr(st.gt_col), st.col0, _ptr(st.s_gt64), _ptr(st.band_t), _ptr(st.band_v), _ptr(st.count), _ptr(st.pairs), st.pair_cap)
     return S
@@ -1303,9 +1299,7 @@ def sim_gemm_banded(st, want_scores=True, out=None):
 
 def rank_resolve(st, S=None):
     """Third launch: exact re-score of the listed pairs; state.count (+ S) are final afterwards."""
-    lds = 0
-    if S is not None:
-        S, lds = _rows(S, 'S')
+    S, lds = _opt_scores(S)
     Nt, H, d = st.Et.shape
     lib, h = _context(st.Et.device)
     _call('rank_resolve', lib.laff_rank_resolve, h, _ptr(st.Et), _ptr(st.Ev), Nt, st.Ev.shape[0], H, d, _ptr(st.s_gt64), _ptr(st.count),
@@ -1318,26 +1312,15 @@ def rank_resolve_metrics(st, S=None, out_pinned=None, base=1, ranks_out=None):
     the final counts into ranks (ranks_out <- count + base) and the seven metrics.
     out_pinned None: synchronises, returns the 7-tuple (RuntimeError if a rank < 1 was flagged: overflowed pair list).
     out_pinned (pinned float64 tensor of >= 8): no sync, capturable; the device writes the 8 doubles into it directly; returns None."""
-    lds = 0
-    if S is not None:
-        S, lds = _rows(S, 'S')
+    S, lds = _opt_scores(S)
     Nt, H, d = st.Et.shape
-    lib, h = _context(st.Et.device)
-    if ('metrics', h.value) not in _ctx:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('call ops.ctx_prepare_metrics(device) before capturing a graph (it allocates scratch)')
-        ctx_prepare_metrics(st.Et.device)
+    lib, h = _metrics_context(st.Et.device)
     ro = _ranks_out(st.count, ranks_out)
-    if out_pinned is None:
-        out = (C.c_double * 8)()
-        _call('rank_resolve', lib.laff_rank_resolve_metrics, h, _ptr(st.Et), _ptr(st.Ev), Nt, st.Ev.shape[0], H, d, _ptr(st.s_gt64),
-              _ptr(st.count), _ptr(S), lds, _ptr(st.pairs), st.pair_cap, int(base), _ptr(ro), out, 1)
-        return tuple(out)[:7]
-    if out_pinned.dtype != torch.float64 or out_pinned.numel() < 8 or not out_pinned.is_pinned():
-        raise ValueError('out_pinned must be a pinned float64 tensor of >= 8 elements')
+    sync = out_pinned is None
+    out = (C.c_double * 8)() if sync else _pinned8(out_pinned)
     _call('rank_resolve', lib.laff_rank_resolve_metrics, h, _ptr(st.Et), _ptr(st.Ev), Nt, st.Ev.shape[0], H, d, _ptr(st.s_gt64),
-          _ptr(st.count), _ptr(S), lds, _ptr(st.pairs), st.pair_cap, int(base), _ptr(ro), C.c_void_p(out_pinned.data_ptr()), 0)
-    return None
+          _ptr(st.count), _ptr(S), lds, _ptr(st.pairs), st.pair_cap, int(base), _ptr(ro), out, 1 if sync else 0)
+    return tuple(out)[:7] if sync else None
 
 
 def exact_ranks(Et, Ev, T, V, gt_col, want_scores=True, col0=0, pair_cap=None):
@@ -1567,6 +1550,23 @@ def _ranks_out(r, ranks_out):
     return ranks_out
 
 
+def _pinned8(out_pinned):
+    """The address of a pinned result buffer (the device writes the 8 doubles into it itself)."""
+    if out_pinned.dtype != torch.float64 or out_pinned.numel() < 8 or not out_pinned.is_pinned():
+        raise ValueError('out_pinned must be a pinned float64 tensor of >= 8 elements')
+    return C.c_void_p(out_pinned.data_ptr())
+
+
+def _metrics_context(device):
+    """_context for a call that takes an asynchronous metrics slot: the context's metrics scratch must exist before a capture."""
+    lib, h = _context(device)
+    if ('metrics', h.value) not in _ctx:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('call ops.ctx_prepare_metrics(device) before capturing a graph (it allocates scratch)')
+        ctx_prepare_metrics(device)
+    return lib, h
+
+
 def rank_metrics(rank1, base=0, ranks_out=None):
     """(r1, r5, r10, medr, meanr, mir, mAP) from int32 device values r with rank = r + base (1-based ranks: base 0; counts of
     better-scoring videos: base 1); ranks_out optionally receives the ranks.  Synchronises the stream."""
@@ -1581,15 +1581,10 @@ def rank_metrics_async(rank1, out_pinned, base=0, ranks_out=None):
     """Launch the metrics reduction and the 64-byte D2H copy without synchronising (HIP-graph capturable).
     out_pinned: pinned CPU float64 tensor of 8; after a stream sync [:7] are the metrics, [7] != 0 flags a rank < 1."""
     _dev(rank1, 'rank1', torch.int32)
-    if out_pinned.dtype != torch.float64 or out_pinned.numel() < 8 or not out_pinned.is_pinned():
-        raise ValueError('out_pinned must be a pinned float64 tensor of >= 8 elements')
-    lib, h = _context(rank1.device)
-    if ('metrics', h.value) not in _ctx:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('call ops.ctx_prepare_metrics(device) before capturing a graph (it allocates scratch)')
-        ctx_prepare_metrics(rank1.device)
+    out = _pinned8(out_pinned)
+    lib, h = _metrics_context(rank1.device)
     _call('rank_metrics', lib.laff_rank_metrics_async, h, _ptr(rank1.contiguous()), rank1.numel(), int(base), _ptr(_ranks_out(rank1, ranks_out)),
-          C.c_void_p(out_pinned.data_ptr()))
+          out)
 
 
 def ctx_prepare_metrics(device):
