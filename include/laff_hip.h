@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 32
+#define LAFF_ABI_VERSION 33
 
 enum {
     LAFF_OK = 0,
@@ -716,6 +716,19 @@ int laff_rerank_run(laff_ctx* ctx, const laff_rerank_problem* problems /*host ar
  * that hold the column (a histogram pass); out [Q, ldo] receives log(count + 1) at each row's candidate columns and 0 in its other
  * G - K columns.  The caller L2-normalises the rows (loss.l2norm).  An index outside [0, G) is skipped. */
 int laff_rerank_tkb(laff_ctx* ctx, const int* nn, int G, int k1, const int* cand, int Q, int K, int* count, float* out, int ldo);
+
+/* ---- the 'hist' measure: generalised Jaccard / histogram intersection (loss.py:43-65, evaluation.py:19-41) ------------------------
+ *   S[t, v] = (1 / H) sum_h J(T[t, h, :], V[v, h, :]),   J(x, y) = sum_k min(x_k, y_k) / (sum_k max(x_k, y_k) + eps)
+ * the mean over heads of the per-head measure, as the reference's 3-D get_txt2vis_matrix takes it (model/model.py:1008-1014); H = 1 is
+ * the plain 2-D case.  T [Nt, H d] and V [Nv, H d] fp32 with row pitches ldt, ldv >= H d; S [Nt, Nv] fp32 with row pitch lds >= Nv,
+ * columns Nv .. lds-1 are not written.  Pointers and pitches need 4-byte alignment only (16-byte loads are used where base, pitch and
+ * head width allow them; the result does not depend on it).  eps >= 0 is added to the union of every head before the division;
+ * eps = 0 gives IEEE results (0 / 0 = NaN, as evaluation.hist_sim).  Inputs may be negative.  Both sums are accumulated in fp32 in
+ * one fixed order (no atomics: bitwise reproducible).
+ * Refused before any GPU work (LAFF_E_ARG / LAFF_E_SHAPE, the message names the value): null T / V / S when Nt Nv > 0, Nt < 0, Nv < 0,
+ * H < 1, d < 1, H d beyond int, ldt / ldv < H d, lds < Nv, eps < 0 or NaN.  Nt == 0 or Nv == 0: returns 0, launches nothing. */
+int laff_sim_hist(laff_ctx* ctx, const float* T, long ldt, const float* V, long ldv, int Nt, int Nv, int H, int d, float eps, float* S,
+                  long lds);
 
 /* ---- a13: evaluation.eval (evaluation.py:92-109) for single-GT rows ---------------------------------------
  * rank[i] = r[i] + base must be >= 1: pass 1-based ranks with base = 0, or the counts of better-scoring videos that

@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 
 class Plane(C.Structure):
@@ -196,6 +196,7 @@ SIGNATURES = {
     'laff_rerank_workspace_bytes': (C.c_int, [C.POINTER(RerankProblem), _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_rerank_run': (C.c_int, [_P, C.POINTER(RerankProblem), _I, _I, _I, _F, _P, C.c_size_t]),
     'laff_rerank_tkb': (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I]),
+    'laff_sim_hist': (C.c_int, [_P, _P, C.c_long, _P, C.c_long, _I, _I, _I, _I, _F, _P, C.c_long]),
 }
 
 _lib = None

@@ -1122,6 +1122,40 @@ int laff_rerank_tkb(laff_ctx* ctx, const int* nn, int G, int k1, const int* cand
     return LAFF_OK;
 }
 
+int laff_sim_hist(laff_ctx* ctx, const float* T, long ldt, const float* V, long ldv, int Nt, int Nv, int H, int d, float eps, float* S,
+                  long lds) {
+    const char* fn = "laff_sim_hist";
+    // every argument is checked before the ctx: a bad call needs no GPU
+    if (Nt < 0) return fail(LAFF_E_SHAPE, "%s: Nt=%d is negative", fn, Nt);
+    if (Nv < 0) return fail(LAFF_E_SHAPE, "%s: Nv=%d is negative", fn, Nv);
+    if (H < 1) return fail(LAFF_E_SHAPE, "%s: H=%d, need H >= 1", fn, H);
+    if (d < 1) return fail(LAFF_E_SHAPE, "%s: d=%d, need d >= 1", fn, d);
+    const long K = (long)H * d;
+    if (K > INT_MAX) return fail(LAFF_E_SHAPE, "%s: H*d=%ld does not fit an int (H=%d d=%d)", fn, K, H, d);
+    if (ldt < K) return fail(LAFF_E_SHAPE, "%s: ldt=%ld is shorter than a row (H*d=%ld)", fn, ldt, K);
+    if (ldv < K) return fail(LAFF_E_SHAPE, "%s: ldv=%ld is shorter than a row (H*d=%ld)", fn, ldv, K);
+    if (lds < Nv) return fail(LAFF_E_SHAPE, "%s: lds=%ld is shorter than a row (Nv=%d)", fn, lds, Nv);
+    if (!(eps >= 0.0f)) return fail(LAFF_E_ARG, "%s: eps=%g, need eps >= 0", fn, (double)eps);
+    if (Nt == 0 || Nv == 0) return LAFF_OK;                 /* an empty side: nothing to launch, pointers may be null */
+    if (!T) return fail(LAFF_E_ARG, "%s: T is null", fn);
+    if (!V) return fail(LAFF_E_ARG, "%s: V is null", fn);
+    if (!S) return fail(LAFF_E_ARG, "%s: S is null", fn);
+    laff::SimHistArgs a{};
+    unsigned tiles = 0;
+    if (!laff::sim_hist_tiles(Nt, Nv, &a.tilesV, &tiles))
+        return fail(LAFF_E_SHAPE, "%s: Nt=%d x Nv=%d is more tiles than one grid holds", fn, Nt, Nv);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    a.T = T; a.V = V; a.S = S;
+    a.ldt = ldt; a.ldv = ldv; a.lds = lds;
+    a.Nt = Nt; a.Nv = Nv; a.H = H; a.d = d;
+    a.eps = eps;
+    const bool heads16 = H == 1 || d % 4 == 0;              // every head of a row starts on 16 bytes when the row does
+    a.vec = (heads16 && aligned16(T) && ldt % 4 == 0 ? 1 : 0) | (heads16 && aligned16(V) && ldv % 4 == 0 ? 2 : 0);
+    HIP_TRY(laff::launch_sim_hist(a, tiles, ctx->stream));
+    return LAFF_OK;
+}
+
 int laff_split_rows_bytes(int N, int K, size_t* out) {
     if (!out || N < 0 || K < 1) return fail(LAFF_E_ARG, "laff_split_rows_bytes: bad args");
     const size_t Kp = (size_t)(K + 63) / 64 * 64;

@@ -488,4 +488,17 @@ hipError_t launch_rerank(const RerankArgs& a, int maxQ, int maxG, int maxN, hipS
 hipError_t launch_rerank_tkb(const int* nn, int G, int k1, const int* cand, int Q, int K, int* count, float* out, long ldo,
                              hipStream_t st);
 
+// sim_hist.hip: the 'hist' measure (laff_sim_hist): S[t, v] = 1/H sum_h sum_k min / (sum_k max + eps), fp32
+struct SimHistArgs {
+    const float *T, *V;                   // [Nt, H d], [Nv, H d]
+    float* S;                             // [Nt, Nv]
+    long ldt, ldv, lds;
+    int Nt, Nv, H, d;
+    float eps;
+    int vec;                              // bit 0 / 1: T / V may be read in 16-byte groups (base, pitch and head width allow it)
+    unsigned tilesV;                      // tiles along Nv; blockIdx.x = text tile * tilesV + video tile
+};
+bool sim_hist_tiles(int Nt, int Nv, unsigned* tilesV, unsigned* tiles);    // false: more tiles than a grid holds
+hipError_t launch_sim_hist(const SimHistArgs& a, unsigned tiles, hipStream_t st);
+
 }  // namespace laff

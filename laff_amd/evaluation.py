@@ -26,7 +26,16 @@ def cosine_sim(query_embs, retro_embs, precision='fp16x3', device='cuda'):
     return ops.sim_gemm(Q, R).cpu().numpy()
 
 
+def hist_sim(im, s, device='cuda'):
+    """evaluation.py:19-41: sum min / sum max of every row of im against every row of s, no eps (a pair of all-zero rows gives NaN,
+    as there); computed on the GPU, returned as numpy float32."""
+    a = torch.as_tensor(np.ascontiguousarray(im, dtype=np.float32), device=device)
+    b = torch.as_tensor(np.ascontiguousarray(s, dtype=np.float32), device=device)
+    return ops.sim_hist(a, b, 1, 0.0).cpu().numpy()
+
+
 def compute_sim(query_embs, retro_embs, measure='cosine', device='cuda'):
+    # measure='hist' stays refused here (call hist_sim): the refusal is part of this function's tested contract
     if measure != 'cosine':
         raise NotImplementedError("measure '%s' is never configured on the path" % measure)
     return cosine_sim(query_embs, retro_embs, device=device)

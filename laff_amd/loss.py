@@ -1,4 +1,4 @@
-"""loss.l2norm / loss.cosine_sim of the reference (/root/reference/loss.py:8-34) on the HIP kernels."""
+"""loss.l2norm / loss.cosine_sim / loss.hist_sim / loss.jaccard_sim of the reference (/root/reference/loss.py:8-65) on the HIP kernels."""
 import torch
 
 from . import ops
@@ -22,6 +22,17 @@ def cosine_sim(query, retrio, precision=None):
     q = ops.pack_rows(query.contiguous(), True, 1e-13, precision)
     r = ops.pack_rows(retrio.contiguous(), True, 1e-13, precision)
     return ops.sim_gemm(q, r, heads=1)
+
+
+def hist_sim(im, s, eps=1e-14):
+    """sum min(im, s) / (sum max(im, s) + eps) of every row of im against every row of s (loss.py:43-50).  The reference's version
+    expands both sides by im's row count and so only works on square input; any (N_im, N_s) is accepted here."""
+    return ops.sim_hist(im, s, 1, eps)
+
+
+def jaccard_sim(query, retrieval_base, eps=1e-8):
+    """The same measure as the reference's per-query loop states it (loss.py:53-65): (N_query, N_base)."""
+    return ops.sim_hist(query, retrieval_base, 1, eps)
 
 
 # ---- training loss (SURVEY.md section 8f-4) ---------------------------------------------------------------------------
@@ -49,6 +60,7 @@ class MarginRankingLoss(torch.nn.Module):
 
     def __init__(self, margin=0, measure='cosine', max_violation=False, cost_style='sum', direction='bidir', device=None):
         super().__init__()
+        # measure='hist' stays refused: the scores exist (hist_sim above), the margin loss on them and its backward do not
         if measure != 'cosine':
             raise NotImplementedError("only measure='cosine' is on the path ('hist' is the Jaccard variant of task 2)")
         self.margin, self.max_violation, self.cost_style, self.direction = margin, max_violation, cost_style, direction

@@ -772,18 +772,24 @@ class W2VVPP(nn.Module):
     # -- similarity -----------------------------------------------------------------------------------------
     @staticmethod
     def compute_sim(query_embs, retro_embs, measure='cosine', device=None):
-        if measure != 'cosine':
+        if measure not in ('cosine', 'hist'):
             raise NotImplementedError("measure '%s' is never configured on the path (base_config.py:92)" % measure)
         dev = device if device is not None else globals()['device']
+        if measure == 'hist':
+            return _loss.hist_sim(query_embs.to(dev), retro_embs.to(dev))
         return _loss.cosine_sim(query_embs.to(dev), retro_embs.to(dev), W2VVPP.sim_precision)
 
     def get_txt2vis_matrix(self, txt_embs, vis_embs, measure='cosine', precision=None):
         """2-D: cosine; 3-D: mean over heads of per-head cosine == one GEMM over the concatenated,
-        per-head normalised embeddings divided by H."""
-        if measure != 'cosine':
+        per-head normalised embeddings divided by H.
+        measure='hist': the generalised Jaccard measure, 2-D, or 3-D as the mean over heads of the per-head measure (eps 1e-14 as
+        loss.hist_sim); one fp32 kernel on the embeddings as they are -- nothing is packed and `precision` is ignored."""
+        if measure not in ('cosine', 'hist'):
             raise NotImplementedError("measure '%s'" % measure)
         if txt_embs.dim() != vis_embs.dim() or txt_embs.dim() not in (2, 3):
             raise ValueError('txt_embs %s / vis_embs %s' % (tuple(txt_embs.shape), tuple(vis_embs.shape)))
+        if measure == 'hist':
+            return ops.sim_hist(to_device_and_float16(txt_embs).contiguous(), to_device_and_float16(vis_embs).contiguous())
         precision = precision or self.sim_precision or _loss.DEFAULT_PRECISION
         heads = txt_embs.shape[1] if txt_embs.dim() == 3 else 1
         T = ops.pack_rows(to_device_and_float16(txt_embs).contiguous(), True, 1e-13, precision)
@@ -846,8 +852,11 @@ class W2VVPP(nn.Module):
         produced by the exact-rank pipeline: the text->video ranks counted from it (predictor.t2v_ranks, or an argsort on the host
         as the reference does) are the ranks of the exact cosine scores whatever the operand precision; they are also kept in
         `self.last_t2v_ranks`, and the pipeline's state in `self.last_rank_state` (exact video->text positions:
-        predictor.retrieval_metrics(S, txt_ids, vis_ids, state=model.last_rank_state))."""
-        if measure != 'cosine':
+        predictor.retrieval_metrics(S, txt_ids, vis_ids, state=model.last_rank_state)).
+
+        measure='hist': the embeddings are made the same way, S is ops.sim_hist of them; under the id protocol `last_t2v_ranks` are
+        the ranks counted on that S itself (1 + the number of other videos scoring higher), and `last_rank_state` stays None."""
+        if measure not in ('cosine', 'hist'):
             raise NotImplementedError("measure '%s'" % measure)
         self.eval()
         if not hasattr(self, 'video_all_embs'):
@@ -890,7 +899,12 @@ class W2VVPP(nn.Module):
                     owner = gt_columns(txt_ids, self.vis_ids)
                 except (IndexError, ValueError, AttributeError):
                     owner = None                 # ids do not follow the protocol: plain scores
-            if owner is not None:
+            if measure == 'hist':
+                S = self.get_txt2vis_matrix(txt_all, vis_used, measure)
+                if owner is not None:
+                    gt = torch.as_tensor(owner, dtype=torch.int32, device=S.device)
+                    self.last_t2v_ranks = ops.rank_count(S, gt, ops.gather_gt(S, gt)) + 1
+            elif owner is not None:
                 gt = torch.as_tensor(owner, dtype=torch.int32, device=txt_all.device)
                 Et, Ev = txt_all.contiguous(), vis_used.contiguous()
                 # The pair list of the exact-rank pipeline overflows only on degenerate scores (thousands of videos inside one

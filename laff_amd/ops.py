@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -987,6 +987,41 @@ def sim_gemm(T, V, heads=1, out=None, want_scores=True, gt_col=None, s_gt=None, 
     lib, h = _context(T.buf.device)
     _call('sim_gemm', lib.laff_sim_gemm, h, _ptr(T.buf), _ptr(V.buf), T.N, V.N, T.K, scale, PREC[T.precision], _ptr(S), lds,
                             _ptr(gt_col), col0, _ptr(s_gt), _ptr(count))
+    return S
+
+
+def _hist_rows(E, name, heads):
+    """An operand of sim_hist as rows: (2-D view, its pitch, heads, d)."""
+    _dev(E, name)
+    rows = E
+    if E.dim() == 3:
+        N, heads, d = E.shape
+        if E.numel() and (E.stride(2) != 1 or E.stride(1) != d):
+            raise ValueError('%s must be (N, H, d) with the heads of a row contiguous, got strides %s' % (name, E.stride()))
+        rows = E.as_strided((N, heads * d), (E.stride(0), 1)) if E.numel() else E.reshape(N, heads * d)
+    rows, ld = _rows(rows, name)
+    if heads < 1 or rows.shape[1] < 1 or rows.shape[1] % heads:
+        raise ValueError('%s: width %d does not split into %d heads' % (name, rows.shape[1], heads))
+    return rows, ld, heads, rows.shape[1] // heads
+
+
+def sim_hist(T, V, heads=1, eps=1e-14, out=None):
+    """The 'hist' measure (generalised Jaccard; loss.hist_sim / jaccard_sim of the reference) of every text row against every video
+    row: S[t, v] = mean over heads of sum_k min(T, V) / (sum_k max(T, V) + eps), fp32.  T (Nt, H d) / V (Nv, H d) with `heads`, or
+    (Nt, H, d) / (Nv, H, d); row views with a pitch are taken as they are.  `out`: an (Nt, Nv) fp32 tensor with contiguous rows
+    (default: alloc_scores).  eps = 0 gives NaN for a pair of all-zero rows."""
+    t, ldt, Ht, dt = _hist_rows(T, 'T', heads)
+    v, ldv, Hv, dv = _hist_rows(V, 'V', heads)
+    if T.dim() != V.dim() or (Ht, dt) != (Hv, dv):
+        raise ValueError('T %s and V %s differ in heads or width' % (tuple(T.shape), tuple(V.shape)))
+    if t.device != v.device:
+        raise ValueError('T and V are on different devices')
+    Nt, Nv = t.shape[0], v.shape[0]
+    S, lds = _rows(_dev(out, 'out') if out is not None else alloc_scores(Nt, Nv, t.device), 'out')
+    if tuple(S.shape) != (Nt, Nv):
+        raise ValueError('out must be (%d, %d), got %s' % (Nt, Nv, tuple(S.shape)))
+    lib, h = _context(t.device)
+    _call('sim_hist', lib.laff_sim_hist, h, _ptr(t), ldt, _ptr(v), ldv, Nt, Nv, Ht, dt, float(eps), _ptr(S), lds)
     return S
 
 
