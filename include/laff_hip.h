@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 33
+#define LAFF_ABI_VERSION 34
 
 enum {
     LAFF_OK = 0,
@@ -232,6 +232,23 @@ enum { LAFF_LOSS_MAX_VIOLATION = 1, LAFF_LOSS_COST_MEAN = 2, LAFF_LOSS_DIR_I2T =
 int laff_margin_loss_workspace_bytes(int B, int H, int d, size_t* out);
 int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int H, int d, float margin, unsigned flags,
                      float* loss, float* d_s, float* d_im, void* workspace, size_t workspace_bytes);
+
+/* DualSoftmaxLoss (loss.py:291-310) per head, summed over heads: the criterion of opt.loss == 'dsl' (model/model.py:1992-1993).
+ * s, im as above.  M_h = l2norm(s_h) . l2norm(im_h)^T (rows = captions); with A = softmax of M / temp down each column,
+ * cal(M) = -sum_i log softmax_row(B * M (.) A)[i][i] and loss_h = (cal(M_h) + cal(M_h^T)) / 2, every softmax taken about its
+ * maximum (any temp > 0).  Writes loss[0] and, when non-NULL, d_s / d_im [B, H, d]; with both NULL the call is forward-only and
+ * no gradient is formed.  B as laff_margin_loss accepts it, and B == 0 (nothing is touched).  workspace: caller-owned device
+ * scratch of laff_dsl_loss_workspace_bytes(B, H, d), 16-byte aligned. */
+int laff_dsl_loss_workspace_bytes(int B, int H, int d, size_t* out);
+int laff_dsl_loss(laff_ctx* ctx, const float* s, const float* im, int B, int H, int d, float temp, float* loss, float* d_s,
+                  float* d_im, void* workspace, size_t workspace_bytes);
+
+/* MarginRankingLossWithScore (loss.py:138-200): the margin ranking loss on a score matrix the caller formed, score [B, ld >= B]
+ * fp32 with any row pitch.  cost_s compares along the rows against score[i][i] ('i2t'), cost_im along the columns against
+ * score[j][j] ('t2i'), the diagonal cleared; flags are LAFF_LOSS_*.  Writes loss[0] and, when non-NULL, d_score with the pitch of
+ * score ([B, ld]; the columns past B are scratch).  B as laff_margin_loss accepts it, and B == 0 (nothing is touched). */
+int laff_margin_loss_scores(laff_ctx* ctx, const float* score, int ld, int B, float margin, unsigned flags, float* loss,
+                            float* d_score);
 
 /* ---- text tower: the GRU caption encoder (model/model.py:323-396 GruTxtEncoder / BiGruTxtEncoder), inference, one layer ----------
  * torch.nn.GRU arithmetic (gate order r, z, n; h0 = 0) over captions given as token ids, then pooling over each caption's steps:

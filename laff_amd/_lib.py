@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 
 class Plane(C.Structure):
@@ -127,6 +127,9 @@ SIGNATURES = {
     'laff_fc_concat_act_bn_grouped': (C.c_int, [_P, C.POINTER(FcConcatProblem), _I]),
     'laff_margin_loss_workspace_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_margin_loss': (C.c_int, [_P, _P, _P, _I, _I, _I, C.c_float, C.c_uint, _P, _P, _P, _P, C.c_size_t]),
+    'laff_dsl_loss_workspace_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_dsl_loss': (C.c_int, [_P, _P, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, C.c_size_t]),
+    'laff_margin_loss_scores': (C.c_int, [_P, _P, _I, _I, C.c_float, C.c_uint, _P, _P]),
     'laff_row_scales_grouped': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),
                                           C.POINTER(C.c_void_p)]),
     'laff_fc_act_bn_fused_grouped': (C.c_int, [_P, C.POINTER(FcFusedProblem), _I]),

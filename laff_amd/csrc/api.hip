@@ -409,6 +409,12 @@ LossLayout loss_layout(int B, int H, int d) {
     L.total = o;
     return L;
 }
+// the upper end of the B range of the loss entry points (they share the reduction's shape; each checks its own lower end)
+int loss_check_batch(const char* fn, int B) {
+    if (B > 16384) return fail(LAFF_E_SHAPE, "%s: bad shape B=%d", fn, B);
+    if ((size_t)(2 * B + 16) * sizeof(float) > 64 * 1024) return fail(LAFF_E_UNSUPPORTED, "%s: B=%d exceeds the reduction kernel's LDS budget", fn, B);
+    return LAFF_OK;
+}
 }  // namespace
 
 int laff_margin_loss_workspace_bytes(int B, int H, int d, size_t* out) {
@@ -421,12 +427,15 @@ int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int 
                      float* loss, float* d_s, float* d_im, void* workspace, size_t workspace_bytes) {
     CHECK_CTX(ctx);
     if (!s || !im || !loss || !workspace) return fail(LAFF_E_ARG, "laff_margin_loss: null argument");
-    if (B < 1 || H < 1 || d < 1 || B > 16384) return fail(LAFF_E_SHAPE, "laff_margin_loss: bad shape B=%d H=%d d=%d", B, H, d);
+    if (B < 1 || H < 1 || d < 1) return fail(LAFF_E_SHAPE, "laff_margin_loss: bad shape B=%d H=%d d=%d", B, H, d);
+    // the upper limit of B is a shape error and keeps its place in front of the flags / workspace checks (the order of the error
+    // codes is part of the ABI); the LDS budget, an 'unsupported', stays behind them, below
+    if (B > 16384) return loss_check_batch("laff_margin_loss", B);
     if (flags & ~15u) return fail(LAFF_E_ARG, "laff_margin_loss: unknown flags 0x%x", flags);
     const LossLayout L = loss_layout(B, H, d);
     if (workspace_bytes < L.total * sizeof(float)) return fail(LAFF_E_ARG, "laff_margin_loss: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total * sizeof(float));
     if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_margin_loss: workspace must be 16-byte aligned");
-    if ((size_t)(2 * B + 16) * sizeof(float) > 64 * 1024) return fail(LAFF_E_UNSUPPORTED, "laff_margin_loss: B=%d exceeds the reduction kernel's LDS budget", B);
+    if (int rc = loss_check_batch("laff_margin_loss", B)) return rc;
     DeviceGuard g(ctx->device);
     float* ws = (float*)workspace;
     const int dp = L.dp, Bp = L.Bp;
@@ -456,6 +465,89 @@ int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int 
     }
     if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), (int)probs.size())) return rc;
     HIP_TRY(laff::launch_loss_normalize_bwd(ws + L.XH, ws + L.G, ws + L.nrm, ws + L.npr, B, H, d, dp, d_s, d_im, ctx->stream));
+    return LAFF_OK;
+}
+
+namespace {
+struct DslLayout {
+    LossLayout L;
+    size_t ST, stat, total;   // offsets in floats, behind the margin loss's layout
+};
+DslLayout dsl_layout(int B, int H, int d) {
+    DslLayout D{};
+    D.L = loss_layout(B, H, d);
+    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    size_t o = D.L.total;
+    D.ST = o;   o += up4((size_t)H * B * D.L.Bp);
+    D.stat = o; o += up4((size_t)H * laff::DSL_STAT_ROWS * B);
+    D.total = o;
+    return D;
+}
+}  // namespace
+
+int laff_dsl_loss_workspace_bytes(int B, int H, int d, size_t* out) {
+    if (!out || B < 0 || H < 1 || d < 1) return fail(LAFF_E_ARG, "laff_dsl_loss_workspace_bytes: bad args");
+    *out = B ? dsl_layout(B, H, d).total * sizeof(float) : 0;
+    return LAFF_OK;
+}
+
+int laff_dsl_loss(laff_ctx* ctx, const float* s, const float* im, int B, int H, int d, float temp, float* loss, float* d_s,
+                  float* d_im, void* workspace, size_t workspace_bytes) {
+    CHECK_CTX(ctx);
+    if (B < 0 || H < 1 || d < 1) return fail(LAFF_E_SHAPE, "laff_dsl_loss: bad shape B=%d H=%d d=%d", B, H, d);
+    if (int rc = loss_check_batch("laff_dsl_loss", B)) return rc;
+    if (!(temp > 0.0f) || !std::isfinite(temp)) return fail(LAFF_E_ARG, "laff_dsl_loss: temp must be positive and finite, got %g", (double)temp);
+    if (B == 0) return LAFF_OK;
+    if (!s || !im || !loss) return fail(LAFF_E_ARG, "laff_dsl_loss: null argument");
+    const DslLayout D = dsl_layout(B, H, d);
+    const LossLayout& L = D.L;
+    if (!workspace || workspace_bytes < D.total * sizeof(float)) return fail(LAFF_E_ARG, "laff_dsl_loss: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, D.total * sizeof(float));
+    if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_dsl_loss: workspace must be 16-byte aligned");
+    DeviceGuard g(ctx->device);
+    float* ws = (float*)workspace;
+    const int dp = L.dp, Bp = L.Bp;
+    const bool grad = d_s || d_im;
+    HIP_TRY(laff::launch_loss_normalize(s, im, B, H, d, dp, Bp, 1e-13f, ws + L.XH, ws + L.XHT, ws + L.nrm, ws + L.npr, ctx->stream));
+    auto XH = [&](int z, int h) { return ws + L.XH + ((size_t)z * H + h) * B * dp; };
+    auto XHT = [&](int z, int h) { return ws + L.XHT + ((size_t)z * H + h) * d * Bp; };
+    auto G = [&](int z, int h) { return ws + L.G + ((size_t)z * H + h) * B * dp; };
+    std::vector<laff_fc_problem> probs((size_t)H);
+    for (int h = 0; h < H; ++h)      // M_h [B captions, B videos] = S^_h . I^_h^T  (cosine_sim(s, im), loss.py:296)
+        probs[h] = laff_fc_problem{XH(0, h), B, d, dp, XH(1, h), dp, nullptr, nullptr, nullptr, B, LAFF_ACT_NONE,
+                                   ws + L.S + (size_t)h * B * Bp, Bp};
+    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), H)) return rc;
+    HIP_TRY(laff::launch_dsl_reduce(ws + L.S, ws + D.ST, ws + D.stat, grad ? ws + L.dS : nullptr, grad ? ws + L.dST : nullptr,
+                                    ws + L.loss_h, loss, B, Bp, H, temp, ctx->stream));
+    if (!grad) return LAFF_OK;
+    probs.clear();
+    for (int h = 0; h < H; ++h) {
+        // dL/dS^_h = dM_h . I^_h   (column operand = I^_h^T, K = videos);  dL/dI^_h = dM_h^T . S^_h
+        probs.push_back(laff_fc_problem{ws + L.dS + (size_t)h * B * Bp, B, B, Bp, XHT(1, h), Bp, nullptr, nullptr, nullptr, d,
+                                        LAFF_ACT_NONE, G(0, h), dp});
+        probs.push_back(laff_fc_problem{ws + L.dST + (size_t)h * B * Bp, B, B, Bp, XHT(0, h), Bp, nullptr, nullptr, nullptr, d,
+                                        LAFF_ACT_NONE, G(1, h), dp});
+    }
+    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), (int)probs.size())) return rc;
+    HIP_TRY(laff::launch_loss_normalize_bwd(ws + L.XH, ws + L.G, ws + L.nrm, ws + L.npr, B, H, d, dp, d_s, d_im, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_margin_loss_scores(laff_ctx* ctx, const float* score, int ld, int B, float margin, unsigned flags, float* loss,
+                            float* d_score) {
+    CHECK_CTX(ctx);
+    if (B < 0 || (B > 0 && ld < B)) return fail(LAFF_E_SHAPE, "laff_margin_loss_scores: bad shape B=%d ld=%d", B, ld);
+    if (int rc = loss_check_batch("laff_margin_loss_scores", B)) return rc;
+    if (flags & ~15u) return fail(LAFF_E_ARG, "laff_margin_loss_scores: unknown flags 0x%x", flags);
+    if (B == 0) return LAFF_OK;
+    if (!score || !loss) return fail(LAFF_E_ARG, "laff_margin_loss_scores: null argument");
+    DeviceGuard g(ctx->device);
+    const int use_s = (flags & LAFF_LOSS_DIR_I2T) ? 1 : 0, use_im = (flags & LAFF_LOSS_DIR_T2I) ? 1 : 0;
+    const int maxv = (flags & LAFF_LOSS_MAX_VIOLATION) ? 1 : 0;
+    const float gmean = maxv ? 1.0f / (float)B : 1.0f / ((float)B * (float)B);
+    const float gw = (flags & LAFF_LOSS_COST_MEAN) ? gmean : 1.0f;
+    // margin_reduce_kernel as it is, one head: the score matrix in place of the GEMM's, its pitch as Bp, no transposed gradient, and
+    // loss[0] as the per-head slot that the head sum then copies onto itself
+    HIP_TRY(laff::launch_margin_reduce(score, d_score, nullptr, loss, loss, B, ld, 1, margin, maxv, use_s, use_im, gw, gw, ctx->stream));
     return LAFF_OK;
 }
 

@@ -248,6 +248,12 @@ hipError_t launch_margin_reduce(const float* S, float* dS, float* dST, float* lo
                                 float margin, int max_violation, int use_s, int use_im, float g_s, float g_im, hipStream_t st);
 hipError_t launch_loss_normalize_bwd(const float* XH, const float* G, const float* nrm, const float* npr, int B, int H, int d,
                                      int dp, float* d_s, float* d_im, hipStream_t st);
+hipError_t launch_loss_sum_heads(const float* loss_h, int H, float* loss, hipStream_t st);
+// loss_dsl.hip: the dual-softmax criterion on S [H][B][Bp] (rows = captions); ST [H][B][Bp] and stat [H][DSL_STAT_ROWS][B] are scratch,
+// dS / dST [H][B][Bp] are written (padding columns zeroed) unless both are null
+constexpr int DSL_STAT_ROWS = 10;
+hipError_t launch_dsl_reduce(const float* S, float* ST, float* stat, float* dS, float* dST, float* loss_h, float* loss, int B, int Bp,
+                             int H, float temp, hipStream_t st);
 hipError_t launch_fc_gather(const int* indptr, const int* indices, const float* values, int N, int Dk, const float* Wt, int ldwt,
                             const float* bias, const float* bn_scale, const float* bn_shift, int D, int act, float* Y, int ldy,
                             hipStream_t st);

@@ -45,8 +45,8 @@ __global__ __launch_bounds__(64) void loss_normalize_kernel(const float* __restr
 
 struct MarginArgs {
     const float* S;       // [H][B][Bp] scores (rows = videos, columns = captions)
-    float* dS;            // [H][B][Bp] dLoss/dScores
-    float* dST;           // [H][B][Bp] its transpose
+    float* dS;            // [H][B][Bp] dLoss/dScores; null = forward only (laff_margin_loss_scores without d_score)
+    float* dST;           // [H][B][Bp] its transpose; null = not wanted
     float* loss_h;        // [H]
     int B, Bp, H;
     float margin;
@@ -59,8 +59,9 @@ __global__ __launch_bounds__(1024) void margin_reduce_kernel(MarginArgs a) {
     extern __shared__ float sh[];
     const int B = a.B, Bp = a.Bp, h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* S = a.S + (long)h * B * Bp;
-    float* dS = a.dS + (long)h * B * Bp;
-    float* dST = a.dST + (long)h * B * Bp;
+    float* dS = a.dS ? a.dS + (long)h * B * Bp : nullptr;
+    float* dST = a.dST ? a.dST + (long)h * B * Bp : nullptr;
+    const bool grad = dS != nullptr;
     float* diag = sh;                 // [B]
     float* dacc = sh + B;             // [B]  gradient collected on the diagonal
     float* red = sh + 2 * B;          // [16]
@@ -85,11 +86,12 @@ __global__ __launch_bounds__(1024) void margin_reduce_kernel(MarginArgs a) {
                     if (c > 0.0f) { loss += a.g_im * c; g += a.g_im; atomicAdd(&dacc[j], -a.g_im); }
                 }
             }
-            dS[(long)i * Bp + j] = g;
+            if (grad) dS[(long)i * Bp + j] = g;
         }
         __syncthreads();
     } else {
-        for (long e = tid; e < (long)B * Bp; e += 1024) dS[e] = 0.0f;
+        if (grad)
+            for (long e = tid; e < (long)B * Bp; e += 1024) dS[e] = 0.0f;
         __syncthreads();
         if (a.use_s) {                               // hardest caption of every video: wave per row
             for (int i = wave; i < B; i += 16) {
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(1024) void margin_reduce_kernel(MarginArgs a) {
                 }
                 if (lane == 0 && bj >= 0) {
                     loss += a.g_s * best;
-                    atomicAdd(&dS[(long)i * Bp + bj], a.g_s);
+                    if (grad) atomicAdd(&dS[(long)i * Bp + bj], a.g_s);
                     atomicAdd(&dacc[i], -a.g_s);
                 }
             }
@@ -122,14 +124,15 @@ __global__ __launch_bounds__(1024) void margin_reduce_kernel(MarginArgs a) {
                 }
                 if (bi >= 0) {
                     loss += a.g_im * best;
-                    atomicAdd(&dS[(long)bi * Bp + j], a.g_im);
+                    if (grad) atomicAdd(&dS[(long)bi * Bp + j], a.g_im);
                     atomicAdd(&dacc[j], -a.g_im);
                 }
             }
         }
         __syncthreads();
     }
-    for (int i = tid; i < B; i += 1024) dS[(long)i * Bp + i] = dacc[i];
+    if (grad)
+        for (int i = tid; i < B; i += 1024) dS[(long)i * Bp + i] = dacc[i];
     // block sum of the loss
     loss = wave_sum(loss);
     if (lane == 0) red[wave] = loss;
@@ -140,6 +143,7 @@ __global__ __launch_bounds__(1024) void margin_reduce_kernel(MarginArgs a) {
         a.loss_h[h] = t;
     }
     __syncthreads();
+    if (!grad || !dST) return;
     for (long e = tid; e < (long)B * B; e += 1024) {
         const int i = (int)(e / B), j = (int)(e % B);
         dST[(long)j * Bp + i] = dS[(long)i * Bp + j];
@@ -181,6 +185,12 @@ hipError_t launch_margin_reduce(const float* S, float* dS, float* dST, float* lo
                                 float margin, int max_violation, int use_s, int use_im, float g_s, float g_im, hipStream_t st) {
     MarginArgs a{S, dS, dST, loss_h, B, Bp, H, margin, max_violation, use_s, use_im, g_s, g_im};
     hipLaunchKernelGGL(margin_reduce_kernel, dim3(H), dim3(1024), (2 * B + 16) * sizeof(float), st, a);
+    if (loss_h != loss)      // one head written straight to loss[0] (laff_margin_loss_scores) needs no sum
+        hipLaunchKernelGGL(loss_sum_heads_kernel, dim3(1), dim3(1), 0, st, loss_h, H, loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_sum_heads(const float* loss_h, int H, float* loss, hipStream_t st) {
     hipLaunchKernelGGL(loss_sum_heads_kernel, dim3(1), dim3(1), 0, st, loss_h, H, loss);
     return hipGetLastError();
 }

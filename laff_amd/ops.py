@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -312,6 +312,52 @@ def margin_loss(s, im, margin, max_violation=True, cost_style='sum', direction='
     _call('margin_loss', lib.laff_margin_loss, h, _ptr(s_c), _ptr(im_c), B, H, d, float(margin), flags, _ptr(loss), _ptr(d_s),
           _ptr(d_im), _ptr(ws), nbytes.value)
     return loss, d_s, d_im
+
+
+def dsl_loss(s, im, temp=1000, want_grad=True):
+    """DualSoftmaxLoss over heads (laff_dsl_loss).  s, im: (B, d) or (B, H, d) fp32 CUDA tensors.
+    Returns (loss 0-d tensor, d_s, d_im) -- the gradients are None, and no gradient buffer is allocated, when want_grad is False."""
+    if s.shape != im.shape or s.dim() not in (2, 3):
+        raise ValueError('s and im must both be (B, d) or (B, H, d); got %s and %s' % (tuple(s.shape), tuple(im.shape)))
+    if not temp > 0:
+        raise ValueError('temp must be positive, got %r' % (temp,))
+    s_c = _dev(s.contiguous(), 's')
+    im_c = _dev(im.contiguous(), 'im')
+    if im_c.device != s_c.device:
+        raise ValueError('s and im must be on one device, got %s and %s' % (s_c.device, im_c.device))
+    B, H, d = (s.shape[0], 1, s.shape[1]) if s.dim() == 2 else s.shape
+    lib, h = _context(s_c.device)
+    nbytes = _size_query('laff_dsl_loss_workspace_bytes', B, H, d)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s_c.device)
+    loss = (torch.empty if B else torch.zeros)((), dtype=torch.float32, device=s_c.device)     # an empty batch sums to 0
+    d_s = torch.empty_like(s_c) if want_grad else None
+    d_im = torch.empty_like(im_c) if want_grad else None
+    _call('dsl_loss', lib.laff_dsl_loss, h, _ptr(s_c), _ptr(im_c), B, H, d, float(temp), _ptr(loss), _ptr(d_s), _ptr(d_im), _ptr(ws),
+          nbytes)
+    return loss, d_s, d_im
+
+
+def margin_loss_scores(score, margin, max_violation=True, cost_style='sum', direction='t2i', want_grad=True):
+    """MarginRankingLossWithScore (laff_margin_loss_scores) on score (B, B), an fp32 CUDA matrix with any row stride.
+    Returns (loss 0-d tensor, d_score (B, B)) -- d_score is None when want_grad is False."""
+    if score.dim() != 2 or score.shape[0] != score.shape[1]:
+        raise ValueError('score must be (B, B); got %s' % (tuple(score.shape),))
+    if direction not in ('i2t', 't2i', 'bidir'):
+        raise ValueError("direction must be 'i2t', 't2i' or 'bidir'")
+    if cost_style not in ('sum', 'mean'):
+        raise ValueError("cost_style must be 'sum' or 'mean'")
+    _dev(score, 'score')
+    if score.numel() and score.stride(1) != 1:
+        score = score.contiguous()
+    score, ld = _rows(score, 'score')
+    B = score.shape[0]
+    flags = (LOSS_FLAGS['max_violation'] if max_violation else 0) | (LOSS_FLAGS['mean'] if cost_style == 'mean' else 0)
+    flags |= {'i2t': LOSS_FLAGS['i2t'], 't2i': LOSS_FLAGS['t2i'], 'bidir': LOSS_FLAGS['i2t'] | LOSS_FLAGS['t2i']}[direction]
+    lib, h = _context(score.device)
+    loss = (torch.empty if B else torch.zeros)((), dtype=torch.float32, device=score.device)
+    d_score = torch.empty((B, ld), dtype=torch.float32, device=score.device) if want_grad else None     # the pitch of score
+    _call('margin_loss_scores', lib.laff_margin_loss_scores, h, _ptr(score), ld, B, float(margin), flags, _ptr(loss), _ptr(d_score))
+    return loss, (d_score[:, :B] if want_grad else None)
 
 
 def gru_pack_whh(w_hh):
