@@ -1,6 +1,6 @@
-"""Dual-softmax and score-matrix margin criteria, the part that needs no GPU: the C ABI's declarations, exports, bindings and argument
-checks, the float64 restatement (tests/loss_ref.py) against the golden vectors and against central differences, and the routing of
-loss.criterion_for."""
+"""Dual-softmax and margin criteria, the part that needs no GPU: the C ABI's declarations, exports, bindings and argument checks, the
+float64 restatement (tests/loss_ref.py) against the golden vectors, central differences and float64 autograd, the inputs and the
+derived gradient bound of the embedding margin test (tests/test_gpu_losses.py), and the routing of loss.criterion_for."""
 import ctypes as C
 import os
 import re
@@ -145,6 +145,131 @@ def test_margin_scores_analytic_gradient_matches_central_differences(B, maxv, st
             b[i, j] -= eps
             num = (loss_ref.margin_scores(a, 0.2, maxv, style, direction)[0] - loss_ref.margin_scores(b, 0.2, maxv, style, direction)[0]) / (2 * eps)
             assert abs(num - d[i, j]) <= 2e-3 * max(1.0, abs(num)), (i, j, num, d[i, j])
+
+
+# ------------------------------------------------------------------------------------------------ margin loss from embeddings
+from test_gpu_losses import FLAGS, MARGIN, MARGIN_SHAPES, MIN_ACTIVE, _margin_inputs, margin_active_share, margin_scores64  # noqa: E402
+
+
+def _autograd64(s, im, margin, maxv, style, direction):
+    """The reference's formula per head on torch float64 autograd: l2norm, mm, hinge, optional max, sum or mean."""
+    import torch
+    s = torch.tensor(np.asarray(s, np.float64).reshape(len(s), -1, s.shape[-1]), requires_grad=True)
+    im = torch.tensor(np.asarray(im, np.float64).reshape(len(im), -1, im.shape[-1]), requires_grad=True)
+
+    def l2norm(x):
+        return x / (x.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-13 + 1e-14)
+
+    total = 0
+    for h in range(s.shape[1]):
+        scores = l2norm(im[:, h]).mm(l2norm(s[:, h]).t())
+        dg = scores.diag().view(-1, 1)
+        eye = torch.eye(len(scores), dtype=torch.bool)
+        for name, ref, dim in (('i2t', dg.expand_as(scores), 1), ('t2i', dg.t().expand_as(scores), 0)):
+            if direction in (name, 'bidir'):
+                cost = (margin + scores - ref).clamp(min=0).masked_fill(eye, 0)
+                if maxv:
+                    cost = cost.max(dim)[0]
+                total = total + (cost.sum() if style == 'sum' else cost.mean())
+    total.backward()
+    return float(total.item()), s.grad.numpy(), im.grad.numpy()
+
+
+@pytest.mark.parametrize('maxv,style,direction', FLAGS)
+@pytest.mark.parametrize('shape', [(2, 5), (7, 3, 6), (19, 2, 12)])
+def test_margin_restatement_matches_float64_autograd(shape, maxv, style, direction):
+    g = np.random.default_rng(sum(shape))
+    s, im = g.normal(0, 1, shape), g.normal(0, 1, shape)
+    loss, d_s, d_im, b_s, b_im = loss_ref.margin(s, im, 0.2, maxv, style, direction)
+    rl, rs, ri = _autograd64(s, im, 0.2, maxv, style, direction)
+    assert d_s.shape == shape and d_im.shape == shape and b_s.shape == shape and b_im.shape == shape
+    assert abs(loss - rl) <= 1e-12 * max(1.0, abs(rl))
+    assert np.abs(d_s - rs.reshape(shape)).max() <= 1e-12 and np.abs(d_im - ri.reshape(shape)).max() <= 1e-12
+    assert (b_s >= 0).all() and (b_im >= 0).all() and ((b_s > 0) | (d_s == 0)).all() and ((b_im > 0) | (d_im == 0)).all()
+
+
+@pytest.mark.parametrize('B,H,d', MARGIN_SHAPES)
+def test_margin_inputs_converge_with_every_decision_clear_and_many_hinges_active(B, H, d):
+    s, im = _margin_inputs(B, H, d)
+    assert s.shape == im.shape == (B, H, d) and s.dtype == im.dtype == np.float32
+    assert not s.flags.writeable and not im.flags.writeable and _margin_inputs(B, H, d)[0] is s
+    for h in range(H):
+        S = margin_scores64(s, im, h)
+        for maxv in (False, True):
+            for direction in ('i2t', 't2i', 'bidir'):
+                assert loss_ref.margin_scores_slack(S, MARGIN, maxv, direction) >= 1e-4, (h, maxv, direction)
+        if B >= 17:
+            assert margin_active_share(S) >= MIN_ACTIVE, (h, margin_active_share(S))
+
+
+def _fp32_chain(s, im, margin, maxv, style, direction, fault=None):
+    """(d_s, d_im) of laff_margin_loss's chain in fp32 numpy with every sum strictly sequential (one rounded product and one rounded
+    addition per term, in index order): the worst order a kernel could take.  The decisions come from the float64 restatement, as the
+    inputs guarantee.  fault = 'pair' drops one active off-diagonal pair from dS of the last head, 'row' zeroes its last row."""
+    f = np.float32
+    B, H, d = s.shape
+    d_s, d_im = np.zeros((B, H, d), f), np.zeros((B, H, d), f)
+
+    def seq_sum(terms):                       # over axis -1, in order
+        acc = np.zeros(terms.shape[:-1], f)
+        for k in range(terms.shape[-1]):
+            acc = acc + terms[..., k]
+        return acc
+
+    def matmul(a, b):                         # a (n, K) . b (K, m), K in order
+        acc = np.zeros((a.shape[0], b.shape[1]), f)
+        for k in range(a.shape[1]):
+            acc = acc + a[:, k, None] * b[None, k, :]
+        return acc
+
+    def normalize(x):
+        r = np.sqrt(seq_sum(x * x))
+        n = r + f(1e-13) + f(1e-14)
+        return x / n[:, None], r, n
+
+    def bwd(xh, r, n, G):
+        return G / n[:, None] - xh * (seq_sum(xh * G) / r)[:, None]
+
+    w = f(1.0)
+    if style == 'mean':
+        w = f(1.0) / f(B) if maxv else f(1.0) / (f(B) * f(B))
+    for h in range(H):
+        sh, rs, ns = normalize(s[:, h])
+        ih, ri, ni = normalize(im[:, h])
+        _, d64 = loss_ref.margin_scores(margin_scores64(s, im, h), margin, maxv, 'sum', direction)     # integer pair counts
+        count = np.rint(d64).astype(int)
+        dS = np.zeros((B, B), f)
+        for t in range(1, int(np.abs(count).max()) + 1):          # one rounded addition of +-w per counted term
+            dS = np.where(np.abs(count) >= t, dS + np.sign(count).astype(f) * w, dS)
+        if h == H - 1 and fault == 'pair':
+            i, j = np.argwhere((count > 0) & ~np.eye(B, dtype=bool))[-1]
+            dS[i, j] = 0
+        if h == H - 1 and fault == 'row':
+            dS[-1] = 0
+        d_im[:, h] = bwd(ih, ri, ni, matmul(dS, sh))
+        d_s[:, h] = bwd(sh, rs, ns, matmul(dS.T.copy(), ih))
+    return d_s, d_im
+
+
+@pytest.mark.parametrize('maxv,style,direction', FLAGS)
+@pytest.mark.parametrize('B,H,d', [(65, 1, 30), (130, 2, 30)])
+def test_margin_gradient_bound_holds_for_sequential_fp32_and_catches_planted_faults(B, H, d, maxv, style, direction):
+    s, im = _margin_inputs(B, H, d)
+    _, ds64, di64, b_s, b_im = loss_ref.margin(s, im, MARGIN, maxv, style, direction)
+    d_s, d_im = _fp32_chain(s, im, MARGIN, maxv, style, direction)
+    assert d_s.dtype == np.float32
+    e_s, e_i = np.abs(d_s - ds64), np.abs(d_im - di64)
+    assert (e_s <= b_s).all() and (e_i <= b_im).all()
+    pos_s, pos_i = b_s > 0, b_im > 0
+    worst = max((e_s[pos_s] / b_s[pos_s]).max(), (e_i[pos_i] / b_im[pos_i]).max())
+    assert worst <= 0.5, worst                # the worst order stays well inside: the kernel's tree sums have room
+    # the bound is small against the gradient ...
+    assert max(b_s.max(), b_im.max()) <= 1e-3 * max(np.abs(ds64).max(), np.abs(di64).max())
+    # ... so a single dropped pair, or a dropped row, of one head's dS is far outside it
+    for fault in ('pair', 'row'):
+        f_s, f_i = _fp32_chain(s, im, MARGIN, maxv, style, direction, fault)
+        over = max((np.abs(f_s - ds64)[pos_s] / b_s[pos_s]).max(), (np.abs(f_i - di64)[pos_i] / b_im[pos_i]).max())
+        assert over >= 100.0, (fault, over)
 
 
 # ------------------------------------------------------------------------------------------------ Python surface
