@@ -9,10 +9,9 @@ DEFAULT_PRECISION = 'fp16'
 
 def l2norm(X, eps=1e-13, dim=1):
     """X / (sqrt(sum X^2 along dim) + eps + 1e-14); dim must be the last axis of a 2-D/3-D tensor."""
-    if X.dim() == 2 and dim in (1, -1):
-        return ops.pack_rows(X.contiguous(), True, eps, 'fp32', 1.0).buf.view(torch.float32).view(X.shape)
-    if X.dim() == 3 and dim in (2, -1):
-        return ops.pack_rows(X.contiguous(), True, eps, 'fp32', 1.0).buf.view(torch.float32).view(X.shape)
+    if (X.dim() == 2 and dim in (1, -1)) or (X.dim() == 3 and dim in (2, -1)):
+        # pack_rows never allocates less than 16 bytes: a result of fewer than four floats is the front of its buffer
+        return ops.pack_rows(X.contiguous(), True, eps, 'fp32', 1.0).buf[:4 * X.numel()].view(torch.float32).view(X.shape)
     raise NotImplementedError('l2norm along dim=%d of a %d-D tensor is outside the hot path' % (dim, X.dim()))
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import rerank_cases as RC
 import rerank_ref as R
 from laff_amd import synth
 from laff_amd.model import ReRank
@@ -126,6 +127,167 @@ def test_largest_supported_problem_runs_in_bounds():
     D = R.distances(qg.cpu().numpy(), qq.cpu().numpy(), gg.cpu().numpy())[0, 1:]
     o = out.cpu().numpy()[0].astype(np.float64)
     assert (o >= 0.3 * D - 1e-6).all() and (o <= 0.7 + 0.3 * D + 1e-6).all() and (o < 0.7 + 0.3 * D - 1e-3).any()
+
+
+# ---- every stage against float64, up to the limits ---------------------------------------------------------------------------------
+# The device runs each case once with a workspace the test owns (filled with a sentinel first); what the four kernels left in it
+# is compared in the order they ran, so a failure names the first stage that went wrong: rank / colmax (exact), cnt1 / idx1 (the
+# expansion sets, and nothing written past them), val1, cnt2 / idx2 (the non-zero pattern after query expansion), val2, the output.
+# The bound of val1, val2 and the output is the project's rule with e32 = |fp32 - fp64| of the fp32 rendering of the same stage
+# on the same inputs (rerank_cases.case); the lists and sets have no tolerance.
+SENT = 0xA5
+SENT_I = int(np.frombuffer(bytes([SENT] * 4), dtype=np.int32)[0])
+
+
+def run_on_device(cases, lambda_value=0.3):
+    """the cases as ONE ops.rerank_run call; per case what the workspace holds afterwards, and the output, as numpy"""
+    from laff_amd import ops
+    k1, k2 = cases[0]['k1'], cases[0]['k2']
+    assert all(c['k1'] == k1 and c['k2'] == k2 for c in cases)
+    sizes = [(c['Q'], c['G']) for c in cases]
+    probs = [tuple(torch.from_numpy(a).to(DEV) for a in c['blocks']) for c in cases]
+    ws = torch.full((ops.rerank_workspace_bytes(sizes, k1, k2),), SENT, dtype=torch.uint8, device=DEV)
+    outs = ops.rerank_run(probs, k1, k2, lambda_value, workspace=ws)
+    views = R.workspace_views(ws, sizes, k1, k2)
+    return [dict({k: t.cpu().numpy() for k, t in v.items()}, out=o.cpu().numpy()) for v, o in zip(views, outs)]
+
+
+def first_bad_row(ok):
+    bad = np.flatnonzero(~np.asarray(ok).reshape(len(ok), -1).all(axis=1))
+    return 'first wrong row %d of %d wrong' % (bad[0], len(bad)) if len(bad) else 'none'
+
+
+def report(label, stage, got, want, b):
+    err = float(np.abs(got.astype(np.float64) - want).max())
+    print('stages %-16s %-4s err %.3e  bound %.3e  ratio %.2f' % (label, stage, err, b, err / b))
+    return err
+
+
+def check_sparse(label, which, c, dev):
+    """cnt / idx equal to the float64 index lists, strictly increasing, the rest of every row untouched; val to the bound"""
+    want_idx, want_val = c['s64']['idx' + which], c['s64']['val' + which]
+    cnt, idx, val = dev['cnt' + which], dev['idx' + which], dev['val' + which]
+    N, L = idx.shape
+    n = np.array([len(e) for e in want_idx])
+    assert N == c['N'] and n.max() <= L
+    assert np.array_equal(cnt, n), '%s: cnt%s: %s' % (label, which, first_bad_row(cnt == n))
+    used = np.arange(L)[None, :] < n[:, None]
+    want = np.full((N, L), SENT_I, dtype=np.int32)
+    want[used] = np.concatenate(want_idx)
+    assert np.array_equal(idx, want), '%s: idx%s (members, or a write past cnt): %s' % (label, which, first_bad_row(idx == want))
+    assert (np.diff(idx.astype(np.int64), axis=1)[used[:, 1:]] > 0).all(), '%s: idx%s not strictly increasing' % (label, which)
+    clean = val.view(np.int32) == SENT_I
+    assert clean[~used].all(), '%s: val%s written past cnt: %s' % (label, which, first_bad_row(clean | used))
+    want = np.concatenate(want_val)
+    err = report(label, 'val' + which, val[used], want, c['bound']['val' + which])
+    assert err <= c['bound']['val' + which], '%s: val%s' % (label, which)
+
+
+def check_stages(c, dev, label):
+    s = c['s64']
+    assert dev['rank'].shape == s['rank'].shape and dev['out'].shape == s['out'].shape == (c['Q'], c['G'])
+    assert np.array_equal(dev['rank'], s['rank']), '%s: rank: %s' % (label, first_bad_row(dev['rank'] == s['rank']))
+    assert dev['colmax'].dtype == np.float32 and np.array_equal(dev['colmax'].astype(np.float64), s['colmax']), '%s: colmax' % label
+    check_sparse(label, '1', c, dev)
+    if c['k2'] != 1:
+        check_sparse(label, '2', c, dev)
+    err = report(label, 'out', dev['out'], s['out'], c['bound']['out'])
+    print('stages %-16s largest cnt1 %d cnt2 %d  N %d  gap %.2e' % (label, c['cnt1'], c['cnt2'], c['N'], c['gap']))
+    assert np.isfinite(dev['out']).all() and err <= c['bound']['out'], '%s: out' % label
+
+
+@pytest.mark.parametrize('name', list(RC.CASES))
+def test_every_stage_against_float64(name):
+    """n4096 is every limit at once (N = 4096, k1 = 32, k2 = 8), every element of every stage compared."""
+    c = RC.case(name)
+    check_stages(c, run_on_device([c])[0], name)
+
+
+def test_one_launch_group_of_unequal_problems_every_stage():
+    """N = 33, 1030, 65 and 257 in one launch group: grids and LDS slabs sized for the largest, which is not the first."""
+    cs = [RC.case(n) for n in RC.GROUP]
+    assert [c['N'] for c in cs] == [33, 1030, 65, 257]
+    for c, dev in zip(cs, run_on_device(cs)):
+        check_stages(c, dev, 'group/' + c['name'])
+
+
+@pytest.mark.parametrize('lam', [0.0, 1.0])
+def test_the_blend_at_its_ends(lam):
+    """lambda = 1: the result is D; lambda = 0: the Jaccard term alone (what stages() gives at that lambda), both to the bound"""
+    c = RC.case(RC.LAMBDA_CASE, lam)
+    dev = run_on_device([c], lam)[0]
+    check_stages(c, dev, '%s/lambda=%g' % (c['name'], lam))
+    s, Q = c['s64'], c['Q']
+    if lam == 1.0:
+        assert np.abs(dev['out'].astype(np.float64) - s['D'][:, Q:]).max() <= RC.bound(c['e32']['out'], s['D'][:, Q:])
+    else:
+        mid = RC.case(RC.LAMBDA_CASE)['s64']
+        jac = (mid['out'] - 0.3 * mid['D'][:, Q:]) / 0.7
+        assert np.abs(s['out'] - jac).max() <= 1e-12 and s['out'].min() >= 0.0 and (s['out'] < 0.999).any()
+
+
+def tkb_inputs(seed, Q, G):
+    """rows without ties: a permutation of G distinct values each"""
+    g = np.random.default_rng(seed)
+    base = (np.arange(G, dtype=np.float64) / G).astype(np.float32)
+    return g.permuted(np.tile(base, (Q, 1)), axis=1), g.permuted(np.tile(base, (G, 1)), axis=1)
+
+
+def tkb32(q_g, g_g, topK, k1):
+    """the neighbour-count re-ranking with fp32 log, square, sum and division: where its tolerance comes from"""
+    count = R.tkb_counts(g_g, k1)
+    out = np.zeros(q_g.shape, dtype=np.float32)
+    for r in range(q_g.shape[0]):
+        cand = np.argsort(-q_g[r].astype(np.float64), kind='stable')[:topK]
+        out[r, cand] = np.log((count[cand] + 1).astype(np.float32))
+    return out / (np.sqrt((out * out).sum(axis=1, keepdims=True)) + np.float32(1e-13) + np.float32(1e-14))
+
+
+@pytest.mark.parametrize('Q,G,k1,K', [(1, 1, 1, 1), (2, 7, 7, 7), (2, 7, 3, 0), (0, 7, 3, 4), (0, 7, 7, 0), (3, 300, 300, 300),
+                                      (2, 257, 1, 256)])
+def test_neighbour_count_kernels_at_their_argument_edges(Q, G, k1, K):
+    """ops.rerank_tkb at G = 1, k1 = G, K = G, K = 0 and Q = 0: counts exactly equal, log(count + 1) on the candidates, 0 elsewhere"""
+    from laff_amd import ops
+    q_g, g_g = tkb_inputs(100 * G + k1, Q, G)
+    nn = np.argsort(-g_g.astype(np.float64), axis=1, kind='stable')[:, :k1].astype(np.int32)
+    cand = np.argsort(-q_g.astype(np.float64), axis=1, kind='stable')[:, :K].astype(np.int32).reshape(Q, K)
+    out, count = ops.rerank_tkb(torch.from_numpy(nn).to(DEV), torch.from_numpy(cand).to(DEV), G)
+    want_count = R.tkb_counts(g_g, k1)
+    assert count.dtype == torch.int32 and np.array_equal(count.cpu().numpy(), want_count)
+    assert k1 != G or (want_count == G + 1).all()
+    want = np.zeros((Q, G))
+    for r in range(Q):
+        want[r, cand[r]] = np.log(want_count[cand[r]] + 1.0)
+    got = out.cpu().numpy()
+    assert got.shape == (Q, G) and got.dtype == np.float32 and np.array_equal(got == 0, want == 0)
+    assert (want == 0).sum() == Q * (G - K)
+    if Q and K:
+        e32 = np.abs(np.log((want_count + 1).astype(np.float32)).astype(np.float64) - np.log(want_count + 1.0)).max()
+        assert np.abs(got - want).max() <= bound(e32, want)
+
+
+@pytest.mark.parametrize('shape', [(1, 1), (1, 3), (3, 1), (2, 2), (1, 2, 1)])
+def test_l2norm_of_fewer_than_four_floats(shape):
+    """the row normalisation behind re_ranking_tkb_simple at G = 1: its packed buffer is never shorter than 16 bytes"""
+    from laff_amd import loss
+    x = (np.arange(int(np.prod(shape)), dtype=np.float32).reshape(shape) + 1.5) * np.float32(0.75)
+    got = loss.l2norm(torch.from_numpy(x).to(DEV), dim=len(shape) - 1).cpu().numpy()
+    want = x.astype(np.float64) / (np.sqrt((x.astype(np.float64) ** 2).sum(axis=-1, keepdims=True)) + 1e-13 + 1e-14)
+    assert got.shape == shape and np.abs(got - want).max() <= 4 * ulp32(want)
+
+
+@pytest.mark.parametrize('Q,G,k1,topK', [(1, 1, 1, 1), (2, 7, 7, 7), (2, 7, 7, 3000), (3, 9, 1, 1), (2, 130, 130, 129)])
+def test_re_ranking_tkb_simple_at_its_argument_edges(Q, G, k1, topK):
+    q_g, g_g = tkb_inputs(100 * G + k1 + topK, Q, G)
+    got = ReRank.re_ranking_tkb_simple(torch.from_numpy(q_g).to(DEV), torch.ones(Q, Q, device=DEV), torch.from_numpy(g_g).to(DEV),
+                                       topK=topK, k1=k1).cpu().numpy()
+    assert np.array_equal(ReRank.tkb_counts(torch.from_numpy(g_g).to(DEV), k1).cpu().numpy(), R.tkb_counts(g_g, k1))
+    want = R.re_ranking_tkb_simple(q_g, None, g_g, topK=topK, k1=k1)
+    e32 = float(np.abs(tkb32(q_g, g_g, topK, k1) - want).max())
+    err, b = float(np.abs(got - want).max()), bound(e32, want)
+    print('tkb edge (%d, %d, k1 %d, topK %d) err %.3e  bound %.3e  ratio %.2f' % (Q, G, k1, topK, err, b, err / b))
+    assert got.shape == (Q, G) and np.array_equal(got == 0, want == 0) and (want == 0).sum() == Q * (G - min(topK, G))
+    assert err <= b
 
 
 # ---- the predictors ------------------------------------------------------------------------------------------------------------

@@ -157,3 +157,106 @@ def test_rerank_entry_points_in_header_library_and_binding_at_the_header_abi():
     fields = re.search(r'typedef struct laff_rerank_problem \{(.*?)\} laff_rerank_problem;', text, flags=re.S).group(1)
     names = re.findall(r'(\w+);', fields.replace(', ', '; int '))
     assert names == [n for n, _ in _lib.RerankProblem._fields_]
+
+
+# ---- the stage-by-stage restatement, its fp32 rendering, the workspace layout and the generated cases ----------------------------
+def test_stages_and_re_ranking_are_one_computation(golden):
+    z = golden('rerank')
+    for n in CASES:
+        c = case(z, n)
+        s = R.stages(c['q_g'], c['q_q'], c['g_g'], c['k1'], c['k2'], 0.3)
+        assert np.array_equal(s['out'], R.re_ranking(c['q_g'], c['q_q'], c['g_g'], k1=c['k1'], k2=c['k2']))
+        N = c['Q'] + c['G']
+        assert s['rank'].shape == (N, c['k1'] + 1) and s['colmax'].shape == (N,) and len(s['idx1']) == len(s['idx2']) == N
+        for i in range(N):
+            assert (np.diff(s['idx1'][i]) > 0).all() and (np.diff(s['idx2'][i]) > 0).all()
+            assert abs(s['val1'][i].sum() - 1.0) <= 1e-12 and abs(s['val2'][i].sum() - 1.0) <= 1e-12
+            assert (s['idx1'][i] is s['idx2'][i]) == (c['k2'] == 1)
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_fp32_rendering_has_the_reference_s_own_fp32_error(golden, name):
+    """stages(dtype=float32) is the reference's fp32 computation: on the fixture its distance from float64 is the recorded e_ref
+    within a factor 2 either way, and its output is within the project's bound of the reference's fp32 output."""
+    import rerank_cases as RC
+    z = golden('rerank')
+    c = case(z, name)
+    s32 = R.stages(c['q_g'], c['q_q'], c['g_g'], c['k1'], c['k2'], 0.3, dtype=np.float32)
+    assert s32['out'].dtype == np.float32 and s32['val1'][0].dtype == np.float32 and s32['colmax'].dtype == np.float32
+    out64, e_ref = z[name + '/out64'], float(z[name + '/e_ref'])
+    e32 = float(np.abs(s32['out'].astype(np.float64) - out64).max())
+    print('%-12s e_ref %.3e  rendering %.3e' % (name, e_ref, e32))
+    assert e_ref / 2 <= e32 <= 2 * e_ref
+    assert np.abs(s32['out'].astype(np.float64) - z[name + '/out32']).max() <= RC.bound(e_ref, out64)
+
+
+def test_vectorised_expansion_sets_equal_the_loop_form(golden):
+    import rerank_cases as RC
+    z = golden('rerank')
+    todo = [(tuple(case(z, n)[k] for k in ('q_g', 'q_q', 'g_g')), case(z, n)['k1']) for n in CASES]
+    todo += [(RC.blocks_of(n)[0], RC.CASES[n][2]) for n in ('n2', 'n6', 'n33_q2', 'n65', 'g129_q5', 'n257')]
+    todo.append((RC.ring_blocks(402, 32), 32))
+    for blocks, k1 in todo:
+        rank = R.neighbour_lists(R.distances(*blocks), k1)
+        slow, fast = R.expansion_sets(rank, k1), R.expansion_sets_fast(rank, k1)
+        assert len(slow) == len(fast) and all(a == b.tolist() for a, b in zip(slow, fast))
+
+
+def test_workspace_layout_total_is_the_library_s():
+    import torch
+    from laff_amd import ops
+    combos = [([(1, 1)], 1, 1), ([(1, 1)], 1, 2), ([(1, 5)], 5, 3), ([(1, 32)], 32, 8), ([(2, 31)], 32, 8), ([(3, 60)], 20, 6),
+              ([(3, 70)], 6, 1), ([(5, 1025)], 32, 1), ([(2, 4094)], 32, 8), ([(1, 3000)], 20, 6), ([(1, 40)], 7, 2),
+              ([(1, 32), (3, 1027), (1, 64), (5, 252)], 32, 8), ([(3, 70), (2, 50), (1, 9)], 6, 3), ([(1, 600), (4, 590)], 31, 1)]
+    for sizes, k1, k2 in combos:
+        layout, total = R.workspace_layout(sizes, k1, k2)
+        assert total == ops.rerank_workspace_bytes(sizes, k1, k2), (sizes, k1, k2)
+        assert len(layout) == len(sizes) and all(o % 256 == 0 for d in layout for o, _, _ in d.values())
+    sizes, k1, k2 = [(1, 32), (2, 40)], 32, 8
+    _, total = R.workspace_layout(sizes, k1, k2)
+    ws = torch.zeros(total, dtype=torch.uint8)
+    views = R.workspace_views(ws, sizes, k1, k2)
+    assert tuple(views[0]['rank'].shape) == (33, 33) and views[0]['rank'].dtype == torch.int32
+    assert tuple(views[1]['val2'].shape) == (42, 42) and views[1]['val2'].dtype == torch.float32      # L2 = min(8 * 594, 42)
+    end = views[1]['val2'].data_ptr() - ws.data_ptr() + 4 * views[1]['val2'].numel()      # the last piece ends inside the last 256 bytes
+    assert total - 256 < end <= total
+    one = R.workspace_views(torch.zeros(R.workspace_layout([(3, 70)], 6, 1)[1], dtype=torch.uint8), [(3, 70)], 6, 1)[0]
+    assert one['idx2'].data_ptr() == one['idx1'].data_ptr() and one['cnt2'].data_ptr() == one['cnt1'].data_ptr()
+
+
+def test_generated_cases_meet_their_conditions_and_cover_what_they_are_there_for():
+    """Every case of the table: values on the 2^-17 lattice, neighbour gap >= 2e-6 (asserted inside rerank_cases.case, for the tie
+    case on all pairs but the planted ones), fp32 lists equal to the float64 lists -- and the coverage the table exists for."""
+    import rerank_cases as RC
+    cs = {n: RC.case(n) for n in RC.CASES}
+    for n, c in cs.items():
+        print('%-11s N %4d  gap %.2e  largest cnt1 %3d cnt2 %3d' % (n, c['N'], c['gap'], c['cnt1'], c['cnt2']))
+        assert c['gap'] >= 2e-6
+    cap = 33 * 18
+    for n in RC.SMALLEST:                                              # L1 == N: every list is the whole problem
+        c = cs[n]
+        assert c['N'] == c['k1'] + 1 and min((c['k1'] + 1) * (R.round_half_even(c['k1']) + 2), c['N']) == c['N']
+        assert all(sorted(r.tolist()) == list(range(c['N'])) for r in c['s64']['rank'])
+    assert any(min(c['k2'] * cap, c['N']) == c['N'] for c in cs.values() if c['k1'] == 32 and c['k2'] != 1)      # L2 == N
+    assert {c['N'] % 4 for c in cs.values()} == {0, 1, 2, 3}
+    assert {cs[n]['N'] for n in ('n63', 'n64', 'n65', 'n66', 'n67')} == {63, 64, 65, 66, 67}
+    assert [cs[n]['N'] for n in RC.GROUP] == [33, 1030, 65, 257] and all(cs[n]['k1'] == 32 and cs[n]['k2'] == 8 for n in RC.GROUP)
+    assert cs['ring']['cnt1'] > 64 and cs['n1030']['cnt1'] > 64        # the second trip of the expansion write-out
+    ring = cs['ring']['s64']
+    assert cs['ring']['cnt2'] > 512 and len(ring['idx2'][0]) > 256     # the Jaccard scatter's third and second trip
+    assert (np.abs(ring['out'] - (0.7 + 0.3 * ring['D'][:, 1:])) > 1e-3).all()      # no output at its trivial value
+    # the ring's lists are the ones written down
+    offs = np.array(RC.ring_offsets(32))
+    assert all(np.array_equal(ring['rank'][1 + i], 1 + (i + offs) % 1028) for i in range(1028))
+    # the planted ties: equal values 64, 1 and far apart, inside the list and across its end, resolved to the lower index
+    t = cs['ties']
+    D = R.distances(*t['blocks'])
+    order = np.argsort(D, axis=1, kind='stable')
+    seen = set()
+    for i, p in t['planted']:
+        a, b = int(order[i, p]), int(order[i, p + 1])
+        assert D[i, a] == D[i, b] and a < b and (p + 1 <= 32) == (b in t['s64']['rank'][i]) and a in t['s64']['rank'][i]
+        seen.add((min(b - a, 2), p))
+        assert b - a in (1, 64) or (b - a) % 64 not in (0, 1, 63)
+    assert seen == {(1, 4), (2, 4), (1, 32), (2, 32)} and len(t['planted']) == 6
+    assert not np.array_equal(t['s64']['rank'], cs['n1030']['s64']['rank'])
