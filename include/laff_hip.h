@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 34
+#define LAFF_ABI_VERSION 35
 
 enum {
     LAFF_OK = 0,
@@ -495,6 +495,25 @@ int laff_plane_row_norms(laff_ctx* ctx, const laff_plane* planes /*host array of
  * L <= 8, d % 4 == 0.  With NO_SPLIT_HEAD every head reads columns [0,d) (d = D). */
 int laff_fuse(laff_ctx* ctx, const laff_plane* planes /*host array of L*/, int L, int N, int H, int d,
               const float* w, const float* b, const float* gw, unsigned flags, float* E, float* attn_w);
+
+/* Backward of laff_fuse over PLAIN DENSE planes (no activation, tiling, folded affine, gather or row_scale: in training those are
+ * upstream ops with their own autograd).  x / dx: HOST arrays of L device pointers with their row pitches ldx / lddx (elements), so the
+ * L slices of a stacked (N, L, H*d) tensor and of its gradient are used in place.  Split heads: plane l holds x_l[n, h*d + c]; with
+ * LAFF_ATT_NO_SPLIT_HEAD every head reads columns [0, d) and dx_l is the sum over the heads.  dE [N, lde >= H*d] is the gradient of
+ * laff_fuse's E.  The forward is recomputed from the planes (nothing else is saved) and
+ *   dx_l [N, lddx_l]  the gradient of every plane, always written;
+ *   dw [H, d]         the gradient of w (NULL: not formed), a deterministic two-stage sum over the rows;
+ *   db [H]            zeros (softmax does not see a shift of its logits); NULL: not written.
+ * gw gets no gradient (the reference reads it through .item(), model/Attention.py:96).  LAFF_ATT_JUST_AVERAGE: dx_l = dE / L, dw = 0.
+ * No atomics: two calls on the same inputs give the same bits.  No allocation, no host synchronisation; ordered on the ctx's stream.
+ * workspace: caller-owned device scratch of laff_fuse_backward_workspace_bytes(L, N, H, d, flags), 16-byte aligned; only read when dw
+ * is given.  Limits as laff_fuse: 1 <= L <= 8, d % 4 == 0, rows 16-byte aligned (pitches % 4 == 0); N == 0 touches nothing. */
+int laff_fuse_backward_workspace_bytes(int L, int N, int H, int d, unsigned flags, size_t* out);
+int laff_fuse_backward(laff_ctx* ctx, const float* const* x /*host array of L device pointers*/, const int* ldx /*host, L row pitches*/,
+                       int L, int N, int H, int d, const float* w /*[H,d]*/, const float* b /*[H]*/, const float* gw /*[H]*/,
+                       unsigned flags /*LAFF_ATT_*/, const float* dE /*[N, lde >= H*d]*/, int lde,
+                       float* const* dx /*host array of L device pointers*/, const int* lddx /*host, L pitches*/,
+                       float* dw /*[H,d], nullable*/, float* db /*[H], nullable*/, void* workspace, size_t workspace_bytes);
 
 /* laff_fuse that ALSO emits the single-plane 16-bit similarity operand E16[N, H*d] = E * prescale (LAFF_PREC_FP16 or
  * LAFF_PREC_BF16), saving the separate laff_pack_rows pass.  E is already unit-norm per (n,h) to fp32 rounding, so the

@@ -1639,6 +1639,62 @@ int laff_plane_row_norms(laff_ctx* ctx, const laff_plane* planes, int L, int N, 
     return LAFF_OK;
 }
 
+// the shape and flags of laff_fuse_backward and its workspace query
+static int fuse_backward_shape(const char* fn, int L, int N, int H, int d, unsigned flags) {
+    if (L < 1 || L > laff::MAX_L) return fail(LAFF_E_SHAPE, "%s: L=%d outside [1,%d]", fn, L, laff::MAX_L);
+    if (N < 0 || H < 1 || d < 4 || (d & 3)) return fail(LAFF_E_SHAPE, "%s: need N>=0, H>=1, d%%4==0 (N=%d H=%d d=%d)", fn, N, H, d);
+    if ((long long)H * d > INT_MAX) return fail(LAFF_E_SHAPE, "%s: H * d = %lld columns", fn, (long long)H * d);
+    if (flags & ~31u) return fail(LAFF_E_ARG, "%s: unknown flags 0x%x", fn, flags);
+    return LAFF_OK;
+}
+
+int laff_fuse_backward_workspace_bytes(int L, int N, int H, int d, unsigned flags, size_t* out) {
+    if (!out) return fail(LAFF_E_ARG, "laff_fuse_backward_workspace_bytes: null out");
+    if (int rc = fuse_backward_shape("laff_fuse_backward_workspace_bytes", L, N, H, d, flags)) return rc;
+    int R = 0, P = 0, rows = 0;
+    laff::fuse_bwd_plan(N, H, d, flags, &R, &P, &rows);
+    *out = N ? (size_t)H * rows * d * sizeof(float) : 0;
+    return LAFF_OK;
+}
+
+int laff_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int L, int N, int H, int d, const float* w, const float* b,
+                       const float* gw, unsigned flags, const float* dE, int lde, float* const* dx, const int* lddx, float* dw, float* db,
+                       void* workspace, size_t workspace_bytes) {
+    CHECK_CTX(ctx);
+    if (int rc = fuse_backward_shape("laff_fuse_backward", L, N, H, d, flags)) return rc;
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
+    if (!x || !ldx || !dx || !lddx || !dE) return fail(LAFF_E_ARG, "laff_fuse_backward: null x / ldx / dx / lddx / dE");
+    const bool javg = flags & LAFF_ATT_JUST_AVERAGE, nosplit = flags & LAFF_ATT_NO_SPLIT_HEAD;
+    if (!javg && (!w || !b)) return fail(LAFF_E_ARG, "laff_fuse_backward: null w/b");
+    if (!javg && (flags & LAFF_ATT_WITH_AVE) && !gw) return fail(LAFF_E_ARG, "laff_fuse_backward: WITH_AVE needs gw");
+    if (lde < H * d || (lde & 3)) return fail(LAFF_E_SHAPE, "laff_fuse_backward: lde=%d (need >= %d, multiple of 4)", lde, H * d);
+    if (!aligned16(dE) || (w && !aligned16(w)) || (dw && !aligned16(dw)))
+        return fail(LAFF_E_ALIGN, "laff_fuse_backward: dE / w / dw must be 16-byte aligned");
+    laff::FuseBwdArgs a{};
+    const int need = nosplit ? d : H * d;
+    for (int l = 0; l < L; ++l) {
+        if (!x[l] || !dx[l]) return fail(LAFF_E_ARG, "laff_fuse_backward: plane %d has a null x / dx", l);
+        if (ldx[l] < need || (ldx[l] & 3) || lddx[l] < need || (lddx[l] & 3))
+            return fail(LAFF_E_SHAPE, "laff_fuse_backward: plane %d ldx=%d lddx=%d (need >= %d, multiples of 4)", l, ldx[l], lddx[l], need);
+        if (!aligned16(x[l]) || !aligned16(dx[l])) return fail(LAFF_E_ALIGN, "laff_fuse_backward: plane %d not 16-byte aligned", l);
+        a.x[l] = x[l]; a.dx[l] = dx[l]; a.ldx[l] = ldx[l]; a.lddx[l] = lddx[l];
+    }
+    a.L = L; a.N = N; a.H = H; a.d = d; a.head_stride = nosplit ? 0 : d;
+    a.w = w; a.b = b; a.gw = gw; a.flags = flags; a.dE = dE; a.lde = lde;
+    if (dw && !javg) {
+        int R = 0, P = 0, rows = 0;
+        laff::fuse_bwd_plan(N, H, d, flags, &R, &P, &rows);
+        const size_t bytes = (size_t)H * rows * d * sizeof(float);
+        if (!workspace || workspace_bytes < bytes)
+            return fail(LAFF_E_ARG, "laff_fuse_backward: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, bytes);
+        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_fuse_backward: workspace must be 16-byte aligned");
+        a.dw_part = (float*)workspace;
+    }
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_fuse_backward(a, dw, db, ctx->stream));
+    return LAFF_OK;
+}
+
 static int frame_fuse_grouped(laff_ctx* ctx, int count, const float* const* frames, const int* lens, const float* mask, int ldm, int B, int Fmax,
                               int d, const float* const* w, const float* const* b, const float* const* gw, unsigned flags, float* const* V) {
     CHECK_CTX(ctx);

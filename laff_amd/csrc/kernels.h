@@ -222,6 +222,26 @@ struct FuseArgs {
 hipError_t launch_fuse(const FuseArgs& a, hipStream_t st);
 hipError_t launch_plane_row_norms(const FuseArgs& a, float* out /*[L][N]*/, hipStream_t st);
 
+// fuse_bwd.hip: backward of the fusion over plain dense planes (laff_fuse_backward)
+struct FuseBwdArgs {
+    const float* x[MAX_L];    // [N, ldx]
+    float* dx[MAX_L];         // [N, lddx]
+    int ldx[MAX_L], lddx[MAX_L];
+    int L, N, H, d;
+    int head_stride;          // d (split heads) or 0 (every head sees all columns; dx_l is the sum over the heads)
+    const float* w;           // [H, d]
+    const float* b;           // [H]
+    const float* gw;          // [H]
+    unsigned flags;
+    const float* dE;          // [N, lde >= H * d]
+    int lde;
+    float* dw_part;           // workspace [H][part_rows][d], or null when dw is not wanted
+    int rows_per_block, part_rows;       // filled by launch_fuse_backward from fuse_bwd_plan
+};
+// how a shape is cut: rows per block (a multiple of 4), row chunks, and the partial rows of dw per head that the workspace holds
+void fuse_bwd_plan(int N, int H, int d, unsigned flags, int* rows_per_block, int* chunks, int* part_rows);
+hipError_t launch_fuse_backward(FuseBwdArgs& a, float* dw, float* db, hipStream_t st);
+
 struct FrameArgs {
     const float* frames;  // [B, Fmax, d]
     const int* lens;      // [B] or null

@@ -1,5 +1,7 @@
 """Fusion blocks of the reference's model/Attention.py that lie on the hot path, same class names, constructor
-arguments, parameter names (state_dict keys) and output shapes; forward() runs the `laff_fuse` HIP kernel.
+arguments, parameter names (state_dict keys) and output shapes; forward() runs the `laff_fuse` HIP kernel.  In training mode
+(`module.train()`) the blocks are differentiable: the same forward kernel under torch.autograd, `laff_fuse_backward` behind it
+(_FuseFn below).
 
   Attention_1                    /root/reference/model/Attention.py:40-105
   Multi_head_MyApply_Attention   /root/reference/model/Attention.py:473-552
@@ -23,6 +25,66 @@ def _planes_of(local_embs):
     return [(local_embs[:, l, :], False, None, None) for l in range(local_embs.shape[1])]
 
 
+class _FuseFn(torch.autograd.Function):
+    """ops.fuse over plain dense fp32 planes with ops.fuse_backward as its backward: (E (N, H, d), softmax weights (N, H, L) or None).
+    The planes come either as `stacked`, one (N, L, D) tensor whose slices are read in place and whose gradient is written in place,
+    or one by one in `planes` (then stacked is None).  w and b receive gradients, gw does not (the reference reads it through
+    .item(), model/Attention.py:96).  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, H, d, flags, w, b, gw, stacked, *planes):
+        srcs = [stacked[:, l, :] for l in range(stacked.shape[1])] if stacked is not None else list(planes)
+        for t in srcs + [t for t in (w, b, gw) if t is not None]:
+            if t.dtype != torch.float32:
+                raise TypeError('the differentiable fusion is fp32 only, got %s' % t.dtype)
+        just_average = bool(flags & ops.ATT_JUST_AVERAGE)
+        res = ops.fuse([(t.detach(), False, None, None) for t in srcs], H, d, w, b, gw, flags, return_weights=not just_average)
+        E, aw = (res, None) if just_average else res
+        ctx.save_for_backward(*[t for t in (w, b, gw, stacked) if t is not None], *planes)
+        ctx.meta = (H, d, flags, w is not None, b is not None, gw is not None, stacked is not None, len(planes))
+        if aw is not None:
+            ctx.mark_non_differentiable(aw)
+        return E, aw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_E, _grad_weights=None):
+        H, d, flags, has_w, has_b, has_gw, has_stacked, nplanes = ctx.meta
+        saved = list(ctx.saved_tensors)
+        w = saved.pop(0) if has_w else None
+        b = saved.pop(0) if has_b else None
+        gw = saved.pop(0) if has_gw else None
+        stacked = saved.pop(0) if has_stacked else None
+        want = has_w and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        out = d_stacked = None
+        if has_stacked:
+            d_stacked = torch.empty_like(stacked, memory_format=torch.contiguous_format)
+            srcs = [stacked[:, l, :] for l in range(stacked.shape[1])]
+            out = [d_stacked[:, l, :] for l in range(stacked.shape[1])]
+        else:
+            srcs = saved
+        dxs, dw, db = ops.fuse_backward(srcs, H, d, w, b, gw, flags, grad_E, want_param_grads=want, out=out)
+        return (None, None, None, dw.view_as(w) if want else None, db.view_as(b) if want else None, None, d_stacked) + \
+            (tuple(dxs) if not has_stacked else ())
+
+
+def _train_stacked(local_embs):
+    """(N, L, D) whose slices the kernels can read in place, as the training-mode forward hands it to _FuseFn: unit inner stride, pitches
+    that are multiples of 4 floats and a 16-byte aligned base -- the rule ops.fuse_backward applies to grad_E; anything else is copied."""
+    if local_embs.dim() != 3:
+        raise ValueError('local_embs must be (batch, L, embed_dim)')
+    ok = local_embs.stride(2) == 1 and local_embs.stride(0) % 4 == 0 and local_embs.stride(1) % 4 == 0 and local_embs.data_ptr() % 16 == 0
+    return local_embs if ok or not local_embs.numel() else local_embs.contiguous()
+
+
+def _train_sources(planes, l2norm_planes):
+    """The tensors of `planes` when every one of them is plain and dense -- what the training-mode forward accepts."""
+    if l2norm_planes:
+        raise NotImplementedError('training mode: the backward of the fusion has no row_scale (l2norm_planes); normalise the planes '
+                                  'upstream with torch ops')
+    return [ops.dense_plane(p, i) for i, p in enumerate(planes)]
+
+
 def _full_width(plane, heads, D):
     """a tiled plane (src (N, D / heads), tile, scale, shift) written out as (N, D): repeat over heads + the folded affine"""
     out = ops.fuse([plane], heads, D // heads, None, None, None, ops.attention_flags(just_average=True))
@@ -31,9 +93,16 @@ def _full_width(plane, heads, D):
 
 class JustAverage(nn.Module):
     def forward(self, local_embs, raw_global_emb=None):
+        if self.training:
+            x = _train_stacked(local_embs)
+            return _FuseFn.apply(1, x.shape[2], ops.attention_flags(just_average=True), None, None, None, x)[0].view(x.shape[0], x.shape[2])
         return self.fuse_planes(_planes_of(local_embs))
 
     def fuse_planes(self, planes, heads=1, l2norm_planes=False):
+        if self.training:
+            srcs = _train_sources(planes, l2norm_planes)
+            D = srcs[0].shape[1]
+            return _FuseFn.apply(1, D, ops.attention_flags(just_average=True), None, None, None, None, *srcs)[0].view(-1, D)
         H = heads if any(p[1] for p in planes) else 1
         D = planes[0][0].shape[1] * (heads if planes[0][1] else 1)
         out = ops.fuse(planes, H, D // H, None, None, None, ops.attention_flags(just_average=True), l2norm_planes=l2norm_planes)
@@ -72,7 +141,7 @@ class Attention_1(nn.Module):
         tower path leaves it off unless `self.record_weights` is set (get_attention_weight does): it is an extra N x L store per
         launch that only that consumer reads."""
         if self.training:
-            raise NotImplementedError('laff_amd implements the inference path only; call .eval()')
+            return self._fuse_train(None, _train_sources(planes, l2norm_planes), record_weights)
         w, b, gw = self._params()
         flags = ops.attention_flags(self.with_ave, self.mul)
         if heads > 1 and any(p[1] for p in planes):
@@ -95,10 +164,25 @@ class Attention_1(nn.Module):
             self.weights = aw
         return E.view(E.shape[0], self.embed_dim)
 
+    def _fuse_train(self, stacked, srcs, record_weights):
+        """Training mode: the block under autograd (_FuseFn) over a stacked (N, L, D) tensor or over plain dense planes.  The
+        parameters go in as they are (w and b receive gradients), gw detached; emit_packed / rank_side are not read."""
+        lin = self.embedding_common[0]
+        gw = self.global_emb_weight_net.weight.detach().reshape(1)
+        E, aw = _FuseFn.apply(1, self.embed_dim, ops.attention_flags(self.with_ave, self.mul), lin.weight.reshape(1, -1),
+                              lin.bias.reshape(1), gw, stacked, *srcs)
+        self.last_packed = None
+        if getattr(self, 'record_weights', False) if record_weights is None else record_weights:
+            aw = aw.detach()[:, 0, :]
+            self.weights = aw + gw / aw.shape[1] if self.with_ave else aw
+        return E.view(E.shape[0], self.embed_dim)
+
     def forward(self, local_embs, raw_global_emb=None):
         if raw_global_emb is not None:
             raise NotImplementedError('raw_global_emb is never passed on the retrieval path '
                                       '(and is undefined in the reference when mul=False)')
+        if self.training:
+            return self._fuse_train(_train_stacked(local_embs), [], True)
         return self.fuse_planes(_planes_of(local_embs), record_weights=True)
 
 
@@ -141,7 +225,7 @@ class Multi_head_MyApply_Attention(nn.Module):
 
     def fuse_planes(self, planes, heads=None, l2norm_planes=False, record_weights=None):
         if self.training:
-            raise NotImplementedError('laff_amd implements the inference path only; call .eval()')
+            return self._fuse_train(None, _train_sources(planes, l2norm_planes), record_weights)
         w, b, gw = self._params()
         flags = ops.attention_flags(self.with_ave, self.mul, self.l2norm_each_head, self.split_head)
         packed = getattr(self, 'emit_packed', None)       # 'fp16' | 'bf16': also emit the GEMM operand (last_packed)
@@ -159,7 +243,26 @@ class Multi_head_MyApply_Attention(nn.Module):
                 self.attention_layer[h].weights = a + gw[h] / a.shape[1] if self.with_ave else a
         return E
 
+    def _fuse_train(self, stacked, srcs, record_weights):
+        """Training mode: the block under autograd (_FuseFn).  w and b are stacked from the heads' parameters WITHOUT detach, so
+        autograd hands every head's embedding_common[0].weight / .bias its slice; gw is detached (no gradient, as in the reference);
+        emit_packed / rank_side are not read."""
+        heads = [self.attention_layer[h] for h in range(self.multi_heads)]
+        w = torch.stack([a.embedding_common[0].weight.reshape(-1) for a in heads])
+        b = torch.cat([a.embedding_common[0].bias.reshape(1) for a in heads])
+        gw = torch.cat([a.global_emb_weight_net.weight.detach().reshape(1) for a in heads])
+        flags = ops.attention_flags(self.with_ave, self.mul, self.l2norm_each_head, self.split_head)
+        E, aw = _FuseFn.apply(self.multi_heads, self.head_dim, flags, w, b, gw, stacked, *srcs)
+        self.last_packed = None
+        if getattr(self, 'record_weights', False) if record_weights is None else record_weights:
+            aw = aw.detach()
+            for h, a in enumerate(heads):
+                a.weights = aw[:, h, :] + gw[h] / aw.shape[2] if self.with_ave else aw[:, h, :]
+        return E
+
     def forward(self, local_embs, raw_global_emb=None, attn_mask=None):
+        if self.training:
+            return self._fuse_train(_train_stacked(local_embs), [], True)
         return self.fuse_planes(_planes_of(local_embs), record_weights=True)
 
     def get_raw_global_emb_weight(self):

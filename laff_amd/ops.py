@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -911,6 +911,79 @@ def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=N
     if packed_precision is not None:
         out = out + (packed,)
     return out if len(out) > 1 else out[0]
+
+
+def dense_plane(plane, i=0):
+    """The source of a plane that the fusion's backward covers: a tensor, or a (src, tile, scale, shift[, act[, gather]]) tuple of
+    fuse() that is plain and dense.  Anything else -- tiling, a folded affine, a deferred activation, a gather plane -- belongs to an
+    upstream op with its own autograd and is refused by name."""
+    if isinstance(plane, torch.Tensor):
+        return plane
+    src, tile, scale, shift = plane[:4]
+    missing = [name for name, on in (('a tiled plane', bool(tile)), ('a folded affine (scale / shift)', scale is not None or shift is not None),
+                                     ('a deferred activation', len(plane) > 4 and plane[4] is not None),
+                                     ('a gather plane', len(plane) > 5 and plane[5] is not None)) if on]
+    if missing:
+        raise NotImplementedError('plane %d: the backward of the fusion has no %s; apply it upstream as a torch op, which brings its own '
+                                  'autograd' % (i, ' / '.join(missing)))
+    return src
+
+
+def fuse_backward(planes, H, d, w, b, gw, flags, grad_E, want_param_grads=True, out=None):
+    """Backward of fuse() over plain dense planes (laff_fuse_backward): planes as fuse() takes them (tensors, or (src, False, None, None)
+    tuples; row views with a pitch are read in place), grad_E (N, H, d) or (N, H * d) with any strides.
+    Returns (list of dx, dw (H, d), db (H)) -- dw and db are None when want_param_grads is False or the flags say just_average.
+    out: a list of L fp32 row views (N, H * d; (N, d) without split heads) that receive the dx, e.g. the slices of a stacked gradient."""
+    L = len(planes)
+    srcs = [dense_plane(p, i) for i, p in enumerate(planes)]
+    N, dev = srcs[0].shape[0], srcs[0].device
+    need = d if (flags & ATT_NO_SPLIT_HEAD) else H * d
+    rows = []
+    for i, s in enumerate(srcs):
+        s, ld = _rows(s, 'plane %d' % i)
+        if s.shape[0] != N or s.shape[1] != need:
+            raise ValueError('plane %d is %s, expected (%d, %d)' % (i, tuple(s.shape), N, need))
+        rows.append((s, ld))
+    _dev(grad_E, 'grad_E')
+    if grad_E.numel() != N * H * d:
+        raise ValueError('grad_E has %d elements, expected (%d, %d, %d)' % (grad_E.numel(), N, H, d))
+    g = grad_E.reshape(N, H * d)                                      # a view where the strides allow it
+    if N and (g.stride(1) != 1 or (N > 1 and g.stride(0) % 4) or g.data_ptr() % 16):
+        g = g.contiguous()
+    g, lde = _rows(g, 'grad_E')
+    if out is None:
+        dxs = [torch.empty((N, need), device=dev, dtype=torch.float32) for _ in range(L)]
+    else:
+        dxs = list(out)
+        if len(dxs) != L or any(tuple(t.shape) != (N, need) or t.device != dev for t in dxs):
+            raise ValueError('out must hold %d tensors of (%d, %d) on %s' % (L, N, need, dev))
+    drows = [_rows(t, 'out %d' % i) for i, t in enumerate(dxs)]
+    just_average = bool(flags & ATT_JUST_AVERAGE)
+    for t, nm in ((w, 'w'), (b, 'b'), (gw, 'gw')):
+        if t is not None:
+            _dev(t, nm)
+            if not t.is_contiguous():
+                raise ValueError('%s must be contiguous' % nm)
+    if not just_average and (w is None or b is None or tuple(w.shape) != (H, d) or b.numel() != H):
+        raise ValueError('w must be (%d, %d) and b (%d,)' % (H, d, H))
+    want = want_param_grads and not just_average
+    dw = torch.empty((H, d), device=dev, dtype=torch.float32) if want else None
+    db = torch.empty((H,), device=dev, dtype=torch.float32) if want else None
+    if N == 0:
+        if want:
+            dw.zero_()
+            db.zero_()
+        return dxs, dw, db
+    lib, h = _context(dev)
+    nbytes = _size_query('laff_fuse_backward_workspace_bytes', L, N, H, d, flags) if want else 0
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want else None
+    xp = (C.c_void_p * L)(*[s.data_ptr() for s, _ in rows])
+    xl = (C.c_int * L)(*[ld for _, ld in rows])
+    dp = (C.c_void_p * L)(*[t.data_ptr() for t, _ in drows])
+    dl = (C.c_int * L)(*[ld for _, ld in drows])
+    _call('fuse_backward', lib.laff_fuse_backward, h, xp, xl, L, N, H, d, _ptr(w), _ptr(b), _ptr(gw), flags, _ptr(g), lde, dp, dl,
+          _ptr(dw), _ptr(db), _ptr(ws), nbytes)
+    return dxs, dw, db
 
 
 def frame_fuse(frames, lens, w, b, gw, flags, out=None):
