@@ -1468,9 +1468,6 @@ __device__ __forceinline__ unsigned f2key(float f) {
     if (b == 0x80000000u) b = 0u;                    // -0.0 == +0.0 for argsort: one key, ties resolved by index
     return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
-__device__ __forceinline__ float key2f(unsigned k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
 
 // among elements i with pred(i), find the byte-wise prefix of the `need`-th largest value of val(i);
 // returns the full 32-bit value; *above = how many selected elements are strictly greater.
@@ -1549,9 +1546,9 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             __syncthreads();
         }
     for (int i = threadIdx.x; i < K; i += 256) {
-        const unsigned long long e = sel[i];
-        idx_out[t * K + i] = (int)(unsigned)e;
-        val_out[t * K + i] = key2f((unsigned)(e >> 32));
+        const unsigned c = (unsigned)sel[i];                            // a column of the row: K were selected, padding is 0
+        idx_out[t * K + i] = (int)c;
+        val_out[t * K + i] = row[c];                                    // the entry itself: its key has lost the sign of a zero
     }
 }
 
