@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 35
+#define LAFF_ABI_VERSION 36
 
 enum {
     LAFF_OK = 0,
@@ -514,6 +514,27 @@ int laff_fuse_backward(laff_ctx* ctx, const float* const* x /*host array of L de
                        unsigned flags /*LAFF_ATT_*/, const float* dE /*[N, lde >= H*d]*/, int lde,
                        float* const* dx /*host array of L device pointers*/, const int* lddx /*host, L pitches*/,
                        float* dw /*[H,d], nullable*/, float* db /*[H], nullable*/, void* workspace, size_t workspace_bytes);
+
+/* Backward of the FC projection A = act(X W^T + bias), the forward laff_fc_act_bn computes without a BatchNorm stage; fp32 MFMA.
+ * X [N, ldx >= Dk], W [D, ldw >= Dk], A [N, lda >= D] the SAVED forward output, dA [N, ldda >= D] its gradient.  With
+ *   dZ = dA (.) act'(A)      tanh: 1 - A^2   sigmoid: A (1 - A)   relu: A > 0   none: 1
+ * the call writes whichever outputs are given (each may be NULL):
+ *   dX [N, lddx >= Dk] = dZ W        (reads W, not X)
+ *   dW [D, lddw >= Dk] = dZ^T X      (reads X, not W)
+ *   db [D]             = sum_n dZ[n, :]
+ * dZ is formed while dA and A are loaded and never stored.  Any N >= 0, Dk, D >= 1 and any pitch >= the width; rows that start on
+ * 16-byte boundaries (base and pitch % 4 == 0) are read with 16-byte loads, others element by element.  Pointers 4-byte aligned.
+ * N == 0: dW and db are set to zero, nothing else is touched.  Where the output tiles alone would not fill the chip a sum is cut into
+ * chunks that depend on (N, Dk, D) only: the sum over N of dW and db (1 chunk for N <= 128), the sum over D of dX (1 for D <= 128).
+ * With more than one the partial tiles go to `workspace` (16-byte aligned) and are added in chunk order.  No atomics: two calls give
+ * the same bits.  No allocation, no host synchronisation; ordered on the ctx's stream, capturable.
+ * laff_fc_backward_plan (host only, no ctx): out = {chunks of the dW / db sum, workspace bytes, chunks of the dX sum, tile variants:
+ * bit 0 dW and bit 1 dX on 128 x 128 tiles, else 64 x 64}.  The chunks do not depend on want_dx / want_dw; the workspace bytes cover
+ * dX's partial tiles with want_dx, dW's and db's with want_dw, and db's alone in any case. */
+int laff_fc_backward_plan(int N, int Dk, int D, int want_dx, int want_dw, int out[4]);
+int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, const float* W, int ldw, int D, int act /*LAFF_ACT_*/,
+                     const float* A, int lda, const float* dA, int ldda, float* dX, int lddx, float* dW, int lddw, float* db,
+                     void* workspace, size_t workspace_bytes);
 
 /* laff_fuse that ALSO emits the single-plane 16-bit similarity operand E16[N, H*d] = E * prescale (LAFF_PREC_FP16 or
  * LAFF_PREC_BF16), saving the separate laff_pack_rows pass.  E is already unit-norm per (n,h) to fp32 rounding, so the

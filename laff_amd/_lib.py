@@ -10,7 +10,7 @@ ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 
 class Plane(C.Structure):
@@ -153,6 +153,8 @@ SIGNATURES = {
     'laff_fuse_backward_workspace_bytes': (C.c_int, [_I, _I, _I, _I, C.c_uint, C.POINTER(C.c_size_t)]),
     'laff_fuse_backward': (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(_I), _I, _I, _I, _I, _P, _P, _P, C.c_uint, _P, _I,
                                      C.POINTER(C.c_void_p), C.POINTER(_I), _P, _P, _P, C.c_size_t]),
+    'laff_fc_backward_plan': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    'laff_fc_backward': (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, C.c_size_t]),
     'laff_frame_fuse': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_uint, _P]),
     'laff_packed_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_pack_rows': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

@@ -1695,6 +1695,64 @@ int laff_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int
     return LAFF_OK;
 }
 
+static int fc_backward_shape(const char* fn, int N, int Dk, int D) {
+    if (N < 0 || Dk < 1 || D < 1) return fail(LAFF_E_SHAPE, "%s: need N>=0, Dk>=1, D>=1 (N=%d Dk=%d D=%d)", fn, N, Dk, D);
+    return LAFF_OK;
+}
+
+int laff_fc_backward_plan(int N, int Dk, int D, int want_dx, int want_dw, int out[4]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_fc_backward_plan: null out");
+    if (int rc = fc_backward_shape("laff_fc_backward_plan", N, Dk, D)) return rc;
+    laff::FcBwdPlan p;
+    laff::fc_bwd_plan(N, Dk, D, &p);
+    /* the cuts depend on the shape alone; want_dx / want_dw only say whose partial tiles the workspace has to hold (db's always) */
+    const size_t bytes = std::max(want_dx ? p.ws_dx : (size_t)0, want_dw ? p.ws_dw : p.ws_db);
+    if (bytes > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "laff_fc_backward_plan: workspace of %zu bytes", bytes);
+    out[0] = p.chunks; out[1] = (int)bytes; out[2] = p.chunks_dx; out[3] = (p.tile_dw == 128 ? 1 : 0) | (p.tile_dx == 128 ? 2 : 0);
+    return LAFF_OK;
+}
+
+int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, const float* W, int ldw, int D, int act, const float* A, int lda,
+                     const float* dA, int ldda, float* dX, int lddx, float* dW, int lddw, float* db, void* workspace,
+                     size_t workspace_bytes) {
+    CHECK_CTX(ctx);
+    const char* fn = "laff_fc_backward";
+    if (int rc = fc_backward_shape(fn, N, Dk, D)) return rc;
+    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", fn, act);
+    if (dW && lddw < Dk) return fail(LAFF_E_SHAPE, "%s: lddw=%d < Dk=%d", fn, lddw, Dk);
+    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
+    if (!aligned4(dW) || !aligned4(db)) return fail(LAFF_E_ALIGN, "%s: dW / db must be 4-byte aligned", fn);
+    DeviceGuard g(ctx->device);
+    if (N == 0) {                                /* the empty sum: zeros in dW and db, nothing else is read or written */
+        if (dW) HIP_TRY(hipMemset2DAsync(dW, (size_t)lddw * sizeof(float), 0, (size_t)Dk * sizeof(float), D, ctx->stream));
+        if (db) HIP_TRY(hipMemsetAsync(db, 0, (size_t)D * sizeof(float), ctx->stream));
+        return LAFF_OK;
+    }
+    if (!dX && !dW && !db) return LAFF_OK;
+    if (!A || !dA || (dW && !X) || (dX && !W)) return fail(LAFF_E_ARG, "%s: null A / dA, X (read for dW) or W (read for dX)", fn);
+    if (lda < D || ldda < D || (dW && ldx < Dk) || (dX && (ldw < Dk || lddx < Dk)))
+        return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (ldx=%d ldw=%d lddx=%d Dk=%d; lda=%d ldda=%d D=%d)", fn, ldx, ldw,
+                    lddx, Dk, lda, ldda, D);
+    if (!aligned4(X) || !aligned4(W) || !aligned4(A) || !aligned4(dA) || !aligned4(dX))
+        return fail(LAFF_E_ALIGN, "%s: X / W / A / dA / dX must be 4-byte aligned", fn);
+    laff::FcBwdArgs a{};
+    a.X = X; a.W = W; a.A = A; a.dA = dA; a.dX = dX; a.dW = dW; a.db = db;
+    a.N = N; a.Dk = Dk; a.D = D; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.ldda = ldda; a.lddx = lddx; a.lddw = lddw; a.act = act;
+    a.vec = (aligned16(A) && aligned16(dA) && lda % 4 == 0 && ldda % 4 == 0 ? 1u : 0u) | (X && aligned16(X) && ldx % 4 == 0 ? 2u : 0u) |
+            (W && aligned16(W) && ldw % 4 == 0 ? 4u : 0u);
+    laff::FcBwdPlan p;
+    laff::fc_bwd_plan(N, Dk, D, &p);
+    const size_t need = std::max(dX ? p.ws_dx : (size_t)0, dW ? p.ws_dw : db ? p.ws_db : (size_t)0);
+    if (need) {
+        if (!workspace || workspace_bytes < need)
+            return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace ? workspace_bytes : (size_t)0, need);
+        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "%s: workspace must be 16-byte aligned", fn);
+        a.part = (float*)workspace;
+    }
+    HIP_TRY(laff::launch_fc_backward(a, ctx->stream));
+    return LAFF_OK;
+}
+
 static int frame_fuse_grouped(laff_ctx* ctx, int count, const float* const* frames, const int* lens, const float* mask, int ldm, int B, int Fmax,
                               int d, const float* const* w, const float* const* b, const float* const* gw, unsigned flags, float* const* V) {
     CHECK_CTX(ctx);

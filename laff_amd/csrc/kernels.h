@@ -242,6 +242,32 @@ struct FuseBwdArgs {
 void fuse_bwd_plan(int N, int H, int d, unsigned flags, int* rows_per_block, int* chunks, int* part_rows);
 hipError_t launch_fuse_backward(FuseBwdArgs& a, float* dw, float* db, hipStream_t st);
 
+// fc_bwd.hip: backward of the FC projection A = act(X W^T + bias) (laff_fc_backward)
+struct FcBwdArgs {
+    const float* X;           // [N, ldx >= Dk]   read for dW
+    const float* W;           // [D, ldw >= Dk]   read for dX
+    const float* A;           // [N, lda >= D]    the saved forward output
+    const float* dA;          // [N, ldda >= D]
+    float* dX;                // [N, lddx >= Dk] or null
+    float* dW;                // [D, lddw >= Dk] or null
+    float* db;                // [D] or null
+    int N, Dk, D, ldx, ldw, lda, ldda, lddx, lddw, act;
+    unsigned vec;             // 16-byte loads allowed: bit 0 A and dA, bit 1 X, bit 2 W (base aligned and pitch % 4 == 0)
+    float* part;              // workspace: [chunks][D][Dk] partial dW, then [chunks][D] partial db; afterwards [chunks_dx][N][Dk] partial dX
+    float* part_db;           // filled by launch_fc_backward, as are the four below (from fc_bwd_plan)
+    int chunks, chunk_rows;   // dW, db: the cut of the sum over N
+    int chunks_dx, chunk_len_dx;         // dX: the cut of the sum over D
+};
+// how a shape is cut, from (N, Dk, D) alone: per product the edge (64 or 128) of its output tiles and the chunks of its sum (each a
+// multiple of 32 long), and the workspace that dW with db, db alone and dX need (0 with one chunk)
+struct FcBwdPlan {
+    int chunks, chunk_rows, tile_dw;
+    int chunks_dx, chunk_len_dx, tile_dx;
+    size_t ws_dw, ws_db, ws_dx;
+};
+void fc_bwd_plan(int N, int Dk, int D, FcBwdPlan* p);
+hipError_t launch_fc_backward(const FcBwdArgs& a, hipStream_t st);
+
 struct FrameArgs {
     const float* frames;  // [B, Fmax, d]
     const int* lens;      // [B] or null

@@ -14,7 +14,8 @@ as /root/reference/model/model.py for the symbols on the hot path (SURVEY.md sec
   MultiScaleTxtEncoder / MultiScaleTxtNet :552-726     the concatenated input never formed
   get_model                            :2501-2519
 
-Inference only: training (forward(), losses, optimisers) is out of scope and raises.
+The towers are inference only: their training-mode forward raises.  A single TransformNet is differentiable in .train() mode
+(_FcActFn: laff_fc_act_bn forward, laff_fc_backward behind it), as the fusion blocks are (section 4.19).
 Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: features arrive pre-extracted in
 `caption_feat_dict` (the reference already does this for frozen CLIP via 'CLIP_encoding', :497-498); any module
 returning {'text_features': tensor} can be plugged into `txt_net.encoder.<name>`.
@@ -23,6 +24,7 @@ import numpy as np
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import loss as _loss
 from .. import ops
@@ -178,6 +180,34 @@ def get_attention_layer(attention_type, common_space_dim, encoder_num, opt):
 # ------------------------------------------------------------------------------------------------------
 # a1/a2: TransformNet
 # ------------------------------------------------------------------------------------------------------
+class _FcActFn(torch.autograd.Function):
+    """a = act(x @ weight.T + bias) on laff_fc_act_bn (the fp32 route, whatever FC_PRECISION says) with ops.fc_backward as its backward.
+    Saves x, weight and the output a: act' is a function of a for every activation of the reference.  Only the gradients that
+    needs_input_grad asks for are formed -- no dx launch for pre-extracted features.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, activation):
+        for t, nm in ((x, 'the input'), (weight, 'fc1.weight'), (bias, 'fc1.bias')):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError('the differentiable projection is fp32 only, %s is %s' % (nm, t.dtype))
+        x = x.detach()
+        if x.dim() == 2 and x.numel() and x.stride(1) != 1:
+            x = x.contiguous()
+        a = ops.fc_act_bn(x, weight.detach(), None if bias is None else bias.detach(), None, None, activation)
+        ctx.save_for_backward(x, weight, a)
+        ctx.activation, ctx.has_bias = activation, bias is not None
+        return a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_a):
+        x, weight, a = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, db = ops.fc_backward(x, weight.detach(), a, grad_a, ctx.activation, want_dx=need[0], want_dw=need[1],
+                                     want_db=ctx.has_bias and need[2])
+        return dx, dw, db, None
+
+
 class TransformNet(nn.Module):
     """fc -> activation -> dropout (identity in eval) -> BatchNorm1d, as one GEMM with a fused epilogue."""
 
@@ -283,10 +313,29 @@ class TransformNet(nn.Module):
             self._w_strip = (key, ops.fc_strip_pack(w.detach(), None if b is None else b.detach(), scale, shift, self.activation_name))
         return self._w_strip[1]
 
+    def _forward_train(self, x, heads=1, extra_shift=None):
+        """Training mode: fc1 + activation under autograd (_FcActFn), then torch's own dropout and training-mode BatchNorm1d (batch
+        statistics, running-stat updates), each a single elementwise / column pass with its own autograd.  What has no backward here
+        is refused by name."""
+        if self.fc1 is None:
+            raise NotImplementedError('training mode: a TransformNet without fc (fc=False%s) has no differentiable path; apply its '
+                                      'BatchNorm upstream as a torch op' % (', tiled over %d heads' % heads if heads > 1 else ''))
+        if x.layout != torch.strided:
+            raise NotImplementedError('training mode: a sparse (CSR) input has no backward (laff_fc_gather_act_bn is inference only)')
+        if extra_shift is not None:
+            raise NotImplementedError('training mode: extra_shift (the expert embedding) is not differentiable here; add it upstream '
+                                      'as a torch op')
+        y = _FcActFn.apply(x, self.fc1.weight, self.fc1.bias, self.activation_name)
+        if self.dropout_p is not None:
+            y = F.dropout(y, self.dropout_p, training=True)
+        return y if self.bn1 is None else self.bn1(y)
+
     def plane(self, x, heads=1, extra_shift=None, pending=None, head_dim=None):
         """(src, tile, scale, shift) for laff_fuse.  With an FC the projection either runs now or, when `pending`
-        (a list) is given, is appended to it so that the caller launches all features' GEMMs as one grouped kernel."""
-        _eval_only(self)
+        (a list) is given, is appended to it so that the caller launches all features' GEMMs as one grouped kernel.
+        In training mode the projection runs at once under autograd (`pending` is not used) and the plane is plain and dense."""
+        if self.training:
+            return (self._forward_train(x, heads, extra_shift), False, None, None)
         scale, shift = self.bn_affine(extra_shift)
         if self.fc1 is not None and x.layout == torch.sparse_csr:
             # sparse feature (bag-of-words): gather-sum of columns of W instead of a dense N x |vocab| x D GEMM
@@ -315,6 +364,8 @@ class TransformNet(nn.Module):
         return (x, tile, scale, shift)
 
     def forward(self, input_x):
+        if self.training:
+            return self._forward_train(input_x)
         src, tile, scale, shift = self.plane(input_x)[:4]
         if scale is None and not tile:
             return src

@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -984,6 +984,52 @@ def fuse_backward(planes, H, d, w, b, gw, flags, grad_E, want_param_grads=True, 
     _call('fuse_backward', lib.laff_fuse_backward, h, xp, xl, L, N, H, d, _ptr(w), _ptr(b), _ptr(gw), flags, _ptr(g), lde, dp, dl,
           _ptr(dw), _ptr(db), _ptr(ws), nbytes)
     return dxs, dw, db
+
+
+def fc_backward_plan(N, Dk, D, want_dx=True, want_dw=True):
+    """laff_fc_backward_plan (host only): (chunks of dW's and db's sum over N, workspace bytes for the wanted outputs -- db's always
+    counted --, chunks of dX's sum over D, tile variants: bit 0 dW and bit 1 dX on 128 x 128 tiles, else 64 x 64)."""
+    out = (C.c_int * 4)()
+    check(_lib.load().laff_fc_backward_plan(int(N), int(Dk), int(D), int(bool(want_dx)), int(bool(want_dw)), out))
+    return tuple(out)
+
+
+def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, want_db=True, out=None):
+    """Backward of a = act(x @ weight.T + bias) (laff_fc_backward): x (N, Dk), weight (D, Dk), a (N, D) the saved forward output,
+    grad_a (N, D) its gradient; device fp32, row views with a pitch are read in place, a non-unit inner stride is made dense first.
+    Returns (dx (N, Dk) | None, dw (D, Dk) | None, db (D,) | None).  out: a (dx, dw, db) triple of fp32 buffers (None entries are
+    allocated here; dx and dw may be row views with a pitch, db is contiguous) that receive the wanted outputs."""
+    if activation not in ACT:
+        raise ValueError('unknown activation %r' % (activation,))
+    mats = []
+    for t, nm in ((x, 'x'), (weight, 'weight'), (a, 'a'), (grad_a, 'grad_a')):
+        _dev(t, nm)
+        if t.dim() != 2:
+            raise ValueError('%s must be 2-D, got shape %s' % (nm, tuple(t.shape)))
+        if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):      # e.g. an expanded gradient
+            t = t.contiguous()
+        mats.append(_rows(t, nm))
+    (x, ldx), (w, ldw), (a, lda), (g, ldg) = mats
+    (N, Dk), D, dev = x.shape, w.shape[0], x.device
+    if w.shape[1] != Dk or tuple(a.shape) != (N, D) or tuple(g.shape) != (N, D):
+        raise ValueError('x %s, weight %s, a %s and grad_a %s do not fit together' % (tuple(x.shape), tuple(w.shape), tuple(a.shape),
+                                                                                    tuple(g.shape)))
+    odx, odw, odb = out if out is not None else (None, None, None)
+    dx, pdx, lddx = _out_rows(odx, (N, Dk), dev, 'out dx') if want_dx else (None, None, 0)
+    dw, pdw, lddw = _out_rows(odw, (D, Dk), dev, 'out dw') if want_dw else (None, None, 0)
+    db = None
+    if want_db:
+        db = torch.empty((D,), device=dev, dtype=torch.float32) if odb is None else _dev(odb, 'out db')
+        if tuple(db.shape) != (D,) or not db.is_contiguous():
+            raise ValueError('out db must be a contiguous vector of %d' % D)
+    if not (want_dx or want_dw or want_db):
+        return None, None, None
+    nbytes = fc_backward_plan(N, Dk, D, want_dx, want_dw)[1]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    lib, h = _context(dev)
+    _call('fc_backward', lib.laff_fc_backward, h, _ptr(x), N, Dk, ldx, _ptr(w), ldw, D, ACT[activation], _ptr(a), lda, _ptr(g), ldg,
+          pdx, lddx, pdw, lddw, _ptr(db), _ptr(ws), nbytes)
+    return dx, dw, db
 
 
 def frame_fuse(frames, lens, w, b, gw, flags, out=None):
