@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 36
+#define LAFF_ABI_VERSION 37
 
 enum {
     LAFF_OK = 0,
@@ -535,6 +535,40 @@ int laff_fc_backward_plan(int N, int Dk, int D, int want_dx, int want_dw, int ou
 int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, const float* W, int ldw, int D, int act /*LAFF_ACT_*/,
                      const float* A, int lda, const float* dA, int ldda, float* dX, int lddx, float* dW, int lddw, float* db,
                      void* workspace, size_t workspace_bytes);
+
+/* The optimizer step: the global L2 norm of a list of gradients, the clip by it, and Adam / RMSprop with that clip folded in.
+ * A tensor list is `count` flat fp32 device tensors of n[i] >= 0 elements, each base 4-byte aligned (nothing stronger is assumed; a
+ * launch whose bases are all 16-byte aligned runs the variant with 16-byte accesses).  Pointer arrays and n are HOST arrays.
+ *   laff_grad_sqnorm   leaves float64 partial sums of g*g in `workspace` (8-byte aligned, bytes >= 8 * partials of the plan);
+ *   laff_grad_scale    total = sqrt(sum of the partials), c = min(1, max_norm / (total + 1e-6)) in float64, c rounded to fp32 once (a NaN
+ *                      total gives a NaN c); g *= c in place; (float)total to total_norm_out (device, nullable).  This is
+ *                      torch.nn.utils.clip_grad_norm_ with norm_type 2 and error_if_nonfinite=False;
+ *   laff_optim_step    the same c when max_norm > 0 (else c = 1, workspace and total_norm_out are not touched), then per element in fp32,
+ *                      one rounding per operation, in torch's order:  gh = c g;  gh += weight_decay p  when weight_decay != 0;
+ *                        Adam:     m = m + (gh - m)(1 - beta1);  v = beta2 v + ((1 - beta2) gh) gh;
+ *                                  p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)),  bc = 1 - beta^step
+ *                        RMSprop:  s = alpha s + ((1 - alpha) gh) gh;  p = p - lr (gh / (sqrt(s) + eps))     (momentum 0, not centered)
+ *                      with 1 - beta, bc1, bc2 formed in float64 on the host and rounded to fp32 once.  g is NOT written.  total_norm_out
+ *                      is stored when max_norm > 0 and at least one tensor is not empty.
+ * The norm of a step is over whatever list laff_grad_sqnorm was given (all parameter groups); laff_optim_step may then be called once
+ * per group with the same workspace and `partials`.  No atomics: every block re-sums the partials in index order, two calls give the
+ * same bits.  The tensor table travels in the launch arguments: no allocation, no copy, no host synchronisation; ordered on the ctx's
+ * stream, capturable.  Refused before any GPU work: null pointers with n > 0, n < 0, unknown kind, step < 1, beta outside [0, 1),
+ * eps < 0, weight_decay < 0 (LAFF_E_ARG), a workspace too small (LAFF_E_ARG), misaligned pointers (LAFF_E_ALIGN).  n == 0 entries and
+ * count == 0 are accepted and do nothing.
+ * laff_optim_plan (host only, no ctx): out = {elements of a chunk, tensors of one launch's table, norm launches, partials (workspace =
+ * 8 * partials bytes), update launches, blocks a launch has at most}.  laff_optim_last_launches (host only): the launches the calling
+ * thread's last laff_grad_sqnorm / laff_grad_scale / laff_optim_step issued, out = {16-byte variant, single-float variant}. */
+enum { LAFF_OPT_ADAM = 0, LAFF_OPT_RMSPROP = 1 };
+typedef struct { float* p; const float* g; float* s1; float* s2; long long n; } laff_optim_tensor;  /* s2 NULL for RMSprop */
+typedef struct { int kind /*LAFF_OPT_*/; double lr, beta1, beta2 /*alpha for RMSprop in beta2*/, eps, weight_decay; long long step; } laff_optim_hyper;
+int laff_optim_plan(int count, const long long* n, int out[6]);
+int laff_optim_last_launches(int out[2]);
+int laff_grad_sqnorm(laff_ctx* ctx, int count, const float* const* g, const long long* n, void* workspace, size_t bytes);
+int laff_grad_scale(laff_ctx* ctx, int count, float* const* g, const long long* n, double max_norm, const void* workspace, int partials,
+                    float* total_norm_out);
+int laff_optim_step(laff_ctx* ctx, const laff_optim_tensor* t /*host array*/, int count, const laff_optim_hyper* h,
+                    double max_norm /*<= 0: no clipping*/, const void* workspace, int partials, float* total_norm_out /*nullable*/);
 
 /* laff_fuse that ALSO emits the single-plane 16-bit similarity operand E16[N, H*d] = E * prescale (LAFF_PREC_FP16 or
  * LAFF_PREC_BF16), saving the separate laff_pack_rows pass.  E is already unit-norm per (n,h) to fp32 rounding, so the

@@ -9,8 +9,9 @@ LIB_PATH = os.environ.get('LAFF_HIP_LIB') or os.path.join(_HERE, 'lib', 'liblaff
 ACT = {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
 ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE = 1, 2, 4, 8, 16
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
+OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 
 class Plane(C.Structure):
@@ -100,6 +101,15 @@ class BertText(C.Structure):
                 ('pooler_bias', C.c_void_p)]
 
 
+class OptimTensor(C.Structure):
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('s1', C.c_void_p), ('s2', C.c_void_p), ('n', C.c_longlong)]
+
+
+class OptimHyper(C.Structure):
+    _fields_ = [('kind', C.c_int), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double),
+                ('weight_decay', C.c_double), ('step', C.c_longlong)]
+
+
 class FrameDesc(C.Structure):
     _fields_ = [('offset', C.c_int64), ('height', C.c_int32), ('width', C.c_int32), ('htab', C.c_int32), ('vtab', C.c_int32),
                 ('reserved', C.c_int32 * 2)]
@@ -155,6 +165,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_void_p), C.POINTER(_I), _P, _P, _P, C.c_size_t]),
     'laff_fc_backward_plan': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     'laff_fc_backward': (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, C.c_size_t]),
+    'laff_optim_plan': (C.c_int, [_I, C.POINTER(C.c_longlong), C.POINTER(_I)]),
+    'laff_optim_last_launches': (C.c_int, [C.POINTER(_I)]),
+    'laff_grad_sqnorm': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _P, C.c_size_t]),
+    'laff_grad_scale': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_double, _P, _I, _P]),
+    'laff_optim_step': (C.c_int, [_P, C.POINTER(OptimTensor), _I, C.POINTER(OptimHyper), C.c_double, _P, _I, _P]),
     'laff_frame_fuse': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_uint, _P]),
     'laff_packed_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_pack_rows': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

@@ -1753,6 +1753,116 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
     return LAFF_OK;
 }
 
+static_assert(sizeof(laff_optim_tensor) == 40, "laff_optim_tensor is five 8-byte words (laff_amd/ops.py fills the host array as such)");
+
+/* the launches of the calling thread's last optimizer call, by variant */
+static thread_local laff::OptimLaunches g_optim_launches{};
+
+/* a tensor list as the optimizer entry points take it: sizes and 4-byte alignment of `slots` pointers an entry (null only with n == 0) */
+static int optim_check_list(const char* fn, const laff_optim_tensor* t, int count, bool want_s1, bool want_s2) {
+    if (count < 0) return fail(LAFF_E_ARG, "%s: count=%d", fn, count);
+    if (count > 0 && !t) return fail(LAFF_E_ARG, "%s: null tensor list", fn);
+    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+    for (int i = 0; i < count; ++i) {
+        if (t[i].n < 0) return fail(LAFF_E_ARG, "%s: tensor %d has n=%lld", fn, i, t[i].n);
+        if (t[i].n == 0) continue;
+        if (!t[i].g || (want_s1 && (!t[i].p || !t[i].s1)) || (want_s2 && !t[i].s2))
+            return fail(LAFF_E_ARG, "%s: tensor %d has a null pointer with n=%lld", fn, i, t[i].n);
+        if (misaligned(t[i].p) || misaligned(t[i].g) || misaligned(t[i].s1) || misaligned(t[i].s2))
+            return fail(LAFF_E_ALIGN, "%s: tensor %d: pointers must be 4-byte aligned", fn, i);
+    }
+    return LAFF_OK;
+}
+
+static int optim_check_workspace(const char* fn, const void* workspace, int partials) {
+    if (partials < 0) return fail(LAFF_E_ARG, "%s: partials=%d", fn, partials);
+    if (partials > 0 && !workspace) return fail(LAFF_E_ARG, "%s: null workspace with %d partials", fn, partials);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(LAFF_E_ALIGN, "%s: workspace must be 8-byte aligned", fn);
+    return LAFF_OK;
+}
+
+int laff_optim_plan(int count, const long long* n, int out[6]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_optim_plan: null out");
+    if (count < 0 || (count > 0 && !n)) return fail(LAFF_E_ARG, "laff_optim_plan: count=%d, n %s", count, n ? "given" : "null");
+    for (int i = 0; i < count; ++i)
+        if (n[i] < 0) return fail(LAFF_E_ARG, "laff_optim_plan: tensor %d has n=%lld", i, n[i]);
+    laff::OptimPlan p;
+    laff::optim_plan(count, n, &p);
+    out[0] = laff::OPTIM_CHUNK; out[1] = laff::OPTIM_TABLE; out[2] = p.launches; out[3] = p.partials; out[4] = p.launches;
+    out[5] = laff::OPTIM_GRID_CAP;
+    return LAFF_OK;
+}
+
+int laff_optim_last_launches(int out[2]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_optim_last_launches: null out");
+    out[0] = g_optim_launches.fast; out[1] = g_optim_launches.generic;
+    return LAFF_OK;
+}
+
+int laff_grad_sqnorm(laff_ctx* ctx, int count, const float* const* g, const long long* n, void* workspace, size_t bytes) {
+    CHECK_CTX(ctx);
+    const char* fn = "laff_grad_sqnorm";
+    if (count < 0 || (count > 0 && (!g || !n))) return fail(LAFF_E_ARG, "%s: count=%d with null g or n", fn, count);
+    std::vector<laff_optim_tensor> t((size_t)count);
+    for (int i = 0; i < count; ++i) t[i] = laff_optim_tensor{nullptr, g[i], nullptr, nullptr, n[i]};
+    if (int rc = optim_check_list(fn, t.data(), count, false, false)) return rc;
+    laff::OptimPlan p;
+    laff::optim_plan(count, n, &p);
+    if (bytes < 8 * (size_t)p.partials) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, bytes, 8 * (size_t)p.partials);
+    if (int rc = optim_check_workspace(fn, workspace, p.partials)) return rc;
+    g_optim_launches = {};
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(laff::launch_optim_sqnorm(t.data(), count, (double*)workspace, &g_optim_launches, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_grad_scale(laff_ctx* ctx, int count, float* const* g, const long long* n, double max_norm, const void* workspace, int partials,
+                    float* total_norm_out) {
+    CHECK_CTX(ctx);
+    const char* fn = "laff_grad_scale";
+    if (count < 0 || (count > 0 && (!g || !n))) return fail(LAFF_E_ARG, "%s: count=%d with null g or n", fn, count);
+    std::vector<laff_optim_tensor> t((size_t)count);
+    for (int i = 0; i < count; ++i) t[i] = laff_optim_tensor{g[i], g[i], nullptr, nullptr, n[i]};
+    if (int rc = optim_check_list(fn, t.data(), count, false, false)) return rc;
+    if (int rc = optim_check_workspace(fn, workspace, partials)) return rc;
+    if (reinterpret_cast<uintptr_t>(total_norm_out) & 3) return fail(LAFF_E_ALIGN, "%s: total_norm_out must be 4-byte aligned", fn);
+    g_optim_launches = {};
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(laff::launch_optim_scale(t.data(), count, max_norm, (const double*)workspace, partials, total_norm_out, &g_optim_launches,
+                                     ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_optim_step(laff_ctx* ctx, const laff_optim_tensor* t, int count, const laff_optim_hyper* h, double max_norm, const void* workspace,
+                    int partials, float* total_norm_out) {
+    CHECK_CTX(ctx);
+    const char* fn = "laff_optim_step";
+    if (!h) return fail(LAFF_E_ARG, "%s: null hyper-parameters", fn);
+    if (h->kind != LAFF_OPT_ADAM && h->kind != LAFF_OPT_RMSPROP) return fail(LAFF_E_ARG, "%s: unknown kind %d", fn, h->kind);
+    const bool adam = h->kind == LAFF_OPT_ADAM;
+    if (h->step < 1) return fail(LAFF_E_ARG, "%s: step=%lld < 1", fn, h->step);
+    if ((adam && !(h->beta1 >= 0.0 && h->beta1 < 1.0)) || !(h->beta2 >= 0.0 && h->beta2 < 1.0))
+        return fail(LAFF_E_ARG, "%s: beta1=%g / beta2=%g outside [0, 1)", fn, h->beta1, h->beta2);
+    if (!(h->eps >= 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g < 0", fn, h->eps);
+    if (!(h->weight_decay >= 0.0)) return fail(LAFF_E_ARG, "%s: weight_decay=%g < 0", fn, h->weight_decay);
+    if (int rc = optim_check_list(fn, t, count, true, adam)) return rc;
+    const bool clip = max_norm > 0.0;
+    if (clip) {
+        if (int rc = optim_check_workspace(fn, workspace, partials)) return rc;
+        if (reinterpret_cast<uintptr_t>(total_norm_out) & 3) return fail(LAFF_E_ALIGN, "%s: total_norm_out must be 4-byte aligned", fn);
+    }
+    laff::OptimScalars s{};
+    s.lr = (float)h->lr; s.omb1 = (float)(1.0 - h->beta1); s.b2 = (float)h->beta2; s.omb2 = (float)(1.0 - h->beta2);
+    s.eps = (float)h->eps; s.wd = (float)h->weight_decay;
+    s.bc1 = adam ? (float)(1.0 - std::pow(h->beta1, (double)h->step)) : 1.0f;
+    s.bc2 = adam ? (float)(1.0 - std::pow(h->beta2, (double)h->step)) : 1.0f;
+    g_optim_launches = {};
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(laff::launch_optim_update(t, count, h->kind, s, clip ? max_norm : 0.0, clip ? (const double*)workspace : nullptr,
+                                      clip ? partials : 0, clip ? total_norm_out : nullptr, &g_optim_launches, ctx->stream));
+    return LAFF_OK;
+}
+
 static int frame_fuse_grouped(laff_ctx* ctx, int count, const float* const* frames, const int* lens, const float* mask, int ldm, int B, int Fmax,
                               int d, const float* const* w, const float* const* b, const float* const* gw, unsigned flags, float* const* V) {
     CHECK_CTX(ctx);

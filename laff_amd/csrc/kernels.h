@@ -268,6 +268,36 @@ struct FcBwdPlan {
 void fc_bwd_plan(int N, int Dk, int D, FcBwdPlan* p);
 hipError_t launch_fc_backward(const FcBwdArgs& a, hipStream_t st);
 
+// optim.hip: global-norm clipping and the Adam / RMSprop step over a list of flat fp32 tensors (laff_grad_sqnorm, laff_grad_scale,
+// laff_optim_step)
+constexpr int OPTIM_CHUNK = 4096;        // elements of one chunk: 256 threads x 4 accesses of 16 bytes
+constexpr int OPTIM_TABLE = 72;          // tensors of one launch: the table travels in the launch arguments (72 x 48 bytes)
+constexpr int OPTIM_GRID_CAP = 1024;     // blocks of one launch, striding over the chunks; also the partials a norm launch leaves
+struct OptimEntry {
+    float* p;                 // the parameter (laff_grad_scale: the gradient that is scaled in place)
+    const float* g;
+    float* s1;                // exp_avg / square_avg
+    float* s2;                // exp_avg_sq, Adam only
+    long long n;              // elements, > 0
+    long long first;          // the tensor's first chunk in the launch
+};
+struct OptimTable {
+    long long chunks;         // of the whole launch
+    int count;
+    OptimEntry t[OPTIM_TABLE];
+};
+struct OptimScalars {         // the step's constants, rounded to fp32 once on the host from float64
+    float lr, omb1 /*1 - beta1*/, b2 /*beta2, RMSprop's alpha*/, omb2 /*1 - b2*/, eps, wd, bc1, bc2;
+};
+struct OptimPlan { int launches, partials; };
+struct OptimLaunches { int fast, generic; };             // launches issued, by variant
+void optim_plan(int count, const long long* n, OptimPlan* p);
+hipError_t launch_optim_sqnorm(const laff_optim_tensor* t, int count, double* part, OptimLaunches* done, hipStream_t st);
+hipError_t launch_optim_scale(const laff_optim_tensor* t, int count, double max_norm, const double* part, int np, float* total_out,
+                              OptimLaunches* done, hipStream_t st);
+hipError_t launch_optim_update(const laff_optim_tensor* t, int count, int kind, const OptimScalars& h, double max_norm, const double* part,
+                               int np, float* total_out, OptimLaunches* done, hipStream_t st);
+
 struct FrameArgs {
     const float* frames;  // [B, Fmax, d]
     const int* lens;      // [B] or null

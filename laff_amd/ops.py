@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1030,6 +1030,116 @@ def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, wa
     _call('fc_backward', lib.laff_fc_backward, h, _ptr(x), N, Dk, ldx, _ptr(w), ldw, D, ACT[activation], _ptr(a), lda, _ptr(g), ldg,
           pdx, lddx, pdw, lddw, _ptr(db), _ptr(ws), nbytes)
     return dx, dw, db
+
+
+def optim_plan(sizes):
+    """laff_optim_plan (host only) for a tensor list with these element counts: (elements of a chunk, tensors of one launch's table,
+    norm launches, partials -- the workspace of grad_sqnorm holds 8 bytes each --, update launches, blocks a launch has at most)."""
+    sizes = [int(s) for s in sizes]
+    out = (C.c_int * 6)()
+    check(_lib.load().laff_optim_plan(len(sizes), (C.c_longlong * len(sizes))(*sizes), out))
+    return tuple(out)
+
+
+def optim_last_launches():
+    """(launches of the 16-byte variant, launches of the single-float variant) that this thread's last grad_sqnorm / grad_scale /
+    optim_step issued."""
+    out = (C.c_int * 2)()
+    check(_lib.load().laff_optim_last_launches(out))
+    return tuple(out)
+
+
+def _flat_list(tensors, name):
+    """A tensor list of the optimizer entry points: device fp32, contiguous, on one device.  Returns (device, element counts)."""
+    dev = _dev(tensors[0], '%s[0]' % name).device if tensors else None
+    for i, t in enumerate(tensors):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev:
+            continue
+        _dev(t, '%s[%d]' % (name, i))                      # names what is wrong
+        if not t.is_contiguous():
+            raise ValueError('%s[%d] must be contiguous, got shape %s strides %s' % (name, i, tuple(t.shape), t.stride()))
+        raise ValueError('%s[%d] is on %s, %s[0] on %s' % (name, i, t.device, name, dev))
+    return dev, [t.numel() for t in tensors]
+
+
+def grad_sqnorm(grads, workspace=None):
+    """laff_grad_sqnorm: float64 partial sums of g*g over the list into `workspace` (a uint8 device buffer of 8 bytes a partial,
+    allocated here when None).  Returns (workspace, partials) for grad_scale / optim_step."""
+    grads = list(grads)
+    dev, sizes = _flat_list(grads, 'grads')
+    partials = optim_plan(sizes)[3]
+    if dev is None:
+        return workspace, 0
+    if workspace is None:
+        workspace = torch.empty(max(8 * partials, 16), dtype=torch.uint8, device=dev)
+    _dev(workspace, 'workspace', torch.uint8)
+    lib, h = _context(dev)
+    L = len(grads)
+    _call('grad_sqnorm', lib.laff_grad_sqnorm, h, L, (C.c_void_p * L)(*[g.data_ptr() for g in grads]), (C.c_longlong * L)(*sizes),
+          _ptr(workspace), workspace.numel())
+    return workspace, partials
+
+
+def grad_scale(grads, max_norm, workspace, partials, total_norm_out=None):
+    """laff_grad_scale: g *= min(1, max_norm / (total + 1e-6)) in place over the list, total = the L2 norm grad_sqnorm left in
+    (workspace, partials).  Returns the total norm, a 0-d fp32 device tensor (total_norm_out when given)."""
+    grads = list(grads)
+    dev, sizes = _flat_list(grads, 'grads')
+    if dev is None:
+        raise ValueError('grad_scale of an empty list has no device to answer on')
+    if total_norm_out is None:
+        total_norm_out = torch.empty((), dtype=torch.float32, device=dev)
+    _dev(total_norm_out, 'total_norm_out')
+    if workspace is not None:
+        _dev(workspace, 'workspace', torch.uint8)
+    if int(partials) < 0 or 8 * int(partials) > (workspace.numel() if workspace is not None else 0):
+        raise ValueError('workspace holds %d bytes, %d partials need %d' % (workspace.numel() if workspace is not None else 0,
+                                                                           partials, 8 * int(partials)))
+    lib, h = _context(dev)
+    L = len(grads)
+    _call('grad_scale', lib.laff_grad_scale, h, L, (C.c_void_p * L)(*[g.data_ptr() for g in grads]), (C.c_longlong * L)(*sizes),
+          float(max_norm), _ptr(workspace), int(partials), _ptr(total_norm_out))
+    return total_norm_out
+
+
+def optim_step(kind, params, grads, state1, state2, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, max_norm=0.0,
+               workspace=None, partials=0, total_norm_out=None, checked=False):
+    """laff_optim_step over a tensor list: kind 'adam' (state1 = exp_avg, state2 = exp_avg_sq, bias corrections of `step` >= 1) or
+    'rmsprop' (state1 = square_avg, beta2 = alpha, state2 = None).  With max_norm > 0 the gradients enter scaled by
+    min(1, max_norm / (total + 1e-6)), total from grad_sqnorm's (workspace, partials), and the norm goes to total_norm_out (0-d, optional);
+    the gradients themselves are not written.  params and states are updated in place.  checked: the caller has held grads and states
+    to what this function checks (device fp32, contiguous, of their parameter's size and device), as laff_amd.optim has."""
+    if kind not in _lib.OPT_KIND:
+        raise ValueError('unknown optimizer kind %r' % (kind,))
+    params, grads, state1 = list(params), list(grads), list(state1)
+    adam = kind == 'adam'
+    state2 = list(state2) if adam else [None] * len(params)
+    if not (len(params) == len(grads) == len(state1) == len(state2)):
+        raise ValueError('params, grads and states must have one entry per tensor')
+    dev, sizes = _flat_list(params, 'params')
+    for nm, ts in () if checked else (('grads', grads), ('state1', state1)) + ((('state2', state2),) if adam else ()):
+        d, ns = _flat_list(ts, nm)
+        if ns != sizes or d != dev:
+            raise ValueError('%s do not match params in size or device' % nm)
+    if dev is None:
+        return
+    clip = float(max_norm) > 0.0
+    if clip:
+        _dev(workspace, 'workspace', torch.uint8)
+        if int(partials) < 0 or 8 * int(partials) > workspace.numel():
+            raise ValueError('workspace holds %d bytes, %d partials need %d' % (workspace.numel(), partials, 8 * int(partials)))
+        if total_norm_out is not None:
+            _dev(total_norm_out, 'total_norm_out')
+    L = len(params)
+    # laff_optim_tensor is five 8-byte words {p, g, s1, s2, n}: the host array is filled in one constructor call, not L structures
+    words = []
+    for p, g, a, b, n in zip(params, grads, state1, state2, sizes):
+        words += (p.data_ptr(), g.data_ptr(), a.data_ptr(), b.data_ptr() if adam else 0, n)
+    table = C.cast((C.c_longlong * (5 * L))(*words), C.POINTER(_lib.OptimTensor))
+    hyper = _lib.OptimHyper(_lib.OPT_KIND[kind], float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+    lib, h = _context(dev)
+    _call('optim_step', lib.laff_optim_step, h, table, L, C.byref(hyper), float(max_norm), _ptr(workspace) if clip else None,
+          int(partials) if clip else 0, _ptr(total_norm_out) if clip else None)
 
 
 def frame_fuse(frames, lens, w, b, gw, flags, out=None):
