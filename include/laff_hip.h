@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 37
+#define LAFF_ABI_VERSION 38
 
 enum {
     LAFF_OK = 0,
@@ -623,6 +623,28 @@ int laff_frame_fuse_grouped(laff_ctx* ctx, int count, const float* const* frames
 int laff_frame_fuse_grouped_mask(laff_ctx* ctx, int count, const float* const* frames, const float* mask, int ldm, int B, int Fmax,
                                  int d, const float* const* w, const float* const* b, const float* const* gw, unsigned flags,
                                  float* const* V);
+
+/* Backward of laff_frame_fuse_grouped: `count` frame features of one tower (same B / Fmax / d / flags / lens), up to 8 per launch, more
+ * in further launches.  Host arrays of `count` device pointers: frames [B, Fmax, d], w [d], b [1], gw [1] (the array may be NULL without
+ * WITH_AVE), dV [B, lddv >= d] the gradient of V, dframes [B, Fmax, d], dw [d] and db [1] (either array may be NULL: not formed).
+ * lens [B] device int32 or NULL (all Fmax frames real).  The forward is recomputed from the frames (nothing else is saved):
+ *   dframes   rows below lens[b]: the gradient; rows at or past it: zeros (the frames there are never read, whatever they hold);
+ *             a video with lens[b] == 0 (V = 0) gets zero rows and adds nothing to dw;
+ *   dw        a deterministic two-stage sum over the videos: one partial row per (feature, video) in `workspace`, added per feature in a
+ *             fixed order by a second small launch; identically zero at Fmax == 1;
+ *   db        zeros (softmax does not see a shift of its logits).
+ * gw gets no gradient (the reference reads it through .item(), model/Attention.py:96).  No atomics: two calls give the same bits.  No
+ * allocation, no host synchronisation; ordered on the ctx's stream, capturable.  workspace: caller-owned device scratch, 16-byte
+ * aligned, count * B * d * 4 bytes (laff_frame_fuse_backward_plan), only used when dw is given.
+ * Limits: d % 4 == 0, 4 <= d <= 1024, Fmax >= 1, lddv >= d and lddv % 4 == 0 (LAFF_E_SHAPE), flags within WITH_AVE | MUL (LAFF_E_ARG),
+ * 16-byte aligned bases (LAFF_E_ALIGN); all refused before any GPU work.  B == 0 or count == 0 touches nothing.
+ * laff_frame_fuse_backward_plan (host only, no ctx): out = {workspace bytes, kernel variant = the 256-column chunks a lane owns (1, 2 or
+ * 4 for d <= 256 / 512 / 1024), launches of the main kernel (ceil(count / 8)), partial rows of dw per feature (B; 0 without dw)}. */
+int laff_frame_fuse_backward_plan(int count, int B, int Fmax, int d, int want_dw, int out[4]);
+int laff_frame_fuse_backward(laff_ctx* ctx, int count, const float* const* frames, const int* lens /*NULL: all Fmax*/, int B, int Fmax,
+                             int d, const float* const* w, const float* const* b, const float* const* gw /*may be NULL without WITH_AVE*/,
+                             unsigned flags, const float* const* dV, int lddv, float* const* dframes, float* const* dw /*may be NULL*/,
+                             float* const* db /*may be NULL*/, void* workspace, size_t workspace_bytes);
 
 /* ---- a8: loss.l2norm (loss.py:8-13) + operand packing for the similarity GEMM ---------------------------
  * For each (n,h): y = x / (||x||_2 + eps + 1e-14) if normalize, then y * prescale, converted to `precision`.

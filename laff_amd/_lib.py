@@ -11,7 +11,7 @@ ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 
 class Plane(C.Structure):
@@ -171,6 +171,10 @@ SIGNATURES = {
     'laff_grad_scale': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_double, _P, _I, _P]),
     'laff_optim_step': (C.c_int, [_P, C.POINTER(OptimTensor), _I, C.POINTER(OptimHyper), C.c_double, _P, _I, _P]),
     'laff_frame_fuse': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_uint, _P]),
+    'laff_frame_fuse_backward_plan': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    'laff_frame_fuse_backward': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), _P, _I, _I, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.c_uint, C.POINTER(C.c_void_p), _I, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P, C.c_size_t]),
     'laff_packed_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_pack_rows': (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
     'laff_sim_gemm': (C.c_int, [_P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _I, _P, _P]),

@@ -1904,6 +1904,64 @@ int laff_frame_fuse(laff_ctx* ctx, const float* frames, const int* lens, int B, 
     return laff_frame_fuse_grouped(ctx, 1, &frames, lens, B, Fmax, d, &w, &b, gw ? &gw : nullptr, flags, &V);
 }
 
+// the shape of laff_frame_fuse_backward and its plan: plain integers, checked before anything else
+static int frame_backward_shape(const char* fn, int count, int B, int Fmax, int d) {
+    if (count < 0 || B < 0 || Fmax < 1 || d < 4 || (d & 3) || d > 1024)
+        return fail(LAFF_E_SHAPE, "%s: need count>=0, B>=0, Fmax>=1, d%%4==0, 4<=d<=1024 (count=%d B=%d Fmax=%d d=%d)", fn, count, B, Fmax, d);
+    if ((long long)B * (count < 8 ? count : 8) > INT_MAX) return fail(LAFF_E_SHAPE, "%s: grid too large", fn);
+    if ((long long)B * Fmax * d > (long long)INT_MAX * 4) return fail(LAFF_E_SHAPE, "%s: a feature of %lld elements", fn, (long long)B * Fmax * d);
+    return LAFF_OK;
+}
+
+int laff_frame_fuse_backward_plan(int count, int B, int Fmax, int d, int want_dw, int out[4]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_frame_fuse_backward_plan: null out");
+    if (int rc = frame_backward_shape("laff_frame_fuse_backward_plan", count, B, Fmax, d)) return rc;
+    const long long bytes = want_dw ? (long long)count * B * d * (long long)sizeof(float) : 0;
+    if (bytes > INT_MAX) return fail(LAFF_E_SHAPE, "laff_frame_fuse_backward_plan: workspace of %lld bytes", bytes);
+    out[0] = (int)bytes; out[1] = laff::frame_bwd_variant(d); out[2] = (count + 7) / 8; out[3] = want_dw ? B : 0;
+    return LAFF_OK;
+}
+
+int laff_frame_fuse_backward(laff_ctx* ctx, int count, const float* const* frames, const int* lens, int B, int Fmax, int d,
+                             const float* const* w, const float* const* b, const float* const* gw, unsigned flags, const float* const* dV,
+                             int lddv, float* const* dframes, float* const* dw, float* const* db, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_frame_fuse_backward";
+    if (int rc = frame_backward_shape(fn, count, B, Fmax, d)) return rc;
+    if (flags & ~(unsigned)(LAFF_ATT_WITH_AVE | LAFF_ATT_MUL)) return fail(LAFF_E_ARG, "%s: unknown flags 0x%x", fn, flags);
+    if (lddv < d || (lddv & 3)) return fail(LAFF_E_SHAPE, "%s: lddv=%d (need >= %d, multiple of 4)", fn, lddv, d);
+    CHECK_CTX(ctx);
+    if (B == 0 || count == 0) return LAFF_OK;                 /* empty problem: nothing to launch, pointers may be null */
+    if (!frames || !w || !b || !dV || !dframes) return fail(LAFF_E_ARG, "%s: null frames / w / b / dV / dframes", fn);
+    if ((flags & LAFF_ATT_WITH_AVE) && !gw) return fail(LAFF_E_ARG, "%s: WITH_AVE needs gw", fn);
+    for (int k = 0; k < count; ++k) {
+        if (!frames[k] || !w[k] || !b[k] || !dV[k] || !dframes[k] || (dw && !dw[k]) || (db && !db[k]))
+            return fail(LAFF_E_ARG, "%s: feature %d has a null pointer", fn, k);
+        if ((flags & LAFF_ATT_WITH_AVE) && !gw[k]) return fail(LAFF_E_ARG, "%s: WITH_AVE needs gw (feature %d)", fn, k);
+        if (!aligned16(frames[k]) || !aligned16(w[k]) || !aligned16(dV[k]) || !aligned16(dframes[k]) || (dw && !aligned16(dw[k])))
+            return fail(LAFF_E_ALIGN, "%s: feature %d: frames / w / dV / dframes / dw must be 16-byte aligned", fn, k);
+    }
+    if (dw) {
+        const size_t bytes = (size_t)count * B * d * sizeof(float);
+        if (!workspace || workspace_bytes < bytes)
+            return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace ? workspace_bytes : (size_t)0, bytes);
+        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "%s: workspace must be 16-byte aligned", fn);
+    }
+    DeviceGuard g(ctx->device);
+    for (int i0 = 0; i0 < count; i0 += 8) {
+        laff::FrameBwdGroup grp{};
+        grp.count = count - i0 < 8 ? count - i0 : 8;
+        grp.B = B; grp.Fmax = Fmax; grp.d = d; grp.lddv = lddv; grp.flags = flags; grp.lens = lens;
+        grp.dw_part = dw ? (float*)workspace + (size_t)i0 * B * d : nullptr;
+        for (int i = 0; i < grp.count; ++i) {
+            const int k = i0 + i;
+            grp.f[i] = laff::FrameBwdArgs{frames[k], w[k], b[k], gw ? gw[k] : nullptr, dV[k], dframes[k], dw ? dw[k] : nullptr,
+                                          db ? db[k] : nullptr};
+        }
+        HIP_TRY(laff::launch_frame_fuse_backward(grp, dw || db, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
 int laff_packed_bytes(int N, int K, int precision, size_t* out) {
     if (!out || N < 0 || K < 0) return fail(LAFF_E_ARG, "laff_packed_bytes: bad args");
     if (int rc = bad_precision("laff_packed_bytes", precision)) return rc;

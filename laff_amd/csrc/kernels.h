@@ -316,6 +316,28 @@ struct FrameGroup {       // up to 8 frame features of the same shape in ONE lau
 };
 hipError_t launch_frame_fuse(const FrameGroup& g, hipStream_t st);
 
+// frame_bwd.hip: backward of the frame attention (laff_frame_fuse_backward)
+struct FrameBwdArgs {
+    const float* frames;  // [B, Fmax, d]
+    const float* w;       // [d]
+    const float* b;       // [1]
+    const float* gw;      // [1] or null without WITH_AVE
+    const float* dV;      // [B, lddv]
+    float* dframes;       // [B, Fmax, d]
+    float* dw;            // [d] or null
+    float* db;            // [1] or null
+};
+struct FrameBwdGroup {    // up to 8 frame features of the same shape in ONE launch: block -> (feature, video)
+    int count, B, Fmax, d, lddv;
+    unsigned flags;
+    const int* lens;      // [B] or null
+    float* dw_part;       // workspace [count][B][d]: one partial row of dw per (feature, video); null when dw is not wanted
+    FrameBwdArgs f[8];
+};
+int frame_bwd_variant(int d);            // NCH, the 256-column chunks a lane owns: 1 / 2 / 4
+// tail: also run the second launch (dw from the partial rows, db = 0)
+hipError_t launch_frame_fuse_backward(const FrameBwdGroup& g, bool tail, hipStream_t st);
+
 hipError_t launch_split_rows_grouped(int count, const float* const* X, const int* N, const int* K, const int* ldx, void* const* out,
                                      float* const* rscale, hipStream_t st);
 hipError_t launch_loss_normalize(const float* s, const float* im, int B, int H, int d, int dp, int Bp, float eps, float* XH,

@@ -68,6 +68,35 @@ class _FuseFn(torch.autograd.Function):
             (tuple(dxs) if not has_stacked else ())
 
 
+class _FrameFuseFn(torch.autograd.Function):
+    """ops.frame_fuse over (B, Fmax, d) fp32 frames with ops.frame_fuse_backward as its backward: V (B, d), the very bits of
+    ops.frame_fuse.  Saves the frames, lens and the parameters; the forward is recomputed in the backward launch.  w and b receive
+    gradients (b's is zero), gw does not.  Rows of the frames' gradient at or past a video's length are zeros.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, flags, lens, w, b, gw, frames):
+        for t in (frames, w, b) + ((gw,) if gw is not None else ()):
+            if t.dtype != torch.float32:
+                raise TypeError('the differentiable frame attention is fp32 only, got %s' % t.dtype)
+        frames, wd, bd = frames.detach().contiguous(), w.detach().contiguous(), b.detach().contiguous()
+        V = ops.frame_fuse(frames, lens, wd, bd, gw, flags)
+        ctx.save_for_backward(frames, wd, bd, *[t for t in (gw, lens) if t is not None])
+        ctx.meta = (flags, gw is not None, lens is not None)
+        return V
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_V):
+        flags, has_gw, has_lens = ctx.meta
+        saved = list(ctx.saved_tensors)
+        frames, w, b = saved[:3]
+        gw = saved[3] if has_gw else None
+        lens = saved[-1] if has_lens else None
+        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dfs, dws, dbs = ops.frame_fuse_backward([frames], lens, [(w, b, gw)], flags, [grad_V], want_param_grads=want)
+        return None, None, dws[0] if want else None, dbs[0] if want else None, None, dfs[0]
+
+
 def _train_stacked(local_embs):
     """(N, L, D) whose slices the kernels can read in place, as the training-mode forward hands it to _FuseFn: unit inner stride, pitches
     that are multiples of 4 floats and a 16-byte aligned base -- the rule ops.fuse_backward applies to grad_E; anything else is copied."""
@@ -176,6 +205,22 @@ class Attention_1(nn.Module):
             aw = aw.detach()[:, 0, :]
             self.weights = aw + gw / aw.shape[1] if self.with_ave else aw
         return E.view(E.shape[0], self.embed_dim)
+
+    def fuse_frames(self, frames, lens=None):
+        """This block over the frames of each video, (B, Fmax, d) zero padded -> (B, d), in one launch (ops.frame_fuse): what the
+        reference's loop over the batch computes (model/model.py:2167-2173).  lens: int32 (B,), frames at or past it count as zeros.
+        In training mode the call is differentiable (_FrameFuseFn): the frames and embedding_common receive gradients, gw is detached;
+        the values are the eval-mode bits."""
+        ops._dev(frames, 'frames')
+        if frames.dim() != 3 or frames.shape[2] != self.embed_dim:
+            raise ValueError('frames must be (B, Fmax, %d), got shape %s' % (self.embed_dim, tuple(frames.shape)))
+        flags = ops.attention_flags(self.with_ave, self.mul)
+        if not self.training:
+            w, b, gw = self._params()
+            return ops.frame_fuse(frames.contiguous(), lens, w.reshape(-1), b, gw, flags)
+        lin = self.embedding_common[0]
+        return _FrameFuseFn.apply(flags, lens, lin.weight.reshape(-1), lin.bias.reshape(1),
+                                  self.global_emb_weight_net.weight.detach().reshape(1), frames)
 
     def forward(self, local_embs, raw_global_emb=None):
         if raw_global_emb is not None:

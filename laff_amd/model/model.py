@@ -719,7 +719,10 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
         Replaces the per-sample Python loop of model/model.py:2167-2173.  The reference's mask slice is a no-op, so
         padded frames take part in softmax / mean; without a frame FC they are exact zeros and are accounted for
         analytically from `lens`; with vis_frame_addFC the Linear turns them into the bias vector and all Fmax
-        frames are processed."""
+        frames are processed.
+
+        In training mode the method is differentiable: the frame Linear runs under _FcActFn, the attention
+        under Attention_1.fuse_frames, so the frames, the Linear and the attention's embedding_common receive gradients."""
         seq = self.frame_attention[feat_name]
         att = seq[-1]
         frames = to_device_and_float16(frames).contiguous()
@@ -727,11 +730,13 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
         lens = None
         if len(seq) == 2:
             fc = seq[0]
-            frames = ops.fc_act_bn(frames.view(B * Fmax, d), fc.weight.detach(), fc.bias.detach()).view(B, Fmax, d)
+            if self.training:
+                frames = _FcActFn.apply(frames.view(B * Fmax, d), fc.weight, fc.bias, None).view(B, Fmax, d)
+            else:
+                frames = ops.fc_act_bn(frames.view(B * Fmax, d), fc.weight.detach(), fc.bias.detach()).view(B, Fmax, d)
         else:
             lens = mask_tensor.to(device=frames.device).sum(dim=1).to(torch.int32).contiguous()
-        w, b, gw = att._params()
-        return ops.frame_fuse(frames, lens, w.reshape(-1), b, gw, ops.attention_flags(att.with_ave, att.mul))
+        return att.fuse_frames(frames, lens)
 
     def forward(self, vis_input, vis_frame_feat_dict_input, txt_emb=None):
         pending = []

@@ -14,7 +14,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1157,6 +1157,74 @@ def frame_fuse(frames, lens, w, b, gw, flags, out=None):
     _call('frame_fuse', lib.laff_frame_fuse, h, _ptr(frames), _ptr(lens), B, Fmax, d, _ptr(_dev(w, 'w')), _ptr(_dev(b, 'b')),
                               _ptr(gw), flags, _ptr(V))
     return V
+
+
+def frame_fuse_backward_plan(count, B, Fmax, d, want_dw=True):
+    """laff_frame_fuse_backward_plan (host only): (workspace bytes, kernel variant -- the 256-column chunks a lane owns: 1 / 2 / 4 for
+    d <= 256 / 512 / 1024 --, launches of the main kernel, partial rows of dw per feature)."""
+    out = (C.c_int * 4)()
+    check(_lib.load().laff_frame_fuse_backward_plan(int(count), int(B), int(Fmax), int(d), int(bool(want_dw)), out))
+    return tuple(out)
+
+
+def frame_fuse_backward(frames_list, lens, params, flags, grad_list, want_param_grads=True, out=None):
+    """Backward of frame_fuse / frame_fuse_grouped (laff_frame_fuse_backward).  frames_list: [(B, Fmax, d)] contiguous, lens int32 (B,)
+    or None, params: [(w (d,), b (1,), gw (1,) | None)], grad_list: [(B, d)] the gradients of the outputs (a row pitch that all of
+    them share is read in place, anything else is made dense).  Returns (list of dframes (B, Fmax, d), list of dw (d,) | None, list of
+    db (1,) | None) -- the last two are None when want_param_grads is False.  Rows at or past a video's length come back as zeros.
+    out: one contiguous fp32 (B, Fmax, d) buffer per feature that receives dframes."""
+    n = len(frames_list)
+    if n == 0 or len(params) != n or len(grad_list) != n or (out is not None and len(out) != n):
+        raise ValueError('frames_list, params, grad_list (and out) must hold one entry per frame feature, at least one')
+    for fr in frames_list:
+        _dev(fr, 'frames')
+    if frames_list[0].dim() != 3:
+        raise ValueError('frames must be (B, Fmax, d), got shape %s' % (tuple(frames_list[0].shape),))
+    B, Fmax, d = frames_list[0].shape
+    dev = frames_list[0].device
+    for fr in frames_list:
+        if tuple(fr.shape) != (B, Fmax, d) or not fr.is_contiguous() or fr.device != dev:
+            raise ValueError('the frame features must share one contiguous (B, Fmax, d) shape on one device')
+    if lens is not None:
+        _dev(lens, 'lens', torch.int32)
+        if lens.numel() != B or not lens.is_contiguous():
+            raise ValueError('lens must be a contiguous vector of %d entries' % B)
+    grads = []
+    for g in grad_list:
+        _dev(g, 'grad')
+        if g.numel() != B * d:
+            raise ValueError('a grad has %d elements, expected (%d, %d)' % (g.numel(), B, d))
+        grads.append(g.reshape(B, d))
+    pitch = {_rows(g, 'grad')[1] if g.numel() and g.stride(1) == 1 else -1 for g in grads}
+    if B and (len(pitch) != 1 or min(pitch) < d or min(pitch) % 4 or any(g.data_ptr() % 16 for g in grads)):     # (an expanded grad: 0)
+        grads = [g.contiguous() for g in grads]
+    lddv = _rows(grads[0], 'grad')[1] if B else d
+    for w, b, gw in params:
+        for t, nm, k in ((w, 'w', d), (b, 'b', 1)) + (((gw, 'gw', 1),) if gw is not None else ()):
+            _dev(t, nm)
+            if t.numel() != k or not t.is_contiguous():
+                raise ValueError('%s must be a contiguous vector of %d' % (nm, k))
+        if gw is None and (flags & ATT_WITH_AVE):
+            raise ValueError('with_ave needs gw')
+    dfs = [_out_buffer(out[i] if out is not None else None, (B, Fmax, d), dev, 'out[%d]' % i) for i in range(n)]
+    dws = [torch.empty((d,), device=dev, dtype=torch.float32) for _ in range(n)] if want_param_grads else None
+    dbs = [torch.empty((1,), device=dev, dtype=torch.float32) for _ in range(n)] if want_param_grads else None
+    if B == 0:
+        for t in (dws or []) + (dbs or []):
+            t.zero_()
+        return dfs, dws, dbs
+    nbytes = frame_fuse_backward_plan(n, B, Fmax, d, want_param_grads)[0]
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want_param_grads else None
+
+    def table(ts):
+        return (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    has_gw = all(p[2] is not None for p in params)
+    lib, h = _context(dev)
+    _call('frame_fuse_backward', lib.laff_frame_fuse_backward, h, n, table(frames_list), _ptr(lens), B, Fmax, d,
+          table([p[0] for p in params]), table([p[1] for p in params]), table([p[2] for p in params]) if has_gw else None, flags,
+          table(grads), lddv, table(dfs), table(dws) if want_param_grads else None, table(dbs) if want_param_grads else None, _ptr(ws),
+          nbytes)
+    return dfs, dws, dbs
 
 
 def frame_fuse_grouped(frames_list, lens, params, flags, mask=None, out=None):
