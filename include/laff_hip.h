@@ -204,7 +204,11 @@ int laff_fc_route(laff_ctx* ctx, int family, const laff_fc_shape* shapes /*host*
  *   laff_fc_strip_pack(W[D,512], bias, bn_scale, bn_shift, act) -> img  (laff_fc_strip_pack_bytes(D) bytes, 16-byte aligned: the hi/lo
  *   fragments of W in LDS order + the per-column epilogue constants with bias, activation and folded BatchNorm pre-combined)
  * Needs Dk == 512, D % 32 == 0, ldx % 4 == 0, 16-byte aligned X; any N, any ldy >= D.  Up to 8 problems per launch; problems of
- * different D or activation kind are launched separately.  |Y - fp64| as the other fp16x3 forms (<= ~1e-6 of the row / weight scale). */
+ * different D or activation kind are launched separately.  |Y - fp64| as the other fp16x3 forms (<= ~1e-6 of the row / weight scale).
+ * The kernel exists on two MFMA shapes; LAFF_FC_STRIP_MFMA, read when a ctx is created (process-wide, as LAFF_STRIP), picks: 16 =
+ * v_mfma_f32_16x16x32_f16 (default), 32 = v_mfma_f32_32x32x16_f16.  Both laff_fc_strip_pack and laff_fc_act_bn_strip_grouped follow it,
+ * and the two image layouts differ (same size): AN IMAGE MUST BE LAUNCHED UNDER THE MODE IT WAS PACKED UNDER -- re-pack after changing
+ * the mode.  Results of the two agree to rounding (the MFMA-internal summation order differs), not bit for bit. */
 int laff_fc_strip_pack_bytes(int D, int Dk, size_t* out);
 int laff_fc_strip_pack(laff_ctx* ctx, const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D,
                        int Dk, int act, void* img);

@@ -167,6 +167,7 @@ int laff_ctx_create(int device, void* hip_stream, laff_ctx** out) {
     // test that set LAFF_STRIP=2, dropped it and made a new ctx used to leave every later bf16 similarity on the strip kernel)
     auto knob = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
     laff::g_strip_mode = knob("LAFF_STRIP", 1);
+    laff::g_fc_strip_mfma = knob("LAFF_FC_STRIP_MFMA", 16) == 32 ? 32 : 16;
     int n = 0;
     HIP_TRY(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return fail(LAFF_E_ARG, "laff_ctx_create: device %d out of range (%d devices)", device, n);

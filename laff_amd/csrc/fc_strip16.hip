@@ -1,32 +1,24 @@
-// fc_strip.hip -- TransformNet.forward (FC -> activation -> folded BatchNorm; /root/reference/model/model.py:257-276) for K = 512 inputs
-// as a STRIP kernel for gfx950, X stationary:
+// fc_strip16.hip -- fc_strip.hip's strip kernel (TransformNet.forward for K = 512 inputs: FC -> activation -> folded BatchNorm, X
+// stationary in the accumulator registers, W streamed from a packed LDS image) on v_mfma_f32_16x16x32_f16 instead of
+// v_mfma_f32_32x32x16_f16: the same flops in the same cycles, at less energy per flop -- the chip holds a higher clock on this shape
+// (docs/experiments.md, "fc_strip on 16x16x32 MFMAs"; tools/probe/fcshapeprobe.hip).  Selected by LAFF_FC_STRIP_MFMA (api.hip).
 //
-//   Y[r][c] = bn_s[c] * act( sum_k X[r][k] W[c][k] + bias[c] ) + bn_t[c]          fp32 in / fp32 out, fp32-class accuracy
-//
-// on the fp16 matrix pipe: X = s_r (Xhi + Xlo), W = s_c (Whi + Wlo) with power-of-two scales (row maximum scaled into [512, 1024)), the
-// three products lo*hi + hi*lo + hi*hi accumulate in fp32 (fp16 x fp16 products are exact in fp32), the epilogue undoes the scales.
-//
-// The tiled kernel this replaces (gemm_nt.hip, gemm_tile_x3 with the input split fused) ran at 39 % MFMA utilisation and needed a separate
-// pass over the inputs for the row scales.  Here:
-//   * a workgroup is 4 wavefronts, ONE PER SIMD, 512 registers each.  A wavefront owns 32 input rows: it loads them ONCE (fp32, straight
-//     into the accumulator half of the register file), finds the row maxima there (a row lives in two lanes), and converts them in
-//     place into the MFMA A fragments of hi and lo for the WHOLE K = 512 (2 x 128 registers).  No row-scale launch, no split planes
-//     in memory, the conversion happens once per row -- not once per column tile;
-//   * only W moves: it is packed once per model (laff_fc_strip_pack) into an LDS image -- per block of 32 output columns and half of
-//     K one 32 KiB ring slot {hi plane, lo plane} x 16 sub-steps x 64 lanes x 16 bytes, i.e. exactly the ds_read_b128 fragment
-//     order -- so the LDS-DMA is a linear copy and a fragment read is lane-linear (conflict-free by construction).  W of a feature is
-//     1 MiB: it streams from L2;
-//   * per sub-step (16 k) two fragment reads feed three MFMAs 32x32x16 (Xlo.Whi, Xhi.Wlo, Xhi.Whi);
-//   * MFMA roles: A = X rows, B = W columns, so a lane's accumulators are 16 ROWS of ONE output column: the per-column epilogue
-//     parameters are four lane constants per block, and a store instruction (dword per lane) writes 2 rows x 128 contiguous bytes --
-//     whole cache lines without a transposing slab;
-//   * two accumulator sets alternate: the epilogue of block b - 1 (scale, bias, tanh on v_exp/v_rcp, BatchNorm, store) is issued in
-//     the shadow of block b's MFMAs, a few instructions behind each one, at places computed at compile time (make_plan) together
-//     with the operands of the counted s_waitcnt;
-//   * persistent grid: the (feature, strip, column block) units of ALL problems of a launch are cut into equal contiguous ranges.
-//
-// The k index inside a sub-step is permuted (any bijection is legal as long as A and B agree): lane (i, hh) element e holds
-// k = 16 j + 4 hh + (e & 3) + 8 (e >> 2), so that the strip load's 16-byte pieces of lanes hh = 0, 1 are adjacent in the row.
+// The decomposition is fc_strip.hip's, comment for comment: 4 wavefronts of 32 rows x K = 512 {hi, lo}, the 4 x 32 KiB ring + the
+// staging buffer, 8 LDS-DMA pieces per wave and slot, 64 fragment reads per column block of 32 outputs, persistent ranges, the early
+// rounds of the next strip, the accumulator-file guard, the three epilogue kinds, the image size and the [D][4] constant table.  What
+// differs is the fragment geometry:
+//   * A (the strip): lane (i = lane & 15, g = lane >> 4) holds rows i and i + 16 of the wave's 32 (row tiles t = 0, 1).  K step J
+//     (32 k), row tile t: a[16 J + 8 t .. + 3] = hi halves, a[16 J + 8 t + 4 .. + 7] = lo halves; element e <-> k = 32 J + 4 g +
+//     (e & 3) + 16 (e >> 2), so that the four lanes of a row read adjacent 16-byte pieces of it.  One power-of-two scale per row,
+//     i.e. two per lane;
+//   * B (the W image): per ring slot {plane}{16 fragments = 8 K steps x 2 column tiles u}{64 lanes}{16 bytes}; MFMA column n of tile u
+//     is output column 2 n + u of the block, the k order is A's;
+//   * per K step twelve MFMAs of 16 cycles: for each product (Xlo.Whi, Xhi.Wlo, Xhi.Whi), column tile u, row tile t:
+//     acc[t][u] += ... -- an accumulator comes up every fourth MFMA;
+//   * a lane's 16 accumulators are 8 rows (16 t + 4 g + e) x 2 ADJACENT columns: the epilogue stores a dwordx2 per (t, e) -- 4 rows x
+//     128 contiguous bytes per instruction, 8 stores per block -- and the lane constants are two 16-byte loads;
+//   * the planner gives a 16-cycle MFMA slot at most 8 cycles of epilogue: one or two plain VALU, or one v_exp / v_rcp, or one store.
+// An image is read in the geometry it was packed in: fc_strip16_pack_kernel's images are not fc_strip_pack_kernel's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -36,6 +28,7 @@
 
 #include "kernels.h"
 #include "strip_util.h"
+#include "wave_reduce.h"
 
 namespace laff {
 
@@ -44,6 +37,7 @@ namespace {
 using namespace su;
 
 typedef __attribute__((address_space(1))) unsigned gu32;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FR = FC_STRIP_ROWS;              // 128 rows per strip: 4 wavefronts x 32
 constexpr int SLOT = 32 * 1024;                // one ring slot: 32 columns x 256 k x {hi, lo}
@@ -54,11 +48,11 @@ constexpr int XB_OFF = RING * SLOT;            // a fifth 32 KiB buffer, strip s
 constexpr int SMEM = XB_OFF + SLOT;
 static_assert(SMEM <= 160 * 1024, "LDS budget");
 
-constexpr int FD = 6;                          // fragment reads run FD sub-steps ahead,
-constexpr int NSETS = 8;                       // into 8 register sets (two planes each; 32 sub-steps per block: a divisor of 32)
-static_assert(32 % NSETS == 0 && FD < NSETS, "the set of a sub-step must not depend on the block");
-constexpr int BAR_J = 16 - FD;                 // the body's barrier sits in front of this sub-step
-constexpr int NSLOT = 96;                      // MFMA issue slots of a column block: 2 bodies x 16 sub-steps x 3
+constexpr int FD = 6;                          // fragment reads run FD fragments (K step, column tile) ahead,
+constexpr int NSETS = 8;                       // into 8 register sets (two planes each; 32 fragments per block: a divisor of 32)
+static_assert(32 % NSETS == 0 && FD < NSETS - 1 && FD % 2 == 0, "the set of a fragment must not depend on the block");
+constexpr int BAR_J = 16 - FD;                 // the body's barrier sits in front of this fragment (an even one: a K step)
+constexpr int NSLOT = 192;                     // MFMA issue slots of a column block: 2 bodies x 16 fragments x 6
 
 // ---- all 256 accumulator registers are named literally (the strip).  hipcc must not put anything of its own there (left alone it parks
 // long-lived values in a0.. when the 256 architectural registers get tight -- silently overwritten by the strip): 64 dummy quads are
@@ -92,9 +86,9 @@ __device__ __forceinline__ void agpr_write(unsigned x) { asm volatile("v_accvgpr
 
 // acc (+)= A(strip fragment in a[R .. R + 3]: rows of X) x B(fragment of the W stream: output columns)
 template <int R, bool FIRST>
-__device__ __forceinline__ void mfma_strip(f32x16& acc, const u32x4& wfrag) {
-    if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, a[%c2:%c3], %1, 0" : "=v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
-    else asm volatile("v_mfma_f32_32x32x16_f16 %0, a[%c2:%c3], %1, %0" : "+v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
+__device__ __forceinline__ void mfma_strip(f32x4& acc, const u32x4& wfrag) {
+    if constexpr (FIRST) asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c2:%c3], %1, 0" : "=v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
+    else asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c2:%c3], %1, %0" : "+v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
 }
 
 template <int IMM>
@@ -125,8 +119,8 @@ template <typename T>
 __device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
 // address = voff0 + ROWMUL * ldy4, made right in front of the store (one address register instead of one per accumulator)
 template <int ROWMUL>
-__device__ __forceinline__ void store_row(unsigned& tmp, float data, unsigned voff0, unsigned ldy4, u32x4 rsrc, unsigned soff) {
-    asm volatile("v_mad_u32_u24 %0, %3, %4, %2\n\tbuffer_store_dword %1, %0, %5, %6 offen nt"
+__device__ __forceinline__ void store_row(unsigned& tmp, f32x2 data, unsigned voff0, unsigned ldy4, u32x4 rsrc, unsigned soff) {
+    asm volatile("v_mad_u32_u24 %0, %3, %4, %2\n\tbuffer_store_dwordx2 %1, %0, %5, %6 offen nt"
                  : "=&v"(tmp) : "v"(data), "v"(voff0), "s"(ldy4), "n"(ROWMUL), "s"(rsrc), "s"(soff) : "memory");
 }
 
@@ -146,7 +140,7 @@ __device__ __forceinline__ void stash_chunk(const u32x4& q0, const u32x4& q1, fl
                  "v_accvgpr_write_b32 a[%c10+6], %8\n\tv_accvgpr_write_b32 a[%c10+7], %9"
                  : "+v"(m0), "+v"(m1) : "v"(q0.x), "v"(q0.y), "v"(q0.z), "v"(q0.w), "v"(q1.x), "v"(q1.y), "v"(q1.z), "v"(q1.w), "n"(R));
 }
-// a[R .. R + 7] (eight fp32: k = 16 g + 4 hh + {0..3}, + 8) -> a[R .. R + 3] = their fp16 hi halves, a[R + 4 .. R + 7] = the lo halves.
+// a[R .. R + 7] (eight fp32: k = 32 J + 4 g + {0..3}, + 16) -> a[R .. R + 3] = their fp16 hi halves, a[R + 4 .. R + 7] = the lo halves.
 //   hi = f16(x s) (x s is exact: s is a power of two), residual x s - hi exact in fp32, lo = f16(residual): split_rows_kernel's
 //   arithmetic (fuse.hip), as one statement with the four pairs' chains interleaved (a dependent VALU pair costs 7 cycles, not 4)
 template <int R>
@@ -181,19 +175,19 @@ __device__ __forceinline__ void split_pair(float& x0, float& x1, float s, unsign
 }
 
 // ---- the epilogue of a column block as a static stream of micro-ops -----------------------------------------------------------------
-// Per accumulator i (row 8 (i >> 2) + 4 hh + (i & 3) of the wave's 32, the lane's column):
-//   MUL t = acc * rs[i]   FMA1 t = t * c.x + c.y   [EXP t = 2^t   ADD1 t = t + 1   RCP t = 1 / t] | [MAX t = max(t, 0)]   FMA2 t = t * c.z + c.w   ST
-// with the lane constants c = {cs', b', c1, c0} folded by laff_fc_strip_pack so that the chain is the whole FC epilogue:
-//   tanh:    y' = 2 log2(e) (cs acc rs + bias), tanh = 1 - 2 / (2^y' + 1), out = (bn_s + bn_t) + (-2 bn_s) / (2^y' + 1)
-//   sigmoid: y' = -log2(e) (...),              out = bn_t + bn_s / (2^y' + 1)
-//   relu:    out = bn_s max(y, 0) + bn_t;      none: out = (cs bn_s) acc rs + (bn_s bias + bn_t)   (one fma)
-// Elements go in groups of four, stage by stage, so that a dependent pair is four instructions apart (the transcendental ->
-// VALU forwarding hazard needs one; hipcc pads nothing inside or between asm statements it cannot see into).
+// Per accumulator i = 8 t + 2 e + u (row 16 t + 4 g + e of the wave's 32, column 2 n + u of the block):
+//   MUL t = acc * rs[4 t + e]   FMA1 t = t * c.x + c.y   [EXP t = 2^t   ADD1 t = t + 1   RCP t = 1 / t] | [MAX t = max(t, 0)]   FMA2 t = t * c.z + c.w
+// and per pair (u = 0, 1) ST: one dwordx2.  The lane constants c = cv[u] = {cs', b', c1, c0} of the lane's two columns are folded by
+// laff_fc_strip_pack so that the chain is the whole FC epilogue (fc_strip.hip has the formulas).
+// Elements go in groups of four (two rows x two columns), stage by stage, so that a dependent pair is four instructions apart (the
+// transcendental -> VALU forwarding hazard needs one; hipcc pads nothing inside or between asm statements it cannot see into).
 enum : unsigned char { OP_WAITCV = 0, OP_MUL, OP_FMA1, OP_EXP, OP_ADD1, OP_RCP, OP_MAX, OP_FMA2, OP_ST };
 enum { ACT_LIN = 0, ACT_RELU = 1, ACT_EXP = 2 };                 // epilogue kinds (template parameter)
 struct EpiOp { unsigned char kind, elem; };
 struct EpiStream { EpiOp op[160]; int n; };
-constexpr int op_cost(unsigned char k) { return (k == OP_EXP || k == OP_RCP) ? 3 : (k == OP_WAITCV ? 0 : (k == OP_ST ? 2 : 1)); }
+// issue cycles beside a 16-cycle MFMA, which itself holds the vector issue for 8: a slot takes 8 more
+constexpr int op_cost(unsigned char k) { return (k == OP_EXP || k == OP_RCP || k == OP_ST) ? 8 : (k == OP_WAITCV ? 0 : 4); }
+constexpr int SLOT_CYCLES = 8;
 
 template <int ACTK>
 constexpr EpiStream make_stream() {
@@ -207,27 +201,30 @@ constexpr EpiStream make_stream() {
         stage(OP_FMA1);
         if (ACTK == ACT_EXP) { stage(OP_EXP); stage(OP_ADD1); stage(OP_RCP); stage(OP_FMA2); }
         if (ACTK == ACT_RELU) { stage(OP_MAX); stage(OP_FMA2); }
-        stage(OP_ST);
+        push(OP_ST, 4 * g);
+        push(OP_ST, 4 * g + 2);
     }
     return s;
 }
+constexpr int DRAIN_STORES = 8;                       // OP_ST items of the stream: what a drain leaves in the vector-memory queue
 
-// ---- the schedule of one column block (two bodies H = 0, 1 of 16 sub-steps J, three MFMAs M each): slot sg = 48 H + 3 J + M ----------
-//   * (J, 0): the two fragment reads (hi, lo plane) of the sub-step FD ahead -- from J = BAR_J on that is the NEXT ring slot;
-//   * in front of sub-step BAR_J: counted vmcnt (this wave's pieces of the next slot have landed) + s_barrier (everybody's have, and
+// ---- the schedule of one column block (two bodies H = 0, 1 of 16 fragments F = 2 Jl + u, six MFMAs each): slot sg = 96 H + 6 F + m ---
+// (the MFMAs of a K step's two fragments interleave -- see body -- but the slot of everything else is counted per fragment)
+//   * (F, 0): the two fragment reads (hi, lo plane) of the fragment FD ahead -- from F = BAR_J on that is the NEXT ring slot;
+//   * in front of fragment BAR_J: counted vmcnt (this wave's pieces of the next slot have landed) + s_barrier (everybody's have, and
 //     everybody is done with the previous slot, which the pieces issued right behind the barrier refill -- 4 slots: 3 ahead);
-//   * (BAR_J .. 15, M = 1) and two M = 2 slots: the 8 DMA pieces;  (H = 0, J = 0, M = 1): this block's four lane constants (one load);
-//     -- in the LAST THREE bodies of a segment those pieces would fetch W slots beyond it: they carry the first three K-eighth rounds
-//     of the NEXT strip's input rows instead (same count, same LDS targets: this wave's 8 KiB of the slot being freed); the first of
-//     the three also issues round 3 into the staging-only fifth buffer, and round 4 goes into the last body's slot in front of the
-//     drain: the strip switch starts with 40 of its 64 KiB per wave in LDS or on the way;
-//   * everything else: the epilogue stream of the previous block, spread evenly (cost-weighted).  It starts behind the third MFMA
-//     of the block (the previous block's last MFMA has retired by then) and ends before the block does.
+//   * (BAR_J .. 15, m = 2) and two m = 4 slots: the 8 DMA pieces;  slot 1 of the block: its lane constants (two loads);
+//     -- in the LAST THREE bodies of a segment the pieces carry the first three K-eighth rounds of the NEXT strip's input rows
+//     instead, the first of the three also issues round 3 into the staging-only fifth buffer, and round 4 goes into the last body's
+//     slot in front of the drain (fc_strip.hip);
+//   * everything else but the read slots: the epilogue stream of the previous block, spread evenly by issue cycles, at most
+//     SLOT_CYCLES per slot.  It starts behind the sixth MFMA of the block (the previous block's last MFMA has retired by then)
+//     and ends before the block does.
 constexpr int slot_piece(int sg) {
-    const int J = (sg % 48) / 3, M = sg % 3;
-    if (M == 1 && J >= BAR_J) return J - BAR_J;          // one per sub-step behind the barrier ...
-    if (M == 2 && J == BAR_J + 1) return 6;              // ... and two sub-steps with a second one: the four waves leave the barrier
-    if (M == 2 && J == BAR_J + 4) return 7;              // together, and pieces packed into four sub-steps queue up in the CU's one TA path
+    const int F = (sg % 96) / 6, m = sg % 6;
+    if (m == 2 && F >= BAR_J) return F - BAR_J;          // one per fragment behind the barrier ...
+    if (m == 4 && F == BAR_J + 1) return 6;              // ... and two fragments with a second one: the four waves leave the barrier
+    if (m == 4 && F == BAR_J + 4) return 7;              // together, and pieces packed into four fragments queue up in the CU's one TA path
     return -1;
 }
 constexpr bool slot_cvload(int sg) { return sg == 1; }
@@ -235,6 +232,7 @@ struct Plan {
     short begin[NSLOT + 1];
     short vm_bar[2];      // vmcnt operand at the barrier of body H
     short vm_cv;          // vmcnt operand in front of the first use of the previous block's lane constants
+    short st_half[2];     // stores of the stream issued in body H
     bool fits;
 };
 template <int ACTK>
@@ -242,17 +240,22 @@ constexpr Plan make_plan() {
     Plan p{};
     const EpiStream st = make_stream<ACTK>();
     int usable = 0, total = 0;
-    auto ok = [](int sg) { return sg >= 3 && slot_piece(sg) < 0; };
+    auto ok = [](int sg) { return sg >= 6 && sg % 6 != 0 && slot_piece(sg) < 0; };
     for (int sg = 0; sg < NSLOT; ++sg) usable += ok(sg) ? 1 : 0;
     for (int i = 0; i < st.n; ++i) total += op_cost(st.op[i].kind);
-    usable -= 4;                                        // finish a few slots early
+    usable -= 6;                                        // finish a few slots early
     int at = 0, k = 0, spent = 0;
     for (int sg = 0; sg < NSLOT; ++sg) {
         p.begin[sg] = (short)at;
         if (!ok(sg)) continue;
         ++k;
         const int target = (int)(((long)k * total + usable - 1) / usable);
-        while (at < st.n && spent < target) { spent += op_cost(st.op[at].kind); ++at; }
+        int here = 0;
+        while (at < st.n && spent < target) {
+            const int c = op_cost(st.op[at].kind);
+            if (here + c > SLOT_CYCLES) break;
+            here += c; spent += c; ++at;
+        }
     }
     p.begin[NSLOT] = (short)at;
     p.fits = at == st.n;
@@ -260,13 +263,13 @@ constexpr Plan make_plan() {
     int vm_n = 0, last_piece[3][2] = {}, cv_ord[3] = {}, bar_at[3][2] = {}, waitcv_at[3] = {};
     for (int blk = 0; blk < 3; ++blk)
         for (int sg = 0; sg < NSLOT; ++sg) {
-            const int H = sg / 48, J = (sg % 48) / 3, M = sg % 3;
-            if (J == BAR_J && M == 0) bar_at[blk][H] = vm_n;
-            if (slot_cvload(sg)) cv_ord[blk] = ++vm_n;
+            const int H = sg / 96, F = (sg % 96) / 6, m = sg % 6;
+            if (F == BAR_J && m == 0) bar_at[blk][H] = vm_n;
+            if (slot_cvload(sg)) { vm_n += 2; cv_ord[blk] = vm_n; }
             if (slot_piece(sg) >= 0) { ++vm_n; last_piece[blk][H] = vm_n; }
             for (int i = p.begin[sg]; i < p.begin[sg + 1]; ++i) {
                 if (st.op[i].kind == OP_WAITCV) waitcv_at[blk] = vm_n;
-                if (st.op[i].kind == OP_ST) ++vm_n;
+                if (st.op[i].kind == OP_ST) { ++vm_n; if (blk == 2) ++p.st_half[H]; }
             }
         }
     auto clamp = [](int c) { return c < 0 ? 0 : (c > 63 ? 63 : c); };
@@ -279,13 +282,13 @@ constexpr Plan make_plan() {
 }  // namespace
 
 template <int ACTK>
-__global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
+__global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     AgprHold hold;
     agpr_hold_begin(hold);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n31 = lane & 31, hh = lane >> 5;
+    const int n15 = lane & 15, g4 = lane >> 4;
     const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem);
 
     const int nblk = pin_s(a.nblk), count = pin_s(a.count);
@@ -298,7 +301,6 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
 
     constexpr Plan PLAN = make_plan<ACTK>();
     constexpr EpiStream STREAM = make_stream<ACTK>();
-    constexpr int DRAIN_STORES = 16;                      // OP_ST items of the stream: what a drain leaves in the vector-memory queue
     static_assert(PLAN.fits, "the epilogue stream does not fit behind the MFMAs of one column block");
 
     // per-lane constants of the loops
@@ -307,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
     const unsigned xa0 = lds0 + lane16, xa1 = lds0 + lane16 + 2u * SLOT;      // fragment addresses: ring slots 0, 1 | 2, 3
     const unsigned wslot = (unsigned)wave * (PIECES * 1024u);                   // this wave's 8 KiB of a slot (LDS and source offset)
     const unsigned ldsw = pin_s(lds0 + wslot);                                  // LDS address of this wave's 8 KiB of ring slot 0
-    const unsigned cvoff = (unsigned)n31 * 16u;
+    const unsigned cvoff = (unsigned)n15 * 32u;                                 // the constants of columns 2 n, 2 n + 1: 32 bytes
     int pre_base = -1;           // >= 0: the previous segment's last three bodies brought rounds 0..2 of this segment's strip into buffers (e + pre_base) & 3
     const unsigned m0_keep = m0_get();
 #ifdef LAFF_FCS_TRACE
@@ -370,63 +372,65 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         const unsigned long long pVec = pin_s((unsigned long long)a.p[p].vec), pY = pin_s((unsigned long long)a.p[p].Y);
         const int row0 = strip * FR;
 
-        f32x16 acc[2];
+        f32x4 acc[2][2][2];              // [set][row tile t][column tile u]
         u32x4 fr[NSETS][2];
-        float rs[16];
-        float tt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float rs[8];
+        f32x2 tt[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
         unsigned ta[4] = {0, 0, 0, 0};
-        f32x4 cv[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        f32x4 cv[2][2] = {{{0, 0, 0, 0}, {0, 0, 0, 0}}, {{0, 0, 0, 0}, {0, 0, 0, 0}}};      // [set][column u]
 
-        int e_row = 0;                   // exponent of this lane's row maximum: scale 2^(9 - e) in, 2^(e - 9) out
+        int e_row[2] = {0, 0};           // exponents of this lane's two row maxima: scale 2^(9 - e) in, 2^(e - 9) out
         // ---- the strip: this wave's 32 rows x 512 fp32 -> a[0:255] (raw), eight rounds through four wave-private buffers -- this wave's
         // 8 KiB of each (idle) ring slot; round e lives in buffer (e + base) & 3.  Rounds 0..2 are already there when the previous
-        // segment's last bodies brought them (pre_base); up to four rounds are in flight.  The read-back (lane (row n31, half hh) takes
-        // 16-byte pieces 4 cc + hh and 4 cc + 2 + hh of chunk cc) folds the row maxima and parks the raw values in the accumulator file.
+        // segment's last bodies brought them (pre_base); up to four rounds are in flight.  The read-back (a round is two K steps jj; chunk
+        // cc = 2 jj + t: lane (i, g) takes the 16-byte pieces 8 jj + g and 8 jj + 4 + g of row i + 16 t) folds the row maxima and parks
+        // the raw values in the accumulator file.  Within each of ds_read_b128's four lane groups the sixteen lanes have sixteen
+        // different i, and g only xors a constant into the swizzled position: sixteen different 16-byte columns, no bank conflict.
         {
             const unsigned long long xbase = pX + (unsigned long long)row0 * (unsigned)ldx * 4ull;
             unsigned xv[8];
             xoff(p, strip, xv);
             const bool pre = pre_base >= 0;
             const int base = pre ? pre_base : 0;
-            unsigned XA[8];                            // read-back addresses inside a buffer: (cc, quad) -> piece 4 cc + 2 quad + hh, swizzled
+            unsigned XA[8];                            // read-back addresses inside a buffer: (cc, quad) -> row i + 16 t, piece 8 jj + 4 quad + g, swizzled
             {
                 unsigned ln = (unsigned)lane;
                 asm volatile("" : "+v"(ln));
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    XA[j] = (ln & 31u) * 256u + ((((unsigned)(4 * (j >> 1) + 2 * (j & 1)) + (ln >> 5)) ^ (ln & 15u)) << 4);
+                    XA[j] = ((ln & 15u) + 16u * (unsigned)((j >> 1) & 1)) * 256u + ((((unsigned)(8 * (j >> 2) + 4 * (j & 1)) + (ln >> 4)) ^ (ln & 15u)) << 4);
             }
             // round -> buffer.  Without early rounds: 0 1 2 3 X 0 1 2 (five in flight).  With them: rounds 0..2 sit in ring slots b0 b1 b2
             // (b_i = (i + base) & 3), round 3 in X, round 4 in b3 (the previous segment's last slot): b0 b1 b2 X b3 b0 b1 X -- round 7 follows
             // round 3, which landed long ago, not round 2, the last one to have been issued.
-            auto buf_of = [&](int e) {
+            auto buf_of = [&](int e) __attribute__((always_inline)) {
                 const int ring = pre ? (e < 3 ? e : (e == 4 ? 3 : e - 5)) : (e < 4 ? e : e - 5);
                 const bool x = pre ? (e == 3 || e == 7) : e == 4;
                 return ldsw + (unsigned)(x ? RING : ((ring + base) & 3)) * (unsigned)SLOT;
             };
-            auto issue_round = [&](auto EC) {
+            auto issue_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
                 const unsigned long long ebase = xbase + (unsigned long long)(e * 256);
                 const unsigned b = pin_s(buf_of(e));
-                static_for<0, 8>([&](auto TC) {
+                static_for<0, 8>([&](auto TC) __attribute__((always_inline)) {
                     constexpr int t = decltype(TC)::value;
                     dma_rows<t * 1024>(xv[t], ebase, b);
                 });
             };
-            float m0 = 0.f, m1 = 0.f;                  // running maxima of |x| over this lane's half of its row
+            float m0[2] = {0.f, 0.f}, m1[2] = {0.f, 0.f};   // running maxima of |x| over this lane's quarter of its two rows [t]
             u32x4 rq[8];
-            auto read_round = [&](auto EC) {
+            auto read_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
                 const unsigned b = buf_of(e);
-                static_for<0, 8>([&](auto JC) { constexpr int j = decltype(JC)::value; lds_read128<0>(rq[j], XA[j] + b); });
+                static_for<0, 8>([&](auto JC) __attribute__((always_inline)) { constexpr int j = decltype(JC)::value; lds_read128<0>(rq[j], XA[j] + b); });
                 wait_lgkm<0>();
-                static_for<0, 8>([&](auto IC) { pin_v(rq[decltype(IC)::value]); });
+                static_for<0, 8>([&](auto IC) __attribute__((always_inline)) { pin_v(rq[decltype(IC)::value]); });
             };
-            auto stash_round = [&](auto EC) {
+            auto stash_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
-                static_for<0, 4>([&](auto CC) {
+                static_for<0, 4>([&](auto CC) __attribute__((always_inline)) {
                     constexpr int cc = decltype(CC)::value;
-                    stash_chunk<8 * (4 * e + cc)>(rq[2 * cc], rq[2 * cc + 1], m0, m1);
+                    stash_chunk<8 * (4 * e + cc)>(rq[2 * cc], rq[2 * cc + 1], m0[cc & 1], m1[cc & 1]);
                 });
             };
             using E0 = std::integral_constant<int, 0>; using E1 = std::integral_constant<int, 1>; using E2 = std::integral_constant<int, 2>;
@@ -440,12 +444,12 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
                 wait_vm<32>(); read_round(E3{}); stash_round(E3{});
                 wait_vm<24>(); read_round(E4{}); stash_round(E4{});
             } else {
-                // The queue holds, oldest first: round 3 and round 0 (tail body 1), round 1 (body 2: 8 pieces, 8 stores, the lane constants),
-                // round 2 (body 3: 8 + 8), round 4 (8, in front of the drain), the drain's stores.  The counts are lower bounds of what was
+                // The queue holds, oldest first: round 3 and round 0 (tail body 1), round 1 (body 2: 8 pieces, its stores, the two loads of the
+                // lane constants), round 2 (body 3: 8 + its stores), round 4 (8, in front of the drain), the drain's stores.  The counts are lower bounds of what was
                 // issued behind the round waited for.
-                constexpr int DR = DRAIN_STORES;
-                wait_vm<17 + 16 + 8 + DR>(); read_round(E0{}); issue_round(E5{}); stash_round(E0{});
-                wait_vm<16 + 8 + DR + 8>(); read_round(E1{}); issue_round(E6{}); stash_round(E1{});
+                constexpr int DR = DRAIN_STORES, S1 = PLAN.st_half[1];       // (DR = the stores of bodies 2 and 3 together)
+                wait_vm<(10 + 8 + DR) + 8 + DR>(); read_round(E0{}); issue_round(E5{}); stash_round(E0{});
+                wait_vm<(8 + S1) + 8 + DR + 8>(); read_round(E1{}); issue_round(E6{}); stash_round(E1{});
                 read_round(E3{}); issue_round(E7{}); stash_round(E3{});
                 wait_vm<8 + DR + 24>(); read_round(E2{}); stash_round(E2{});
                 wait_vm<24>(); read_round(E4{}); stash_round(E4{});
@@ -453,9 +457,13 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             wait_vm<16>(); read_round(E5{}); stash_round(E5{});
             wait_vm<8>(); read_round(E6{}); stash_round(E6{});
             wait_vm<0>(); read_round(E7{}); stash_round(E7{});
-            float m = fmaxf(m0, m1);
-            m = fmaxf(m, __shfl_xor(m, 32));           // a row lives in lanes l and l + 32
-            e_row = split_exponent(m);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {              // a row lives in lanes i, i + 16, i + 32, i + 48
+                float m = fmaxf(m0[t], m1[t]);
+                m = wave_step32<16>(m, [](float x, float y) { return fmaxf(x, y); });
+                m = wave_step32<32>(m, [](float x, float y) { return fmaxf(x, y); });
+                e_row[t] = split_exponent(m);
+            }
             pre_base = has_next ? ((n & 1) ? 2 : 0) : -1;   // where this segment's last three bodies will leave the next strip's rounds 0..2
         }
         __builtin_amdgcn_s_barrier();            // every wave has emptied its staging quarter: the ring may fill
@@ -466,9 +474,9 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         // strip is converted.  The image as a raw buffer starting at this wave's 8 KiB of a slot ----
         const u32x4 rsrcW = rebased_rsrc(pW, img_bytes, wslot);
         unsigned soffW = (unsigned)blk0 * (2u * SLOT);                        // image offset of the slot the next pieces belong to
-        static_for<0, 3>([&](auto SC) {
+        static_for<0, 3>([&](auto SC) __attribute__((always_inline)) {
             constexpr int s = decltype(SC)::value;
-            static_for<0, PIECES>([&](auto PC) {
+            static_for<0, PIECES>([&](auto PC) __attribute__((always_inline)) {
                 constexpr int P = decltype(PC)::value;
                 dma_piece<s * SLOT + P * 1024>(lane16 + (unsigned)(P * 1024), rsrcW, std::min(soffW, img_bytes - SLOT), ldsw);
             });
@@ -478,39 +486,39 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         // ---- the raw strip is converted in place ----
         STAMP(2);
         {
-            const float s = pow2f(9 - e_row);
+            const float s0 = pow2f(9 - e_row[0]), s1 = pow2f(9 - e_row[1]);
             asm volatile("s_nop 1" ::: "memory");
-            // sub-step g: hi <- a[8 g .. 8 g + 3], lo <- a[8 g + 4 .. 8 g + 7]; halves e = 0 .. 7 <-> raw registers 8 g + e
-            static_for<0, 32>([&](auto GC) { convert_chunk_inplace<8 * decltype(GC)::value>(s); });
+            // chunk c = 2 J + t: hi <- a[8 c .. 8 c + 3], lo <- a[8 c + 4 .. 8 c + 7]; halves e = 0 .. 7 <-> raw registers 8 c + e
+            static_for<0, 32>([&](auto GC) __attribute__((always_inline)) { convert_chunk_inplace<8 * decltype(GC)::value>((decltype(GC)::value & 1) ? s1 : s0); });
         }
         asm volatile("s_nop 3" ::: "memory");            // v_accvgpr_write -> MFMA reading it
         STAMP(3);
         {
-            // the epilogue's row scales: lane (n31, hh) needs those of rows 8 q + 4 hh + e, which lane 8 q + 4 hh + e has
-            const float mine = pow2f(e_row - 9);
+            // the epilogue's row scales: lane (n, g) needs those of rows 16 t + 4 g + e, which lane 4 g + e has for both t
+            const float mine0 = pow2f(e_row[0] - 9), mine1 = pow2f(e_row[1] - 9);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) rs[i] = __shfl(mine, 8 * (i >> 2) + 4 * hh + (i & 3));
+            for (int i = 0; i < 8; ++i) rs[i] = __shfl((i >> 2) ? mine1 : mine0, 4 * g4 + (i & 3));
         }
-        // output addressing: row 8 q + 4 hh + e of the wave's 32 at voff0 + (8 q + e) ldy4
+        // output addressing: row 16 t + 4 g + e of the wave's 32, columns 2 n, 2 n + 1 of the block, at voff0 + (16 t + e) ldy4
         const unsigned ldy4 = (unsigned)ldy * 4u;
-        unsigned voff0 = ((unsigned)(wave * 32 + 4 * hh) * (unsigned)ldy + (unsigned)n31) * 4u;
+        unsigned voff0 = ((unsigned)(wave * 32 + 4 * g4) * (unsigned)ldy + 2u * (unsigned)n15) * 4u;
         // the output rows of this strip as a raw buffer: rows beyond N are dropped by its bounds check (voff carries the row)
         const u32x4 rsrcY = rebased_rsrc(pY + (unsigned long long)row0 * (unsigned)ldy * 4ull,
                                          ((unsigned long long)(std::min(FR, N - row0) - 1) * (unsigned)ldy + (unsigned)(nblk * 32)) * 4ull, 0ull);
         const u32x4 rsrcNone = {0u, 0u, 0u, 0x00020000u};
-        // the lane constants {cs', b', c1, c0} of column 32 blk + n31: [D][4] floats
+        // the lane constants {cs', b', c1, c0} of columns 32 blk + 2 n, + 1: [D][4] floats
         const u32x4 rsrcV = rebased_rsrc(pVec, (unsigned long long)nblk * 512ull, 0ull);
 
         // everything the prologue loaded is in registers by now: pin hipcc's own waits here, not inside the hand-counted loops
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(rs[i]));
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(rs[i]));
         asm volatile("" : "+v"(voff0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         STAMP(4);
-        // fragments of sub-steps 0 .. FD - 1 of the first slot
-        static_for<0, FD>([&](auto JC) {
+        // fragments 0 .. FD - 1 of the first slot
+        static_for<0, FD>([&](auto JC) __attribute__((always_inline)) {
             constexpr int j = decltype(JC)::value;
             lds_read128<j * 1024>(fr[j][0], xa0);
             lds_read128<PLANE + j * 1024>(fr[j][1], xa0);
@@ -523,37 +531,37 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
         using IM1 = std::integral_constant<int, -1>;
-        auto epi_item = [&](auto QC, auto IC, auto DRAIN) {
+        auto epi_item = [&](auto QC, auto IC, auto DRAIN) __attribute__((always_inline)) {
             constexpr int Q = decltype(QC)::value;
             constexpr EpiOp op = STREAM.op[decltype(IC)::value];
-            constexpr int i = op.elem;
+            constexpr int i = op.elem, u = i & 1, e = (i >> 1) & 3, t = i >> 3, k = (i >> 1) & 3;     // tt[k] = the pair (u = 0, 1)
             if constexpr (op.kind == OP_WAITCV) {
-                // (drain: the lane constants were the block's first vector-memory operation: 16 pieces and 16 stores came behind them --
-                // a vmcnt(0) here would also wait for the next strip's rows the last bodies have just asked for)
-                // (a drain: the two bodies behind the load issued 2 x (8 pieces + 8 stores); DRAIN counts what else was)
-                if constexpr (decltype(DRAIN)::value >= 0) wait_vm<32 + decltype(DRAIN)::value>(); else wait_vm<PLAN.vm_cv>();
-                asm volatile("" : "+v"(cv[Q]));
+                // (drain: the lane constants were the block's first vector-memory operations: 16 pieces and the block's stores came behind
+                // them -- a vmcnt(0) here would also wait for the next strip's rows the last bodies have just asked for; DRAIN counts
+                // what else was issued)
+                if constexpr (decltype(DRAIN)::value >= 0) wait_vm<16 + DRAIN_STORES + decltype(DRAIN)::value>(); else wait_vm<PLAN.vm_cv>();
+                asm volatile("" : "+v"(cv[Q][0]), "+v"(cv[Q][1]));
             } else if constexpr (op.kind == OP_MUL) {
-                asm volatile("v_mul_f32 %0, %1, %2" : "=v"(tt[i & 7]) : "v"(acc[Q][i]), "v"(rs[i]));
+                asm volatile("v_mul_f32 %0, %1, %2" : "=v"(tt[k][u]) : "v"(acc[Q][t][u][e]), "v"(rs[4 * t + e]));
             } else if constexpr (op.kind == OP_FMA1) {
-                asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(tt[i & 7]) : "v"(cv[Q].x), "v"(cv[Q].y));
+                asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(tt[k][u]) : "v"(cv[Q][u].x), "v"(cv[Q][u].y));
             } else if constexpr (op.kind == OP_EXP) {
-                asm volatile("v_exp_f32 %0, %0" : "+v"(tt[i & 7]));
+                asm volatile("v_exp_f32 %0, %0" : "+v"(tt[k][u]));
             } else if constexpr (op.kind == OP_ADD1) {
-                asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(tt[i & 7]));
+                asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(tt[k][u]));
             } else if constexpr (op.kind == OP_RCP) {
-                asm volatile("v_rcp_f32 %0, %0" : "+v"(tt[i & 7]));
+                asm volatile("v_rcp_f32 %0, %0" : "+v"(tt[k][u]));
             } else if constexpr (op.kind == OP_MAX) {
-                asm volatile("v_max_f32 %0, 0, %0" : "+v"(tt[i & 7]));
+                asm volatile("v_max_f32 %0, 0, %0" : "+v"(tt[k][u]));
             } else if constexpr (op.kind == OP_FMA2) {
-                asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(tt[i & 7]) : "v"(cv[Q].z), "v"(cv[Q].w));
+                asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(tt[k][u]) : "v"(cv[Q][u].z), "v"(cv[Q][u].w));
             } else if constexpr (op.kind == OP_ST) {
-                store_row<8 * (i >> 2) + (i & 3)>(ta[i & 3], tt[i & 7], voff0, ldy4, rsrcYe, soffY);
+                store_row<16 * t + e>(ta[k], tt[k], voff0, ldy4, rsrcYe, soffY);
             }
         };
 
         // ---- one body: half a column block (ring slot 2 PAR + H), see "the schedule of one column block" --------------------------------
-        auto body = [&](auto PARC, auto HC, auto XRC, int blk) {
+        auto body = [&](auto PARC, auto HC, auto XRC, int blk) __attribute__((always_inline)) {
             constexpr int PAR = decltype(PARC)::value, H = decltype(HC)::value, Q = PAR ^ 1;
             constexpr int XR = decltype(XRC)::value;                 // >= 0: the pieces carry round XR of the next strip's rows, not the W stream
             constexpr int RSLOT = 2 * PAR + H;                                   // this body's ring slot
@@ -562,29 +570,32 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             const unsigned soff_here = std::min(soffW, img_bytes - SLOT);
             soffW += SLOT;
             if constexpr (H == 0) soffY = (unsigned)(blk - 1) * 128u;
-            static_for<0, 16>([&](auto JC) {
-                constexpr int J = decltype(JC)::value;
-                constexpr int G = 16 * H + J;                                    // sub-step of the block: strip registers 8 G ..
-                if constexpr (J == BAR_J) {
+            static_for<0, 16>([&](auto FC) __attribute__((always_inline)) {
+                constexpr int F = decltype(FC)::value;                           // fragment of the slot: K step Jl = F >> 1, column tile F & 1
+                constexpr int G = 16 * H + F;                                    // fragment of the block: register set G % NSETS
+                if constexpr (F == BAR_J) {
                     // (the segment's last body has no next slot to wait for: what is in flight is the next strip's)
                     if constexpr (XR != 2) wait_vm<PLAN.vm_bar[H]>();
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
                 }
-                wait_lgkm<2 * (FD - 1)>();                                       // the two fragments of this sub-step have arrived
+                if constexpr (F % 2 == 0) wait_lgkm<2 * (FD - 2)>();             // the four fragments of this K step have arrived
                 __builtin_amdgcn_sched_barrier(0);
-                static_for<0, 3>([&](auto MC) {
-                    constexpr int M = decltype(MC)::value, SG = 48 * H + 3 * J + M;
-                    // lo.hi, hi.lo (small terms first), hi.hi
-                    if constexpr (M == 0) mfma_strip<8 * G + 4, (G == 0)>(acc[PAR], fr[G % NSETS][0]);
-                    else if constexpr (M == 1) mfma_strip<8 * G, false>(acc[PAR], fr[G % NSETS][1]);
-                    else mfma_strip<8 * G, false>(acc[PAR], fr[G % NSETS][0]);
+                static_for<0, 6>([&](auto MC) __attribute__((always_inline)) {
+                    constexpr int m = decltype(MC)::value, SG = 96 * H + 6 * F + m;
+                    // the twelve MFMAs of a K step: product by product -- lo.hi, hi.lo (small terms first), hi.hi -- over the four
+                    // accumulators (column tile, row tile): an accumulator comes up every fourth MFMA
+                    constexpr int s12 = SG % 12, JG = SG / 12, M = s12 / 4, u = (s12 % 4) / 2, t = s12 & 1;
+                    constexpr int R = 16 * JG + 8 * t, GS = (2 * JG + u) % NSETS;
+                    if constexpr (M == 0) mfma_strip<R + 4, (JG == 0)>(acc[PAR][t][u], fr[GS][0]);
+                    else if constexpr (M == 1) mfma_strip<R, false>(acc[PAR][t][u], fr[GS][1]);
+                    else mfma_strip<R, false>(acc[PAR][t][u], fr[GS][0]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (M == 0) {
-                        // fragments of the sub-step FD ahead (this slot, or the next one behind the barrier)
-                        constexpr int JN = J + FD;
-                        constexpr int RS = JN < 16 ? RSLOT : NSLOT_R, JJ = JN & 15, GN = (G + FD) % NSETS;
-                        constexpr int OFFS = (RS & 1) * SLOT + JJ * 1024;
+                    if constexpr (m == 0) {
+                        // the fragment FD ahead (this slot, or the next one behind the barrier)
+                        constexpr int FN = F + FD;
+                        constexpr int RS = FN < 16 ? RSLOT : NSLOT_R, FF = FN & 15, GN = (G + FD) % NSETS;
+                        constexpr int OFFS = (RS & 1) * SLOT + FF * 1024;
                         if constexpr (RS < 2) {
                             lds_read128<OFFS>(fr[GN][0], xa0);
                             lds_read128<OFFS + PLANE>(fr[GN][1], xa0);
@@ -596,11 +607,12 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
                     if constexpr (slot_cvload(SG)) {
                         // this block's lane constants (used by its epilogue, in the next block's bodies or in the drain)
                         const unsigned so = (unsigned)blk * 512u;
-                        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(cv[PAR]) : "v"(cvoff), "s"(rsrcV), "s"(so) : "memory");
+                        asm volatile("buffer_load_dwordx4 %0, %2, %3, %4 offen\n\tbuffer_load_dwordx4 %1, %2, %3, %4 offen offset:16"
+                                     : "=&v"(cv[PAR][0]), "=&v"(cv[PAR][1]) : "v"(cvoff), "s"(rsrcV), "s"(so) : "memory");
                     }
-                    if constexpr (XR == 0 && M == 1 && J < 8) {
+                    if constexpr (XR == 0 && m == 2 && F < 8) {
                         // round 3 of the next strip, to the staging-only buffer (no ring slot: no barrier to respect)
-                        dma_piece<XB_OFF + J * 1024>(xvn[J], rsrcXn, 3u * 256u, ldsw);
+                        dma_piece<XB_OFF + F * 1024>(xvn[F], rsrcXn, 3u * 256u, ldsw);
                     }
                     constexpr int dp = slot_piece(SG);
                     if constexpr (dp >= 0) {
@@ -609,7 +621,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
                         if constexpr (XR >= 0) dma_piece<DSLOT * SLOT + dp * 1024>(xvn[dp], rsrcXn, (unsigned)(256 * XR), ldsw);
                         else dma_piece<DSLOT * SLOT + dp * 1024>(lane16 + (unsigned)(dp * 1024), rsrcW, soff_here, ldsw);
                     }
-                    static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) {
+                    static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) __attribute__((always_inline)) {
                         __builtin_amdgcn_sched_barrier(0);
                         epi_item(std::integral_constant<int, Q>{}, IC, IM1{});
                     });
@@ -618,20 +630,20 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             });
         };
 
-        auto drain = [&](auto QC, auto EXTRA, int blk) {
+        auto drain = [&](auto QC, auto EXTRA, int blk) __attribute__((always_inline)) {
             STAMP(5);
             mfma_drain_nops();
             rsrcYe = rsrcY;
             soffY = (unsigned)blk * 128u;
-            static_for<0, STREAM.n>([&](auto IC) { epi_item(QC, IC, EXTRA); });
+            static_for<0, STREAM.n>([&](auto IC) __attribute__((always_inline)) { epi_item(QC, IC, EXTRA); });
         };
         // The segment's blocks: a plain loop, then -- when a next segment exists -- its last two blocks as the copies whose last three bodies
         // fetch the next strip's first three rounds (compile-time copies: the plain loop keeps its one branch per two blocks).
-        auto plain = [&](auto PARC, int b) {
+        auto plain = [&](auto PARC, int b) __attribute__((always_inline)) {
             body(PARC, I0{}, IM1{}, blk0 + b);
             body(PARC, I1{}, IM1{}, blk0 + b);
         };
-        auto tail = [&](auto PARC, int b) {
+        auto tail = [&](auto PARC, int b) __attribute__((always_inline)) {
             constexpr int P = decltype(PARC)::value;
             body(PARC, I0{}, IM1{}, blk0 + b);
             body(PARC, I1{}, I0{}, blk0 + b);
@@ -642,14 +654,14 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             // body's slot and flies while the drain computes.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            static_for<0, 8>([&](auto TC) {
+            static_for<0, 8>([&](auto TC) __attribute__((always_inline)) {
                 constexpr int t = decltype(TC)::value;
                 dma_piece<(2 * (P ^ 1) + 1) * SLOT + t * 1024>(xvn[t], rsrcXn, 4u * 256u, ldsw);
             });
             drain(std::integral_constant<int, P ^ 1>{}, std::integral_constant<int, 8>{}, blk0 + b + 1);
         };
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[1][e] = 0.0f;
+        for (int e = 0; e < 4; ++e) acc[1][0][0][e] = acc[1][0][1][e] = acc[1][1][0][e] = acc[1][1][1][e] = 0.0f;
         {
             const int m = has_next ? n - 2 : n;          // blocks of the plain loop
             int b = 0, par = 0;                          // par: parity of the block behind the plain loop
@@ -689,10 +701,10 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
 
 // ---- W [D][512] fp32 (+ bias, BatchNorm, activation) -> the LDS image + the lane-constant table -------------------------------------
 // One workgroup (256 threads) per output column: row maximum -> power-of-two scale (as split_rows_kernel), hi / lo halves scattered
-// into the image {block n / 32}{K half}{plane}{sub-step}{lane = 32 hh + n % 32}{8 halves}.
-__global__ __launch_bounds__(256) void fc_strip_pack_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias,
-                                                            const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int D,
-                                                            int act, _Float16* __restrict__ img, float* __restrict__ vec) {
+// into the image {block n / 32}{K half}{plane}{fragment = 2 (K step % 8) + (n & 1)}{lane = 16 g + (n % 32) / 2}{8 halves}.
+__global__ __launch_bounds__(256) void fc_strip16_pack_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias,
+                                                              const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int D,
+                                                              int act, _Float16* __restrict__ img, float* __restrict__ vec) {
     __shared__ float red[4];
     const int n = blockIdx.x, tid = threadIdx.x;
     if (n >= D) return;
@@ -705,16 +717,16 @@ __global__ __launch_bounds__(256) void fc_strip_pack_kernel(const float* __restr
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     const int e = split_exponent(m);
     const float s = pow2f(9 - e), cs = pow2f(e - 9);
-    const int blk = n >> 5, n31 = n & 31;
+    const int blk = n >> 5, n15 = (n & 31) >> 1, u = n & 1;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int k = t * 256 + tid;
         const float x = (t ? x1 : x0) * s;
         const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-        const int j = k >> 4, w = k & 15;
-        const int half = j >> 4, jj = j & 15, hh = (w >> 2) & 1, pos = (w & 3) + 4 * (w >> 3);
+        const int J = k >> 5, w = k & 31;                                         // k = 32 J + 4 g + (pos & 3) + 16 (pos >> 2)
+        const int half = J >> 3, Jl = J & 7, g = (w >> 2) & 3, pos = (w & 3) + 4 * (w >> 4);
         const size_t base = ((size_t)(blk * 2 + half) * 2) * (PLANE / 2);        // in halves: slot start
-        const size_t at = (size_t)(jj * 64 + 32 * hh + n31) * 8 + pos;
+        const size_t at = (size_t)((2 * Jl + u) * 64 + 16 * g + n15) * 8 + pos;
         img[base + at] = h;
         img[base + PLANE / 2 + at] = l;
     }
@@ -729,42 +741,23 @@ __global__ __launch_bounds__(256) void fc_strip_pack_kernel(const float* __restr
     }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
-size_t fc_strip_image_bytes(int D) { return (size_t)(D / 32) * (2 * SLOT) + (size_t)D * 16; }
-size_t fc_strip_vec_offset(int D) { return (size_t)(D / 32) * (2 * SLOT); }
+// ---- host side (the image size and the constant table's place are fc_strip.hip's: fc_strip_image_bytes, fc_strip_vec_offset) ---------
+int g_fc_strip_mfma = 16;    // LAFF_FC_STRIP_MFMA (read when a ctx is created): 16 = this file's kernels (default), 32 = fc_strip.hip's
 
-hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
-                                void* img, hipStream_t st) {
-    if (g_fc_strip_mfma != 32) return launch_fc_strip16_pack(W, ldw, bias, bn_scale, bn_shift, D, act, img, st);   // (fc_strip16.hip)
-    hipLaunchKernelGGL(fc_strip_pack_kernel, dim3((unsigned)D), dim3(256), 0, st, W, ldw, bias, bn_scale, bn_shift, D, act,
+hipError_t launch_fc_strip16_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
+                                  void* img, hipStream_t st) {
+    hipLaunchKernelGGL(fc_strip16_pack_kernel, dim3((unsigned)D), dim3(256), 0, st, W, ldw, bias, bn_scale, bn_shift, D, act,
                        (_Float16*)img, (float*)((char*)img + fc_strip_vec_offset(D)));
     return hipGetLastError();
 }
 
-hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st) {
-    long U = 0;
-    for (int i = 0; i < a.count; ++i) {
-        a.p[i].unit0 = (int)U;
-        U += (long)((a.p[i].N + FR - 1) / FR) * a.nblk;
-    }
-    if (U == 0) return hipSuccess;
-    if (U >= (1l << 31)) return hipErrorInvalidValue;
-    a.total_units = (int)U;
-    a.trace = nullptr;
-#ifdef LAFF_FCS_TRACE
-    if (const char* e = getenv("LAFF_GEMM_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-    const int G = (int)std::min<long>(std::min(g_num_cus, STRIP_MAX_WG), U);
-    a.nranges = G;
-    // Workgroup b runs on XCD b % 8 (observed; only speed depends on it): XCD x takes the contiguous eighth x of the ranges, so its L2
-    // holds the W images of the one or two features its CUs are working on.
-    for (int b = 0; b < G; ++b) a.range_of_wg[b] = (unsigned short)((G % 8 == 0) ? (b % 8) * (G / 8) + b / 8 : b);
-    if (g_fc_strip_mfma != 32) return launch_fc_strip16(a, act, st);      // the same launch on 16x16x32 MFMAs (fc_strip16.hip)
+// (a with unit0, total_units, nranges and range_of_wg filled in by launch_fc_strip, which hands over to this one)
+hipError_t launch_fc_strip16(const FcStripArgs& a, int act, hipStream_t st) {
 #define LAFF_FCS_LAUNCH(K)                                                                                                    \
     do {                                                                                                                      \
         static unsigned long long attr_done = 0;                                                                              \
-        if (hipError_t e = smem_attr_once(attr_done, fc_strip_kernel<K>, SMEM); e != hipSuccess) return e;                    \
-        hipLaunchKernelGGL((fc_strip_kernel<K>), dim3((unsigned)G), dim3(256), SMEM, st, a);                                  \
+        if (hipError_t e = smem_attr_once(attr_done, fc_strip16_kernel<K>, SMEM); e != hipSuccess) return e;                  \
+        hipLaunchKernelGGL((fc_strip16_kernel<K>), dim3((unsigned)a.nranges), dim3(256), SMEM, st, a);                        \
     } while (0)
     if (act == LAFF_ACT_TANH || act == LAFF_ACT_SIGMOID) LAFF_FCS_LAUNCH(ACT_EXP);
     else if (act == LAFF_ACT_RELU) LAFF_FCS_LAUNCH(ACT_RELU);

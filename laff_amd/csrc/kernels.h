@@ -125,6 +125,12 @@ size_t fc_strip_vec_offset(int D);
 hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
                                 void* img, hipStream_t st);
 hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st);
+// fc_strip16.hip: the same kernel on v_mfma_f32_16x16x32_f16.  g_fc_strip_mfma (LAFF_FC_STRIP_MFMA, read when a ctx is created) says
+// which of the two launch_fc_strip_pack and launch_fc_strip run: an image must be launched in the mode it was packed in.
+extern int g_fc_strip_mfma;
+hipError_t launch_fc_strip16_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
+                                  void* img, hipStream_t st);
+hipError_t launch_fc_strip16(const FcStripArgs& a, int act, hipStream_t st);
 
 // ---- concat tower (fc_concat.hip): Y = bn(act(sum_s X_s . W[:, c_s : c_s + Dk_s]^T + bias)), dense + CSR segments, one launch ------
 constexpr int CONCAT_MAX_SEG = 8;        // segments per problem, dense and sparse together

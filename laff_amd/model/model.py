@@ -308,7 +308,7 @@ class TransformNet(nn.Module):
         scale, shift = self.bn_affine(None)
         w, b = self.fc1.weight, self.fc1.bias
         key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version),
-               None if self.bn1 is None else self._bn_cache[0], self.activation_name)
+               None if self.bn1 is None else self._bn_cache[0], self.activation_name, ops.fc_strip_mfma(w.device))
         if getattr(self, '_w_strip', None) is None or self._w_strip[0] != key:
             self._w_strip = (key, ops.fc_strip_pack(w.detach(), None if b is None else b.detach(), scale, shift, self.activation_name))
         return self._w_strip[1]

@@ -5,6 +5,8 @@ passes raw pointers to liblaff_hip.so on the current torch stream and returns to
 CPU or eager-PyTorch fallback: CPU tensors are rejected.
 """
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import torch
@@ -18,6 +20,9 @@ __all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'fr
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
+#: the library's LAFF_FC_STRIP_MFMA mode (process-wide; the library reads the variable whenever a context is created, and so does
+#: _context, by the same rule: 32 selects the 32x32x16 kernels, anything else the 16x16x32 ones)
+_fc_strip_mfma = 16
 
 #: optional per-launch profiler (bench.py): object with begin(name) / end(name), called on the launching stream
 profiler = None
@@ -36,6 +41,18 @@ def _call(name, fn, *args):
         profiler.end(name)
 
 
+def _atoi(text):
+    """C's atoi: optional blanks and sign, leading digits, 0 when there are none."""
+    m = re.match(r'\s*[+-]?\d+', text)
+    return int(m.group(0)) if m else 0
+
+
+def fc_strip_mfma(device):
+    """The MFMA shape (16 or 32) of the strip-form FC kernels that the device's context packs for and launches."""
+    _context(device)
+    return _fc_strip_mfma
+
+
 def _context(device):
     """One laff_ctx per device ordinal, re-bound to torch's current stream at every call."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -44,6 +61,8 @@ def _context(device):
         h = C.c_void_p()
         check(lib.laff_ctx_create(idx, None, C.byref(h)))
         _ctx[idx] = h
+        global _fc_strip_mfma
+        _fc_strip_mfma = 32 if _atoi(os.environ.get('LAFF_FC_STRIP_MFMA', '16')) == 32 else 16
     h = _ctx[idx]
     check(lib.laff_ctx_set_stream(h, C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)))
     return lib, h
@@ -767,12 +786,15 @@ class StripWeights:
     """A TransformNet's parameters packed for the strip-form FC (laff_fc_strip_pack): the W stream's LDS image + the per-column
     epilogue constants (bias, activation and folded BatchNorm combined)."""
 
-    def __init__(self, img, D, K, act):
-        self.img, self.D, self.K, self.act = img, D, K, act
+    def __init__(self, img, D, K, act, mfma):
+        self.img, self.D, self.K, self.act, self.mfma = img, D, K, act, mfma       # mfma: the LAFF_FC_STRIP_MFMA mode it was packed under
 
 
 def fc_strip_pack(weight, bias=None, bn_scale=None, bn_shift=None, activation=None):
-    """Pack W [D, 512] (+ bias / folded BatchNorm / activation) once per model for fc_act_bn_strip_grouped."""
+    """Pack W [D, 512] (+ bias / folded BatchNorm / activation) once per model for fc_act_bn_strip_grouped.
+    The image's layout follows the context's LAFF_FC_STRIP_MFMA mode (16 by default, 32: the 32x32x16 kernel; read when the context
+    is created) and is recorded in the result: fc_act_bn_strip_grouped refuses an image packed under the other mode, so pack again
+    after changing the mode (ops.reset_contexts())."""
     w, ldw = _rows(weight, 'weight')
     D, K = w.shape
     lib, h = _context(w.device)
@@ -781,7 +803,7 @@ def fc_strip_pack(weight, bias=None, bn_scale=None, bn_shift=None, activation=No
     vecs = _fc_vectors(dict(bias=bias, bn_scale=bn_scale, bn_shift=bn_shift), D)
     img = torch.empty((nbytes.value,), device=w.device, dtype=torch.uint8)
     _call('fc_strip_pack', lib.laff_fc_strip_pack, h, _ptr(w), ldw, *vecs, D, K, ACT[activation], _ptr(img))
-    return StripWeights(img, D, K, ACT[activation])
+    return StripWeights(img, D, K, ACT[activation], _fc_strip_mfma)
 
 
 def fc_strip_eligible(x, D):
@@ -812,6 +834,10 @@ def fc_act_bn_strip_grouped(problems):
         arr[i] = FcStripProblem(x.data_ptr(), max(ldx, 512), x.shape[0], sw.img.data_ptr(), sw.D, sw.act, y.data_ptr(), ldy)
         outs.append(out)
     lib, h = _context(dev)
+    for i, q in enumerate(problems):
+        if q['strip'].mfma != _fc_strip_mfma:
+            raise ValueError('problem %d: its image was packed under LAFF_FC_STRIP_MFMA=%d, the context runs %d: pack it again'
+                             % (i, q['strip'].mfma, _fc_strip_mfma))
     _call('fc_act_bn', lib.laff_fc_act_bn_strip_grouped, h, arr, n)
     return outs
 
