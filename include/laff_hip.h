@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 38
+#define LAFF_ABI_VERSION 39
 
 enum {
     LAFF_OK = 0,
@@ -275,6 +275,40 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
                     int V, int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
                     const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
                     void* workspace, size_t workspace_bytes);
+
+/* ---- the GRU caption encoder, differentiable: the training forward and backpropagation through time (fp32, one layer, h0 = 0) ----
+ * Packed positions: pos(t, row) = off[t] + row with off the prefix sum of batch_sizes; M = sum of batch_sizes rows in all.
+ * laff_gru_gather_rows: X [M, D] = table[ids] (an id outside [0, V) gives a NaN row).  With X = we[tokens in packed order], form
+ *   GI = X . W_ih^T + b_ih [M, 3H] per direction with laff_fc_act_bn (act none): the table of this batch only.
+ * laff_gru_encode_train: laff_gru_encode with P := GI, V := M and pos [T, N] in place of the tokens (pos[t, row] = off[t] + row for the
+ *   active entries; the others are not read).  Same arithmetic, same out.  It also fills reserve (laff_gru_train_reserve_bytes, 16-byte
+ *   aligned): per direction the planes r, z, n, q = W_hn h_prev + b_hn and h_prev, [M, H] each, addressed by packed position.
+ * laff_gru_pack_whh_t: W_hh [3H, H] -> the backward step's operand layout (the transposed pack), 3*H*H floats, 16-byte aligned.
+ * laff_gru_backward: from dout [N, lddo] (the gradient of out, input order) one launch per time step, then the parameter gradients
+ *   through laff_fc_backward's launch path and the embedding gradient.  grads_fwd / grads_rev: {dW_ih [3H, we_dim], dW_hh [3H, H],
+ *   db_ih [3H], db_hh [3H]} of a direction, HOST arrays of four device pointers, each may be null (not wanted); grads_rev is read only
+ *   when bidirectional and pooling is LAFF_GRU_MEAN (under bigru + last the reverse direction has no gradient).  d_we [V, we_dim] or
+ *   null: the sum of the rows of dX = dGI . W_ih that share a token, from the token segments seg_off [U + 1], seg_tok [U], seg_pos [M]
+ *   (device; distinct token -> its packed positions in ascending order), each segment summed in that order; rows of unused tokens
+ *   are zeros.  X is read for dW_ih only, W_ih for d_we only.  workspace: laff_gru_backward_workspace_bytes, 16-byte aligned.
+ *   No allocation, no host synchronisation, no atomics: capturable, and two calls give the same bits.
+ * laff_gru_backward_plan (host only, no ctx): per launch i in [0, T) whether the saving forward (fwd_big[i]) and the backward
+ *   (bwd_big[i]) take the 64 x 32 tile (1) or the 16 x 16 one (0). */
+int laff_gru_pack_whh_t(laff_ctx* ctx, const float* W_hh, int H, float* packed);
+int laff_gru_gather_rows(laff_ctx* ctx, const float* table, int V, int D, const int* ids, int M, float* X);
+int laff_gru_train_reserve_bytes(int M, int H, int num_layers, int bidirectional, int pooling, size_t* out);
+int laff_gru_encode_train(laff_ctx* ctx, const int* pos, const int* lengths, const int* perm, const int* batch_sizes /*host*/, int T, int N,
+                          int M, int H, int num_layers, int bidirectional, int pooling, const float* GI_fwd, const float* whh_fwd,
+                          const float* bhh_fwd, const float* GI_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
+                          void* workspace, size_t workspace_bytes, void* reserve, size_t reserve_bytes);
+int laff_gru_backward_plan(const int* batch_sizes /*host*/, int T, int H, int bidirectional, int pooling, int* fwd_big, int* bwd_big);
+int laff_gru_backward_workspace_bytes(const int* batch_sizes /*host*/, int T, int N, int H, int we_dim, int num_layers, int bidirectional,
+                                      int pooling, int want_dwe, size_t* out);
+int laff_gru_backward(laff_ctx* ctx, const int* lengths, const int* perm, const int* batch_sizes /*host*/, int T, int N, int M, int H,
+                      int we_dim, int num_layers, int bidirectional, int pooling, const float* dout, int lddo, const void* reserve,
+                      size_t reserve_bytes, const float* X, const float* wih_fwd, const float* whht_fwd, const float* wih_rev,
+                      const float* whht_rev, const int* seg_off, const int* seg_tok, const int* seg_pos, int U, int V, float* d_we,
+                      float* const grads_fwd[4] /*host*/, float* const grads_rev[4] /*host*/, void* workspace, size_t workspace_bytes);
 
 /* ---- text tower: the CLIP text encoder (clip.model.CLIP.encode_text, model/clip/model.py:153-206, 245-358), inference -----------
  * token + positional embedding -> layers x ResidualAttentionBlock (pre-LN, causal MHA with head dim 64, QuickGELU MLP of 4 width)

@@ -11,7 +11,7 @@ ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 
 class Plane(C.Structure):
@@ -206,6 +206,15 @@ SIGNATURES = {
     'laff_gru_workspace_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_gru_encode': (C.c_int, [_P, _P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                                   C.c_size_t]),
+    'laff_gru_pack_whh_t': (C.c_int, [_P, _P, _I, _P]),
+    'laff_gru_gather_rows': (C.c_int, [_P, _P, _I, _I, _P, _I, _P]),
+    'laff_gru_train_reserve_bytes': (C.c_int, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_gru_encode_train': (C.c_int, [_P, _P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
+                                        C.c_size_t, _P, C.c_size_t]),
+    'laff_gru_backward_plan': (C.c_int, [C.POINTER(_I), _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    'laff_gru_backward_workspace_bytes': (C.c_int, [C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_gru_backward': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, C.c_size_t, _P, _P, _P, _P, _P,
+                                    _P, _P, _P, _I, _I, _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P, C.c_size_t]),
     'laff_clip_pack_weight': (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     'laff_clip_workspace_bytes': (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_clip_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(ClipText), _I, _P, _I, _P, C.c_size_t]),

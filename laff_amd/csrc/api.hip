@@ -588,11 +588,11 @@ int laff_gru_workspace_bytes(int N, int H, int num_layers, int bidirectional, in
     return LAFF_OK;
 }
 
-int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const int* perm, const int* batch_sizes, int T, int N, int V,
-                    int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
-                    const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
-                    void* workspace, size_t workspace_bytes) {
-    const char* fn = "laff_gru_encode";
+// laff_gru_encode, and with a reserve laff_gru_encode_train: the same steps with the saving kernel, V = M = sum of batch_sizes
+static int gru_encode_run(const char* fn, laff_ctx* ctx, const int* tokens, const int* lengths, const int* perm, const int* batch_sizes,
+                          int T, int N, int V, int H, int num_layers, int bidirectional, int pooling, const float* P_fwd,
+                          const float* whh_fwd, const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev,
+                          float* out, int ldo, void* workspace, size_t workspace_bytes, bool train, void* reserve, size_t reserve_bytes) {
     // every argument is checked before any GPU work
     if (int rc = gru_check_size(fn, H, num_layers)) return rc;
     if (int rc = gru_check_mode(fn, bidirectional, pooling)) return rc;
@@ -614,7 +614,21 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
     if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
     if (!aligned16(workspace) || !aligned16(whh_fwd) || (ndirs == 2 && !aligned16(whh_rev)))
         return fail(LAFF_E_ALIGN, "%s: workspace / packed W_hh must be 16-byte aligned", fn);
-    CHECK_CTX(ctx);
+    std::vector<int> off;
+    if (train) {
+        long M = 0;
+        off.resize(T);
+        for (int t = 0; t < T; ++t) {
+            off[t] = (int)M;
+            M += batch_sizes[t];
+        }
+        if (M != V) return fail(LAFF_E_ARG, "%s: M=%d but batch_sizes sum to %ld", fn, V, M);
+        const size_t rneed = (size_t)ndirs * 5 * M * H * sizeof(float);
+        if (!reserve || reserve_bytes < rneed)
+            return fail(LAFF_E_ARG, "%s: reserve too small (%zu < %zu bytes)", fn, reserve ? reserve_bytes : (size_t)0, rneed);
+        if (!aligned16(reserve)) return fail(LAFF_E_ALIGN, "%s: reserve must be 16-byte aligned", fn);
+    }
+    if (!ctx) return fail(LAFF_E_ARG, "%s: null ctx", fn);
     DeviceGuard g(ctx->device);
     // h_0 = 0 and the sums start at 0; a reverse-direction row reads its buffer untouched (zero) at its first step
     HIP_TRY(hipMemsetAsync(workspace, 0, need, ctx->stream));
@@ -639,7 +653,9 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
         dir[d]->bhh = bh[d];
         dir[d]->sum = ws + (3 * d + 2) * plane;
         dir[d]->col0 = d * H;
+        if (train) dir[d]->res = (float*)reserve + (size_t)d * 5 * V * H;
     }
+    if (train) a.M = V;
     for (int i = 0; i < T; ++i) {
         for (int d = 0; d < ndirs; ++d) {
             const int t = d ? T - 1 - i : i;      // the reverse direction walks the same sorted prefix backwards
@@ -647,9 +663,243 @@ int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const 
             dir[d]->B = batch_sizes[t];
             dir[d]->h_in = ws + (3 * d + (i & 1)) * plane;
             dir[d]->h_out = ws + (3 * d + ((i + 1) & 1)) * plane;
+            if (train) dir[d]->off = off[t];
         }
         a.skip_gemm = i == 0;                     // h = 0 for every row of the first step of either direction
-        HIP_TRY(laff::launch_gru_step(a, ndirs, ctx->stream));
+        HIP_TRY(laff::launch_gru_step(a, ndirs, ctx->stream, train));
+    }
+    return LAFF_OK;
+}
+
+int laff_gru_encode(laff_ctx* ctx, const int* tokens, const int* lengths, const int* perm, const int* batch_sizes, int T, int N, int V,
+                    int H, int num_layers, int bidirectional, int pooling, const float* P_fwd, const float* whh_fwd,
+                    const float* bhh_fwd, const float* P_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
+                    void* workspace, size_t workspace_bytes) {
+    return gru_encode_run("laff_gru_encode", ctx, tokens, lengths, perm, batch_sizes, T, N, V, H, num_layers, bidirectional, pooling, P_fwd,
+                          whh_fwd, bhh_fwd, P_rev, whh_rev, bhh_rev, out, ldo, workspace, workspace_bytes, false, nullptr, 0);
+}
+
+/* ---- the differentiable GRU encoder ---- */
+namespace {
+// M = sum of batch_sizes after the checks that laff_gru_encode makes of them; < 0: the error code
+long gru_packed_rows(const char* fn, const int* batch_sizes, int T, int N) {
+    if (!batch_sizes) return fail(LAFF_E_ARG, "%s: null batch_sizes", fn);
+    if (T < 1) return fail(LAFF_E_SHAPE, "%s: T=%d: every caption has at least one token", fn, T);
+    if (batch_sizes[0] != N) return fail(LAFF_E_ARG, "%s: batch_sizes[0]=%d != N=%d", fn, batch_sizes[0], N);
+    long M = 0;
+    for (int t = 0; t < T; ++t) {
+        if (batch_sizes[t] < 1 || (t && batch_sizes[t] > batch_sizes[t - 1]))
+            return fail(LAFF_E_ARG, "%s: batch_sizes must be positive and non-increasing (batch_sizes[%d]=%d)", fn, t, batch_sizes[t]);
+        M += batch_sizes[t];
+    }
+    if (M > INT_MAX / 8) return fail(LAFF_E_SHAPE, "%s: %ld packed rows in one call", fn, M);
+    return M;
+}
+
+// where laff_gru_backward keeps what in its workspace, in bytes from its start; every region starts on 256 bytes
+struct GruBwdLayout {
+    size_t carry, dgi, dgh, dx, fc, total;
+};
+GruBwdLayout gru_bwd_layout(int N, long M, int H, int we_dim, int ndirs, bool want_dwe) {
+    auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    GruBwdLayout l{};
+    size_t at = 0;
+    l.carry = at; at += r256((size_t)ndirs * N * H * sizeof(float));
+    l.dgi = at;   at += r256((size_t)ndirs * M * 3 * H * sizeof(float));
+    l.dgh = at;   at += r256((size_t)ndirs * M * 3 * H * sizeof(float));
+    l.dx = at;    at += want_dwe ? r256((size_t)ndirs * M * we_dim * sizeof(float)) : 0;
+    laff::FcBwdPlan hh, ih;
+    laff::fc_bwd_plan((int)M, H, 3 * H, &hh);
+    laff::fc_bwd_plan((int)M, we_dim, 3 * H, &ih);
+    l.fc = at;    at += r256(std::max(std::max(hh.ws_dw, ih.ws_dw), want_dwe ? ih.ws_dx : (size_t)0));
+    l.total = at;
+    return l;
+}
+
+// laff_fc_backward's launch path with activation none: dW [D, Dk] = dA^T X, db = column sums of dA, dX = dA W; null outputs are left out
+hipError_t gru_fc_backward(const float* X, int Dk, const float* W, const float* dA, int M, int D, float* dX, float* dW, float* db,
+                           void* fc_ws, hipStream_t st) {
+    if (!dX && !dW && !db) return hipSuccess;
+    laff::FcBwdArgs a{};
+    a.X = X; a.W = W; a.A = dA; a.dA = dA; a.dX = dX; a.dW = dW; a.db = db;
+    a.N = M; a.Dk = Dk; a.D = D; a.ldx = Dk; a.ldw = Dk; a.lda = D; a.ldda = D; a.lddx = Dk; a.lddw = Dk; a.act = LAFF_ACT_NONE;
+    a.vec = (aligned16(dA) && D % 4 == 0 ? 1u : 0u) | (X && aligned16(X) && Dk % 4 == 0 ? 2u : 0u) |
+            (W && aligned16(W) && Dk % 4 == 0 ? 4u : 0u);
+    a.part = (float*)fc_ws;
+    return laff::launch_fc_backward(a, st);
+}
+}  // namespace
+
+int laff_gru_pack_whh_t(laff_ctx* ctx, const float* W_hh, int H, float* packed) {
+    if (int rc = gru_check_size("laff_gru_pack_whh_t", H, 1)) return rc;
+    if (!W_hh || !packed) return fail(LAFF_E_ARG, "laff_gru_pack_whh_t: null argument");
+    if (!aligned16(packed)) return fail(LAFF_E_ALIGN, "laff_gru_pack_whh_t: packed must be 16-byte aligned");
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_gru_pack_whh_t(W_hh, H, packed, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_gru_gather_rows(laff_ctx* ctx, const float* table, int V, int D, const int* ids, int M, float* X) {
+    if (V < 1 || D < 1 || M < 0) return fail(LAFF_E_SHAPE, "laff_gru_gather_rows: bad shape V=%d D=%d M=%d", V, D, M);
+    if (M == 0) return LAFF_OK;
+    if (!table || !ids || !X) return fail(LAFF_E_ARG, "laff_gru_gather_rows: null argument");
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_gru_gather_rows(table, V, D, ids, M, X, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_gru_train_reserve_bytes(int M, int H, int num_layers, int bidirectional, int pooling, size_t* out) {
+    if (!out || M < 0) return fail(LAFF_E_ARG, "laff_gru_train_reserve_bytes: bad args");
+    if (int rc = gru_check_size("laff_gru_train_reserve_bytes", H, num_layers)) return rc;
+    if (int rc = gru_check_mode("laff_gru_train_reserve_bytes", bidirectional, pooling)) return rc;
+    *out = (size_t)gru_dirs(bidirectional, pooling) * 5 * M * H * sizeof(float);
+    return LAFF_OK;
+}
+
+int laff_gru_encode_train(laff_ctx* ctx, const int* pos, const int* lengths, const int* perm, const int* batch_sizes, int T, int N, int M,
+                          int H, int num_layers, int bidirectional, int pooling, const float* GI_fwd, const float* whh_fwd,
+                          const float* bhh_fwd, const float* GI_rev, const float* whh_rev, const float* bhh_rev, float* out, int ldo,
+                          void* workspace, size_t workspace_bytes, void* reserve, size_t reserve_bytes) {
+    return gru_encode_run("laff_gru_encode_train", ctx, pos, lengths, perm, batch_sizes, T, N, M, H, num_layers, bidirectional, pooling,
+                          GI_fwd, whh_fwd, bhh_fwd, GI_rev, whh_rev, bhh_rev, out, ldo, workspace, workspace_bytes, true, reserve,
+                          reserve_bytes);
+}
+
+int laff_gru_backward_plan(const int* batch_sizes, int T, int H, int bidirectional, int pooling, int* fwd_big, int* bwd_big) {
+    const char* fn = "laff_gru_backward_plan";
+    if (int rc = gru_check_size(fn, H, 1)) return rc;
+    if (int rc = gru_check_mode(fn, bidirectional, pooling)) return rc;
+    if (!fwd_big || !bwd_big) return fail(LAFF_E_ARG, "%s: null out", fn);
+    const long M = gru_packed_rows(fn, batch_sizes, T, batch_sizes ? batch_sizes[0] : 0);
+    if (M < 0) return (int)M;
+    const int ndirs = gru_dirs(bidirectional, pooling);
+    for (int i = 0; i < T; ++i) {
+        /* launch i of the forward: step i with, in a bigru, the reverse direction's step T - 1 - i; launch i of the backward: the same two,
+           each walked the other way */
+        const int Bf = std::max(batch_sizes[i], ndirs > 1 ? batch_sizes[T - 1 - i] : 0);
+        const int Bb = std::max(batch_sizes[T - 1 - i], ndirs > 1 ? batch_sizes[i] : 0);
+        fwd_big[i] = laff::gru_step_big(Bf, H, ndirs) ? 1 : 0;
+        bwd_big[i] = laff::gru_step_big(Bb, H, ndirs) ? 1 : 0;
+    }
+    return LAFF_OK;
+}
+
+int laff_gru_backward_workspace_bytes(const int* batch_sizes, int T, int N, int H, int we_dim, int num_layers, int bidirectional,
+                                      int pooling, int want_dwe, size_t* out) {
+    const char* fn = "laff_gru_backward_workspace_bytes";
+    if (!out || N < 0 || we_dim < 1) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    if (int rc = gru_check_size(fn, H, num_layers)) return rc;
+    if (int rc = gru_check_mode(fn, bidirectional, pooling)) return rc;
+    if (N == 0) {
+        *out = 0;
+        return LAFF_OK;
+    }
+    const long M = gru_packed_rows(fn, batch_sizes, T, N);
+    if (M < 0) return (int)M;
+    *out = gru_bwd_layout(N, M, H, we_dim, gru_dirs(bidirectional, pooling), want_dwe != 0).total;
+    return LAFF_OK;
+}
+
+int laff_gru_backward(laff_ctx* ctx, const int* lengths, const int* perm, const int* batch_sizes, int T, int N, int M, int H, int we_dim,
+                      int num_layers, int bidirectional, int pooling, const float* dout, int lddo, const void* reserve,
+                      size_t reserve_bytes, const float* X, const float* wih_fwd, const float* whht_fwd, const float* wih_rev,
+                      const float* whht_rev, const int* seg_off, const int* seg_tok, const int* seg_pos, int U, int V, float* d_we,
+                      float* const grads_fwd[4], float* const grads_rev[4], void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_gru_backward";
+    if (int rc = gru_check_size(fn, H, num_layers)) return rc;
+    if (int rc = gru_check_mode(fn, bidirectional, pooling)) return rc;
+    if (N < 0 || M < 0 || we_dim < 1 || U < 0 || V < 1)
+        return fail(LAFF_E_SHAPE, "%s: bad shape N=%d M=%d we_dim=%d U=%d V=%d", fn, N, M, we_dim, U, V);
+    if (N == 0) return LAFF_OK;
+    const int ndirs = gru_dirs(bidirectional, pooling);
+    const long Msum = gru_packed_rows(fn, batch_sizes, T, N);
+    if (Msum < 0) return (int)Msum;
+    if (Msum != M) return fail(LAFF_E_ARG, "%s: M=%d but batch_sizes sum to %ld", fn, M, Msum);
+    if (!lengths || !perm || !dout || !reserve || !whht_fwd || !grads_fwd || (ndirs == 2 && (!whht_rev || !grads_rev)) || !workspace)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    float* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* const* G[2] = {grads_fwd, ndirs == 2 ? grads_rev : none};            /* dW_ih, dW_hh, db_ih, db_hh of a direction */
+    const float* wih[2] = {wih_fwd, wih_rev};
+    const float* whht[2] = {whht_fwd, whht_rev};
+    const bool want_dwe = d_we != nullptr;
+    bool need_x = false;
+    for (int d = 0; d < ndirs; ++d) need_x = need_x || G[d][0];
+    if (need_x && !X) return fail(LAFF_E_ARG, "%s: null X (read for dW_ih)", fn);
+    if (want_dwe && (!wih_fwd || (ndirs == 2 && !wih_rev) || !seg_off || !seg_tok || !seg_pos))
+        return fail(LAFF_E_ARG, "%s: d_we needs W_ih of every direction and the token segments", fn);
+    if (U > M) return fail(LAFF_E_ARG, "%s: U=%d distinct tokens in M=%d positions", fn, U, M);
+    const int width = pooling == LAFF_GRU_LAST ? H : (pooling == LAFF_GRU_MEAN_LAST ? 2 * H : ndirs * H);
+    if (lddo < width) return fail(LAFF_E_SHAPE, "%s: lddo=%d < output width %d", fn, lddo, width);
+    const size_t rneed = (size_t)ndirs * 5 * M * H * sizeof(float);
+    if (reserve_bytes < rneed) return fail(LAFF_E_ARG, "%s: reserve too small (%zu < %zu bytes)", fn, reserve_bytes, rneed);
+    const GruBwdLayout L = gru_bwd_layout(N, M, H, we_dim, ndirs, want_dwe);
+    if (workspace_bytes < L.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, L.total);
+    if (!aligned16(workspace) || !aligned16(reserve) || !aligned16(whht_fwd) || (ndirs == 2 && !aligned16(whht_rev)))
+        return fail(LAFF_E_ALIGN, "%s: workspace / reserve / packed W_hh must be 16-byte aligned", fn);
+    for (int d = 0; d < ndirs; ++d)
+        for (int k = 0; k < 4; ++k)
+            if (reinterpret_cast<uintptr_t>(G[d][k]) & 3) return fail(LAFF_E_ALIGN, "%s: the gradients must be 4-byte aligned", fn);
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* ws = (char*)workspace;
+    float* carry = (float*)(ws + L.carry);
+    float* dgi = (float*)(ws + L.dgi);
+    float* dgh = (float*)(ws + L.dgh);
+    float* dx = want_dwe ? (float*)(ws + L.dx) : nullptr;
+    HIP_TRY(hipMemsetAsync(carry, 0, (size_t)ndirs * N * H * sizeof(float), ctx->stream));   // no carry into a row's first backward step
+    std::vector<int> off(T);
+    for (int t = 0, m = 0; t < T; ++t) {
+        off[t] = m;
+        m += batch_sizes[t];
+    }
+    const size_t MH = (size_t)M * H;
+    laff::GruBwdStepArgs a{};
+    a.lens = lengths;
+    a.perm = perm;
+    a.dout = dout;
+    a.lddo = lddo;
+    a.N = N;
+    a.H = H;
+    a.M = M;
+    a.pooling = pooling;
+    laff::GruBwdDirArgs* dir[2] = {&a.d0, &a.d1};
+    for (int d = 0; d < ndirs; ++d) {
+        dir[d]->WpT = whht[d];
+        dir[d]->res = (const float*)reserve + (size_t)d * 5 * MH;
+        dir[d]->carry = carry + (size_t)d * N * H;
+        dir[d]->col0 = d * H;
+    }
+    for (int i = 0; i < T; ++i) {
+        for (int d = 0; d < ndirs; ++d) {
+            const int t = d ? i : T - 1 - i;            // each direction walks its own steps backwards
+            const int nb = d ? t - 1 : t + 1;           // the step that consumed h_t
+            float* gi = dgi + (size_t)d * 3 * MH;
+            float* gh = dgh + (size_t)d * 3 * MH;
+            dir[d]->t = t;
+            dir[d]->off = off[t];
+            dir[d]->B = batch_sizes[t];
+            dir[d]->Bnb = nb < 0 || nb >= T ? 0 : std::min(batch_sizes[nb], batch_sizes[t]);
+            dir[d]->dgh_nb = dir[d]->Bnb ? gh + (size_t)off[nb] * 3 * H : gh;
+            dir[d]->dgi = gi + (size_t)off[t] * 3 * H;
+            dir[d]->dgh = gh + (size_t)off[t] * 3 * H;
+        }
+        HIP_TRY(laff::launch_gru_bwd_step(a, ndirs, ctx->stream));
+    }
+    for (int d = 0; d < ndirs; ++d) {
+        const float* gi = dgi + (size_t)d * 3 * MH;
+        const float* gh = dgh + (size_t)d * 3 * MH;
+        const float* hprev = (const float*)reserve + (size_t)d * 5 * MH + 4 * MH;
+        HIP_TRY(gru_fc_backward(hprev, H, nullptr, gh, M, 3 * H, nullptr, G[d][1], G[d][3], ws + L.fc, ctx->stream));
+        HIP_TRY(gru_fc_backward(X, we_dim, wih[d], gi, M, 3 * H, want_dwe ? dx + (size_t)d * M * we_dim : nullptr, G[d][0], G[d][2],
+                                ws + L.fc, ctx->stream));
+    }
+    if (want_dwe) {
+        /* rows of we that no caption used are zeros; the others are each summed by one workgroup in the host's fixed order */
+        HIP_TRY(hipMemsetAsync(d_we, 0, (size_t)V * we_dim * sizeof(float), ctx->stream));
+        HIP_TRY(laff::launch_gru_embed_grad(dx, ndirs == 2 ? dx + (size_t)M * we_dim : nullptr, M, we_dim, seg_off, seg_tok, seg_pos, U, V,
+                                            d_we, ctx->stream));
     }
     return LAFF_OK;
 }

@@ -1,4 +1,4 @@
-// gru.hip -- the GRU caption encoder of the text tower, inference only
+// gru.hip -- the GRU caption encoder of the text tower: the inference step and its saving variant for training (gru_bwd.hip)
 // (reference model/model.py:323-396 GruTxtEncoder / BiGruTxtEncoder: nn.GRU over the embedded caption + mean / last pooling).
 //
 // torch.nn.GRU arithmetic, gate order r, z, n, h0 = 0:
@@ -52,7 +52,9 @@ __global__ __launch_bounds__(256) void gru_pack_whh_kernel(const float* __restri
     }
 }
 
-template <int RT, int UT>
+// SAVE: the training step (laff_gru_encode_train).  It also stores r, z, n, q = W_hn h + b_hn and h_prev of every active
+// element at the row's packed position D.off + row of the reserve; the inference instantiations have none of it.
+template <int RT, int UT, bool SAVE = false>
 __global__ __launch_bounds__(GRU_THREADS) void gru_step_kernel(GruStepArgs s) {
     const GruDirArgs D = blockIdx.z ? s.d1 : s.d0;
     const int row0 = blockIdx.y * 16 * RT;
@@ -132,6 +134,15 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_step_kernel(GruStepArgs s) {
         const float hp = D.h_in[hi];
         const float h = fmaf(z, hp - n, n);
         D.h_out[hi] = h;
+        if constexpr (SAVE) {
+            const long plane = (long)s.M * H;
+            float* rs = D.res + ((long)D.off + row) * H + u;
+            rs[0] = r;
+            rs[plane] = z;
+            rs[2 * plane] = n;
+            rs[3 * plane] = gn + D.bhh[2 * H + u];
+            rs[4 * plane] = hp;
+        }
         float sum = 0.0f;
         if (s.pooling != LAFF_GRU_LAST) {
             float* sp = D.sum + (long)row * H + u;
@@ -159,16 +170,19 @@ hipError_t launch_gru_pack_whh(const float* W, int H, float* Wp, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st) {
+// the 64 x 32 tile loads 5x fewer operand bytes per MFMA; it pays once there are enough of them to fill the device
+bool gru_step_big(int B, int H, int ndirs) { return (long)((B + 63) / 64) * (H / 32) * ndirs >= 512; }
+
+hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st, bool save) {
     const int B = std::max(s.d0.B, ndirs > 1 ? s.d1.B : 0);
-    // the 64 x 32 tile loads 5x fewer operand bytes per MFMA; it pays once there are enough of them to fill the device
-    const bool big = (long)((B + 63) / 64) * (s.H / 32) * ndirs >= 512;
-    if (big) {
+    if (gru_step_big(B, s.H, ndirs)) {
         dim3 grid(s.H / 32, (B + 63) / 64, ndirs);
-        gru_step_kernel<4, 2><<<grid, GRU_THREADS, 0, st>>>(s);
+        if (save) gru_step_kernel<4, 2, true><<<grid, GRU_THREADS, 0, st>>>(s);
+        else gru_step_kernel<4, 2><<<grid, GRU_THREADS, 0, st>>>(s);
     } else {
         dim3 grid(s.H / 16, (B + 15) / 16, ndirs);
-        gru_step_kernel<1, 1><<<grid, GRU_THREADS, 0, st>>>(s);
+        if (save) gru_step_kernel<1, 1, true><<<grid, GRU_THREADS, 0, st>>>(s);
+        else gru_step_kernel<1, 1><<<grid, GRU_THREADS, 0, st>>>(s);
     }
     return hipGetLastError();
 }

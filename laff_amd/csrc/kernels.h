@@ -414,6 +414,8 @@ struct GruDirArgs {
     int B;                // active rows (a prefix of the length-sorted rows)
     int t;                // token column of this step
     int col0;             // output column of this direction's mean
+    float* res;           // saving step only: this direction's reserve, the planes r, z, n, q, h_prev of [M, H] each
+    int off;              // saving step only: packed position of this step's row 0 (prefix sum of batch_sizes)
 };
 struct GruStepArgs {
     GruDirArgs d0, d1;    // d0 forward, d1 reverse (grid.z)
@@ -423,9 +425,39 @@ struct GruStepArgs {
     int N, H, V, skip_gemm, pooling;
     float* out;
     int ldo;
+    int M;                // saving step only: packed rows in all, sum of batch_sizes
 };
 hipError_t launch_gru_pack_whh(const float* W, int H, float* Wp, hipStream_t st);
-hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st);
+// save: the training step (laff_gru_encode_train), which also fills the reserve; the tile rule is the same
+hipError_t launch_gru_step(const GruStepArgs& s, int ndirs, hipStream_t st, bool save = false);
+// the tile rule of a forward or backward step with B active rows (the larger of the two directions'): true = the 64 x 32 tile
+bool gru_step_big(int B, int H, int ndirs);
+
+// gru_bwd.hip: one direction of a backward time step (laff_gru_backward)
+struct GruBwdDirArgs {
+    const float* WpT;     // laff_gru_pack_whh_t(W_hh)
+    const float* res;     // this direction's reserve (r, z, n, q, h_prev planes of [M, H])
+    const float* dgh_nb;  // dGH rows of the step that consumed this step's h (its row 0); read for rows < Bnb
+    float* dgi;           // dGI rows of this step (its row 0), [B, 3H]
+    float* dgh;           // dGH rows of this step
+    float* carry;         // [N, H]: dh z of the row's previous backward step, updated in place
+    int B, Bnb;           // active rows of this step; rows of it that the consuming step had too (a prefix)
+    int t, off, col0;     // token column, packed position of row 0, this direction's column of dout under mean pooling
+};
+struct GruBwdStepArgs {
+    GruBwdDirArgs d0, d1;
+    const int* lens;
+    const int* perm;
+    const float* dout;    // [N, lddo] gradient of the encoder's output, input order
+    int lddo, N, H, M, pooling;
+};
+hipError_t launch_gru_pack_whh_t(const float* W, int H, float* Wp, hipStream_t st);
+hipError_t launch_gru_bwd_step(const GruBwdStepArgs& s, int ndirs, hipStream_t st);
+// X[m] = table[ids[m]] (NaN for an id outside the table)
+hipError_t launch_gru_gather_rows(const float* table, int V, int D, const int* ids, int M, float* X, hipStream_t st);
+// d_we[seg_tok[s]] = sum over p in [seg_off[s], seg_off[s+1]) of dX0[seg_pos[p]] (+ dX1[seg_pos[p]]), in that order
+hipError_t launch_gru_embed_grad(const float* dX0, const float* dX1, int M, int D, const int* seg_off, const int* seg_tok,
+                                 const int* seg_pos, int U, int V, float* d_we, hipStream_t st);
 
 // clip.hip: the CLIP text encoder (laff_clip_encode) and the transformer core it shares with the image encoder (clip_image.hip)
 typedef float clip_f4 __attribute__((ext_vector_type(4)));

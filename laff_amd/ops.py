@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -396,7 +396,12 @@ def gru_workspace_bytes(N, H, num_layers=1, bidirectional=False, pooling='mean')
 
 
 def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean', num_layers=1, out=None, workspace=None):
-    """laff_gru_encode.  tokens [T, N] int32 (time-major, length-sorted rows), lengths / perm [N] int32 on the device,
+    """laff_gru_encode; the arguments are described at _gru_encode."""
+    return _gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev, pooling, num_layers, out, workspace, None)
+
+
+def _gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev, pooling, num_layers, out, workspace, reserve):
+    """laff_gru_encode (reserve None) / laff_gru_encode_train.  tokens [T, N] int32 (time-major, length-sorted rows), lengths / perm [N] int32 on the device,
     batch_sizes: host sequence of T ints; fwd / rev: (P [V, 3H], packed W_hh, b_hh [3H]) of each direction (rev: bidirectional).
     Returns out [N, width] in the input order given by perm.  workspace: a uint8 device tensor of gru_workspace_bytes(...) bytes,
     or None to allocate one here (pass one for HIP-graph capture)."""
@@ -433,10 +438,144 @@ def gru_encode(tokens, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean'
     o, ldo = _rows(out, 'out')
     Pr, Wr, br = rev if bidir else (None, None, None)
     lib, h = _context(tok.device)
+    if reserve is not None:
+        _call('gru_encode_train', lib.laff_gru_encode_train, h, _ptr(tok), _ptr(lens), _ptr(prm), bs, T, N, V, H, int(num_layers),
+              int(bidir), GRU_POOLING[pooling], _ptr(P), _ptr(Wp), _ptr(bhh), _ptr(Pr), _ptr(Wr), _ptr(br), _ptr(o), ldo,
+              _ptr(workspace), workspace.numel(), _ptr(reserve), reserve.numel())
+        return out
     _call('gru_encode', lib.laff_gru_encode, h, _ptr(tok), _ptr(lens), _ptr(prm), bs, T, N, V, H, int(num_layers), int(bidir),
           GRU_POOLING[pooling], _ptr(P), _ptr(Wp), _ptr(bhh), _ptr(Pr), _ptr(Wr), _ptr(br), _ptr(o), ldo, _ptr(workspace),
           workspace.numel())
     return out
+
+
+def gru_pack_whh_t(w_hh):
+    """laff_gru_pack_whh_t: W_hh [3H, H] -> the backward step's operand layout (a flat fp32 tensor of 3*H*H)."""
+    w = _dev(w_hh, 'w_hh')
+    if w.dim() != 2 or w.shape[0] != 3 * w.shape[1]:
+        raise ValueError('w_hh must be (3H, H), got %s' % (tuple(w.shape),))
+    w = w.contiguous()
+    out = torch.empty(w.numel(), device=w.device, dtype=torch.float32)
+    lib, h = _context(w.device)
+    _call('gru_pack_whh_t', lib.laff_gru_pack_whh_t, h, _ptr(w), int(w.shape[1]), _ptr(out))
+    return out
+
+
+def gru_gather_rows(table, ids, out=None):
+    """laff_gru_gather_rows: table[ids] -- table [V, D] fp32, ids [M] int32 on the device -> [M, D]."""
+    tb = _dev(table, 'table')
+    ix = _dev(ids, 'ids', torch.int32)
+    if tb.dim() != 2 or not tb.is_contiguous() or ix.dim() != 1 or not ix.is_contiguous():
+        raise ValueError('table must be a contiguous matrix and ids a contiguous vector')
+    M, (V, D) = ix.numel(), tb.shape
+    if out is None:
+        out = torch.empty((M, D), device=tb.device, dtype=torch.float32)
+    if tuple(out.shape) != (M, D) or not _dev(out, 'out').is_contiguous():
+        raise ValueError('out must be a contiguous (%d, %d) matrix' % (M, D))
+    lib, h = _context(tb.device)
+    _call('gru_gather_rows', lib.laff_gru_gather_rows, h, _ptr(tb), V, D, _ptr(ix), M, _ptr(out))
+    return out
+
+
+def _batch_sizes(batch_sizes):
+    return (C.c_int * max(1, len(batch_sizes)))(*[int(b) for b in batch_sizes]), len(batch_sizes)
+
+
+def gru_train_reserve_bytes(M, H, num_layers=1, bidirectional=False, pooling='mean'):
+    return _size_query('laff_gru_train_reserve_bytes', M, H, num_layers, bool(bidirectional), GRU_POOLING[pooling])
+
+
+def gru_backward_plan(batch_sizes, H, bidirectional=False, pooling='mean'):
+    """laff_gru_backward_plan (host only): (fwd, bwd), per launch 1 where the saving forward / the backward step takes the 64 x 32 tile."""
+    bs, T = _batch_sizes(batch_sizes)
+    fwd, bwd = (C.c_int * max(1, T))(), (C.c_int * max(1, T))()
+    check(_lib.load().laff_gru_backward_plan(bs, T, int(H), int(bool(bidirectional)), GRU_POOLING[pooling], fwd, bwd))
+    return tuple(fwd[:T]), tuple(bwd[:T])
+
+
+def gru_backward_workspace_bytes(batch_sizes, N, H, we_dim, num_layers=1, bidirectional=False, pooling='mean', want_dwe=True):
+    bs, T = _batch_sizes(batch_sizes)
+    n = C.c_size_t()
+    check(_lib.load().laff_gru_backward_workspace_bytes(bs, T, int(N), int(H), int(we_dim), int(num_layers), int(bool(bidirectional)),
+                                                        GRU_POOLING[pooling], int(bool(want_dwe)), C.byref(n)))
+    return n.value
+
+
+def gru_encode_train(pos, lengths, perm, batch_sizes, fwd, rev=None, pooling='mean', num_layers=1, out=None, workspace=None,
+                     reserve=None):
+    """laff_gru_encode_train: gru_encode with the batch's own table -- fwd / rev = (GI [M, 3H] = X . W_ih^T + b_ih, packed W_hh,
+    b_hh [3H]), pos [T, N] int32 the packed positions -- that also fills reserve (a uint8 device tensor of gru_train_reserve_bytes
+    bytes, allocated here when None) for gru_backward.  Returns (out, reserve)."""
+    M, H = fwd[0].shape[0], fwd[0].shape[1] // 3
+    bidir = rev is not None
+    nbytes = gru_train_reserve_bytes(M, H, num_layers, bidir, pooling)
+    if reserve is None:
+        reserve = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=fwd[0].device)
+    _dev(reserve, 'reserve', torch.uint8)
+    return _gru_encode(pos, lengths, perm, batch_sizes, fwd, rev, pooling, num_layers, out, workspace, reserve), reserve
+
+
+def gru_backward(grad_out, lengths, perm, batch_sizes, reserve, x, fwd, rev=None, pooling='mean', segments=None, vocab=None,
+                 want=None, out=None, workspace=None, num_layers=1):
+    """laff_gru_backward.  grad_out [N, width] (input order); lengths / perm as gru_encode takes them; reserve from gru_encode_train;
+    x [M, we_dim] = we[tokens] in packed order; fwd / rev = (W_ih [3H, we_dim], transposed pack of W_hh) per direction.
+    segments = (seg_off [U + 1], seg_tok [U], seg_pos [M]) int32 device vectors and vocab = V ask for d_we [V, we_dim].
+    want: per direction four flags (dW_ih, dW_hh, db_ih, db_hh), default all.  out: {'d_we': ..., 'fwd': [4], 'rev': [4]} buffers to
+    write into (missing ones are allocated here).  Returns (d_we | None, [4 tensors | None] forward, the same reverse | None)."""
+    g, lddo = _rows(grad_out if grad_out.stride(-1) == 1 else grad_out.contiguous(), 'grad_out')
+    lens, prm = _dev(lengths, 'lengths', torch.int32), _dev(perm, 'perm', torch.int32)
+    x = _dev(x, 'x')
+    dev, N, bidir = g.device, g.shape[0], rev is not None
+    (M, we_dim), H = x.shape, fwd[0].shape[0] // 3
+    if not x.is_contiguous() or lens.numel() != N or prm.numel() != N:
+        raise ValueError('x must be contiguous and lengths / perm vectors of N=%d' % N)
+    for w_ih, wt in (fwd, rev) if bidir else (fwd,):
+        _dev(w_ih, 'W_ih')
+        _dev(wt, 'packed W_hh')
+        if tuple(w_ih.shape) != (3 * H, we_dim) or not w_ih.is_contiguous() or wt.numel() != 3 * H * H or not wt.is_contiguous():
+            raise ValueError('each direction needs a contiguous W_ih [3H, we_dim] and a transposed pack of W_hh (H=%d)' % H)
+    width = H if pooling == 'last' else 2 * H if (pooling == 'mean_last' or bidir) else H
+    if g.shape[1] != width:
+        raise ValueError('grad_out must be (%d, %d), got %s' % (N, width, tuple(g.shape)))
+    bs, T = _batch_sizes(batch_sizes)
+    _dev(reserve, 'reserve', torch.uint8)
+    out = out or {}
+    want = want or ([True] * 4, [True] * 4)
+    shapes = ((3 * H, we_dim), (3 * H, H), (3 * H,), (3 * H,))
+
+    def side(key, flags):
+        given = out.get(key) or [None] * 4
+        ts = []
+        for f, s, t in zip(flags, shapes, given):
+            if f and t is None:
+                t = torch.empty(s, device=dev, dtype=torch.float32)
+            if f and (tuple(_dev(t, key).shape) != s or not t.is_contiguous()):
+                raise ValueError('out %s: a gradient buffer must be contiguous %s' % (key, s))
+            ts.append(t if f else None)
+        return ts, (C.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in ts])
+    gf, pf = side('fwd', want[0])
+    gr, pr = side('rev', want[1]) if bidir else (None, None)
+    d_we, seg = None, (None, None, None)
+    U = V = 0
+    if segments is not None:
+        seg = tuple(_dev(s, 'segments', torch.int32) for s in segments)
+        U, V = seg[1].numel(), int(vocab)
+        if seg[0].numel() != U + 1 or seg[2].numel() != M or not all(s.is_contiguous() for s in seg):
+            raise ValueError('segments must be contiguous vectors of U + 1, U and M = %d entries' % M)
+        d_we = out.get('d_we')
+        if d_we is None:
+            d_we = torch.empty((V, we_dim), device=dev, dtype=torch.float32)
+        if tuple(_dev(d_we, 'd_we').shape) != (V, we_dim) or not d_we.is_contiguous():
+            raise ValueError('out d_we must be a contiguous (%d, %d) matrix' % (V, we_dim))
+    nbytes = gru_backward_workspace_bytes(batch_sizes, N, H, we_dim, num_layers, bidir, pooling, d_we is not None)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    lib, h = _context(dev)
+    _call('gru_backward', lib.laff_gru_backward, h, _ptr(lens), _ptr(prm), bs, T, N, M, H, we_dim, int(num_layers), int(bidir),
+          GRU_POOLING[pooling], _ptr(g), lddo, _ptr(reserve), reserve.numel(), _ptr(x), _ptr(fwd[0]), _ptr(fwd[1]),
+          _ptr(rev[0]) if bidir else None, _ptr(rev[1]) if bidir else None, _ptr(seg[0]), _ptr(seg[1]), _ptr(seg[2]), U, max(V, 1),
+          _ptr(d_we), pf, pr, _ptr(workspace), workspace.numel())
+    return d_we, gf, gr
 
 
 def clip_pack_weight(w, precision='fp16', transpose=False, padded_cols=None):

@@ -272,6 +272,27 @@ tokens [T_max, N] int32 time-major in sorted order (0 = <pad> past a row's end),
 (sorted row -> input position), batch_sizes: list of T_max ints, rows still active at step t (PackedSequence.batch_sizes)."""
 
 
+GruTrainBatch = collections.namedtuple('GruTrainBatch', GruBatch._fields + ('pos', 'flat', 'seg_off', 'seg_tok', 'seg_pos'))
+GruTrainBatch.__doc__ = """A GruBatch with what the differentiable encoder adds (GruTxtEncoder.to_device with differentiable=True), int32
+device tensors: pos [T_max, N] the packed position off[t] + row of every active entry (off = prefix sum of batch_sizes, 0 elsewhere),
+flat [M] the tokens in packed order, and the token segments of the embedding gradient: seg_tok [U] the distinct tokens in ascending
+order, seg_off [U + 1], seg_pos [M] each token's packed positions in ascending order."""
+
+
+def gru_train_arrays(tokens, batch_sizes):
+    """The host arrays (pos, flat, seg_off, seg_tok, seg_pos) of a GruTrainBatch from GruBatch.tokens (numpy) and batch_sizes."""
+    T, N = tokens.shape
+    bs = np.asarray(batch_sizes, dtype=np.int64).reshape(T)
+    off = np.concatenate([[0], np.cumsum(bs)]).astype(np.int64)
+    active = np.arange(N)[None, :] < bs[:, None]
+    pos = np.where(active, off[:T, None] + np.arange(N)[None, :], 0).astype(np.int32)
+    flat = tokens[active].astype(np.int32)                    # row-major over (t, row): packed order
+    order = np.argsort(flat, kind='stable').astype(np.int32)  # ascending token, ascending position inside a token
+    seg_tok, counts = np.unique(flat, return_counts=True)
+    seg_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return pos, flat, seg_off, seg_tok.astype(np.int32), order
+
+
 class IdxVec(object):
     """txt2vec.IndexVec (txt2vec.py:117-131): '<start>' + tokenize(caption) + '<end>' mapped through a 'gru' vocabulary."""
 
@@ -313,15 +334,59 @@ class _GruWeights(nn.Module):
                 self.register_parameter(name + sfx, nn.Parameter(torch.empty(shape).uniform_(-k, k)))   # nn.GRU's init
 
 
+class _GruEncodeFn(torch.autograd.Function):
+    """The training encode (laff_gru_encode_train) with laff_gru_backward behind it.  Saves the reserve, X = we[tokens] and the batch
+    arrays; forms only the gradients that needs_input_grad asks for.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, enc, b, we, *rnn):
+        from . import ops
+        sfxs = ('_l0', '_l0_reverse') if enc.bigru else ('_l0',)
+        par = {n + sfx: rnn[4 * d + k] for d, sfx in enumerate(sfxs) for k, n in enumerate(_GRU_PARAMS)}
+        ndirs = 2 if enc.bigru and enc.pooling == 'mean' else 1       # bigru + last: the output is the forward half only
+        x = ops.gru_gather_rows(we.detach(), b.flat)
+        sets = []
+        for sfx in sfxs[:ndirs]:
+            gi = ops.fc_act_bn(x, par['weight_ih' + sfx].detach(), par['bias_ih' + sfx].detach())
+            sets.append((gi, ops.gru_pack_whh(par['weight_hh' + sfx].detach()), par['bias_hh' + sfx].detach().contiguous()))
+        out, reserve = ops.gru_encode_train(b.pos, b.lengths, b.perm, b.batch_sizes, sets[0], sets[1] if ndirs == 2 else None,
+                                            enc.pooling)
+        ctx.save_for_backward(reserve, x, we, *rnn)
+        ctx.enc, ctx.batch, ctx.ndirs = enc, b, ndirs
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import ops
+        reserve, x, we = ctx.saved_tensors[:3]
+        rnn, enc, b, ndirs = ctx.saved_tensors[3:], ctx.enc, ctx.batch, ctx.ndirs
+        need = ctx.needs_input_grad
+        dirs = [(rnn[4 * d].detach(), ops.gru_pack_whh_t(rnn[4 * d + 1].detach())) for d in range(ndirs)]
+        want = [[bool(need[3 + 4 * d + k]) for k in range(4)] for d in range(ndirs)]
+        d_we, gf, gr = ops.gru_backward(grad_out, b.lengths, b.perm, b.batch_sizes, reserve, x, dirs[0], dirs[1] if ndirs == 2 else None,
+                                        enc.pooling, segments=(b.seg_off, b.seg_tok, b.seg_pos) if need[2] else None,
+                                        vocab=we.shape[0], want=(want[0], want[1] if ndirs == 2 else None))
+        grads = list(gf) + (list(gr) if ndirs == 2 else [None] * (len(rnn) - 4))
+        return (None, None, d_we) + tuple(grads)
+
+
+_GRU_PARAMS = ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')
+
+
 class GruTxtEncoder(nn.Module):
     """Drop-in for model.model.GruTxtEncoder / BiGruTxtEncoder (model/model.py:323-396), inference:
     `txt_net.encoder.rnn_encoder = GruTxtEncoder(IdxVec(vocab), we_dim, rnn_size, bidirectional, pooling)`.
     State-dict keys are the reference's (we.weight, rnn.weight_ih_l0, ...), so its checkpoints load with strict=True.
     Output: {'text_features': (N, H)} for gru mean / last and bigru last, (N, 2H) for gru mean_last and bigru mean, input order.
-    P = we . W_ih^T + b_ih and the packed W_hh are cached and rebuilt whenever a parameter changes (load_state_dict, copy_, ...)."""
+    P = we . W_ih^T + b_ih and the packed W_hh are cached and rebuilt whenever a parameter changes (load_state_dict, copy_, ...).
+    Training: with differentiable=True, .train() and enabled gradients, forward runs the saving encode (laff_gru_encode_train, fp32,
+    from the batch's own input table; the same bits) under autograd, and its backward gives the gradients of we.weight and every
+    rnn.* parameter (laff_gru_backward).  The switch is explicit: without it .train() changes nothing."""
 
-    def __init__(self, t2v_idx, we_dim, rnn_size, bidirectional=False, pooling='mean', rnn_layer=1, device='cuda'):
+    def __init__(self, t2v_idx, we_dim, rnn_size, bidirectional=False, pooling='mean', rnn_layer=1, device='cuda', differentiable=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         if int(rnn_layer) != 1:
             raise NotImplementedError('GruTxtEncoder: rnn_layer=%d; only rnn_layer = 1 is supported' % rnn_layer)
         if pooling not in ('mean', 'last', 'mean_last'):
@@ -354,14 +419,31 @@ class GruTxtEncoder(nn.Module):
     def encode_batch(self, b, out=None, workspace=None):
         """The device half of forward(): a GruBatch (IdxVec.batch) whose arrays are already device tensors."""
         from . import ops
+        if self.differentiable and self.training and torch.is_grad_enabled():
+            return self._encode_train(b)
         sets = self._tables()
         rev = sets[1] if self.bigru and self.pooling == 'mean' else None
         return ops.gru_encode(b.tokens, b.lengths, b.perm, b.batch_sizes, sets[0], rev, self.pooling, out=out, workspace=workspace)
 
+    def _encode_train(self, b):
+        if not isinstance(b, GruTrainBatch):
+            raise TypeError('the differentiable GruTxtEncoder takes a GruTrainBatch (to_device of a host GruBatch)')
+        params = [self.we.weight] + [getattr(self.rnn, n + sfx) for sfx in (('_l0', '_l0_reverse') if self.bigru else ('_l0',))
+                                     for n in _GRU_PARAMS]
+        for p_, nm in zip(params, ['we.weight'] + [n for n, _ in self.rnn.named_parameters()]):
+            if p_.dtype != torch.float32:
+                raise TypeError('the differentiable GRU encoder is fp32 only, %s is %s' % (nm, p_.dtype))
+            if not p_.is_cuda:
+                raise RuntimeError('the differentiable GRU encoder runs on the device only, %s is a CPU tensor: laff_amd has no CPU path' % nm)
+        return _GruEncodeFn.apply(self, b, *params)
+
     def to_device(self, b):
         dev = self.we.weight.device
-        return GruBatch(torch.from_numpy(b.tokens).to(dev), torch.from_numpy(b.lengths).to(dev), torch.from_numpy(b.perm).to(dev),
-                        b.batch_sizes)
+        base = (torch.from_numpy(b.tokens).to(dev), torch.from_numpy(b.lengths).to(dev), torch.from_numpy(b.perm).to(dev),
+                b.batch_sizes)
+        if not self.differentiable:
+            return GruBatch(*base)
+        return GruTrainBatch(*base, *[torch.from_numpy(a).to(dev) for a in gru_train_arrays(b.tokens, b.batch_sizes)])
 
     def forward(self, caption_feat_dict, task3=False):
         b = self.t2v_idx.batch(caption_feat_dict['caption'])
