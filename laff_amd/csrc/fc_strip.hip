@@ -32,63 +32,14 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
 
-#include "kernels.h"
-#include "strip_util.h"
+#include "fc_strip_common.h"
 
 namespace laff {
 
 namespace {
 
-using namespace su;
-
-typedef __attribute__((address_space(1))) unsigned gu32;
-
-constexpr int FR = FC_STRIP_ROWS;              // 128 rows per strip: 4 wavefronts x 32
-constexpr int SLOT = 32 * 1024;                // one ring slot: 32 columns x 256 k x {hi, lo}
-constexpr int PLANE = 16 * 1024;
-constexpr int RING = 4;
-constexpr int PIECES = 8;                      // 1 KiB LDS-DMA pieces per wave per slot
-constexpr int XB_OFF = RING * SLOT;            // a fifth 32 KiB buffer, strip staging only (all of the CU's LDS: 160 KiB)
-constexpr int SMEM = XB_OFF + SLOT;
-static_assert(SMEM <= 160 * 1024, "LDS budget");
-
-constexpr int FD = 6;                          // fragment reads run FD sub-steps ahead,
-constexpr int NSETS = 8;                       // into 8 register sets (two planes each; 32 sub-steps per block: a divisor of 32)
-static_assert(32 % NSETS == 0 && FD < NSETS, "the set of a sub-step must not depend on the block");
-constexpr int BAR_J = 16 - FD;                 // the body's barrier sits in front of this sub-step
-constexpr int NSLOT = 96;                      // MFMA issue slots of a column block: 2 bodies x 16 sub-steps x 3
-
-// ---- all 256 accumulator registers are named literally (the strip).  hipcc must not put anything of its own there (left alone it parks
-// long-lived values in a0.. when the 256 architectural registers get tight -- silently overwritten by the strip): 64 dummy quads are
-// defined in the accumulator file at kernel entry and "used" at its exit, so the allocator sees every one of them occupied throughout;
-// if registers run out it spills to scratch instead, which tools/debug/isa_audit.py reports. ----
-struct AgprHold { u32x4 q[64]; };
-#define HOLD16(OP, h, b)                                                                                                                  \
-    OP(h.q[b], h.q[b + 1], h.q[b + 2], h.q[b + 3], h.q[b + 4], h.q[b + 5], h.q[b + 6], h.q[b + 7], h.q[b + 8], h.q[b + 9], h.q[b + 10], h.q[b + 11], \
-       h.q[b + 12], h.q[b + 13], h.q[b + 14], h.q[b + 15])
-#define HOLD_DEF(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, xa, xb, xc, xd, xe, xf)                                                            \
-    asm volatile("" : "=a"(x0), "=a"(x1), "=a"(x2), "=a"(x3), "=a"(x4), "=a"(x5), "=a"(x6), "=a"(x7), "=a"(x8), "=a"(x9), "=a"(xa), "=a"(xb), \
-                 "=a"(xc), "=a"(xd), "=a"(xe), "=a"(xf))
-#define HOLD_USE(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, xa, xb, xc, xd, xe, xf)                                                            \
-    asm volatile("" ::"a"(x0), "a"(x1), "a"(x2), "a"(x3), "a"(x4), "a"(x5), "a"(x6), "a"(x7), "a"(x8), "a"(x9), "a"(xa), "a"(xb), "a"(xc),   \
-                 "a"(xd), "a"(xe), "a"(xf))
-__device__ __forceinline__ void agpr_hold_begin(AgprHold& h) { HOLD16(HOLD_DEF, h, 0); HOLD16(HOLD_DEF, h, 16); HOLD16(HOLD_DEF, h, 32); HOLD16(HOLD_DEF, h, 48); }
-__device__ __forceinline__ void agpr_hold_end(AgprHold& h) { HOLD16(HOLD_USE, h, 0); HOLD16(HOLD_USE, h, 16); HOLD16(HOLD_USE, h, 32); HOLD16(HOLD_USE, h, 48); }
-
-template <int R, int OFF>
-__device__ __forceinline__ void agpr_load4(const void* p) {            // a[R .. R + 3] <- 16 bytes at p + OFF
-    asm volatile("global_load_dwordx4 a[%c1:%c2], %0, off offset:%c3" ::"v"(p), "n"(R), "n"(R + 3), "n"(OFF) : "memory");
-}
-template <int R>
-__device__ __forceinline__ float agpr_read() {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "n"(R));
-    return x;
-}
-template <int R>
-__device__ __forceinline__ void agpr_write(unsigned x) { asm volatile("v_accvgpr_write_b32 a[%c1], %0" ::"v"(x), "n"(R)); }
+using namespace fcs;
 
 // acc (+)= A(strip fragment in a[R .. R + 3]: rows of X) x B(fragment of the W stream: output columns)
 template <int R, bool FIRST>
@@ -96,33 +47,6 @@ __device__ __forceinline__ void mfma_strip(f32x16& acc, const u32x4& wfrag) {
     if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, a[%c2:%c3], %1, 0" : "=v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
     else asm volatile("v_mfma_f32_32x32x16_f16 %0, a[%c2:%c3], %1, %0" : "+v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
 }
-
-template <int IMM>
-__device__ __forceinline__ void lds_read128(u32x4& d, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
-}
-
-// one 1 KiB piece of the W stream, straight into LDS (lane L lands at M0 base + 16 L; the image is already in LDS order)
-template <int LDSOFF>
-__device__ __forceinline__ void dma_piece(unsigned voff, u32x4 rsrc, unsigned soff, unsigned m0base) {
-    asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(rsrc), "s"(soff), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
-}
-
-// 1 KiB of input rows straight into LDS (lane L lands at M0 base + LDSOFF + 16 L): scalar base + per-lane 32-bit offset.  (No
-// immediate offset: the instruction's offset field moves the LDS address as well as the global one.)
-template <int LDSOFF>
-__device__ __forceinline__ void dma_rows(unsigned voff, unsigned long long base, unsigned m0base) {
-    asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 "
-                 ::"v"(voff), "s"(base), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
-}
-// 16 bytes of the LDS staging -> a[R .. R + 3]
-template <int R, int IMM>
-__device__ __forceinline__ void lds_to_agpr(unsigned addr) {
-    asm volatile("ds_read_b128 a[%c1:%c2], %0 offset:%c3" ::"v"(addr), "n"(R), "n"(R + 3), "n"(IMM) : "memory");
-}
-template <typename T>
-__device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
 // address = voff0 + ROWMUL * ldy4, made right in front of the store (one address register instead of one per accumulator)
 template <int ROWMUL>
 __device__ __forceinline__ void store_row(unsigned& tmp, float data, unsigned voff0, unsigned ldy4, u32x4 rsrc, unsigned soff) {
@@ -130,151 +54,12 @@ __device__ __forceinline__ void store_row(unsigned& tmp, float data, unsigned vo
                  : "=&v"(tmp) : "v"(data), "v"(voff0), "s"(ldy4), "n"(ROWMUL), "s"(rsrc), "s"(soff) : "memory");
 }
 
-// row maximum -> exponent of the power-of-two scale: same rule as split_rows_kernel (fuse.hip): maximum scaled into [512, 1024)
-__device__ __forceinline__ int split_exponent(float m) {
-    const int be = (int)((__float_as_uint(m) >> 23) & 0xffu);
-    if (!(m > 0.f) || be == 0xff) return 0;
-    return max(be - 127, -100);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-// one raw chunk (two quads from the staging read-back) -> a[R .. R + 7], its eight values folded into the two running row maxima
-template <int R>
-__device__ __forceinline__ void stash_chunk(const u32x4& q0, const u32x4& q1, float& m0, float& m1) {
-    asm volatile("v_max3_f32 %0, |%2|, |%3|, %0\n\tv_max3_f32 %1, |%4|, |%5|, %1\n\tv_max3_f32 %0, |%6|, |%7|, %0\n\tv_max3_f32 %1, |%8|, |%9|, %1\n\t"
-                 "v_accvgpr_write_b32 a[%c10+0], %2\n\tv_accvgpr_write_b32 a[%c10+1], %3\n\tv_accvgpr_write_b32 a[%c10+2], %4\n\t"
-                 "v_accvgpr_write_b32 a[%c10+3], %5\n\tv_accvgpr_write_b32 a[%c10+4], %6\n\tv_accvgpr_write_b32 a[%c10+5], %7\n\t"
-                 "v_accvgpr_write_b32 a[%c10+6], %8\n\tv_accvgpr_write_b32 a[%c10+7], %9"
-                 : "+v"(m0), "+v"(m1) : "v"(q0.x), "v"(q0.y), "v"(q0.z), "v"(q0.w), "v"(q1.x), "v"(q1.y), "v"(q1.z), "v"(q1.w), "n"(R));
-}
-// a[R .. R + 7] (eight fp32: k = 16 g + 4 hh + {0..3}, + 8) -> a[R .. R + 3] = their fp16 hi halves, a[R + 4 .. R + 7] = the lo halves.
-//   hi = f16(x s) (x s is exact: s is a power of two), residual x s - hi exact in fp32, lo = f16(residual): split_rows_kernel's
-//   arithmetic (fuse.hip), as one statement with the four pairs' chains interleaved (a dependent VALU pair costs 7 cycles, not 4)
-template <int R>
-__device__ __forceinline__ void convert_chunk_inplace(float s) {
-    float x0, x1, x2, x3, x4, x5, x6, x7;
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    asm volatile(
-        "v_accvgpr_read_b32 %0, a[%c17+0]\n\tv_accvgpr_read_b32 %1, a[%c17+1]\n\tv_accvgpr_read_b32 %2, a[%c17+2]\n\tv_accvgpr_read_b32 %3, a[%c17+3]\n\t"
-        "v_accvgpr_read_b32 %4, a[%c17+4]\n\tv_accvgpr_read_b32 %5, a[%c17+5]\n\tv_accvgpr_read_b32 %6, a[%c17+6]\n\tv_accvgpr_read_b32 %7, a[%c17+7]\n\t"
-        "v_fma_mixlo_f16 %8, %0, %16, 0\n\tv_fma_mixlo_f16 %9, %2, %16, 0\n\tv_fma_mixlo_f16 %10, %4, %16, 0\n\tv_fma_mixlo_f16 %11, %6, %16, 0\n\t"
-        "v_fma_mixhi_f16 %8, %1, %16, 0\n\tv_fma_mixhi_f16 %9, %3, %16, 0\n\tv_fma_mixhi_f16 %10, %5, %16, 0\n\tv_fma_mixhi_f16 %11, %7, %16, 0\n\t"
-        "v_fma_mix_f32 %0, %0, %16, -%8 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %2, %2, %16, -%9 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %4, %4, %16, -%10 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %6, %6, %16, -%11 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %1, %1, %16, -%8 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %3, %3, %16, -%9 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %5, %5, %16, -%10 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %7, %7, %16, -%11 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_accvgpr_write_b32 a[%c17+0], %8\n\tv_accvgpr_write_b32 a[%c17+1], %9\n\tv_accvgpr_write_b32 a[%c17+2], %10\n\tv_accvgpr_write_b32 a[%c17+3], %11\n\t"
-        "v_cvt_pk_f16_f32 %12, %0, %1\n\tv_cvt_pk_f16_f32 %13, %2, %3\n\tv_cvt_pk_f16_f32 %14, %4, %5\n\tv_cvt_pk_f16_f32 %15, %6, %7\n\t"
-        "v_accvgpr_write_b32 a[%c17+4], %12\n\tv_accvgpr_write_b32 a[%c17+5], %13\n\tv_accvgpr_write_b32 a[%c17+6], %14\n\tv_accvgpr_write_b32 a[%c17+7], %15"
-        : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(x5), "=&v"(x6), "=&v"(x7), "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3),
-          "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-        : "v"(s), "n"(R));
-}
-__device__ __forceinline__ void absmax3(float& m, float x, float y) { asm volatile("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(x), "v"(y)); }
-// hi = f16(x s) for two values (x s is exact: s is a power of two), the residuals x s - hi (exact in fp32) replace x, lo = f16(residual):
-// the arithmetic of split_rows_kernel (fuse.hip)
-__device__ __forceinline__ void split_pair(float& x0, float& x1, float s, unsigned& hi, unsigned& lo) {
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(s));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(s));
-    asm volatile("v_fma_mix_f32 %0, %0, %1, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "+v"(x0) : "v"(s), "v"(hi));
-    asm volatile("v_fma_mix_f32 %0, %0, %1, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(x1) : "v"(s), "v"(hi));
-    asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(x0), "v"(x1));
-}
-
-// ---- the epilogue of a column block as a static stream of micro-ops -----------------------------------------------------------------
-// Per accumulator i (row 8 (i >> 2) + 4 hh + (i & 3) of the wave's 32, the lane's column):
-//   MUL t = acc * rs[i]   FMA1 t = t * c.x + c.y   [EXP t = 2^t   ADD1 t = t + 1   RCP t = 1 / t] | [MAX t = max(t, 0)]   FMA2 t = t * c.z + c.w   ST
-// with the lane constants c = {cs', b', c1, c0} folded by laff_fc_strip_pack so that the chain is the whole FC epilogue:
-//   tanh:    y' = 2 log2(e) (cs acc rs + bias), tanh = 1 - 2 / (2^y' + 1), out = (bn_s + bn_t) + (-2 bn_s) / (2^y' + 1)
-//   sigmoid: y' = -log2(e) (...),              out = bn_t + bn_s / (2^y' + 1)
-//   relu:    out = bn_s max(y, 0) + bn_t;      none: out = (cs bn_s) acc rs + (bn_s bias + bn_t)   (one fma)
-// Elements go in groups of four, stage by stage, so that a dependent pair is four instructions apart (the transcendental ->
-// VALU forwarding hazard needs one; hipcc pads nothing inside or between asm statements it cannot see into).
-enum : unsigned char { OP_WAITCV = 0, OP_MUL, OP_FMA1, OP_EXP, OP_ADD1, OP_RCP, OP_MAX, OP_FMA2, OP_ST };
-enum { ACT_LIN = 0, ACT_RELU = 1, ACT_EXP = 2 };                 // epilogue kinds (template parameter)
-struct EpiOp { unsigned char kind, elem; };
-struct EpiStream { EpiOp op[160]; int n; };
-constexpr int op_cost(unsigned char k) { return (k == OP_EXP || k == OP_RCP) ? 3 : (k == OP_WAITCV ? 0 : (k == OP_ST ? 2 : 1)); }
-
-template <int ACTK>
-constexpr EpiStream make_stream() {
-    EpiStream s{};
-    s.n = 0;
-    auto push = [&](unsigned char k, int e) { s.op[s.n++] = EpiOp{k, (unsigned char)e}; };
-    push(OP_WAITCV, 0);
-    for (int g = 0; g < 4; ++g) {
-        auto stage = [&](unsigned char k) { for (int e = 0; e < 4; ++e) push(k, 4 * g + e); };
-        stage(OP_MUL);
-        stage(OP_FMA1);
-        if (ACTK == ACT_EXP) { stage(OP_EXP); stage(OP_ADD1); stage(OP_RCP); stage(OP_FMA2); }
-        if (ACTK == ACT_RELU) { stage(OP_MAX); stage(OP_FMA2); }
-        stage(OP_ST);
-    }
-    return s;
-}
-
-// ---- the schedule of one column block (two bodies H = 0, 1 of 16 sub-steps J, three MFMAs M each): slot sg = 48 H + 3 J + M ----------
-//   * (J, 0): the two fragment reads (hi, lo plane) of the sub-step FD ahead -- from J = BAR_J on that is the NEXT ring slot;
-//   * in front of sub-step BAR_J: counted vmcnt (this wave's pieces of the next slot have landed) + s_barrier (everybody's have, and
-//     everybody is done with the previous slot, which the pieces issued right behind the barrier refill -- 4 slots: 3 ahead);
-//   * (BAR_J .. 15, M = 1) and two M = 2 slots: the 8 DMA pieces;  (H = 0, J = 0, M = 1): this block's four lane constants (one load);
-//     -- in the LAST THREE bodies of a segment those pieces would fetch W slots beyond it: they carry the first three K-eighth rounds
-//     of the NEXT strip's input rows instead (same count, same LDS targets: this wave's 8 KiB of the slot being freed); the first of
-//     the three also issues round 3 into the staging-only fifth buffer, and round 4 goes into the last body's slot in front of the
-//     drain: the strip switch starts with 40 of its 64 KiB per wave in LDS or on the way;
-//   * everything else: the epilogue stream of the previous block, spread evenly (cost-weighted).  It starts behind the third MFMA
-//     of the block (the previous block's last MFMA has retired by then) and ends before the block does.
-constexpr int slot_piece(int sg) {
-    const int J = (sg % 48) / 3, M = sg % 3;
-    if (M == 1 && J >= BAR_J) return J - BAR_J;          // one per sub-step behind the barrier ...
-    if (M == 2 && J == BAR_J + 1) return 6;              // ... and two sub-steps with a second one: the four waves leave the barrier
-    if (M == 2 && J == BAR_J + 4) return 7;              // together, and pieces packed into four sub-steps queue up in the CU's one TA path
-    return -1;
-}
-constexpr bool slot_cvload(int sg) { return sg == 1; }
-struct Plan {
-    short begin[NSLOT + 1];
-    short vm_bar[2];      // vmcnt operand at the barrier of body H
-    short vm_cv;          // vmcnt operand in front of the first use of the previous block's lane constants
-    bool fits;
-};
-template <int ACTK>
-constexpr Plan make_plan() {
-    Plan p{};
-    const EpiStream st = make_stream<ACTK>();
-    int usable = 0, total = 0;
-    auto ok = [](int sg) { return sg >= 3 && slot_piece(sg) < 0; };
-    for (int sg = 0; sg < NSLOT; ++sg) usable += ok(sg) ? 1 : 0;
-    for (int i = 0; i < st.n; ++i) total += op_cost(st.op[i].kind);
-    usable -= 4;                                        // finish a few slots early
-    int at = 0, k = 0, spent = 0;
-    for (int sg = 0; sg < NSLOT; ++sg) {
-        p.begin[sg] = (short)at;
-        if (!ok(sg)) continue;
-        ++k;
-        const int target = (int)(((long)k * total + usable - 1) / usable);
-        while (at < st.n && spent < target) { spent += op_cost(st.op[at].kind); ++at; }
-    }
-    p.begin[NSLOT] = (short)at;
-    p.fits = at == st.n;
-    // vector-memory program order over three consecutive identical blocks; the third one is measured
-    int vm_n = 0, last_piece[3][2] = {}, cv_ord[3] = {}, bar_at[3][2] = {}, waitcv_at[3] = {};
-    for (int blk = 0; blk < 3; ++blk)
-        for (int sg = 0; sg < NSLOT; ++sg) {
-            const int H = sg / 48, J = (sg % 48) / 3, M = sg % 3;
-            if (J == BAR_J && M == 0) bar_at[blk][H] = vm_n;
-            if (slot_cvload(sg)) cv_ord[blk] = ++vm_n;
-            if (slot_piece(sg) >= 0) { ++vm_n; last_piece[blk][H] = vm_n; }
-            for (int i = p.begin[sg]; i < p.begin[sg + 1]; ++i) {
-                if (st.op[i].kind == OP_WAITCV) waitcv_at[blk] = vm_n;
-                if (st.op[i].kind == OP_ST) ++vm_n;
-            }
-        }
-    auto clamp = [](int c) { return c < 0 ? 0 : (c > 63 ? 63 : c); };
-    // barrier of body (b, H): the pieces of ring slot sigma + 1 were issued in body sigma - 2 = (b - 1, H)
-    for (int H = 0; H < 2; ++H) p.vm_bar[H] = (short)clamp(bar_at[2][H] - last_piece[1][H]);
-    p.vm_cv = (short)clamp(waitcv_at[2] - cv_ord[1]);
-    return p;
-}
+// The schedule of one column block (fc_strip_common.h): a fragment is a sub-step J, three MFMAs M behind it: slot sg = 48 H + 3 J + M.
+// The epilogue's accumulator i is row 8 (i >> 2) + 4 hh + (i & 3) of the wave's 32, the lane's column: one store (a dword) each.
+constexpr Geometry GEOM = {.mfmas = 3, .skip_read_slots = false, .piece_m = 1, .piece_m2 = 2, .cv_loads = 1, .early = 4,
+                           .slot_cycles = 0, .cost_valu = 1, .cost_trans = 3, .cost_store = 2};
+constexpr int ST_STEP = 1;
+constexpr int DRAIN_STORES = 16 / ST_STEP;            // OP_ST items of the stream: what a drain leaves in the vector-memory queue
 
 }  // namespace
 
@@ -296,9 +81,8 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
     const int u1 = pin_s((int)(U * (myrange + 1) / nranges));
     const unsigned img_bytes = (unsigned)nblk * (2u * SLOT);
 
-    constexpr Plan PLAN = make_plan<ACTK>();
-    constexpr EpiStream STREAM = make_stream<ACTK>();
-    constexpr int DRAIN_STORES = 16;                      // OP_ST items of the stream: what a drain leaves in the vector-memory queue
+    constexpr EpiStream STREAM = make_stream<ACTK, ST_STEP>();
+    constexpr Plan PLAN = make_plan(GEOM, STREAM);
     static_assert(PLAN.fits, "the epilogue stream does not fit behind the MFMAs of one column block");
 
     // per-lane constants of the loops
@@ -311,13 +95,8 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
     int pre_base = -1;           // >= 0: the previous segment's last three bodies brought rounds 0..2 of this segment's strip into buffers (e + pre_base) & 3
     const unsigned m0_keep = m0_get();
 #ifdef LAFF_FCS_TRACE
-    // debug build: cycle stamps of wave 0 -- per segment s (up to 8): base 8 s: +0 start, +1 strip in the registers (raw), +2 row maxima,
-    // +3 converted, +4 ring prologue landed + barrier, +5 block loop done, +6 drained + segment end | [64 + s] = blocks of the segment
-    unsigned long long* const trc = a.trace ? a.trace + (size_t)blockIdx.x * 80 : nullptr;
+    unsigned long long* const trc = a.trace ? a.trace + (size_t)blockIdx.x * 80 : nullptr;     // (LAFF_FCS_STAMP: fc_strip_common.h)
     int trc_seg = 0;
-#define STAMP(i) do { if (trc && tid == 0 && trc_seg < 8) trc[8 * trc_seg + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
 #endif
 
     while (u0 < u1) {
@@ -330,7 +109,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         const int blk0 = __builtin_amdgcn_readfirstlane(ul - strip * nblk);
         const int n = __builtin_amdgcn_readfirstlane(std::min(nblk - blk0, u1 - u0));
         u0 += n;
-        STAMP(0);
+        LAFF_FCS_STAMP(0);
 #ifdef LAFF_FCS_TRACE
         if (trc && tid == 0 && trc_seg < 8) trc[64 + trc_seg] = (unsigned long long)n;
 #endif
@@ -399,32 +178,32 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             // round -> buffer.  Without early rounds: 0 1 2 3 X 0 1 2 (five in flight).  With them: rounds 0..2 sit in ring slots b0 b1 b2
             // (b_i = (i + base) & 3), round 3 in X, round 4 in b3 (the previous segment's last slot): b0 b1 b2 X b3 b0 b1 X -- round 7 follows
             // round 3, which landed long ago, not round 2, the last one to have been issued.
-            auto buf_of = [&](int e) {
+            auto buf_of = [&](int e) __attribute__((always_inline)) {
                 const int ring = pre ? (e < 3 ? e : (e == 4 ? 3 : e - 5)) : (e < 4 ? e : e - 5);
                 const bool x = pre ? (e == 3 || e == 7) : e == 4;
                 return ldsw + (unsigned)(x ? RING : ((ring + base) & 3)) * (unsigned)SLOT;
             };
-            auto issue_round = [&](auto EC) {
+            auto issue_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
                 const unsigned long long ebase = xbase + (unsigned long long)(e * 256);
                 const unsigned b = pin_s(buf_of(e));
-                static_for<0, 8>([&](auto TC) {
+                static_for<0, 8>([&](auto TC) __attribute__((always_inline)) {
                     constexpr int t = decltype(TC)::value;
                     dma_rows<t * 1024>(xv[t], ebase, b);
                 });
             };
             float m0 = 0.f, m1 = 0.f;                  // running maxima of |x| over this lane's half of its row
             u32x4 rq[8];
-            auto read_round = [&](auto EC) {
+            auto read_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
                 const unsigned b = buf_of(e);
-                static_for<0, 8>([&](auto JC) { constexpr int j = decltype(JC)::value; lds_read128<0>(rq[j], XA[j] + b); });
+                static_for<0, 8>([&](auto JC) __attribute__((always_inline)) { constexpr int j = decltype(JC)::value; lds_read128<0>(rq[j], XA[j] + b); });
                 wait_lgkm<0>();
-                static_for<0, 8>([&](auto IC) { pin_v(rq[decltype(IC)::value]); });
+                static_for<0, 8>([&](auto IC) __attribute__((always_inline)) { pin_v(rq[decltype(IC)::value]); });
             };
-            auto stash_round = [&](auto EC) {
+            auto stash_round = [&](auto EC) __attribute__((always_inline)) {
                 constexpr int e = decltype(EC)::value;
-                static_for<0, 4>([&](auto CC) {
+                static_for<0, 4>([&](auto CC) __attribute__((always_inline)) {
                     constexpr int cc = decltype(CC)::value;
                     stash_chunk<8 * (4 * e + cc)>(rq[2 * cc], rq[2 * cc + 1], m0, m1);
                 });
@@ -460,31 +239,24 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         }
         __builtin_amdgcn_s_barrier();            // every wave has emptied its staging quarter: the ring may fill
         asm volatile("" ::: "memory");
-        STAMP(1);
+        LAFF_FCS_STAMP(1);
 
-        // ---- W ring prologue: the first three slots of the segment (slot s of the segment = image slot 2 blk0 + s); it lands while the
-        // strip is converted.  The image as a raw buffer starting at this wave's 8 KiB of a slot ----
+        // ---- W ring prologue: the segment's first three slots land while the strip is converted.  The image as a raw buffer starting at
+        // this wave's 8 KiB of a slot ----
         const u32x4 rsrcW = rebased_rsrc(pW, img_bytes, wslot);
         unsigned soffW = (unsigned)blk0 * (2u * SLOT);                        // image offset of the slot the next pieces belong to
-        static_for<0, 3>([&](auto SC) {
-            constexpr int s = decltype(SC)::value;
-            static_for<0, PIECES>([&](auto PC) {
-                constexpr int P = decltype(PC)::value;
-                dma_piece<s * SLOT + P * 1024>(lane16 + (unsigned)(P * 1024), rsrcW, std::min(soffW, img_bytes - SLOT), ldsw);
-            });
-            soffW += SLOT;
-        });
+        ring_prologue(lane16, rsrcW, soffW, img_bytes, ldsw);
 
         // ---- the raw strip is converted in place ----
-        STAMP(2);
+        LAFF_FCS_STAMP(2);
         {
             const float s = pow2f(9 - e_row);
             asm volatile("s_nop 1" ::: "memory");
             // sub-step g: hi <- a[8 g .. 8 g + 3], lo <- a[8 g + 4 .. 8 g + 7]; halves e = 0 .. 7 <-> raw registers 8 g + e
-            static_for<0, 32>([&](auto GC) { convert_chunk_inplace<8 * decltype(GC)::value>(s); });
+            static_for<0, 32>([&](auto GC) __attribute__((always_inline)) { convert_chunk_inplace<8 * decltype(GC)::value>(s); });
         }
         asm volatile("s_nop 3" ::: "memory");            // v_accvgpr_write -> MFMA reading it
-        STAMP(3);
+        LAFF_FCS_STAMP(3);
         {
             // the epilogue's row scales: lane (n31, hh) needs those of rows 8 q + 4 hh + e, which lane 8 q + 4 hh + e has
             const float mine = pow2f(e_row - 9);
@@ -508,9 +280,9 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         asm volatile("" : "+v"(voff0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        STAMP(4);
+        LAFF_FCS_STAMP(4);
         // fragments of sub-steps 0 .. FD - 1 of the first slot
-        static_for<0, FD>([&](auto JC) {
+        static_for<0, FD>([&](auto JC) __attribute__((always_inline)) {
             constexpr int j = decltype(JC)::value;
             lds_read128<j * 1024>(fr[j][0], xa0);
             lds_read128<PLANE + j * 1024>(fr[j][1], xa0);
@@ -523,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
         using IM1 = std::integral_constant<int, -1>;
-        auto epi_item = [&](auto QC, auto IC, auto DRAIN) {
+        auto epi_item = [&](auto QC, auto IC, auto DRAIN) __attribute__((always_inline)) {
             constexpr int Q = decltype(QC)::value;
             constexpr EpiOp op = STREAM.op[decltype(IC)::value];
             constexpr int i = op.elem;
@@ -553,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
         };
 
         // ---- one body: half a column block (ring slot 2 PAR + H), see "the schedule of one column block" --------------------------------
-        auto body = [&](auto PARC, auto HC, auto XRC, int blk) {
+        auto body = [&](auto PARC, auto HC, auto XRC, int blk) __attribute__((always_inline)) {
             constexpr int PAR = decltype(PARC)::value, H = decltype(HC)::value, Q = PAR ^ 1;
             constexpr int XR = decltype(XRC)::value;                 // >= 0: the pieces carry round XR of the next strip's rows, not the W stream
             constexpr int RSLOT = 2 * PAR + H;                                   // this body's ring slot
@@ -562,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             const unsigned soff_here = std::min(soffW, img_bytes - SLOT);
             soffW += SLOT;
             if constexpr (H == 0) soffY = (unsigned)(blk - 1) * 128u;
-            static_for<0, 16>([&](auto JC) {
+            static_for<0, 16>([&](auto JC) __attribute__((always_inline)) {
                 constexpr int J = decltype(JC)::value;
                 constexpr int G = 16 * H + J;                                    // sub-step of the block: strip registers 8 G ..
                 if constexpr (J == BAR_J) {
@@ -573,7 +345,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
                 }
                 wait_lgkm<2 * (FD - 1)>();                                       // the two fragments of this sub-step have arrived
                 __builtin_amdgcn_sched_barrier(0);
-                static_for<0, 3>([&](auto MC) {
+                static_for<0, 3>([&](auto MC) __attribute__((always_inline)) {
                     constexpr int M = decltype(MC)::value, SG = 48 * H + 3 * J + M;
                     // lo.hi, hi.lo (small terms first), hi.hi
                     if constexpr (M == 0) mfma_strip<8 * G + 4, (G == 0)>(acc[PAR], fr[G % NSETS][0]);
@@ -602,14 +374,14 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
                         // round 3 of the next strip, to the staging-only buffer (no ring slot: no barrier to respect)
                         dma_piece<XB_OFF + J * 1024>(xvn[J], rsrcXn, 3u * 256u, ldsw);
                     }
-                    constexpr int dp = slot_piece(SG);
+                    constexpr int dp = slot_piece(GEOM, SG);
                     if constexpr (dp >= 0) {
                         // the W stream's piece dp of the slot three ahead -- or, in the segment's last three bodies, instruction dp of round
                         // XR of the next strip's rows; same LDS target either way
                         if constexpr (XR >= 0) dma_piece<DSLOT * SLOT + dp * 1024>(xvn[dp], rsrcXn, (unsigned)(256 * XR), ldsw);
                         else dma_piece<DSLOT * SLOT + dp * 1024>(lane16 + (unsigned)(dp * 1024), rsrcW, soff_here, ldsw);
                     }
-                    static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) {
+                    static_for<PLAN.begin[SG], PLAN.begin[SG + 1]>([&](auto IC) __attribute__((always_inline)) {
                         __builtin_amdgcn_sched_barrier(0);
                         epi_item(std::integral_constant<int, Q>{}, IC, IM1{});
                     });
@@ -618,20 +390,20 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             });
         };
 
-        auto drain = [&](auto QC, auto EXTRA, int blk) {
-            STAMP(5);
+        auto drain = [&](auto QC, auto EXTRA, int blk) __attribute__((always_inline)) {
+            LAFF_FCS_STAMP(5);
             mfma_drain_nops();
             rsrcYe = rsrcY;
             soffY = (unsigned)blk * 128u;
-            static_for<0, STREAM.n>([&](auto IC) { epi_item(QC, IC, EXTRA); });
+            static_for<0, STREAM.n>([&](auto IC) __attribute__((always_inline)) { epi_item(QC, IC, EXTRA); });
         };
         // The segment's blocks: a plain loop, then -- when a next segment exists -- its last two blocks as the copies whose last three bodies
         // fetch the next strip's first three rounds (compile-time copies: the plain loop keeps its one branch per two blocks).
-        auto plain = [&](auto PARC, int b) {
+        auto plain = [&](auto PARC, int b) __attribute__((always_inline)) {
             body(PARC, I0{}, IM1{}, blk0 + b);
             body(PARC, I1{}, IM1{}, blk0 + b);
         };
-        auto tail = [&](auto PARC, int b) {
+        auto tail = [&](auto PARC, int b) __attribute__((always_inline)) {
             constexpr int P = decltype(PARC)::value;
             body(PARC, I0{}, IM1{}, blk0 + b);
             body(PARC, I1{}, I0{}, blk0 + b);
@@ -642,7 +414,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
             // body's slot and flies while the drain computes.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            static_for<0, 8>([&](auto TC) {
+            static_for<0, 8>([&](auto TC) __attribute__((always_inline)) {
                 constexpr int t = decltype(TC)::value;
                 dma_piece<(2 * (P ^ 1) + 1) * SLOT + t * 1024>(xvn[t], rsrcXn, 4u * 256u, ldsw);
             });
@@ -676,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
 #pragma unroll
         for (int s8 = 0; s8 < NSETS; ++s8) asm volatile("" ::"v"(fr[s8][0]), "v"(fr[s8][1]));
         if (!has_next) __builtin_amdgcn_s_barrier();   // every wave is done with the ring before the next segment's strip staging refills it
-        STAMP(6);
+        LAFF_FCS_STAMP(6);
 #ifdef LAFF_FCS_TRACE
         ++trc_seg;
 #endif
@@ -684,60 +456,27 @@ __global__ __launch_bounds__(256, 1) void fc_strip_kernel(const FcStripArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA of this workgroup outlives it
     m0_set(m0_keep);
     agpr_hold_end(hold);
-#undef STAMP
 }
 
-// ---- W [D][512] fp32 (+ bias, BatchNorm, activation) -> the LDS image + the lane-constant table -------------------------------------
-// One workgroup (256 threads) per output column: row maximum -> power-of-two scale (as split_rows_kernel), hi / lo halves scattered
-// into the image {block n / 32}{K half}{plane}{sub-step}{lane = 32 hh + n % 32}{8 halves}.
-__global__ __launch_bounds__(256) void fc_strip_pack_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias,
-                                                            const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int D,
-                                                            int act, _Float16* __restrict__ img, float* __restrict__ vec) {
-    __shared__ float red[4];
-    const int n = blockIdx.x, tid = threadIdx.x;
-    if (n >= D) return;
-    const float x0 = W[(size_t)n * ldw + tid], x1 = W[(size_t)n * ldw + 256 + tid];
-    float m = fmaxf(fabsf(x0), fabsf(x1));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((tid & 63) == 0) red[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const int e = split_exponent(m);
-    const float s = pow2f(9 - e), cs = pow2f(e - 9);
-    const int blk = n >> 5, n31 = n & 31;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int k = t * 256 + tid;
-        const float x = (t ? x1 : x0) * s;
-        const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-        const int j = k >> 4, w = k & 15;
-        const int half = j >> 4, jj = j & 15, hh = (w >> 2) & 1, pos = (w & 3) + 4 * (w >> 3);
-        const size_t base = ((size_t)(blk * 2 + half) * 2) * (PLANE / 2);        // in halves: slot start
-        const size_t at = (size_t)(jj * 64 + 32 * hh + n31) * 8 + pos;
-        img[base + at] = h;
-        img[base + PLANE / 2 + at] = l;
-    }
-    if (tid == 0) {
-        const float b = bias ? bias[n] : 0.f, g = bn_scale ? bn_scale[n] : 1.f, t = bn_shift ? bn_shift[n] : 0.f;
-        float4 c;
-        if (act == LAFF_ACT_TANH) c = make_float4(cs * 2.885390081777927f, b * 2.885390081777927f, -2.f * g, g + t);
-        else if (act == LAFF_ACT_SIGMOID) c = make_float4(cs * -1.4426950408889634f, b * -1.4426950408889634f, g, t);
-        else if (act == LAFF_ACT_RELU) c = make_float4(cs, b, g, t);
-        else c = make_float4(cs * g, fmaf(b, g, t), 0.f, 0.f);
-        *(float4*)(vec + 4 * (size_t)n) = c;
-    }
+hipError_t fc_strip32_launch(const FcStripArgs& a, int kind, hipStream_t st) {
+    if (kind == ACT_EXP) return fc_strip_launch<fc_strip_kernel<ACT_EXP>>(a, st);
+    if (kind == ACT_RELU) return fc_strip_launch<fc_strip_kernel<ACT_RELU>>(a, st);
+    return fc_strip_launch<fc_strip_kernel<ACT_LIN>>(a, st);
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
+// ---- host side, both MFMA shapes ------------------------------------------------------------------------------------------------------
+// LAFF_FC_STRIP_MFMA (read when a ctx is created): 16 = fc_strip16.hip's kernels (default), 32 = this file's.  It picks the image
+// layout launch_fc_strip_pack writes and the kernel launch_fc_strip runs: an image must be launched in the mode it was packed in.
+int g_fc_strip_mfma = 16;
+
 size_t fc_strip_image_bytes(int D) { return (size_t)(D / 32) * (2 * SLOT) + (size_t)D * 16; }
 size_t fc_strip_vec_offset(int D) { return (size_t)(D / 32) * (2 * SLOT); }
 
 hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
                                 void* img, hipStream_t st) {
-    if (g_fc_strip_mfma != 32) return launch_fc_strip16_pack(W, ldw, bias, bn_scale, bn_shift, D, act, img, st);   // (fc_strip16.hip)
-    hipLaunchKernelGGL(fc_strip_pack_kernel, dim3((unsigned)D), dim3(256), 0, st, W, ldw, bias, bn_scale, bn_shift, D, act,
-                       (_Float16*)img, (float*)((char*)img + fc_strip_vec_offset(D)));
+    const auto pack = g_fc_strip_mfma == 32 ? fc_strip_pack_kernel<32> : fc_strip_pack_kernel<16>;
+    hipLaunchKernelGGL(pack, dim3((unsigned)D), dim3(256), 0, st, W, ldw, bias, bn_scale, bn_shift, D, act, (_Float16*)img,
+                       (float*)((char*)img + fc_strip_vec_offset(D)));
     return hipGetLastError();
 }
 
@@ -759,18 +498,8 @@ hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st) {
     // Workgroup b runs on XCD b % 8 (observed; only speed depends on it): XCD x takes the contiguous eighth x of the ranges, so its L2
     // holds the W images of the one or two features its CUs are working on.
     for (int b = 0; b < G; ++b) a.range_of_wg[b] = (unsigned short)((G % 8 == 0) ? (b % 8) * (G / 8) + b / 8 : b);
-    if (g_fc_strip_mfma != 32) return launch_fc_strip16(a, act, st);      // the same launch on 16x16x32 MFMAs (fc_strip16.hip)
-#define LAFF_FCS_LAUNCH(K)                                                                                                    \
-    do {                                                                                                                      \
-        static unsigned long long attr_done = 0;                                                                              \
-        if (hipError_t e = smem_attr_once(attr_done, fc_strip_kernel<K>, SMEM); e != hipSuccess) return e;                    \
-        hipLaunchKernelGGL((fc_strip_kernel<K>), dim3((unsigned)G), dim3(256), SMEM, st, a);                                  \
-    } while (0)
-    if (act == LAFF_ACT_TANH || act == LAFF_ACT_SIGMOID) LAFF_FCS_LAUNCH(ACT_EXP);
-    else if (act == LAFF_ACT_RELU) LAFF_FCS_LAUNCH(ACT_RELU);
-    else LAFF_FCS_LAUNCH(ACT_LIN);
-#undef LAFF_FCS_LAUNCH
-    return hipGetLastError();
+    const int kind = (act == LAFF_ACT_TANH || act == LAFF_ACT_SIGMOID) ? ACT_EXP : (act == LAFF_ACT_RELU ? ACT_RELU : ACT_LIN);
+    return g_fc_strip_mfma == 32 ? fc_strip32_launch(a, kind, st) : fc_strip16_launch(a, kind, st);
 }
 
 }  // namespace laff

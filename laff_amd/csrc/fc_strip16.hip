@@ -3,10 +3,10 @@
 // v_mfma_f32_32x32x16_f16: the same flops in the same cycles, at less energy per flop -- the chip holds a higher clock on this shape
 // (docs/experiments.md, "fc_strip on 16x16x32 MFMAs"; tools/probe/fcshapeprobe.hip).  Selected by LAFF_FC_STRIP_MFMA (api.hip).
 //
-// The decomposition is fc_strip.hip's, comment for comment: 4 wavefronts of 32 rows x K = 512 {hi, lo}, the 4 x 32 KiB ring + the
+// The decomposition is fc_strip.hip's (its header describes it): 4 wavefronts of 32 rows x K = 512 {hi, lo}, the 4 x 32 KiB ring + the
 // staging buffer, 8 LDS-DMA pieces per wave and slot, 64 fragment reads per column block of 32 outputs, persistent ranges, the early
 // rounds of the next strip, the accumulator-file guard, the three epilogue kinds, the image size and the [D][4] constant table.  What
-// differs is the fragment geometry:
+// the two share as code is fc_strip_common.h; the kernel body is this file's own.  What differs is the fragment geometry:
 //   * A (the strip): lane (i = lane & 15, g = lane >> 4) holds rows i and i + 16 of the wave's 32 (row tiles t = 0, 1).  K step J
 //     (32 k), row tile t: a[16 J + 8 t .. + 3] = hi halves, a[16 J + 8 t + 4 .. + 7] = lo halves; element e <-> k = 32 J + 4 g +
 //     (e & 3) + 16 (e >> 2), so that the four lanes of a row read adjacent 16-byte pieces of it.  One power-of-two scale per row,
@@ -18,71 +18,22 @@
 //   * a lane's 16 accumulators are 8 rows (16 t + 4 g + e) x 2 ADJACENT columns: the epilogue stores a dwordx2 per (t, e) -- 4 rows x
 //     128 contiguous bytes per instruction, 8 stores per block -- and the lane constants are two 16-byte loads;
 //   * the planner gives a 16-cycle MFMA slot at most 8 cycles of epilogue: one or two plain VALU, or one v_exp / v_rcp, or one store.
-// An image is read in the geometry it was packed in: fc_strip16_pack_kernel's images are not fc_strip_pack_kernel's.
+// An image is read in the geometry it was packed in: fc_strip_pack_kernel<16>'s images are not fc_strip_pack_kernel<32>'s.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
-#include <vector>
 
-#include "kernels.h"
-#include "strip_util.h"
+#include "fc_strip_common.h"
 #include "wave_reduce.h"
 
 namespace laff {
 
 namespace {
 
-using namespace su;
+using namespace fcs;
 
-typedef __attribute__((address_space(1))) unsigned gu32;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int FR = FC_STRIP_ROWS;              // 128 rows per strip: 4 wavefronts x 32
-constexpr int SLOT = 32 * 1024;                // one ring slot: 32 columns x 256 k x {hi, lo}
-constexpr int PLANE = 16 * 1024;
-constexpr int RING = 4;
-constexpr int PIECES = 8;                      // 1 KiB LDS-DMA pieces per wave per slot
-constexpr int XB_OFF = RING * SLOT;            // a fifth 32 KiB buffer, strip staging only (all of the CU's LDS: 160 KiB)
-constexpr int SMEM = XB_OFF + SLOT;
-static_assert(SMEM <= 160 * 1024, "LDS budget");
-
-constexpr int FD = 6;                          // fragment reads run FD fragments (K step, column tile) ahead,
-constexpr int NSETS = 8;                       // into 8 register sets (two planes each; 32 fragments per block: a divisor of 32)
-static_assert(32 % NSETS == 0 && FD < NSETS - 1 && FD % 2 == 0, "the set of a fragment must not depend on the block");
-constexpr int BAR_J = 16 - FD;                 // the body's barrier sits in front of this fragment (an even one: a K step)
-constexpr int NSLOT = 192;                     // MFMA issue slots of a column block: 2 bodies x 16 fragments x 6
-
-// ---- all 256 accumulator registers are named literally (the strip).  hipcc must not put anything of its own there (left alone it parks
-// long-lived values in a0.. when the 256 architectural registers get tight -- silently overwritten by the strip): 64 dummy quads are
-// defined in the accumulator file at kernel entry and "used" at its exit, so the allocator sees every one of them occupied throughout;
-// if registers run out it spills to scratch instead, which tools/debug/isa_audit.py reports. ----
-struct AgprHold { u32x4 q[64]; };
-#define HOLD16(OP, h, b)                                                                                                                  \
-    OP(h.q[b], h.q[b + 1], h.q[b + 2], h.q[b + 3], h.q[b + 4], h.q[b + 5], h.q[b + 6], h.q[b + 7], h.q[b + 8], h.q[b + 9], h.q[b + 10], h.q[b + 11], \
-       h.q[b + 12], h.q[b + 13], h.q[b + 14], h.q[b + 15])
-#define HOLD_DEF(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, xa, xb, xc, xd, xe, xf)                                                            \
-    asm volatile("" : "=a"(x0), "=a"(x1), "=a"(x2), "=a"(x3), "=a"(x4), "=a"(x5), "=a"(x6), "=a"(x7), "=a"(x8), "=a"(x9), "=a"(xa), "=a"(xb), \
-                 "=a"(xc), "=a"(xd), "=a"(xe), "=a"(xf))
-#define HOLD_USE(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, xa, xb, xc, xd, xe, xf)                                                            \
-    asm volatile("" ::"a"(x0), "a"(x1), "a"(x2), "a"(x3), "a"(x4), "a"(x5), "a"(x6), "a"(x7), "a"(x8), "a"(x9), "a"(xa), "a"(xb), "a"(xc),   \
-                 "a"(xd), "a"(xe), "a"(xf))
-__device__ __forceinline__ void agpr_hold_begin(AgprHold& h) { HOLD16(HOLD_DEF, h, 0); HOLD16(HOLD_DEF, h, 16); HOLD16(HOLD_DEF, h, 32); HOLD16(HOLD_DEF, h, 48); }
-__device__ __forceinline__ void agpr_hold_end(AgprHold& h) { HOLD16(HOLD_USE, h, 0); HOLD16(HOLD_USE, h, 16); HOLD16(HOLD_USE, h, 32); HOLD16(HOLD_USE, h, 48); }
-
-template <int R, int OFF>
-__device__ __forceinline__ void agpr_load4(const void* p) {            // a[R .. R + 3] <- 16 bytes at p + OFF
-    asm volatile("global_load_dwordx4 a[%c1:%c2], %0, off offset:%c3" ::"v"(p), "n"(R), "n"(R + 3), "n"(OFF) : "memory");
-}
-template <int R>
-__device__ __forceinline__ float agpr_read() {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "n"(R));
-    return x;
-}
-template <int R>
-__device__ __forceinline__ void agpr_write(unsigned x) { asm volatile("v_accvgpr_write_b32 a[%c1], %0" ::"v"(x), "n"(R)); }
 
 // acc (+)= A(strip fragment in a[R .. R + 3]: rows of X) x B(fragment of the W stream: output columns)
 template <int R, bool FIRST>
@@ -90,194 +41,22 @@ __device__ __forceinline__ void mfma_strip(f32x4& acc, const u32x4& wfrag) {
     if constexpr (FIRST) asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c2:%c3], %1, 0" : "=v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
     else asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c2:%c3], %1, %0" : "+v"(acc) : "v"(wfrag), "n"(R), "n"(R + 3));
 }
-
-template <int IMM>
-__device__ __forceinline__ void lds_read128(u32x4& d, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
-}
-
-// one 1 KiB piece of the W stream, straight into LDS (lane L lands at M0 base + 16 L; the image is already in LDS order)
-template <int LDSOFF>
-__device__ __forceinline__ void dma_piece(unsigned voff, u32x4 rsrc, unsigned soff, unsigned m0base) {
-    asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(rsrc), "s"(soff), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
-}
-
-// 1 KiB of input rows straight into LDS (lane L lands at M0 base + LDSOFF + 16 L): scalar base + per-lane 32-bit offset.  (No
-// immediate offset: the instruction's offset field moves the LDS address as well as the global one.)
-template <int LDSOFF>
-__device__ __forceinline__ void dma_rows(unsigned voff, unsigned long long base, unsigned m0base) {
-    asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 "
-                 ::"v"(voff), "s"(base), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
-}
-// 16 bytes of the LDS staging -> a[R .. R + 3]
-template <int R, int IMM>
-__device__ __forceinline__ void lds_to_agpr(unsigned addr) {
-    asm volatile("ds_read_b128 a[%c1:%c2], %0 offset:%c3" ::"v"(addr), "n"(R), "n"(R + 3), "n"(IMM) : "memory");
-}
-template <typename T>
-__device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
-// address = voff0 + ROWMUL * ldy4, made right in front of the store (one address register instead of one per accumulator)
+// address = voff0 + ROWMUL * ldy4, made right in front of the store (one address register instead of one per accumulator pair)
 template <int ROWMUL>
 __device__ __forceinline__ void store_row(unsigned& tmp, f32x2 data, unsigned voff0, unsigned ldy4, u32x4 rsrc, unsigned soff) {
     asm volatile("v_mad_u32_u24 %0, %3, %4, %2\n\tbuffer_store_dwordx2 %1, %0, %5, %6 offen nt"
                  : "=&v"(tmp) : "v"(data), "v"(voff0), "s"(ldy4), "n"(ROWMUL), "s"(rsrc), "s"(soff) : "memory");
 }
 
-// row maximum -> exponent of the power-of-two scale: same rule as split_rows_kernel (fuse.hip): maximum scaled into [512, 1024)
-__device__ __forceinline__ int split_exponent(float m) {
-    const int be = (int)((__float_as_uint(m) >> 23) & 0xffu);
-    if (!(m > 0.f) || be == 0xff) return 0;
-    return max(be - 127, -100);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-// one raw chunk (two quads from the staging read-back) -> a[R .. R + 7], its eight values folded into the two running row maxima
-template <int R>
-__device__ __forceinline__ void stash_chunk(const u32x4& q0, const u32x4& q1, float& m0, float& m1) {
-    asm volatile("v_max3_f32 %0, |%2|, |%3|, %0\n\tv_max3_f32 %1, |%4|, |%5|, %1\n\tv_max3_f32 %0, |%6|, |%7|, %0\n\tv_max3_f32 %1, |%8|, |%9|, %1\n\t"
-                 "v_accvgpr_write_b32 a[%c10+0], %2\n\tv_accvgpr_write_b32 a[%c10+1], %3\n\tv_accvgpr_write_b32 a[%c10+2], %4\n\t"
-                 "v_accvgpr_write_b32 a[%c10+3], %5\n\tv_accvgpr_write_b32 a[%c10+4], %6\n\tv_accvgpr_write_b32 a[%c10+5], %7\n\t"
-                 "v_accvgpr_write_b32 a[%c10+6], %8\n\tv_accvgpr_write_b32 a[%c10+7], %9"
-                 : "+v"(m0), "+v"(m1) : "v"(q0.x), "v"(q0.y), "v"(q0.z), "v"(q0.w), "v"(q1.x), "v"(q1.y), "v"(q1.z), "v"(q1.w), "n"(R));
-}
-// a[R .. R + 7] (eight fp32: k = 32 J + 4 g + {0..3}, + 16) -> a[R .. R + 3] = their fp16 hi halves, a[R + 4 .. R + 7] = the lo halves.
-//   hi = f16(x s) (x s is exact: s is a power of two), residual x s - hi exact in fp32, lo = f16(residual): split_rows_kernel's
-//   arithmetic (fuse.hip), as one statement with the four pairs' chains interleaved (a dependent VALU pair costs 7 cycles, not 4)
-template <int R>
-__device__ __forceinline__ void convert_chunk_inplace(float s) {
-    float x0, x1, x2, x3, x4, x5, x6, x7;
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    asm volatile(
-        "v_accvgpr_read_b32 %0, a[%c17+0]\n\tv_accvgpr_read_b32 %1, a[%c17+1]\n\tv_accvgpr_read_b32 %2, a[%c17+2]\n\tv_accvgpr_read_b32 %3, a[%c17+3]\n\t"
-        "v_accvgpr_read_b32 %4, a[%c17+4]\n\tv_accvgpr_read_b32 %5, a[%c17+5]\n\tv_accvgpr_read_b32 %6, a[%c17+6]\n\tv_accvgpr_read_b32 %7, a[%c17+7]\n\t"
-        "v_fma_mixlo_f16 %8, %0, %16, 0\n\tv_fma_mixlo_f16 %9, %2, %16, 0\n\tv_fma_mixlo_f16 %10, %4, %16, 0\n\tv_fma_mixlo_f16 %11, %6, %16, 0\n\t"
-        "v_fma_mixhi_f16 %8, %1, %16, 0\n\tv_fma_mixhi_f16 %9, %3, %16, 0\n\tv_fma_mixhi_f16 %10, %5, %16, 0\n\tv_fma_mixhi_f16 %11, %7, %16, 0\n\t"
-        "v_fma_mix_f32 %0, %0, %16, -%8 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %2, %2, %16, -%9 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %4, %4, %16, -%10 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %6, %6, %16, -%11 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %1, %1, %16, -%8 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %3, %3, %16, -%9 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %5, %5, %16, -%10 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\tv_fma_mix_f32 %7, %7, %16, -%11 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_accvgpr_write_b32 a[%c17+0], %8\n\tv_accvgpr_write_b32 a[%c17+1], %9\n\tv_accvgpr_write_b32 a[%c17+2], %10\n\tv_accvgpr_write_b32 a[%c17+3], %11\n\t"
-        "v_cvt_pk_f16_f32 %12, %0, %1\n\tv_cvt_pk_f16_f32 %13, %2, %3\n\tv_cvt_pk_f16_f32 %14, %4, %5\n\tv_cvt_pk_f16_f32 %15, %6, %7\n\t"
-        "v_accvgpr_write_b32 a[%c17+4], %12\n\tv_accvgpr_write_b32 a[%c17+5], %13\n\tv_accvgpr_write_b32 a[%c17+6], %14\n\tv_accvgpr_write_b32 a[%c17+7], %15"
-        : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(x5), "=&v"(x6), "=&v"(x7), "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3),
-          "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-        : "v"(s), "n"(R));
-}
-__device__ __forceinline__ void absmax3(float& m, float x, float y) { asm volatile("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(x), "v"(y)); }
-// hi = f16(x s) for two values (x s is exact: s is a power of two), the residuals x s - hi (exact in fp32) replace x, lo = f16(residual):
-// the arithmetic of split_rows_kernel (fuse.hip)
-__device__ __forceinline__ void split_pair(float& x0, float& x1, float s, unsigned& hi, unsigned& lo) {
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(s));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(s));
-    asm volatile("v_fma_mix_f32 %0, %0, %1, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "+v"(x0) : "v"(s), "v"(hi));
-    asm volatile("v_fma_mix_f32 %0, %0, %1, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(x1) : "v"(s), "v"(hi));
-    asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(x0), "v"(x1));
-}
-
-// ---- the epilogue of a column block as a static stream of micro-ops -----------------------------------------------------------------
-// Per accumulator i = 8 t + 2 e + u (row 16 t + 4 g + e of the wave's 32, column 2 n + u of the block):
-//   MUL t = acc * rs[4 t + e]   FMA1 t = t * c.x + c.y   [EXP t = 2^t   ADD1 t = t + 1   RCP t = 1 / t] | [MAX t = max(t, 0)]   FMA2 t = t * c.z + c.w
-// and per pair (u = 0, 1) ST: one dwordx2.  The lane constants c = cv[u] = {cs', b', c1, c0} of the lane's two columns are folded by
-// laff_fc_strip_pack so that the chain is the whole FC epilogue (fc_strip.hip has the formulas).
-// Elements go in groups of four (two rows x two columns), stage by stage, so that a dependent pair is four instructions apart (the
-// transcendental -> VALU forwarding hazard needs one; hipcc pads nothing inside or between asm statements it cannot see into).
-enum : unsigned char { OP_WAITCV = 0, OP_MUL, OP_FMA1, OP_EXP, OP_ADD1, OP_RCP, OP_MAX, OP_FMA2, OP_ST };
-enum { ACT_LIN = 0, ACT_RELU = 1, ACT_EXP = 2 };                 // epilogue kinds (template parameter)
-struct EpiOp { unsigned char kind, elem; };
-struct EpiStream { EpiOp op[160]; int n; };
-// issue cycles beside a 16-cycle MFMA, which itself holds the vector issue for 8: a slot takes 8 more
-constexpr int op_cost(unsigned char k) { return (k == OP_EXP || k == OP_RCP || k == OP_ST) ? 8 : (k == OP_WAITCV ? 0 : 4); }
-constexpr int SLOT_CYCLES = 8;
-
-template <int ACTK>
-constexpr EpiStream make_stream() {
-    EpiStream s{};
-    s.n = 0;
-    auto push = [&](unsigned char k, int e) { s.op[s.n++] = EpiOp{k, (unsigned char)e}; };
-    push(OP_WAITCV, 0);
-    for (int g = 0; g < 4; ++g) {
-        auto stage = [&](unsigned char k) { for (int e = 0; e < 4; ++e) push(k, 4 * g + e); };
-        stage(OP_MUL);
-        stage(OP_FMA1);
-        if (ACTK == ACT_EXP) { stage(OP_EXP); stage(OP_ADD1); stage(OP_RCP); stage(OP_FMA2); }
-        if (ACTK == ACT_RELU) { stage(OP_MAX); stage(OP_FMA2); }
-        push(OP_ST, 4 * g);
-        push(OP_ST, 4 * g + 2);
-    }
-    return s;
-}
-constexpr int DRAIN_STORES = 8;                       // OP_ST items of the stream: what a drain leaves in the vector-memory queue
-
-// ---- the schedule of one column block (two bodies H = 0, 1 of 16 fragments F = 2 Jl + u, six MFMAs each): slot sg = 96 H + 6 F + m ---
-// (the MFMAs of a K step's two fragments interleave -- see body -- but the slot of everything else is counted per fragment)
-//   * (F, 0): the two fragment reads (hi, lo plane) of the fragment FD ahead -- from F = BAR_J on that is the NEXT ring slot;
-//   * in front of fragment BAR_J: counted vmcnt (this wave's pieces of the next slot have landed) + s_barrier (everybody's have, and
-//     everybody is done with the previous slot, which the pieces issued right behind the barrier refill -- 4 slots: 3 ahead);
-//   * (BAR_J .. 15, m = 2) and two m = 4 slots: the 8 DMA pieces;  slot 1 of the block: its lane constants (two loads);
-//     -- in the LAST THREE bodies of a segment the pieces carry the first three K-eighth rounds of the NEXT strip's input rows
-//     instead, the first of the three also issues round 3 into the staging-only fifth buffer, and round 4 goes into the last body's
-//     slot in front of the drain (fc_strip.hip);
-//   * everything else but the read slots: the epilogue stream of the previous block, spread evenly by issue cycles, at most
-//     SLOT_CYCLES per slot.  It starts behind the sixth MFMA of the block (the previous block's last MFMA has retired by then)
-//     and ends before the block does.
-constexpr int slot_piece(int sg) {
-    const int F = (sg % 96) / 6, m = sg % 6;
-    if (m == 2 && F >= BAR_J) return F - BAR_J;          // one per fragment behind the barrier ...
-    if (m == 4 && F == BAR_J + 1) return 6;              // ... and two fragments with a second one: the four waves leave the barrier
-    if (m == 4 && F == BAR_J + 4) return 7;              // together, and pieces packed into four fragments queue up in the CU's one TA path
-    return -1;
-}
-constexpr bool slot_cvload(int sg) { return sg == 1; }
-struct Plan {
-    short begin[NSLOT + 1];
-    short vm_bar[2];      // vmcnt operand at the barrier of body H
-    short vm_cv;          // vmcnt operand in front of the first use of the previous block's lane constants
-    short st_half[2];     // stores of the stream issued in body H
-    bool fits;
-};
-template <int ACTK>
-constexpr Plan make_plan() {
-    Plan p{};
-    const EpiStream st = make_stream<ACTK>();
-    int usable = 0, total = 0;
-    auto ok = [](int sg) { return sg >= 6 && sg % 6 != 0 && slot_piece(sg) < 0; };
-    for (int sg = 0; sg < NSLOT; ++sg) usable += ok(sg) ? 1 : 0;
-    for (int i = 0; i < st.n; ++i) total += op_cost(st.op[i].kind);
-    usable -= 6;                                        // finish a few slots early
-    int at = 0, k = 0, spent = 0;
-    for (int sg = 0; sg < NSLOT; ++sg) {
-        p.begin[sg] = (short)at;
-        if (!ok(sg)) continue;
-        ++k;
-        const int target = (int)(((long)k * total + usable - 1) / usable);
-        int here = 0;
-        while (at < st.n && spent < target) {
-            const int c = op_cost(st.op[at].kind);
-            if (here + c > SLOT_CYCLES) break;
-            here += c; spent += c; ++at;
-        }
-    }
-    p.begin[NSLOT] = (short)at;
-    p.fits = at == st.n;
-    // vector-memory program order over three consecutive identical blocks; the third one is measured
-    int vm_n = 0, last_piece[3][2] = {}, cv_ord[3] = {}, bar_at[3][2] = {}, waitcv_at[3] = {};
-    for (int blk = 0; blk < 3; ++blk)
-        for (int sg = 0; sg < NSLOT; ++sg) {
-            const int H = sg / 96, F = (sg % 96) / 6, m = sg % 6;
-            if (F == BAR_J && m == 0) bar_at[blk][H] = vm_n;
-            if (slot_cvload(sg)) { vm_n += 2; cv_ord[blk] = vm_n; }
-            if (slot_piece(sg) >= 0) { ++vm_n; last_piece[blk][H] = vm_n; }
-            for (int i = p.begin[sg]; i < p.begin[sg + 1]; ++i) {
-                if (st.op[i].kind == OP_WAITCV) waitcv_at[blk] = vm_n;
-                if (st.op[i].kind == OP_ST) { ++vm_n; if (blk == 2) ++p.st_half[H]; }
-            }
-        }
-    auto clamp = [](int c) { return c < 0 ? 0 : (c > 63 ? 63 : c); };
-    // barrier of body (b, H): the pieces of ring slot sigma + 1 were issued in body sigma - 2 = (b - 1, H)
-    for (int H = 0; H < 2; ++H) p.vm_bar[H] = (short)clamp(bar_at[2][H] - last_piece[1][H]);
-    p.vm_cv = (short)clamp(waitcv_at[2] - cv_ord[1]);
-    return p;
-}
+// The schedule of one column block (fc_strip_common.h): a fragment is F = 2 Jl + u (K step Jl of the slot, column tile u), six MFMAs
+// behind it: slot sg = 96 H + 6 F + m.  (The MFMAs of a K step's two fragments interleave -- see body -- but the slot of everything
+// else is counted per fragment.)  The epilogue's accumulator i = 8 t + 2 e + u is row 16 t + 4 g + e of the wave's 32, column 2 n + u
+// of the block, its row scale rs[4 t + e], its lane constants cv[u]; one store (a dwordx2) per pair u = 0, 1.
+constexpr Geometry GEOM = {.mfmas = 6, .skip_read_slots = true, .piece_m = 2, .piece_m2 = 4, .cv_loads = 2, .early = 6,
+                           .slot_cycles = 8, .cost_valu = 4, .cost_trans = 8, .cost_store = 8};
+constexpr int ST_STEP = 2;
+constexpr int DRAIN_STORES = 16 / ST_STEP;            // OP_ST items of the stream: what a drain leaves in the vector-memory queue
+static_assert(FD < NSETS - 1 && FD % 2 == 0 && BAR_J % 2 == 0, "the barrier sits in front of a K step, whose two fragments are read together");
 
 }  // namespace
 
@@ -299,8 +78,8 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
     const int u1 = pin_s((int)(U * (myrange + 1) / nranges));
     const unsigned img_bytes = (unsigned)nblk * (2u * SLOT);
 
-    constexpr Plan PLAN = make_plan<ACTK>();
-    constexpr EpiStream STREAM = make_stream<ACTK>();
+    constexpr EpiStream STREAM = make_stream<ACTK, ST_STEP>();
+    constexpr Plan PLAN = make_plan(GEOM, STREAM);
     static_assert(PLAN.fits, "the epilogue stream does not fit behind the MFMAs of one column block");
 
     // per-lane constants of the loops
@@ -313,13 +92,8 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
     int pre_base = -1;           // >= 0: the previous segment's last three bodies brought rounds 0..2 of this segment's strip into buffers (e + pre_base) & 3
     const unsigned m0_keep = m0_get();
 #ifdef LAFF_FCS_TRACE
-    // debug build: cycle stamps of wave 0 -- per segment s (up to 8): base 8 s: +0 start, +1 strip in the registers (raw), +2 row maxima,
-    // +3 converted, +4 ring prologue landed + barrier, +5 block loop done, +6 drained + segment end | [64 + s] = blocks of the segment
-    unsigned long long* const trc = a.trace ? a.trace + (size_t)blockIdx.x * 80 : nullptr;
+    unsigned long long* const trc = a.trace ? a.trace + (size_t)blockIdx.x * 80 : nullptr;     // (LAFF_FCS_STAMP: fc_strip_common.h)
     int trc_seg = 0;
-#define STAMP(i) do { if (trc && tid == 0 && trc_seg < 8) trc[8 * trc_seg + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
 #endif
 
     while (u0 < u1) {
@@ -332,15 +106,12 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
         const int blk0 = __builtin_amdgcn_readfirstlane(ul - strip * nblk);
         const int n = __builtin_amdgcn_readfirstlane(std::min(nblk - blk0, u1 - u0));
         u0 += n;
-        STAMP(0);
+        LAFF_FCS_STAMP(0);
 #ifdef LAFF_FCS_TRACE
         if (trc && tid == 0 && trc_seg < 8) trc[64 + trc_seg] = (unsigned long long)n;
 #endif
-        // Input rows travel in K-eighth ROUNDS: 32 rows x 256 bytes per wave = 8 LDS-DMA instructions of 4 rows x 256 contiguous bytes
-        // (direct 16-byte loads in the fragment layout touch 32 rows per instruction and run at a fifth of the rate).  Instruction t, lane
-        // L: row 4 t + (L >> 4) of the wave's 32, LDS position L & 15 of that row <- source piece (L & 15) ^ (row & 15): the swizzle makes
-        // the fragment-order read-back conflict-free.  xoff(p, strip, xv): the per-lane source offsets (rows beyond the matrix read the
-        // last row), relative to the strip's first row.
+        // The K-eighth ROUNDS the input rows travel in, and their swizzle, are fc_strip.hip's.  xoff(p, strip, xv): the per-lane source
+        // offsets (rows beyond the matrix read the last row), relative to the strip's first row.
         auto xoff = [&](int p_, int strip_, unsigned (&xv)[8]) {
             const int N_ = a.p[p_].N, ldx_ = a.p[p_].ldx, r0_ = strip_ * FR;
             int ln = lane;
@@ -468,23 +239,16 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
         }
         __builtin_amdgcn_s_barrier();            // every wave has emptied its staging quarter: the ring may fill
         asm volatile("" ::: "memory");
-        STAMP(1);
+        LAFF_FCS_STAMP(1);
 
-        // ---- W ring prologue: the first three slots of the segment (slot s of the segment = image slot 2 blk0 + s); it lands while the
-        // strip is converted.  The image as a raw buffer starting at this wave's 8 KiB of a slot ----
+        // ---- W ring prologue: the segment's first three slots land while the strip is converted.  The image as a raw buffer starting at
+        // this wave's 8 KiB of a slot ----
         const u32x4 rsrcW = rebased_rsrc(pW, img_bytes, wslot);
         unsigned soffW = (unsigned)blk0 * (2u * SLOT);                        // image offset of the slot the next pieces belong to
-        static_for<0, 3>([&](auto SC) __attribute__((always_inline)) {
-            constexpr int s = decltype(SC)::value;
-            static_for<0, PIECES>([&](auto PC) __attribute__((always_inline)) {
-                constexpr int P = decltype(PC)::value;
-                dma_piece<s * SLOT + P * 1024>(lane16 + (unsigned)(P * 1024), rsrcW, std::min(soffW, img_bytes - SLOT), ldsw);
-            });
-            soffW += SLOT;
-        });
+        ring_prologue(lane16, rsrcW, soffW, img_bytes, ldsw);
 
         // ---- the raw strip is converted in place ----
-        STAMP(2);
+        LAFF_FCS_STAMP(2);
         {
             const float s0 = pow2f(9 - e_row[0]), s1 = pow2f(9 - e_row[1]);
             asm volatile("s_nop 1" ::: "memory");
@@ -492,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
             static_for<0, 32>([&](auto GC) __attribute__((always_inline)) { convert_chunk_inplace<8 * decltype(GC)::value>((decltype(GC)::value & 1) ? s1 : s0); });
         }
         asm volatile("s_nop 3" ::: "memory");            // v_accvgpr_write -> MFMA reading it
-        STAMP(3);
+        LAFF_FCS_STAMP(3);
         {
             // the epilogue's row scales: lane (n, g) needs those of rows 16 t + 4 g + e, which lane 4 g + e has for both t
             const float mine0 = pow2f(e_row[0] - 9), mine1 = pow2f(e_row[1] - 9);
@@ -516,7 +280,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
         asm volatile("" : "+v"(voff0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        STAMP(4);
+        LAFF_FCS_STAMP(4);
         // fragments 0 .. FD - 1 of the first slot
         static_for<0, FD>([&](auto JC) __attribute__((always_inline)) {
             constexpr int j = decltype(JC)::value;
@@ -614,7 +378,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
                         // round 3 of the next strip, to the staging-only buffer (no ring slot: no barrier to respect)
                         dma_piece<XB_OFF + F * 1024>(xvn[F], rsrcXn, 3u * 256u, ldsw);
                     }
-                    constexpr int dp = slot_piece(SG);
+                    constexpr int dp = slot_piece(GEOM, SG);
                     if constexpr (dp >= 0) {
                         // the W stream's piece dp of the slot three ahead -- or, in the segment's last three bodies, instruction dp of round
                         // XR of the next strip's rows; same LDS target either way
@@ -631,7 +395,7 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
         };
 
         auto drain = [&](auto QC, auto EXTRA, int blk) __attribute__((always_inline)) {
-            STAMP(5);
+            LAFF_FCS_STAMP(5);
             mfma_drain_nops();
             rsrcYe = rsrcY;
             soffY = (unsigned)blk * 128u;
@@ -681,14 +445,12 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
                 if (par == 1) drain(I0{}, I0{}, blk0 + b - 1); else drain(I1{}, I0{}, blk0 + b - 1);
             }
         }
-        // segment end: nothing of this wave may still be in flight towards the fragment registers.  (Vector memory is NOT drained: the
-        // stores need no wait, and the pieces in flight -- the next strip's first rounds -- go to this wave's own parts of the ring, which
-        // nobody else touches before the barrier behind the next strip load, whose counted waits cover them.)
+        // segment end: nothing of this wave may still be in flight towards the fragment registers; vector memory is NOT drained (fc_strip.hip)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int s8 = 0; s8 < NSETS; ++s8) asm volatile("" ::"v"(fr[s8][0]), "v"(fr[s8][1]));
         if (!has_next) __builtin_amdgcn_s_barrier();   // every wave is done with the ring before the next segment's strip staging refills it
-        STAMP(6);
+        LAFF_FCS_STAMP(6);
 #ifdef LAFF_FCS_TRACE
         ++trc_seg;
 #endif
@@ -696,74 +458,13 @@ __global__ __launch_bounds__(256, 1) void fc_strip16_kernel(const FcStripArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA of this workgroup outlives it
     m0_set(m0_keep);
     agpr_hold_end(hold);
-#undef STAMP
 }
 
-// ---- W [D][512] fp32 (+ bias, BatchNorm, activation) -> the LDS image + the lane-constant table -------------------------------------
-// One workgroup (256 threads) per output column: row maximum -> power-of-two scale (as split_rows_kernel), hi / lo halves scattered
-// into the image {block n / 32}{K half}{plane}{fragment = 2 (K step % 8) + (n & 1)}{lane = 16 g + (n % 32) / 2}{8 halves}.
-__global__ __launch_bounds__(256) void fc_strip16_pack_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias,
-                                                              const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int D,
-                                                              int act, _Float16* __restrict__ img, float* __restrict__ vec) {
-    __shared__ float red[4];
-    const int n = blockIdx.x, tid = threadIdx.x;
-    if (n >= D) return;
-    const float x0 = W[(size_t)n * ldw + tid], x1 = W[(size_t)n * ldw + 256 + tid];
-    float m = fmaxf(fabsf(x0), fabsf(x1));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((tid & 63) == 0) red[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const int e = split_exponent(m);
-    const float s = pow2f(9 - e), cs = pow2f(e - 9);
-    const int blk = n >> 5, n15 = (n & 31) >> 1, u = n & 1;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int k = t * 256 + tid;
-        const float x = (t ? x1 : x0) * s;
-        const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-        const int J = k >> 5, w = k & 31;                                         // k = 32 J + 4 g + (pos & 3) + 16 (pos >> 2)
-        const int half = J >> 3, Jl = J & 7, g = (w >> 2) & 3, pos = (w & 3) + 4 * (w >> 4);
-        const size_t base = ((size_t)(blk * 2 + half) * 2) * (PLANE / 2);        // in halves: slot start
-        const size_t at = (size_t)((2 * Jl + u) * 64 + 16 * g + n15) * 8 + pos;
-        img[base + at] = h;
-        img[base + PLANE / 2 + at] = l;
-    }
-    if (tid == 0) {
-        const float b = bias ? bias[n] : 0.f, g = bn_scale ? bn_scale[n] : 1.f, t = bn_shift ? bn_shift[n] : 0.f;
-        float4 c;
-        if (act == LAFF_ACT_TANH) c = make_float4(cs * 2.885390081777927f, b * 2.885390081777927f, -2.f * g, g + t);
-        else if (act == LAFF_ACT_SIGMOID) c = make_float4(cs * -1.4426950408889634f, b * -1.4426950408889634f, g, t);
-        else if (act == LAFF_ACT_RELU) c = make_float4(cs, b, g, t);
-        else c = make_float4(cs * g, fmaf(b, g, t), 0.f, 0.f);
-        *(float4*)(vec + 4 * (size_t)n) = c;
-    }
-}
-
-// ---- host side (the image size and the constant table's place are fc_strip.hip's: fc_strip_image_bytes, fc_strip_vec_offset) ---------
-int g_fc_strip_mfma = 16;    // LAFF_FC_STRIP_MFMA (read when a ctx is created): 16 = this file's kernels (default), 32 = fc_strip.hip's
-
-hipError_t launch_fc_strip16_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
-                                  void* img, hipStream_t st) {
-    hipLaunchKernelGGL(fc_strip16_pack_kernel, dim3((unsigned)D), dim3(256), 0, st, W, ldw, bias, bn_scale, bn_shift, D, act,
-                       (_Float16*)img, (float*)((char*)img + fc_strip_vec_offset(D)));
-    return hipGetLastError();
-}
-
-// (a with unit0, total_units, nranges and range_of_wg filled in by launch_fc_strip, which hands over to this one)
-hipError_t launch_fc_strip16(const FcStripArgs& a, int act, hipStream_t st) {
-#define LAFF_FCS_LAUNCH(K)                                                                                                    \
-    do {                                                                                                                      \
-        static unsigned long long attr_done = 0;                                                                              \
-        if (hipError_t e = smem_attr_once(attr_done, fc_strip16_kernel<K>, SMEM); e != hipSuccess) return e;                  \
-        hipLaunchKernelGGL((fc_strip16_kernel<K>), dim3((unsigned)a.nranges), dim3(256), SMEM, st, a);                        \
-    } while (0)
-    if (act == LAFF_ACT_TANH || act == LAFF_ACT_SIGMOID) LAFF_FCS_LAUNCH(ACT_EXP);
-    else if (act == LAFF_ACT_RELU) LAFF_FCS_LAUNCH(ACT_RELU);
-    else LAFF_FCS_LAUNCH(ACT_LIN);
-#undef LAFF_FCS_LAUNCH
-    return hipGetLastError();
+// (called by launch_fc_strip, fc_strip.hip, which has set up the units and ranges of a)
+hipError_t fc_strip16_launch(const FcStripArgs& a, int kind, hipStream_t st) {
+    if (kind == ACT_EXP) return fc_strip_launch<fc_strip16_kernel<ACT_EXP>>(a, st);
+    if (kind == ACT_RELU) return fc_strip_launch<fc_strip16_kernel<ACT_RELU>>(a, st);
+    return fc_strip_launch<fc_strip16_kernel<ACT_LIN>>(a, st);
 }
 
 }  // namespace laff

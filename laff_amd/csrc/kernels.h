@@ -125,12 +125,11 @@ size_t fc_strip_vec_offset(int D);
 hipError_t launch_fc_strip_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
                                 void* img, hipStream_t st);
 hipError_t launch_fc_strip(FcStripArgs& a, int act, hipStream_t st);
-// fc_strip16.hip: the same kernel on v_mfma_f32_16x16x32_f16.  g_fc_strip_mfma (LAFF_FC_STRIP_MFMA, read when a ctx is created) says
-// which of the two launch_fc_strip_pack and launch_fc_strip run: an image must be launched in the mode it was packed in.
+// The kernel exists on two MFMA shapes: v_mfma_f32_16x16x32_f16 (fc_strip16.hip, the default) and v_mfma_f32_32x32x16_f16
+// (fc_strip.hip); what they share is fc_strip_common.h, the one host path is fc_strip.hip's.  g_fc_strip_mfma (16 or 32:
+// LAFF_FC_STRIP_MFMA, read when a ctx is created) says which image layout launch_fc_strip_pack writes and which kernel
+// launch_fc_strip runs: an image must be launched in the mode it was packed in.
 extern int g_fc_strip_mfma;
-hipError_t launch_fc_strip16_pack(const float* W, int ldw, const float* bias, const float* bn_scale, const float* bn_shift, int D, int act,
-                                  void* img, hipStream_t st);
-hipError_t launch_fc_strip16(const FcStripArgs& a, int act, hipStream_t st);
 
 // ---- concat tower (fc_concat.hip): Y = bn(act(sum_s X_s . W[:, c_s : c_s + Dk_s]^T + bias)), dense + CSR segments, one launch ------
 constexpr int CONCAT_MAX_SEG = 8;        // segments per problem, dense and sparse together

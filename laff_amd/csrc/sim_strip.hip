@@ -29,18 +29,17 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <utility>
 #include <vector>
 
 #include "kernels.h"
+#include "strip_util.h"
 
 namespace laff {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace su;
+
 typedef __attribute__((address_space(1))) unsigned gu32;
 typedef __attribute__((address_space(1))) u32x4 gu32x4;
 typedef __attribute__((address_space(1))) float gf32;
@@ -61,14 +60,6 @@ constexpr int DUMP_BYTES = STRIP_CHUNK * STRIP_ENTRY_WORDS * 4;
 constexpr int SMEM = DUMP_OFF + 4 * DUMP_BYTES;
 static_assert(SMEM <= 160 * 1024 && CB == 32 && DUMP_BYTES % 1024 == 0, "LDS budget / block width / whole-wave flush passes");
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
 template <int IMM>
 __device__ __forceinline__ void lds_read128(u32x4& d, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
@@ -81,10 +72,6 @@ template <int IMM>
 __device__ __forceinline__ void lds_read128_a(u32x4& d, unsigned addr) {        // ... into the accumulator half of the register file
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(d) : "v"(addr), "n"(IMM));
 }
-template <int N>
-__device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // one 1 KiB piece of the video stream: the 1,024 bytes (whole K) of column P of this wave's 8 columns of a block, straight into its
 // LDS row.  LDS-DMA writes lane L at (M0 base) + 16 L, so the bank swizzle is applied to the SOURCE: LDS slot L of column c holds the
@@ -106,36 +93,6 @@ __device__ __forceinline__ void stage_piece(unsigned voff, u32x4 rsrc, unsigned 
     asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                  :: "v"(voff), "s"(rsrc), "s"(soff), "s"(m0base), "n"(LDSOFF) : "memory", "scc");
 }
-// raw buffer descriptor of `bytes_total` bytes at `base`, re-based by `off` bytes (empty when off is beyond the end)
-__device__ __forceinline__ u32x4 rebased_rsrc(unsigned long long base, unsigned long long bytes_total, unsigned long long off) {
-    const unsigned long long b = base + off;
-    const unsigned long long left = bytes_total > off ? bytes_total - off : 0ull;
-    u32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) & 0xffffu;
-    r.z = __builtin_amdgcn_readfirstlane((unsigned)(left > 0xffffffffull ? 0xffffffffull : left));
-    r.w = 0x00020000u;
-    return r;
-}
-
-__device__ __forceinline__ unsigned m0_get() {
-    unsigned k;
-    asm volatile("s_mov_b32 %0, m0" : "=s"(k)::"memory");
-    return k;
-}
-__device__ __forceinline__ void m0_set(unsigned k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k) : "memory"); }
-
-// keep a wave-uniform value in an SGPR and opaque (no re-load from the kernarg segment inside the hand-counted loops)
-__device__ __forceinline__ unsigned pin_s(unsigned x) {
-    x = __builtin_amdgcn_readfirstlane(x);
-    asm volatile("" : "+s"(x));
-    return x;
-}
-__device__ __forceinline__ int pin_s(int x) { return (int)pin_s((unsigned)x); }
-__device__ __forceinline__ float pin_s(float x) { return __uint_as_float(pin_s(__float_as_uint(x))); }
-__device__ __forceinline__ unsigned long long pin_s(unsigned long long x) {
-    return ((unsigned long long)pin_s((unsigned)(x >> 32)) << 32) | pin_s((unsigned)x);
-}
 
 // MFMA from inline asm with the register FILES pinned: the strip fragment (B operand) must live in the accumulator half of the
 // register file ("a": 256 of them are the whole point of this kernel) and the accumulators in the architectural half ("v": the
@@ -152,7 +109,6 @@ __device__ __forceinline__ void mfma16(f32x16& acc, const u32x4& colfrag, const 
         else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(colfrag), "a"(stripfrag));
     }
 }
-__device__ __forceinline__ void mfma_drain_nops() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
 
 // ---- the schedule of one column block, all compile time ---------------------------------------------------------------------------
 // A block is 32 sub-steps J (one 16-element K slice each) of 2 MFMAs (M = row block rb).  Slot sigma = 2 J + M is the issue shadow of

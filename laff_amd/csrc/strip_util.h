@@ -1,5 +1,5 @@
-// strip_util.h -- small device helpers shared by the register-stationary ("strip") kernels (fc_strip.hip; sim_strip.hip keeps its
-// own copies of the same idioms): compile-time loops, counted waits, raw buffer descriptors, values pinned in SGPRs.
+// strip_util.h -- small device helpers shared by the register-stationary ("strip") kernels (sim_strip.hip; fc_strip.hip and
+// fc_strip16.hip through fc_strip_common.h): compile-time loops, counted waits, raw buffer descriptors, values pinned in SGPRs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

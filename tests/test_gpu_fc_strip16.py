@@ -94,16 +94,18 @@ def test_every_segment_form(mfma_mode, N, D):
     assert d64 <= 2e-5
 
 
-@pytest.mark.parametrize('N,D', [(300, 96), (33000, 160)])
-def test_layout_detector(mfma_mode, N, D):
+@pytest.mark.parametrize('N,D,mode', [pytest.param(300, 96, 16, id='300-96'), pytest.param(300, 96, 32, id='300-96-mfma32'),
+                                      pytest.param(33000, 160, 16, id='33000-160')])
+def test_layout_detector(mfma_mode, N, D, mode):
     """W[c][k] = an integer pattern of (c, k), X = one-hot rows (row r has its 1 at k_r), no bias, BatchNorm or activation: Y[r][c] =
     W[c][k_r] exactly (integers below 2048 times powers of two are exact in the fp16 hi halves, the lo halves are zero).  A wrong
     lane <-> (row, k, column) mapping anywhere -- the strip read-back, the image, the epilogue -- puts exact integers in the wrong
-    place.  (300, 96): one-block segments, cold strip loads.  (33000, 160): five units per workgroup -- segments with a successor, so
-    the strips whose first rounds come early, through other buffers and in another order, are read back exactly too.  Input and
-    output rows carry a pitch: nothing outside [N, D] is written."""
+    place.  (300, 96): one-block segments, cold strip loads, in both MFMA modes (the two image layouts are the two branches of one
+    pack kernel).  (33000, 160): five units per workgroup -- segments with a successor, so the strips whose first rounds come early,
+    through other buffers and in another order, are read back exactly too.  Input and output rows carry a pitch: nothing outside
+    [N, D] is written."""
     from laff_amd import ops
-    mfma_mode(16)
+    mfma_mode(mode)
     c, k = np.meshgrid(np.arange(D), np.arange(512), indexing='ij')
     W = dev(((c * 512 + k) % 2039 + 1).astype(np.float32))
     kr = (torch.arange(N, device='cuda') * 37 + 11) % 512
