@@ -84,6 +84,19 @@ int metrics_read_back(laff_ctx* ctx, double out7[7], const char* flagged) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }                       // floats: every region of a float workspace starts on 16 bytes
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }                 // bytes: every region of a byte workspace starts on 256 bytes
+
+// the workspace holds `need` bytes; then it and the packed operands named with it in `what` (others_aligned) sit on 16 bytes
+int check_workspace(const char* fn, const void* workspace, size_t workspace_bytes, size_t need, bool others_aligned, const char* what) {
+    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
+    if (!aligned16(workspace) || !others_aligned) return fail(LAFF_E_ALIGN, "%s: %s must be 16-byte aligned", fn, what);
+    return LAFF_OK;
+}
+// the same for a workspace that a caller may leave out: a null one is reported as 0 bytes
+int need_workspace(const char* fn, const void* workspace, size_t workspace_bytes, size_t need) {
+    return check_workspace(fn, workspace, workspace ? workspace_bytes : (size_t)0, need, true, "workspace");
+}
 
 struct DeviceGuard {
     int prev = -1;
@@ -396,7 +409,6 @@ LossLayout loss_layout(int B, int H, int d) {
     LossLayout L{};
     L.dp = (d + 3) & ~3;
     L.Bp = (B + 3) & ~3;
-    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
     size_t o = 0;
     L.XH = o;     o += up4((size_t)2 * H * B * L.dp);
     L.XHT = o;    o += up4((size_t)2 * H * d * L.Bp);
@@ -416,6 +428,40 @@ int loss_check_batch(const char* fn, int B) {
     if ((size_t)(2 * B + 16) * sizeof(float) > 64 * 1024) return fail(LAFF_E_UNSUPPORTED, "%s: B=%d exceeds the reduction kernel's LDS budget", fn, B);
     return LAFF_OK;
 }
+// The pipeline the embedding losses share around their own reduce launch.  `row` says which side's rows are the rows of the score
+// matrices, 0 = captions (s), 1 = videos (im); the other side is the column operand.
+float* loss_head(float* ws, size_t region, int side, int h, int H, size_t floats) { return ws + region + ((size_t)side * H + h) * floats; }
+// normalize both sides, then per head  scores_h [B rows, B columns] = Row^_h . Col^_h^T  into L.S
+int loss_scores(laff_ctx* ctx, const float* s, const float* im, int B, int H, int d, const LossLayout& L, float* ws, int row) {
+    HIP_TRY(laff::launch_loss_normalize(s, im, B, H, d, L.dp, L.Bp, 1e-13f, ws + L.XH, ws + L.XHT, ws + L.nrm, ws + L.npr, ctx->stream));
+    std::vector<laff_fc_problem> probs((size_t)H);
+    for (int h = 0; h < H; ++h)
+        probs[h] = laff_fc_problem{loss_head(ws, L.XH, row, h, H, (size_t)B * L.dp), B, d, L.dp, loss_head(ws, L.XH, 1 - row, h, H, (size_t)B * L.dp),
+                                   L.dp, nullptr, nullptr, nullptr, B, LAFF_ACT_NONE, ws + L.S + (size_t)h * B * L.Bp, L.Bp};
+    return laff_fc_act_bn_grouped(ctx, probs.data(), H);
+}
+// from dS_h = dL/dscores_h in L.dS and its transpose in L.dST, per head  dL/dRow^_h = dS_h . Col^_h  (column operand = Col^_h^T, K = the
+// column side's items)  and  dL/dCol^_h = dS_h^T . Row^_h;  then the backward of the normalisation into d_s, d_im
+int loss_grads(laff_ctx* ctx, int B, int H, int d, const LossLayout& L, float* ws, int row, float* d_s, float* d_im) {
+    std::vector<laff_fc_problem> probs;
+    for (int h = 0; h < H; ++h) {
+        probs.push_back(laff_fc_problem{ws + L.dS + (size_t)h * B * L.Bp, B, B, L.Bp, loss_head(ws, L.XHT, 1 - row, h, H, (size_t)d * L.Bp), L.Bp,
+                                        nullptr, nullptr, nullptr, d, LAFF_ACT_NONE, loss_head(ws, L.G, row, h, H, (size_t)B * L.dp), L.dp});
+        probs.push_back(laff_fc_problem{ws + L.dST + (size_t)h * B * L.Bp, B, B, L.Bp, loss_head(ws, L.XHT, row, h, H, (size_t)d * L.Bp), L.Bp,
+                                        nullptr, nullptr, nullptr, d, LAFF_ACT_NONE, loss_head(ws, L.G, 1 - row, h, H, (size_t)B * L.dp), L.dp});
+    }
+    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), (int)probs.size())) return rc;
+    HIP_TRY(laff::launch_loss_normalize_bwd(ws + L.XH, ws + L.G, ws + L.nrm, ws + L.npr, B, H, d, L.dp, d_s, d_im, ctx->stream));
+    return LAFF_OK;
+}
+// what the LAFF_LOSS_* flags of the margin criteria ask of margin_reduce_kernel
+struct MarginFlags {
+    int maxv, use_s, use_im;
+    float gw;                 // the weight of a hinge term: 1, or the mean's 1 / B (max violation) or 1 / B^2
+    MarginFlags(unsigned flags, int B)
+        : maxv((flags & LAFF_LOSS_MAX_VIOLATION) ? 1 : 0), use_s((flags & LAFF_LOSS_DIR_I2T) ? 1 : 0), use_im((flags & LAFF_LOSS_DIR_T2I) ? 1 : 0),
+          gw(!(flags & LAFF_LOSS_COST_MEAN) ? 1.0f : maxv ? 1.0f / (float)B : 1.0f / ((float)B * (float)B)) {}
+};
 }  // namespace
 
 int laff_margin_loss_workspace_bytes(int B, int H, int d, size_t* out) {
@@ -434,39 +480,16 @@ int laff_margin_loss(laff_ctx* ctx, const float* s, const float* im, int B, int 
     if (B > 16384) return loss_check_batch("laff_margin_loss", B);
     if (flags & ~15u) return fail(LAFF_E_ARG, "laff_margin_loss: unknown flags 0x%x", flags);
     const LossLayout L = loss_layout(B, H, d);
-    if (workspace_bytes < L.total * sizeof(float)) return fail(LAFF_E_ARG, "laff_margin_loss: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total * sizeof(float));
-    if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_margin_loss: workspace must be 16-byte aligned");
+    if (int rc = need_workspace("laff_margin_loss", workspace, workspace_bytes, L.total * sizeof(float))) return rc;
     if (int rc = loss_check_batch("laff_margin_loss", B)) return rc;
     DeviceGuard g(ctx->device);
     float* ws = (float*)workspace;
-    const int dp = L.dp, Bp = L.Bp;
-    const int use_s = (flags & LAFF_LOSS_DIR_I2T) ? 1 : 0, use_im = (flags & LAFF_LOSS_DIR_T2I) ? 1 : 0;
-    const int maxv = (flags & LAFF_LOSS_MAX_VIOLATION) ? 1 : 0;
-    const float gmean = maxv ? 1.0f / (float)B : 1.0f / ((float)B * (float)B);
-    const float gw = (flags & LAFF_LOSS_COST_MEAN) ? gmean : 1.0f;
-    HIP_TRY(laff::launch_loss_normalize(s, im, B, H, d, dp, Bp, 1e-13f, ws + L.XH, ws + L.XHT, ws + L.nrm, ws + L.npr, ctx->stream));
-    auto XH = [&](int z, int h) { return ws + L.XH + ((size_t)z * H + h) * B * dp; };
-    auto XHT = [&](int z, int h) { return ws + L.XHT + ((size_t)z * H + h) * d * Bp; };
-    auto G = [&](int z, int h) { return ws + L.G + ((size_t)z * H + h) * B * dp; };
-    std::vector<laff_fc_problem> probs((size_t)H);
-    for (int h = 0; h < H; ++h)      // scores_h [B videos, B captions] = I^_h . S^_h^T
-        probs[h] = laff_fc_problem{XH(1, h), B, d, dp, XH(0, h), dp, nullptr, nullptr, nullptr, B, LAFF_ACT_NONE,
-                                   ws + L.S + (size_t)h * B * Bp, Bp};
-    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), H)) return rc;
-    HIP_TRY(laff::launch_margin_reduce(ws + L.S, ws + L.dS, ws + L.dST, ws + L.loss_h, loss, B, Bp, H, margin, maxv, use_s, use_im,
-                                       gw, gw, ctx->stream));
+    const MarginFlags f(flags, B);
+    if (int rc = loss_scores(ctx, s, im, B, H, d, L, ws, 1)) return rc;      // scores_h [B videos, B captions] = I^_h . S^_h^T
+    HIP_TRY(laff::launch_margin_reduce(ws + L.S, ws + L.dS, ws + L.dST, ws + L.loss_h, loss, B, L.Bp, H, margin, f.maxv, f.use_s, f.use_im,
+                                       f.gw, f.gw, ctx->stream));
     if (!d_s && !d_im) return LAFF_OK;
-    probs.clear();
-    for (int h = 0; h < H; ++h) {
-        // dL/dI^_h = dS_h . S^_h   (column operand = S^_h^T, K = captions);  dL/dS^_h = dS_h^T . I^_h
-        probs.push_back(laff_fc_problem{ws + L.dS + (size_t)h * B * Bp, B, B, Bp, XHT(0, h), Bp, nullptr, nullptr, nullptr, d,
-                                        LAFF_ACT_NONE, G(1, h), dp});
-        probs.push_back(laff_fc_problem{ws + L.dST + (size_t)h * B * Bp, B, B, Bp, XHT(1, h), Bp, nullptr, nullptr, nullptr, d,
-                                        LAFF_ACT_NONE, G(0, h), dp});
-    }
-    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), (int)probs.size())) return rc;
-    HIP_TRY(laff::launch_loss_normalize_bwd(ws + L.XH, ws + L.G, ws + L.nrm, ws + L.npr, B, H, d, dp, d_s, d_im, ctx->stream));
-    return LAFF_OK;
+    return loss_grads(ctx, B, H, d, L, ws, 1, d_s, d_im);
 }
 
 namespace {
@@ -477,7 +500,6 @@ struct DslLayout {
 DslLayout dsl_layout(int B, int H, int d) {
     DslLayout D{};
     D.L = loss_layout(B, H, d);
-    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
     size_t o = D.L.total;
     D.ST = o;   o += up4((size_t)H * B * D.L.Bp);
     D.stat = o; o += up4((size_t)H * laff::DSL_STAT_ROWS * B);
@@ -502,35 +524,15 @@ int laff_dsl_loss(laff_ctx* ctx, const float* s, const float* im, int B, int H, 
     if (!s || !im || !loss) return fail(LAFF_E_ARG, "laff_dsl_loss: null argument");
     const DslLayout D = dsl_layout(B, H, d);
     const LossLayout& L = D.L;
-    if (!workspace || workspace_bytes < D.total * sizeof(float)) return fail(LAFF_E_ARG, "laff_dsl_loss: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, D.total * sizeof(float));
-    if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_dsl_loss: workspace must be 16-byte aligned");
+    if (int rc = need_workspace("laff_dsl_loss", workspace, workspace_bytes, D.total * sizeof(float))) return rc;
     DeviceGuard g(ctx->device);
     float* ws = (float*)workspace;
-    const int dp = L.dp, Bp = L.Bp;
     const bool grad = d_s || d_im;
-    HIP_TRY(laff::launch_loss_normalize(s, im, B, H, d, dp, Bp, 1e-13f, ws + L.XH, ws + L.XHT, ws + L.nrm, ws + L.npr, ctx->stream));
-    auto XH = [&](int z, int h) { return ws + L.XH + ((size_t)z * H + h) * B * dp; };
-    auto XHT = [&](int z, int h) { return ws + L.XHT + ((size_t)z * H + h) * d * Bp; };
-    auto G = [&](int z, int h) { return ws + L.G + ((size_t)z * H + h) * B * dp; };
-    std::vector<laff_fc_problem> probs((size_t)H);
-    for (int h = 0; h < H; ++h)      // M_h [B captions, B videos] = S^_h . I^_h^T  (cosine_sim(s, im), loss.py:296)
-        probs[h] = laff_fc_problem{XH(0, h), B, d, dp, XH(1, h), dp, nullptr, nullptr, nullptr, B, LAFF_ACT_NONE,
-                                   ws + L.S + (size_t)h * B * Bp, Bp};
-    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), H)) return rc;
+    if (int rc = loss_scores(ctx, s, im, B, H, d, L, ws, 0)) return rc;      // M_h [B captions, B videos] = S^_h . I^_h^T  (cosine_sim(s, im), loss.py:296)
     HIP_TRY(laff::launch_dsl_reduce(ws + L.S, ws + D.ST, ws + D.stat, grad ? ws + L.dS : nullptr, grad ? ws + L.dST : nullptr,
-                                    ws + L.loss_h, loss, B, Bp, H, temp, ctx->stream));
+                                    ws + L.loss_h, loss, B, L.Bp, H, temp, ctx->stream));
     if (!grad) return LAFF_OK;
-    probs.clear();
-    for (int h = 0; h < H; ++h) {
-        // dL/dS^_h = dM_h . I^_h   (column operand = I^_h^T, K = videos);  dL/dI^_h = dM_h^T . S^_h
-        probs.push_back(laff_fc_problem{ws + L.dS + (size_t)h * B * Bp, B, B, Bp, XHT(1, h), Bp, nullptr, nullptr, nullptr, d,
-                                        LAFF_ACT_NONE, G(0, h), dp});
-        probs.push_back(laff_fc_problem{ws + L.dST + (size_t)h * B * Bp, B, B, Bp, XHT(0, h), Bp, nullptr, nullptr, nullptr, d,
-                                        LAFF_ACT_NONE, G(1, h), dp});
-    }
-    if (int rc = laff_fc_act_bn_grouped(ctx, probs.data(), (int)probs.size())) return rc;
-    HIP_TRY(laff::launch_loss_normalize_bwd(ws + L.XH, ws + L.G, ws + L.nrm, ws + L.npr, B, H, d, dp, d_s, d_im, ctx->stream));
-    return LAFF_OK;
+    return loss_grads(ctx, B, H, d, L, ws, 0, d_s, d_im);
 }
 
 int laff_margin_loss_scores(laff_ctx* ctx, const float* score, int ld, int B, float margin, unsigned flags, float* loss,
@@ -542,13 +544,10 @@ int laff_margin_loss_scores(laff_ctx* ctx, const float* score, int ld, int B, fl
     if (B == 0) return LAFF_OK;
     if (!score || !loss) return fail(LAFF_E_ARG, "laff_margin_loss_scores: null argument");
     DeviceGuard g(ctx->device);
-    const int use_s = (flags & LAFF_LOSS_DIR_I2T) ? 1 : 0, use_im = (flags & LAFF_LOSS_DIR_T2I) ? 1 : 0;
-    const int maxv = (flags & LAFF_LOSS_MAX_VIOLATION) ? 1 : 0;
-    const float gmean = maxv ? 1.0f / (float)B : 1.0f / ((float)B * (float)B);
-    const float gw = (flags & LAFF_LOSS_COST_MEAN) ? gmean : 1.0f;
+    const MarginFlags f(flags, B);
     // margin_reduce_kernel as it is, one head: the score matrix in place of the GEMM's, its pitch as Bp, no transposed gradient, and
     // loss[0] as the per-head slot that the head sum then copies onto itself
-    HIP_TRY(laff::launch_margin_reduce(score, d_score, nullptr, loss, loss, B, ld, 1, margin, maxv, use_s, use_im, gw, gw, ctx->stream));
+    HIP_TRY(laff::launch_margin_reduce(score, d_score, nullptr, loss, loss, B, ld, 1, margin, f.maxv, f.use_s, f.use_im, f.gw, f.gw, ctx->stream));
     return LAFF_OK;
 }
 
@@ -701,32 +700,37 @@ struct GruBwdLayout {
     size_t carry, dgi, dgh, dx, fc, total;
 };
 GruBwdLayout gru_bwd_layout(int N, long M, int H, int we_dim, int ndirs, bool want_dwe) {
-    auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
     GruBwdLayout l{};
     size_t at = 0;
-    l.carry = at; at += r256((size_t)ndirs * N * H * sizeof(float));
-    l.dgi = at;   at += r256((size_t)ndirs * M * 3 * H * sizeof(float));
-    l.dgh = at;   at += r256((size_t)ndirs * M * 3 * H * sizeof(float));
-    l.dx = at;    at += want_dwe ? r256((size_t)ndirs * M * we_dim * sizeof(float)) : 0;
+    l.carry = at; at += round256((size_t)ndirs * N * H * sizeof(float));
+    l.dgi = at;   at += round256((size_t)ndirs * M * 3 * H * sizeof(float));
+    l.dgh = at;   at += round256((size_t)ndirs * M * 3 * H * sizeof(float));
+    l.dx = at;    at += want_dwe ? round256((size_t)ndirs * M * we_dim * sizeof(float)) : 0;
     laff::FcBwdPlan hh, ih;
     laff::fc_bwd_plan((int)M, H, 3 * H, &hh);
     laff::fc_bwd_plan((int)M, we_dim, 3 * H, &ih);
-    l.fc = at;    at += r256(std::max(std::max(hh.ws_dw, ih.ws_dw), want_dwe ? ih.ws_dx : (size_t)0));
+    l.fc = at;    at += round256(std::max(std::max(hh.ws_dw, ih.ws_dw), want_dwe ? ih.ws_dx : (size_t)0));
     l.total = at;
     return l;
 }
 
-// laff_fc_backward's launch path with activation none: dW [D, Dk] = dA^T X, db = column sums of dA, dX = dA W; null outputs are left out
+// the arguments of launch_fc_backward for  dZ = dA (.) act'(A),  dW [D, Dk] = dZ^T X,  db = column sums of dZ,  dX = dZ W  (null outputs
+// are left out); `vec` allows the 16-byte loads per operand: its base on 16 bytes and its pitch a multiple of 4
+laff::FcBwdArgs fc_bwd_args(const float* X, int N, int Dk, int ldx, const float* W, int ldw, int D, int act, const float* A, int lda,
+                            const float* dA, int ldda, float* dX, int lddx, float* dW, int lddw, float* db, void* workspace) {
+    laff::FcBwdArgs a{};
+    a.X = X; a.W = W; a.A = A; a.dA = dA; a.dX = dX; a.dW = dW; a.db = db;
+    a.N = N; a.Dk = Dk; a.D = D; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.ldda = ldda; a.lddx = lddx; a.lddw = lddw; a.act = act;
+    a.vec = (aligned16(A) && aligned16(dA) && lda % 4 == 0 && ldda % 4 == 0 ? 1u : 0u) | (X && aligned16(X) && ldx % 4 == 0 ? 2u : 0u) |
+            (W && aligned16(W) && ldw % 4 == 0 ? 4u : 0u);
+    a.part = (float*)workspace;
+    return a;
+}
+// the GRU's weight gradients: activation none (A = dA), dense rows
 hipError_t gru_fc_backward(const float* X, int Dk, const float* W, const float* dA, int M, int D, float* dX, float* dW, float* db,
                            void* fc_ws, hipStream_t st) {
     if (!dX && !dW && !db) return hipSuccess;
-    laff::FcBwdArgs a{};
-    a.X = X; a.W = W; a.A = dA; a.dA = dA; a.dX = dX; a.dW = dW; a.db = db;
-    a.N = M; a.Dk = Dk; a.D = D; a.ldx = Dk; a.ldw = Dk; a.lda = D; a.ldda = D; a.lddx = Dk; a.lddw = Dk; a.act = LAFF_ACT_NONE;
-    a.vec = (aligned16(dA) && D % 4 == 0 ? 1u : 0u) | (X && aligned16(X) && Dk % 4 == 0 ? 2u : 0u) |
-            (W && aligned16(W) && Dk % 4 == 0 ? 4u : 0u);
-    a.part = (float*)fc_ws;
-    return laff::launch_fc_backward(a, st);
+    return laff::launch_fc_backward(fc_bwd_args(X, M, Dk, Dk, W, Dk, D, LAFF_ACT_NONE, dA, D, dA, D, dX, Dk, dW, Dk, db, fc_ws), st);
 }
 }  // namespace
 
@@ -835,9 +839,10 @@ int laff_gru_backward(laff_ctx* ctx, const int* lengths, const int* perm, const 
     const size_t rneed = (size_t)ndirs * 5 * M * H * sizeof(float);
     if (reserve_bytes < rneed) return fail(LAFF_E_ARG, "%s: reserve too small (%zu < %zu bytes)", fn, reserve_bytes, rneed);
     const GruBwdLayout L = gru_bwd_layout(N, M, H, we_dim, ndirs, want_dwe);
-    if (workspace_bytes < L.total) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, L.total);
-    if (!aligned16(workspace) || !aligned16(reserve) || !aligned16(whht_fwd) || (ndirs == 2 && !aligned16(whht_rev)))
-        return fail(LAFF_E_ALIGN, "%s: workspace / reserve / packed W_hh must be 16-byte aligned", fn);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, L.total,
+                                 aligned16(reserve) && aligned16(whht_fwd) && (ndirs != 2 || aligned16(whht_rev)),
+                                 "workspace / reserve / packed W_hh"))
+        return rc;
     for (int d = 0; d < ndirs; ++d)
         for (int k = 0; k < 4; ++k)
             if (reinterpret_cast<uintptr_t>(G[d][k]) & 3) return fail(LAFF_E_ALIGN, "%s: the gradients must be 4-byte aligned", fn);
@@ -907,7 +912,6 @@ int laff_gru_backward(laff_ctx* ctx, const int* lengths, const int* perm, const 
 namespace {
 // what the ragged entry points share (laff_clip_encode, laff_bert_encode, laff_netvlad_encode, laff_clip_image_encode: items
 // concatenated without padding, their [N+1] offsets on the device and on the host, out with a pitch, a byte workspace)
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }                 // every workspace region starts on 256 bytes
 // the token rows one transformer call takes at most: the GEMMs' grid.y = rows / 128 stays well inside its limit
 constexpr long MAX_TOKEN_ROWS = 1L << 22;
 int check_token_rows(const char* fn, int items, long rows_per_item) {
@@ -930,12 +934,6 @@ int check_offsets(const char* fn, const char* name, const char* item, const char
         return fail(LAFF_E_ARG, "%s: %s: %s %d has %d %.*ss (%d .. %s=%d)", fn, name, item, i, L, unit, name, lo, limit, hi);
     }
     if (off[N] != R) return fail(LAFF_E_ARG, "%s: %s[%c]=%d != %c=%d", fn, name, dims[0], off[N], dims[1], R);
-    return LAFF_OK;
-}
-// the workspace holds `need` bytes; then it and the packed operands named with it in `what` (others_aligned) sit on 16 bytes
-int check_workspace(const char* fn, const void* workspace, size_t workspace_bytes, size_t need, bool others_aligned, const char* what) {
-    if (workspace_bytes < need) return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, need);
-    if (!aligned16(workspace) || !others_aligned) return fail(LAFF_E_ALIGN, "%s: %s must be 16-byte aligned", fn, what);
     return LAFF_OK;
 }
 // the workspace prefix of the transformer encoders: X [rows, W] fp32 | A [rows, W] operand (sz bytes an element) |
@@ -1936,9 +1934,7 @@ int laff_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int
         int R = 0, P = 0, rows = 0;
         laff::fuse_bwd_plan(N, H, d, flags, &R, &P, &rows);
         const size_t bytes = (size_t)H * rows * d * sizeof(float);
-        if (!workspace || workspace_bytes < bytes)
-            return fail(LAFF_E_ARG, "laff_fuse_backward: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, bytes);
-        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "laff_fuse_backward: workspace must be 16-byte aligned");
+        if (int rc = need_workspace("laff_fuse_backward", workspace, workspace_bytes, bytes)) return rc;
         a.dw_part = (float*)workspace;
     }
     DeviceGuard g(ctx->device);
@@ -1986,20 +1982,12 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
                     lddx, Dk, lda, ldda, D);
     if (!aligned4(X) || !aligned4(W) || !aligned4(A) || !aligned4(dA) || !aligned4(dX))
         return fail(LAFF_E_ALIGN, "%s: X / W / A / dA / dX must be 4-byte aligned", fn);
-    laff::FcBwdArgs a{};
-    a.X = X; a.W = W; a.A = A; a.dA = dA; a.dX = dX; a.dW = dW; a.db = db;
-    a.N = N; a.Dk = Dk; a.D = D; a.ldx = ldx; a.ldw = ldw; a.lda = lda; a.ldda = ldda; a.lddx = lddx; a.lddw = lddw; a.act = act;
-    a.vec = (aligned16(A) && aligned16(dA) && lda % 4 == 0 && ldda % 4 == 0 ? 1u : 0u) | (X && aligned16(X) && ldx % 4 == 0 ? 2u : 0u) |
-            (W && aligned16(W) && ldw % 4 == 0 ? 4u : 0u);
     laff::FcBwdPlan p;
     laff::fc_bwd_plan(N, Dk, D, &p);
     const size_t need = std::max(dX ? p.ws_dx : (size_t)0, dW ? p.ws_dw : db ? p.ws_db : (size_t)0);
-    if (need) {
-        if (!workspace || workspace_bytes < need)
-            return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace ? workspace_bytes : (size_t)0, need);
-        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "%s: workspace must be 16-byte aligned", fn);
-        a.part = (float*)workspace;
-    }
+    if (need)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, need)) return rc;
+    const laff::FcBwdArgs a = fc_bwd_args(X, N, Dk, ldx, W, ldw, D, act, A, lda, dA, ldda, dX, lddx, dW, lddw, db, need ? workspace : nullptr);
     HIP_TRY(laff::launch_fc_backward(a, ctx->stream));
     return LAFF_OK;
 }
@@ -2191,12 +2179,8 @@ int laff_frame_fuse_backward(laff_ctx* ctx, int count, const float* const* frame
         if (!aligned16(frames[k]) || !aligned16(w[k]) || !aligned16(dV[k]) || !aligned16(dframes[k]) || (dw && !aligned16(dw[k])))
             return fail(LAFF_E_ALIGN, "%s: feature %d: frames / w / dV / dframes / dw must be 16-byte aligned", fn, k);
     }
-    if (dw) {
-        const size_t bytes = (size_t)count * B * d * sizeof(float);
-        if (!workspace || workspace_bytes < bytes)
-            return fail(LAFF_E_ARG, "%s: workspace too small (%zu < %zu bytes)", fn, workspace ? workspace_bytes : (size_t)0, bytes);
-        if (!aligned16(workspace)) return fail(LAFF_E_ALIGN, "%s: workspace must be 16-byte aligned", fn);
-    }
+    if (dw)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, (size_t)count * B * d * sizeof(float))) return rc;
     DeviceGuard g(ctx->device);
     for (int i0 = 0; i0 < count; i0 += 8) {
         laff::FrameBwdGroup grp{};

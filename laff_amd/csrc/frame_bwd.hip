@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "attn_common.h"
 #include "kernels.h"
 #include "wave_reduce.h"
 
@@ -31,13 +32,6 @@ namespace laff {
 
 namespace {
 
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 scl4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float4 fma4(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
-}
 // a . b added to p as four explicit fused multiply-adds: the rounding does not depend on where the call is inlined, so da_f and c
 // (the same product when a video has one frame of weight 1) come out with the same bits
 __device__ __forceinline__ float dotf(float4 a, float4 b, float p) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, p)))); }
@@ -48,7 +42,6 @@ __device__ __forceinline__ float wdot(const float4 (&a)[NCH], const float4 (&b)[
     for (int j = 0; j < NCH; ++j) p = dotf(a[j], b[j], p);
     return wave_allsum(p);
 }
-__device__ __forceinline__ int pinned(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 }  // namespace
 
@@ -262,31 +255,17 @@ __global__ __launch_bounds__(256) void frame_bwd_kernel(FrameBwdGroup grp) {
     }
 }
 
-// dw of feature blockIdx.y = its B partial rows added in a fixed order (the scheme of fuse_bwd_dw_kernel: 32 interleaved row groups of
-// 8 lanes x 16 bytes, each in row order, then the 32 group sums in group order); db = 0.
-constexpr int FDW_GROUPS = 32, FDW_LANES = 8;
+// dw of feature blockIdx.y = its B partial rows added in a fixed order (sum_rows_fixed_order: a block takes 32 columns); db = 0.
 __global__ __launch_bounds__(256) void frame_bwd_dw_kernel(FrameBwdGroup grp) {
-    __shared__ float4 sh[FDW_GROUPS][FDW_LANES];
+    __shared__ float4 sh[DW_GROUPS][DW_LANES];
     const FrameBwdArgs& a = grp.f[blockIdx.y];
     if (a.db && blockIdx.x == 0 && threadIdx.x == 0) a.db[0] = 0.f;
     if (!a.dw || !grp.dw_part) return;                            // kernel-uniform
-    const int ln = threadIdx.x & (FDW_LANES - 1), g = threadIdx.x / FDW_LANES;
-    const int col = ((int)blockIdx.x * FDW_LANES + ln) * 4;
+    const int ln = threadIdx.x & (DW_LANES - 1), g = threadIdx.x / DW_LANES;
+    const int col = ((int)blockIdx.x * DW_LANES + ln) * 4;
     const bool valid = col < grp.d;
-    float4 acc = zero4();
-    if (valid) {
-        const float* p = grp.dw_part + (long)blockIdx.y * grp.B * grp.d + col;
-#pragma unroll 8
-        for (int r = g; r < grp.B; r += FDW_GROUPS) acc = add4(acc, *(const float4*)(p + (long)r * grp.d));
-    }
-    sh[g][ln] = acc;
-    __syncthreads();
-    if (g == 0 && valid) {
-        float4 t = sh[0][ln];
-#pragma unroll
-        for (int k = 1; k < FDW_GROUPS; ++k) t = add4(t, sh[k][ln]);
-        *(float4*)(a.dw + col) = t;
-    }
+    const float4 t = sum_rows_fixed_order(grp.dw_part + (long)blockIdx.y * grp.B * grp.d + col, valid ? grp.B : 0, grp.d, sh);
+    if (g == 0 && valid) *(float4*)(a.dw + col) = t;
 }
 
 int frame_bwd_variant(int d) { return d <= 256 ? 1 : d <= 512 ? 2 : 4; }
@@ -300,7 +279,7 @@ hipError_t launch_frame_fuse_backward(const FrameBwdGroup& g, bool tail, hipStre
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !tail) return e;
-    hipLaunchKernelGGL(frame_bwd_dw_kernel, dim3((unsigned)((g.d / 4 + FDW_LANES - 1) / FDW_LANES), (unsigned)g.count), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(frame_bwd_dw_kernel, dim3((unsigned)((g.d / 4 + DW_LANES - 1) / DW_LANES), (unsigned)g.count), dim3(256), 0, st, g);
     return hipGetLastError();
 }
 

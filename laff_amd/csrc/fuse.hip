@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "attn_common.h"
 #include "kernels.h"
 #include "exact_cos.h"
 #include "wave_reduce.h"
@@ -24,13 +25,6 @@ namespace laff {
 // `__shfl_xor` loops fuse_reg_kernel<4, 2> held 101 ds_bpermute_b32 with their index arithmetic and LDS waits)
 __device__ __forceinline__ float wave_sum(float v) { return wave_allsum(v); }
 __device__ __forceinline__ float wave_max(float v) { return wave_allmax(v); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 scl4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float4 fma4(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // the same tanh / sigmoid as the GEMM epilogue (v_exp_f32 + v_rcp_f32), so that deferring the activation of a projection
 // to this kernel leaves every bit of the result unchanged
@@ -44,10 +38,8 @@ __device__ __forceinline__ float plane_sigmoid(float x) {
 // x_l[n,h,col..col+3] with the plane's activation, tiling and folded affine applied
 __device__ __forceinline__ float4 load_plane(const FuseArgs& a, int l, long n, int h, int col) {
     const int srccol = a.tile[l] ? col : h * a.head_stride + col;
-    typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     // a projected plane is read exactly once: stream it past the L2 lines that hold the attention / BN vectors and Wt slices
-    const nt_f32x4 nv = __builtin_nontemporal_load((const nt_f32x4*)(a.src[l] + n * a.ld[l] + srccol));
-    float4 v = make_float4(nv.x, nv.y, nv.z, nv.w);
+    float4 v = load_nt((const nt_f32x4*)(a.src[l] + n * a.ld[l] + srccol));
     const int act = a.act[l];                                   // wave-uniform
     if (act == LAFF_ACT_TANH) v = make_float4(plane_tanh(v.x), plane_tanh(v.y), plane_tanh(v.z), plane_tanh(v.w));
     else if (act == LAFF_ACT_RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
@@ -69,9 +61,7 @@ __device__ __forceinline__ float4 load_plane(const FuseArgs& a, int l, long n, i
 // vmcnt(0)` eight times over), the 72 % of its cycles that wavefront spent waiting.  Bit for bit the same values as load_plane.
 __device__ __forceinline__ float4 load_plane_raw(const FuseArgs& a, int l, long n, int h, int col) {
     const int srccol = a.tile[l] ? col : h * a.head_stride + col;
-    typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-    const nt_f32x4 nv = __builtin_nontemporal_load((const nt_f32x4*)(a.src[l] + n * a.ld[l] + srccol));
-    return make_float4(nv.x, nv.y, nv.z, nv.w);
+    return load_nt((const nt_f32x4*)(a.src[l] + n * a.ld[l] + srccol));
 }
 template <int NCH>
 __device__ __forceinline__ void finish_plane(const FuseArgs& a, int l, long n, int h, int lane, int d, float4 (&x)[NCH]) {
@@ -228,23 +218,6 @@ __device__ __forceinline__ void store16x4(void* base, long idx, float4 v, float 
         h4 o = {(_Float16)(v.x * scale), (_Float16)(v.y * scale), (_Float16)(v.z * scale), (_Float16)(v.w * scale)};
         *(h4*)((_Float16*)base + idx) = o;
     }
-}
-
-// softmax over L logits held identically by every lane
-template <int L>
-__device__ __forceinline__ void softmax_L(float (&lg)[L]) {
-    float m = lg[0];
-#pragma unroll
-    for (int l = 1; l < L; ++l) m = fmaxf(m, lg[l]);
-    float s = 0.f;
-#pragma unroll
-    for (int l = 0; l < L; ++l) {
-        lg[l] = expf(lg[l] - m);
-        s += lg[l];
-    }
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int l = 0; l < L; ++l) lg[l] *= inv;
 }
 
 // ---- laff_rank_prepare's work for the rows of a block, right behind their production (FuseArgs::rp_*; H == 1) -----------------------
@@ -418,17 +391,13 @@ void fuse_reg_kernel(FuseArgs a) {
         pld[l] = a.ld[l];
         pdense[l] = !a.g_wt[l];
     }
-    typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     if (d == 256 * NCH) {
 #pragma unroll
         for (int l = 0; l < L; ++l)
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 x[l][j] = make_float4(0, 0, 0, 0);
-                if (pdense[l]) {                                             // wave-uniform
-                    const nt_f32x4 nv = __builtin_nontemporal_load((const nt_f32x4*)(psrc[l] + n * pld[l] + j * 256 + lane * 4));
-                    x[l][j] = make_float4(nv.x, nv.y, nv.z, nv.w);
-                }
+                if (pdense[l]) x[l][j] = load_nt((const nt_f32x4*)(psrc[l] + n * pld[l] + j * 256 + lane * 4));      // wave-uniform
             }
     } else {
 #pragma unroll
@@ -509,8 +478,7 @@ void fuse_reg_kernel(FuseArgs a) {
     for (int j = 0; j < NCH; ++j) {
         const int col = j * 256 + lane * 4;
         if (col < d) {
-            typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-            __builtin_nontemporal_store(nt_f32x4{g[j].x, g[j].y, g[j].z, g[j].w}, (nt_f32x4*)(a.E + item * d + col));
+            store_nt((nt_f32x4*)(a.E + item * d + col), g[j]);
             if (a.E16) store16x4(a.E16, item * d + col, g[j], a.e16_scale, a.e16_bf16);
         }
     }

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "attn_common.h"
 #include "kernels.h"
 #include "wave_reduce.h"
 
@@ -29,17 +30,7 @@ namespace laff {
 
 namespace {
 
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float bsum(float v) { return wave_allsum(v); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 scl4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float4 fma4(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 // A wave-uniform row base + the lane's unsigned byte offset: the scalar-base + 32-bit lane offset form of the global instructions, no
 // 64-bit address arithmetic per lane.  row_base() holds the base in scalar registers and hides it from the optimiser: left to itself
 // hipcc re-associates (base + n * ld) + lane offset into (base + lane offset) + n * ld and keeps one 64-bit per-lane pointer per load
@@ -52,42 +43,10 @@ __device__ __forceinline__ gptr row_base(const float* p) {
     return g;
 }
 __device__ __forceinline__ LAFF_GLOBAL nt_f32x4* at(gptr base, unsigned byte_off) { return (LAFF_GLOBAL nt_f32x4*)(base + byte_off); }
-__device__ __forceinline__ float4 f4(nt_f32x4 v) { return make_float4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ nt_f32x4 v4(float4 v) { return nt_f32x4{v.x, v.y, v.z, v.w}; }
 __device__ __forceinline__ float4 ld(gptr base, unsigned byte_off) { return f4(*at(base, byte_off)); }
 __device__ __forceinline__ void st(gptr base, unsigned byte_off, float4 v) { *at(base, byte_off) = v4(v); }
 __device__ __forceinline__ float4 ld_nt(gptr base, unsigned byte_off) { return f4(__builtin_nontemporal_load(at(base, byte_off))); }
 __device__ __forceinline__ void st_nt(gptr base, unsigned byte_off, float4 v) { __builtin_nontemporal_store(v4(v), at(base, byte_off)); }
-
-// the forward's softmax (fuse.hip softmax_L), bit for bit
-template <int L>
-__device__ __forceinline__ void softmax_L(float (&lg)[L]) {
-    float m = lg[0];
-#pragma unroll
-    for (int l = 1; l < L; ++l) m = fmaxf(m, lg[l]);
-    float s = 0.f;
-#pragma unroll
-    for (int l = 0; l < L; ++l) {
-        lg[l] = expf(lg[l] - m);
-        s += lg[l];
-    }
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int l = 0; l < L; ++l) lg[l] *= inv;
-}
-
-// dz_l = a_l (da_l - sum_k a_k da_k), in place of da
-template <int L>
-__device__ __forceinline__ void softmax_bwd_L(const float (&a)[L], float (&da)[L]) {
-    float abar = 0.f;
-#pragma unroll
-    for (int l = 0; l < L; ++l) abar = fmaf(a[l], da[l], abar);
-#pragma unroll
-    for (int l = 0; l < L; ++l) da[l] = a[l] * (da[l] - abar);
-}
-
-// a wave-uniform value as the scalar it is (the wave index: derived from threadIdx it looks divergent to the compiler)
-__device__ __forceinline__ int pinned(int v) { return __builtin_amdgcn_readfirstlane(v); }
 }  // namespace
 
 // ---- register-resident variant: d <= 256 * NCH -------------------------------------------------------------------------------
@@ -431,11 +390,7 @@ __global__ __launch_bounds__(256) void fuse_bwd_stream_kernel(FuseBwdArgs a) {
     }
 }
 
-// dw[h, c] = the partial rows of head h added in a fixed order; db = 0.  A block takes 32 columns (8 lanes x 16 bytes: one 128-byte line
-// per partial row) and cuts the rows into 32 interleaved groups, one per 8 lanes; each group adds its rows in row order and thread
-// 0..7 adds the 32 group sums in group order.  (One thread per column walking all rows was a chain of rows / 8 round trips on two to
-// sixteen workgroups.)
-constexpr int DW_GROUPS = 32, DW_LANES = 8;
+// dw[h, c] = the partial rows of head h added in a fixed order (sum_rows_fixed_order: a block takes 32 columns); db = 0.
 __global__ __launch_bounds__(256) void fuse_bwd_dw_kernel(const float* __restrict__ part, int rows, int H, int d, float* __restrict__ dw,
                                                           float* __restrict__ db) {
     __shared__ float4 sh[DW_GROUPS][DW_LANES];
@@ -445,21 +400,9 @@ __global__ __launch_bounds__(256) void fuse_bwd_dw_kernel(const float* __restric
     const int ln = threadIdx.x & (DW_LANES - 1), grp = threadIdx.x / DW_LANES;
     const int col = ((int)blockIdx.x * DW_LANES + ln) * 4;        // in the stacked [H d] row; a float4 never straddles heads (d % 4 == 0)
     const bool valid = col < H * d;
-    float4 acc = zero4();
-    if (valid && rows > 0) {
-        const int h = col / d, c = col - h * d;
-        const float* p = part + (long)h * rows * d + c;
-#pragma unroll 8
-        for (int r = grp; r < rows; r += DW_GROUPS) acc = add4(acc, *(const float4*)(p + (long)r * d));
-    }
-    sh[grp][ln] = acc;
-    __syncthreads();
-    if (grp == 0 && valid) {
-        float4 t = sh[0][ln];
-#pragma unroll
-        for (int k = 1; k < DW_GROUPS; ++k) t = add4(t, sh[k][ln]);
-        *(float4*)(dw + col) = t;
-    }
+    const int h = valid ? col / d : 0, c = col - h * d;
+    const float4 t = sum_rows_fixed_order(part + (long)h * rows * d + c, valid ? rows : 0, d, sh);
+    if (grp == 0 && valid) *(float4*)(dw + col) = t;
 }
 
 void fuse_bwd_plan(int N, int H, int d, unsigned flags, int* rows_per_block, int* chunks, int* part_rows) {

@@ -23,14 +23,13 @@ import torch
 import fc_bwd_ref as R
 import fuse_bwd_ref as FR
 import fuse_ref
-import loss_ref
+import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
 NAN = float('nan')
-TOL_UNIT = 1.5e-6             # the forward's own contract (tests/test_gpu_fuse_routes.py)
-GRAD_ABS = 2e-6               # the margin loss's gradient bound (tests/test_gpu_losses.py)
+TOL_UNIT = TR.TOL_UNIT
 
 # layouts of every operand and output: 'dense' rows on a 16-byte aligned base; 'pitch4' a wider pitch that keeps the rows 16-byte aligned
 # (the 16-byte loads, strided); 'pitch3' a wider pitch that does not (the generic loads); 'offset' a base pointer 4 bytes past a 16-byte
@@ -83,12 +82,6 @@ def _out_vec(n, layout):
     return buf, buf[lo:lo + n]
 
 
-def _untouched_around(buf, view):
-    chk = buf.clone()
-    torch.as_strided(chk, view.shape, view.stride(), view.storage_offset()).fill_(NAN)
-    return bool(chk.isnan().all())
-
-
 @functools.lru_cache(maxsize=None)
 def _case(c):
     """The fp32 operands of a case on the CPU, the float64 reference and the bounds -- computed once, shared, never written."""
@@ -126,10 +119,10 @@ def _launch(c, want=(True, True, True)):
             assert r is None
             continue
         assert r.data_ptr() == b[1].data_ptr()
-        assert _untouched_around(*b), '%s: a write outside the output' % name
+        assert TR.untouched_around(*b), '%s: a write outside the output' % name
         assert not r.isnan().any(), '%s: an element was not written (or read a canary)' % name
     for ibuf, iview in _device_inputs(c):
-        assert _untouched_around(ibuf, iview)
+        assert TR.untouched_around(ibuf, iview)
     return res
 
 
@@ -198,7 +191,7 @@ def test_empty_batch_writes_zeros_and_nothing_else():
                                      out=(None, bdw[1], bdb[1]))
         torch.cuda.synchronize()
         assert tuple(dx.shape) == (0, Dk) and not dw.any() and not db.any() and tuple(dw.shape) == (D, Dk) and tuple(db.shape) == (D,)
-        assert _untouched_around(*bdw) and _untouched_around(*bdb)
+        assert TR.untouched_around(*bdw) and TR.untouched_around(*bdb)
 
 
 def test_argument_errors():
@@ -333,20 +326,6 @@ def test_no_dx_launch_for_inputs_without_grad(monkeypatch):
 
 
 # ---- end to end: a LAFF tower's training step with every stage on this library's kernels -------------------------------------------
-def _margin_loss_f64(s, im, margin):
-    """MarginRankingLoss(margin, 'cosine', max_violation=False, 'sum', 'bidir') per head, summed, in torch on (B, H, d)."""
-    total = 0.0
-    B = s.shape[0]
-    off = ~torch.eye(B, dtype=torch.bool)
-    for h in range(s.shape[1]):
-        sh = s[:, h] / (s[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        ih = im[:, h] / (im[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        S = ih @ sh.T
-        dg = torch.diag(S)
-        total = total + (torch.clamp(margin + S - dg[:, None], min=0) * off).sum() + (torch.clamp(margin + S - dg[None, :], min=0) * off).sum()
-    return total
-
-
 class _Side(torch.nn.Module):
     """One tower: L TransformNet projections (fc1 + tanh) whose plane() outputs go to the fusion block's fuse_planes."""
 
@@ -398,8 +377,7 @@ def test_end_to_end_two_towers_margin_loss():
     from laff_amd import loss as laff_loss
     B, L, H, d, margin = 16, 3, 2, 64, 0.2
     dims = (24, 16, 8)
-    for seed in range(40):                       # pairs 1e-4 clear of every hinge decision, in float64
-        torch.manual_seed(100 + seed)
+    def build():
         txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
         with torch.no_grad():
             for p in list(txt.proj) + list(vis.proj):
@@ -408,30 +386,15 @@ def test_end_to_end_two_towers_margin_loss():
         ft = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            Et, Ev = _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
-            slack = min(loss_ref.margin_scores_slack(
-                (Ev[:, h] / Ev[:, h].norm(dim=1, keepdim=True)).numpy() @ (Et[:, h] / Et[:, h].norm(dim=1, keepdim=True)).numpy().T,
-                margin, False, 'bidir') for h in range(H))
-        if slack >= 1e-4:
-            break
-    assert slack >= 1e-4
+            return (txt, vis, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+    txt, vis, ft, fv = TR.hinge_clear_seed(build, margin, 100)
     grads = {}
     for dtype in (torch.float64, torch.float32):
         (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
-        _margin_loss_f64(Et, Ev, margin).backward()
+        TR.margin_loss_f64(Et, Ev, margin).backward()
         grads[dtype] = ({k: v.grad.double() for k, v in lt.items()}, {k: v.grad.double() for k, v in lv.items()}, Et, Ev)
     # sum_j |dT / dE_j| per side, from the float64 graph: one batched backward over the unit vectors of E
-    absjac = []
-    for side in (0, 1):
-        E, leaves = _side_f64((txt, vis)[side], (ft, fv)[side])
-        names = list(leaves)
-        eye = torch.eye(E.numel(), dtype=torch.float64).reshape(E.numel(), *E.shape)
-        acc = {k: torch.zeros_like(leaves[k]) for k in names}
-        for lo in range(0, E.numel(), 256):
-            js = torch.autograd.grad(E, [leaves[k] for k in names], eye[lo:lo + 256], retain_graph=True, is_grads_batched=True)
-            for k, j in zip(names, js):
-                acc[k] += j.abs().sum(0)
-        absjac.append(acc)
+    absjac = [TR.abs_jacobian(*_side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
     # the device
     txt, vis = txt.to(DEV).train(), vis.to(DEV).train()
     dt = [f.to(DEV).requires_grad_(True) for f in ft]
@@ -442,7 +405,7 @@ def test_end_to_end_two_towers_margin_loss():
     loss = crit(Et, Ev)
     loss.backward()
     torch.cuda.synchronize()
-    l64 = float(_margin_loss_f64(grads[torch.float64][2].detach(), grads[torch.float64][3].detach(), margin))
+    l64 = float(TR.margin_loss_f64(grads[torch.float64][2].detach(), grads[torch.float64][3].detach(), margin))
     assert abs(loss.item() - l64) <= 2e-5 * max(1.0, abs(l64))
     worst = 0.0
     for side, (mod, feats) in enumerate(((txt, dt), (vis, dv))):
@@ -459,9 +422,7 @@ def test_end_to_end_two_towers_margin_loss():
             if n.endswith('embedding_common.0.bias'):
                 assert not g.any(), n                                                               # db of the fusion: exactly zero
                 continue
-            top = float(r.abs().max())
-            e32 = FR.rel_err(ref32[n], r)
-            bound = max(4.0 * e32, TOL_UNIT) * top + GRAD_ABS * absjac[side][n]
+            bound, e32, top = TR.end_to_end_bound(r, ref32[n], absjac[side][n])
             err = (g.cpu().double() - r).abs()
             ratio = float((err / bound).max())
             worst = max(worst, ratio)

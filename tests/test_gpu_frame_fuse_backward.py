@@ -23,13 +23,12 @@ import torch
 import frame_bwd_ref as R
 import fuse_bwd_ref as FR
 import fuse_ref
-import loss_ref
+import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
-TOL_UNIT = 1.5e-6
-GRAD_ABS = 2e-6               # the margin loss's gradient bound (tests/test_gpu_losses.py)
+TOL_UNIT = TR.TOL_UNIT
 NAN = float('nan')
 BOTH = (True, True)           # (with_ave, mul): every term of the backward is present
 GUARD = 64                    # floats of NaN on either side of every output buffer
@@ -119,16 +118,6 @@ def _flags(kw):
     return ops.attention_flags(kw['with_ave'], kw['mul'])
 
 
-def _framed(n):
-    """n floats of NaN between two guards of NaN: (the whole buffer, the 16-byte aligned view in its middle)."""
-    whole = torch.full((n + 2 * GUARD,), NAN, dtype=torch.float32, device=DEV)
-    return whole, whole[GUARD:GUARD + n]
-
-
-def _guards_intact(whole):
-    return bool(torch.isnan(whole[:GUARD]).all()) and bool(torch.isnan(whole[whole.numel() - GUARD:]).all())
-
-
 def _table(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
@@ -150,14 +139,14 @@ class _Launch:
             g = torch.full((B, self.lddv), NAN, device=DEV)
             g[:, :d] = f['dV'].to(DEV)
             self.grads.append(g)
-        self.df = [_framed(B * Fmax * d) for _ in range(n)]
-        self.dw = [_framed(d) for _ in range(n)]
-        self.db = [_framed(4) for _ in range(n)]                                  # (db is its first float; the rest stays NaN)
+        self.fr = TR.Frames(GUARD)
+        self.df = [self.fr.floats(B * Fmax * d) for _ in range(n)]
+        self.dw = [self.fr.floats(d) for _ in range(n)]
+        self.db = [self.fr.floats(4) for _ in range(n)]                           # (db is its first float; the rest stays NaN)
         self.nbytes = ops.frame_fuse_backward_plan(n, B, Fmax, d, want_dw)[0]
-        self.ws = _framed(max(self.nbytes // 4, 4))
+        self.ws = self.fr.floats(max(self.nbytes // 4, 4))
         self.tables = (_table(self.frames), _table([p[0] for p in self.params]), _table([p[1] for p in self.params]),
-                       _table([p[2] for p in self.params]), _table(self.grads), _table([v for _, v in self.df]),
-                       _table([v for _, v in self.dw]), _table([v for _, v in self.db]))
+                       _table([p[2] for p in self.params]), _table(self.grads), _table(self.df), _table(self.dw), _table(self.db))
 
     def run(self):
         from laff_amd import ops
@@ -166,18 +155,17 @@ class _Launch:
         F, W, Bb, G, DV, DF, DW, DB = self.tables
         ops.check(lib.laff_frame_fuse_backward(h, self.n, F, ops._ptr(self.lens), cs['B'], cs['Fmax'], cs['d'], W, Bb, G, _flags(cs['kw']),
                                                DV, self.lddv, DF, DW if self.want_dw else None, DB if self.want_dw else None,
-                                               ops._ptr(self.ws[1]), self.nbytes))
+                                               ops._ptr(self.ws), self.nbytes))
         return self
 
     def outputs(self):
         torch.cuda.synchronize()
         cs = self.cs
-        return ([v.view(cs['B'], cs['Fmax'], cs['d']) for _, v in self.df], [v for _, v in self.dw], [v[:1] for _, v in self.db])
+        return ([v.view(cs['B'], cs['Fmax'], cs['d']) for v in self.df], list(self.dw), [v[:1] for v in self.db])
 
     def guards_intact(self):
         torch.cuda.synchronize()
-        return all(_guards_intact(w) for w, _ in self.df + self.dw + self.db + [self.ws]) and \
-            all(bool(torch.isnan(v[1:]).all()) for _, v in self.db)
+        return self.fr.intact() and all(bool(torch.isnan(v[1:]).all()) for v in self.db)
 
 
 def _same(a, b):
@@ -220,7 +208,7 @@ def test_backward_vs_float64(c):
     nodw = _Launch(cs, want_dw=False).run()
     o = nodw.outputs()
     assert _same(o[0], dfs) and nodw.guards_intact()
-    assert all(bool(torch.isnan(t).all()) for t in o[1] + o[2]) and bool(torch.isnan(nodw.ws[1]).all())
+    assert all(bool(torch.isnan(t).all()) for t in o[1] + o[2]) and bool(torch.isnan(nodw.ws).all())
     # a gradient with a wider row pitch: the same bits as its dense copy
     wide = _Launch(cs, pitch=d + 8).run()
     assert all(_same(a, b) for a, b in zip(wide.outputs(), (dfs, dws, dbs))) and wide.guards_intact()
@@ -270,7 +258,9 @@ def test_lens_cases_hold_the_three_lengths_and_nan_padding():
 def test_empty_batch_and_no_features_touch_nothing():
     from laff_amd import ops
     lib, h = ops._context(torch.device(DEV, torch.cuda.current_device()))
-    whole, buf = _framed(64)
+    fr = TR.Frames(GUARD)
+    buf = fr.floats(64)
+    whole = fr.held[0][0]
     t = _table([buf])
     for count, B in ((1, 0), (0, 4)):
         assert lib.laff_frame_fuse_backward(h, count, t, None, B, 2, 8, t, t, t, 3, t, 8, t, t, t, ops._ptr(buf), 0) == 0
@@ -413,20 +403,6 @@ def test_tower_frame_vector_train(add_fc):
 
 
 # ---- end to end: frame features in front of a LAFF tower's training step ------------------------------------------------------------
-def _margin_loss_f64(s, im, margin):
-    """MarginRankingLoss(margin, 'cosine', max_violation=False, 'sum', 'bidir') per head, summed, in torch on (B, H, d)."""
-    total = 0.0
-    B = s.shape[0]
-    off = ~torch.eye(B, dtype=torch.bool)
-    for h in range(s.shape[1]):
-        sh = s[:, h] / (s[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        ih = im[:, h] / (im[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        S = ih @ sh.T
-        dg = torch.diag(S)
-        total = total + (torch.clamp(margin + S - dg[:, None], min=0) * off).sum() + (torch.clamp(margin + S - dg[None, :], min=0) * off).sum()
-    return total
-
-
 def _video_side_device(tower, feats, mask):
     """frame_vector -> TransformNet.plane -> the tower's fusion block, the pieces prepare() strings together in eval mode."""
     planes = [getattr(tower, n).plane(tower.frame_vector(n, x, mask)) for n, x in feats.items()]
@@ -479,8 +455,7 @@ def test_end_to_end_frame_features_margin_loss():
     B, Fmax, d, H, D, margin = 16, 5, 64, 2, 128, 0.2
     lens = torch.tensor([1, 5, 3, 2, 4, 5, 1, 2, 3, 4, 5, 5, 2, 3, 4, 1])
     mask = (torch.arange(Fmax)[None, :] < lens[:, None]).float()
-    for seed in range(40):                       # pairs 1e-4 clear of every hinge decision, in float64
-        torch.manual_seed(300 + seed)
+    def build():
         tower = _tower(False, {'fa': d, 'fb': d}, D=D, H=H)
         with torch.no_grad():
             for n in ('fa', 'fb'):
@@ -489,31 +464,18 @@ def test_end_to_end_frame_features_margin_loss():
         feats = {n: (0.5 * (z @ torch.randn(8, d)) + 0.5 * torch.randn(B, Fmax, d)) * mask[:, :, None] for n in ('fa', 'fb')}
         Et = torch.randn(B, H, D // H)
         with torch.no_grad():
-            Ev = _video_side_ref(tower, feats, mask)[0]
-            E64 = Et.double()
-            slack = min(loss_ref.margin_scores_slack(
-                (Ev[:, h] / Ev[:, h].norm(dim=1, keepdim=True)).numpy() @ (E64[:, h] / E64[:, h].norm(dim=1, keepdim=True)).numpy().T,
-                margin, False, 'bidir') for h in range(H))
-        if slack >= 1e-4:
-            break
-    assert slack >= 1e-4
+            return (tower, feats, Et), Et, _video_side_ref(tower, feats, mask)[0]
+    tower, feats, Et = TR.hinge_clear_seed(build, margin, 300)
     grads = {}
     for dtype in (torch.float64, torch.float32):
         Ev, lv = _video_side_ref(tower, feats, mask, dtype)
         t = Et.detach().clone().to(dtype).requires_grad_(True)
-        _margin_loss_f64(t, Ev, margin).backward()
+        TR.margin_loss_f64(t, Ev, margin).backward()
         grads[dtype] = dict({k: v.grad.double() for k, v in lv.items()}, text=t.grad.double())
         if dtype == torch.float64:
-            l64 = float(_margin_loss_f64(t.detach(), Ev.detach(), margin))
+            l64 = float(TR.margin_loss_f64(t.detach(), Ev.detach(), margin))
     # sum_j |dT / dE_j| of the video side, from the float64 graph: one batched backward over the unit vectors of E
-    E, leaves = _video_side_ref(tower, feats, mask)
-    names = list(leaves)
-    eye = torch.eye(E.numel(), dtype=torch.float64).reshape(E.numel(), *E.shape)
-    absjac = {k: torch.zeros_like(leaves[k]) for k in names}
-    for lo in range(0, E.numel(), 256):
-        js = torch.autograd.grad(E, [leaves[k] for k in names], eye[lo:lo + 256], retain_graph=True, is_grads_batched=True)
-        for k, j in zip(names, js):
-            absjac[k] += j.abs().sum(0)
+    absjac = TR.abs_jacobian(*_video_side_ref(tower, feats, mask))
     absjac['text'] = torch.ones(B, H, D // H, dtype=torch.float64)
     # the device
     tower = tower.train()
@@ -545,9 +507,7 @@ def test_end_to_end_frame_features_margin_loss():
             continue
         if n.startswith('frames.'):
             assert not g.cpu()[pad].any(), n                              # padded frames: exactly zero
-        top = float(r.abs().max())
-        e32 = R.rel_err(ref32[n], r)
-        bound = max(4.0 * e32, TOL_UNIT) * top + GRAD_ABS * absjac[n]
+        bound, e32, top = TR.end_to_end_bound(r, ref32[n], absjac[n])
         err = (g.cpu().double().reshape(r.shape) - r).abs()
         ratio = float((err / bound).max())
         worst = max(worst, ratio)

@@ -23,13 +23,12 @@ import torch
 
 import fuse_bwd_ref as R
 import fuse_ref
-import loss_ref
+import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
-TOL_UNIT = 1.5e-6
-GRAD_ABS = 2e-6               # the margin loss's gradient bound (tests/test_gpu_losses.py)
+TOL_UNIT = TR.TOL_UNIT
 MULTI = dict(with_ave=True, mul=True)              # what Multi_head_MyApply_Attention defaults to
 
 
@@ -300,20 +299,6 @@ def test_attention_1_and_just_average_train():
     assert R.rel_err(y.grad.cpu(), (dE.double() / L)[:, None, :].expand(N, L, D)) <= 2.0 ** -22
 
 
-def _margin_loss_f64(s, im, margin):
-    """MarginRankingLoss(margin, 'cosine', max_violation=False, 'sum', 'bidir') per head, summed, in torch on (B, H, d)."""
-    total = 0.0
-    B = s.shape[0]
-    off = ~torch.eye(B, dtype=torch.bool)
-    for h in range(s.shape[1]):
-        sh = s[:, h] / (s[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        ih = im[:, h] / (im[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        S = ih @ sh.T
-        dg = torch.diag(S)
-        total = total + (torch.clamp(margin + S - dg[:, None], min=0) * off).sum() + (torch.clamp(margin + S - dg[None, :], min=0) * off).sum()
-    return total
-
-
 class _Side(torch.nn.Module):
     """One tower of the end-to-end test: L nn.Linear + tanh projections in torch, torch.stack, the fusion block."""
 
@@ -360,38 +345,22 @@ def test_end_to_end_two_towers_margin_loss():
     from laff_amd import loss as laff_loss
     B, L, H, d, margin = 16, 3, 2, 64, 0.2
     dims = (24, 16, 8)
-    for seed in range(40):                       # pairs 1e-4 clear of every hinge decision, in float64
-        torch.manual_seed(100 + seed)
+    def build():
         txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
         z = torch.randn(B, 8)
         ft = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            Et, Ev = _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
-            slack = min(loss_ref.margin_scores_slack(
-                (Ev[:, h] / Ev[:, h].norm(dim=1, keepdim=True)).numpy() @ (Et[:, h] / Et[:, h].norm(dim=1, keepdim=True)).numpy().T,
-                margin, False, 'bidir') for h in range(H))
-        if slack >= 1e-4:
-            break
-    assert slack >= 1e-4
+            return (txt, vis, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+    txt, vis, ft, fv = TR.hinge_clear_seed(build, margin, 100)
     # float64 and float32 CPU graphs
     grads = {}
     for dtype in (torch.float64, torch.float32):
         (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
-        _margin_loss_f64(Et, Ev, margin).backward()
+        TR.margin_loss_f64(Et, Ev, margin).backward()
         grads[dtype] = ({k: v.grad.double() for k, v in lt.items()}, {k: v.grad.double() for k, v in lv.items()}, Et, Ev, lt, lv)
     # sum_j |dT / dE_j| per side, from the float64 graph: one batched backward over the unit vectors of E
-    absjac = []
-    for side in (0, 1):
-        E, leaves = _side_f64((txt, vis)[side], (ft, fv)[side])
-        names = list(leaves)
-        eye = torch.eye(E.numel(), dtype=torch.float64).reshape(E.numel(), *E.shape)
-        acc = {k: torch.zeros_like(leaves[k]) for k in names}
-        for lo in range(0, E.numel(), 256):
-            js = torch.autograd.grad(E, [leaves[k] for k in names], eye[lo:lo + 256], retain_graph=True, is_grads_batched=True)
-            for k, j in zip(names, js):
-                acc[k] += j.abs().sum(0)
-        absjac.append(acc)
+    absjac = [TR.abs_jacobian(*_side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
     # the device
     txt, vis = txt.to(DEV).train(), vis.to(DEV).train()
     dt = [f.to(DEV).requires_grad_(True) for f in ft]
@@ -402,7 +371,7 @@ def test_end_to_end_two_towers_margin_loss():
     loss = crit(Et, Ev)
     loss.backward()
     torch.cuda.synchronize()
-    l64 = float(_margin_loss_f64(grads[torch.float64][2].detach(), grads[torch.float64][3].detach(), margin))
+    l64 = float(TR.margin_loss_f64(grads[torch.float64][2].detach(), grads[torch.float64][3].detach(), margin))
     assert abs(loss.item() - l64) <= 2e-5 * max(1.0, abs(l64))
     worst = 0.0
     for side, (mod, feats) in enumerate(((txt, dt), (vis, dv))):
@@ -419,9 +388,7 @@ def test_end_to_end_two_towers_margin_loss():
             if n.endswith('embedding_common.0.bias'):
                 assert not g.any(), n                                                               # db: exactly zero
                 continue
-            top = float(r.abs().max())
-            e32 = R.rel_err(ref32[n], r)
-            bound = max(4.0 * e32, TOL_UNIT) * top + GRAD_ABS * absjac[side][n]
+            bound, e32, top = TR.end_to_end_bound(r, ref32[n], absjac[side][n])
             err = (g.cpu().double() - r).abs()
             ratio = float((err / bound).max())
             worst = max(worst, ratio)

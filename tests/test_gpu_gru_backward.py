@@ -21,11 +21,12 @@ import pytest
 import torch
 
 import gru_bwd_ref as R
+import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
-TOL_UNIT = 1.5e-6
+TOL_UNIT = TR.TOL_UNIT
 V, V_DRAWN, WE = 50, 45, 20
 MODES = [('gru', 'mean'), ('gru', 'last'), ('gru', 'mean_last'), ('bigru', 'mean'), ('bigru', 'last')]
 PAD = 64                                             # floats of NaN frame on either side of a buffer
@@ -96,27 +97,6 @@ def _batch(ids):
     bs = [int((slens > t).sum()) for t in range(Tm)]
     dev = [torch.from_numpy(a).to(DEV) for a in (tokens, slens, perm) + tuple(T.gru_train_arrays(tokens, bs))]
     return T.GruTrainBatch(dev[0], dev[1], dev[2], bs, *dev[3:])
-
-
-class Frames:
-    """Buffers inside NaN frames: every float outside what was handed out has to be NaN still after the launches."""
-
-    def __init__(self):
-        self.held = []
-
-    def floats(self, *shape):
-        n = int(np.prod(shape))
-        buf = torch.full((n + 2 * PAD,), float('nan'), dtype=torch.float32, device=DEV)
-        self.held.append((buf, n))
-        return buf[PAD:PAD + n].view(*shape)
-
-    def bytes(self, nbytes):
-        n = (nbytes + 3) // 4
-        return self.floats(max(n, 4)).view(torch.uint8)[:max(nbytes, 16)]
-
-    def check(self):
-        for buf, n in self.held:
-            assert torch.isnan(buf[:PAD]).all() and torch.isnan(buf[PAD + n:]).all()
 
 
 def _device(cs, want_dwe=True, frames=None):
@@ -194,10 +174,10 @@ def _hold(cs, got, label):
 @pytest.mark.parametrize('c', CASES, ids=_case_id)
 def test_against_float64(c):
     cs = _case(c)
-    fr = Frames()
+    fr = TR.Frames(PAD)
     got = _device(cs, frames=fr)
     torch.cuda.synchronize()
-    fr.check()
+    assert fr.intact()
     _hold(cs, got, _case_id(c))
     assert not got['we.weight'][V_DRAWN:].any()                # tokens that no caption used: exactly zero
     unused = np.setdiff1d(np.arange(V), np.concatenate(cs['ids']))
@@ -218,10 +198,10 @@ def test_large_tile_against_float64(c):
     assert fwd[0] == 1 and bwd[-1] == 1
     fewer = ops.gru_backward_plan([min(x, N - 1) for x in bs], H, net == 'bigru', pooling)      # one row less: no launch takes it
     assert set(fewer[0]) == {0} and set(fewer[1]) == {0}
-    fr = Frames()
+    fr = TR.Frames(PAD)
     got = _device(cs, frames=fr)
     torch.cuda.synchronize()
-    fr.check()
+    assert fr.intact()
     _hold(cs, got, _case_id(c))
     assert not got['we.weight'][V_DRAWN:].any()
 
@@ -247,10 +227,10 @@ def test_two_runs_are_bit_identical_and_without_d_we_the_rest_is_the_same_bits(c
     from laff_amd import ops
     cs = _staged(c)
     a, b = _device(cs), _device(cs)
-    fr = Frames()
+    fr = TR.Frames(PAD)
     no = _device(cs, want_dwe=False, frames=fr)                # its workspace has no room for dX: none is formed
     torch.cuda.synchronize()
-    fr.check()
+    assert fr.intact()
     N, H, bs = cs['N'], cs['H'], cs['batch'].batch_sizes
     M = sum(bs)
     assert (ops.gru_backward_workspace_bytes(bs, N, H, WE, 1, cs['ndirs'] == 2, cs['pooling'], True) -
@@ -308,17 +288,6 @@ def _captions(g, n, n_words=40, longest=9):
     return [' '.join('w%d' % i for i in g.integers(0, n_words, L)) for L in lens]
 
 
-def _margin_loss_f64(s, im, margin):
-    """MarginRankingLoss(margin, 'cosine', max_violation=False, 'sum', 'bidir') in torch on (B, d)."""
-    import loss_ref
-    sh = s / (s.pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-    ih = im / (im.pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-    S = ih @ sh.T
-    dg = torch.diag(S)
-    off = ~torch.eye(s.shape[0], dtype=torch.bool)
-    return (torch.clamp(margin + S - dg[:, None], min=0) * off).sum() + (torch.clamp(margin + S - dg[None, :], min=0) * off).sum()
-
-
 class _TextSide(torch.nn.Module):
     """Captions -> GruTxtEncoder -> two TransformNet projections (fc1 + tanh) -> Attention_1 over the two planes."""
 
@@ -369,42 +338,30 @@ def test_module_training_step_against_float64():
     """16 captions -> GruTxtEncoder(differentiable=True).train() at H = 64 -> TransformNet.train().plane() x 2 -> Attention_1.train()
     .fuse_planes -> loss.MarginRankingLoss against fixed video embeddings -> backward.  Every parameter gradient against the same
     graph in float64 (CPU nn.GRU), element by element, under the bound of tests/test_gpu_fc_backward.py's
-    test_end_to_end_two_towers_margin_loss:   max(4 e32, 1.5e-6) max |T|  +  GRAD_ABS sum_j |dT / dE_j|.
+    test_end_to_end_two_towers_margin_loss:   max(4 e32, 1.5e-6) max |T|  +  GRAD_ABS sum_j |dT / dE_j|   (tests/train_ref.py).
     Then one laff_amd.optim.Adam step on the encoder's parameters changes them and the next forward sees the new weights."""
-    import loss_ref
     from laff_amd import loss as laff_loss
     from laff_amd import optim as laff_optim
-    GRAD_ABS = 2e-6                            # the margin loss's gradient bound (tests/test_gpu_losses.py)
     B, H, D, margin = 16, 64, 32, 0.2
     g = np.random.default_rng(11)
     caps = _captions(g, B)
-    for seed in range(40):                     # pairs 1e-4 clear of every hinge decision, in float64
-        torch.manual_seed(300 + seed)
+
+    def build():
         side = _TextSide(H, D)
         with torch.no_grad():
             for p in side.proj:
                 p.fc1.bias.uniform_(-0.2, 0.2)
         vis = torch.randn(B, D)
         with torch.no_grad():
-            Et = _text_side_f64(side, caps)[0]
-            sl = loss_ref.margin_scores_slack(((vis.double() / vis.double().norm(dim=1, keepdim=True)) @
-                                               (Et / Et.norm(dim=1, keepdim=True)).T).numpy(), margin, False, 'bidir')
-        if sl >= 1e-4:
-            break
-    assert sl >= 1e-4
+            return (side, vis), _text_side_f64(side, caps)[0], vis
+    side, vis = TR.hinge_clear_seed(build, margin, 300)
     grads = {}
     for dtype in (torch.float64, torch.float32):
         E, leaves = _text_side_f64(side, caps, dtype)
-        _margin_loss_f64(E, vis.to(dtype), margin).backward()
+        TR.margin_loss_f64(E, vis.to(dtype), margin).backward()
         grads[dtype] = ({k: v.grad.double() for k, v in leaves.items()}, E.detach())
     # sum_j |dT / dE_j| from the float64 graph, one backward per unit vector of E
-    E, leaves = _text_side_f64(side, caps)
-    names = list(leaves)
-    absjac = {k: torch.zeros_like(leaves[k]) for k in names}
-    for j in range(E.numel()):
-        js = torch.autograd.grad(E.reshape(-1)[j], [leaves[k] for k in names], retain_graph=True)
-        for k, t in zip(names, js):
-            absjac[k] += t.abs()
+    absjac = TR.abs_jacobian(*_text_side_f64(side, caps), batched=False)
     # the device
     side.to(DEV).train()
     Ed = side(caps)
@@ -413,7 +370,7 @@ def test_module_training_step_against_float64():
     loss = crit(Ed, vis.to(DEV))
     loss.backward()
     torch.cuda.synchronize()
-    l64 = float(_margin_loss_f64(grads[torch.float64][1], vis.double(), margin))
+    l64 = float(TR.margin_loss_f64(grads[torch.float64][1], vis.double(), margin))
     assert abs(loss.item() - l64) <= 2e-5 * max(1.0, abs(l64))
     got = {n: p.grad for n, p in side.named_parameters()}
     assert got.pop('att.global_emb_weight_net.weight') is None
@@ -425,9 +382,7 @@ def test_module_training_step_against_float64():
         if n == 'att.embedding_common.0.bias':
             assert not gt.any()                                          # db of the fusion: exactly zero
             continue
-        top = float(r.abs().max())
-        e32 = R.rel_err(ref32[n].numpy(), r.numpy())
-        bound = max(4.0 * e32, TOL_UNIT) * top + GRAD_ABS * absjac[n]
+        bound, e32, _ = TR.end_to_end_bound(r, ref32[n], absjac[n])
         ratio = float(((gt.cpu().double() - r).abs() / bound).max())
         worst[n] = ratio
         print('module %-32s e32 %.2e  worst fraction of the bound %.3f' % (n, e32, ratio))

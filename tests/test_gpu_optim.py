@@ -27,15 +27,15 @@ import torch
 
 import fuse_bwd_ref as FR
 import fuse_ref
-import loss_ref
 import optim_ref as R
+import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
 NAN = float('nan')
 U = R.U
-TOL_UNIT = 1.5e-6
+TOL_UNIT = TR.TOL_UNIT
 MIXED = [1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025]
 ROLES = ('p', 'g', 's1', 's2')
 
@@ -534,20 +534,6 @@ def test_state_dict_moves_to_torch_on_the_device():
 
 
 # ---- end to end: one training step with every stage on this library's kernels -------------------------------------------------------
-def _margin_loss_f64(s, im, margin):
-    """MarginRankingLoss(margin, 'cosine', max_violation=False, 'sum', 'bidir') per head, summed, in torch on (B, H, d)."""
-    total = 0.0
-    B = s.shape[0]
-    off = ~torch.eye(B, dtype=torch.bool)
-    for h in range(s.shape[1]):
-        sh = s[:, h] / (s[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        ih = im[:, h] / (im[:, h].pow(2).sum(1, keepdim=True).sqrt() + loss_ref.EPS)
-        S = ih @ sh.T
-        dg = torch.diag(S)
-        total = total + (torch.clamp(margin + S - dg[:, None], min=0) * off).sum() + (torch.clamp(margin + S - dg[None, :], min=0) * off).sum()
-    return total
-
-
 class _Side(torch.nn.Module):
     """One tower: L TransformNet projections (fc1 + tanh) whose plane() outputs go to the fusion block's fuse_planes."""
 
@@ -594,8 +580,7 @@ def _towers():
     (pairs 1e-4 clear of every hinge decision, in float64)."""
     B, H, d, margin = 16, 2, 64, 0.2
     dims = (24, 16, 8)
-    for seed in range(40):
-        torch.manual_seed(100 + seed)
+    def build():
         txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
         with torch.no_grad():
             for p in list(txt.proj) + list(vis.proj):
@@ -604,13 +589,8 @@ def _towers():
         ft = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            Et, Ev = _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
-            slack = min(loss_ref.margin_scores_slack(
-                (Ev[:, h] / Ev[:, h].norm(dim=1, keepdim=True)).numpy() @ (Et[:, h] / Et[:, h].norm(dim=1, keepdim=True)).numpy().T,
-                margin, False, 'bidir') for h in range(H))
-        if slack >= 1e-4:
-            break
-    assert slack >= 1e-4
+            return (txt, vis, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+    txt, vis, ft, fv = TR.hinge_clear_seed(build, margin, 100)
     return txt, vis, ft, fv, margin
 
 
@@ -625,7 +605,7 @@ def test_one_training_step_end_to_end():
     stepped, norms = {}, {}
     for dtype in (torch.float64, torch.float32):
         (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
-        _margin_loss_f64(Et, Ev, margin).backward()
+        TR.margin_loss_f64(Et, Ev, margin).backward()
         leaves = {'txt.' + k: v for k, v in lt.items() if not k.startswith('feat')}
         leaves.update({'vis.' + k: v for k, v in lv.items() if not k.startswith('feat')})
         ps = list(leaves.values())

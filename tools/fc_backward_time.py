@@ -15,33 +15,16 @@ Before anything is timed both results are compared: the float64 formulas are eva
 the element-by-element bound of tests/test_gpu_fc_backward.py, (K + 4) 2^-24 sum |dA| |operand|; the two fp32 results may then differ by
 twice that.  A miss ends the run with exit status 1 and no timing line for that shape.
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
+
+from train_time import median_ms, run_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(128, 512, 4096), (128, 2048, 4096), (8192, 512, 512)]
 HBM_PEAK = 8.0e12
 U = 2.0 ** -24
-
-
-def _median_ms(fn, iters):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(5):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / iters)
-    return sorted(out)[2]
 
 
 def child(iters):
@@ -85,9 +68,9 @@ def child(iters):
                     print('%s at %s: laff_fc_backward uses %.3g of its bound and lies %.3g bounds from torch autograd: nothing is timed'
                           % (k, (N, Dk, D), used[k], apart), file=sys.stderr)
                     return 1
-            kernel_ms = _median_ms(raw, iters)
-            op_ms = _median_ms(lambda: ops.fc_backward(x, wd, a, dA, 'tanh', want_dx=with_dx), iters)
-            torch_bwd_ms = _median_ms(lambda: torch.autograd.grad(A, leaves, dA, retain_graph=True), iters)
+            kernel_ms = median_ms(raw, iters)
+            op_ms = median_ms(lambda: ops.fc_backward(x, wd, a, dA, 'tanh', want_dx=with_dx), iters)
+            torch_bwd_ms = median_ms(lambda: torch.autograd.grad(A, leaves, dA, retain_graph=True), iters)
             mandatory = 4 * (2 * N * D + N * Dk + D * Dk + D + (D * Dk + N * Dk if with_dx else 0))
             print(json.dumps({'shape': [N, Dk, D], 'outputs': 'dW+db+dX' if with_dx else 'dW+db', 'chunks': chunks, 'chunks_dx': chunks_dx if with_dx else None,
                               'kernel_ms': round(kernel_ms, 4), 'op_ms': round(op_ms, 4), 'torch_bwd_ms': round(torch_bwd_ms, 4),
@@ -98,17 +81,5 @@ def child(iters):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--timeout', type=int, default=240)
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
-    if a.child:
-        return child(a.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--iters', str(a.iters)], timeout=a.timeout)
-    return r.returncode
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(run_child(child, 20))

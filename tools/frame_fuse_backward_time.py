@@ -17,12 +17,12 @@ Times are HIP events around K back-to-back calls after a warm-up, the median of 
     mandatory_bytes  sum over the videos of (2 len d + d) 4: the frames read once, their gradient written once, dV read
     hbm_fraction   mandatory_bytes over kernel_ms, as a fraction of HBM_PEAK (8 TB/s)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
+
+from train_time import median_ms, run_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(128, 50, 512), (128, 200, 1024), (3000, 32, 512)]
@@ -53,23 +53,6 @@ def _grads(x, keep, w, b, gw, dV, mul, dtype, device):
 
 def _rel(got, ref):
     return float((got.double() - ref).abs().max() / ref.abs().max())
-
-
-def _median_ms(fn, iters):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(5):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / iters)
-    return sorted(out)[2]
 
 
 def child(iters):
@@ -130,8 +113,8 @@ def child(iters):
         mandatory = int((2 * lens.sum().item() * d + B * d) * 4)
         for k in COUNTS:
             raw, wsp = raw_call(k)
-            kernel_ms = _median_ms(raw, iters)
-            op_ms = _median_ms(lambda: ops.frame_fuse_backward(xs[:k], lens, list(zip(ws, bs, gws))[:k], flags, dVs[:k]), iters)
+            kernel_ms = median_ms(raw, iters)
+            op_ms = median_ms(lambda: ops.frame_fuse_backward(xs[:k], lens, list(zip(ws, bs, gws))[:k], flags, dVs[:k]), iters)
             leaves = [(xs[i].clone().requires_grad_(True), ws[i].clone().requires_grad_(True), bs[i].clone().requires_grad_(True))
                       for i in range(k)]
             Vs = [_torch_block(x, keep, w, b, gws[i], mul) for i, (x, w, b) in enumerate(leaves)]
@@ -139,9 +122,9 @@ def child(iters):
             def torch_bwd():
                 for i in range(k):
                     torch.autograd.grad(Vs[i], list(leaves[i]), dVs[i], retain_graph=True)
-            torch_bwd_ms = _median_ms(torch_bwd, max(iters // 4, 2))
+            torch_bwd_ms = median_ms(torch_bwd, max(iters // 4, 2))
             with torch.no_grad():
-                torch_fwd_ms = _median_ms(lambda: [_torch_block(x, keep, w, b, gws[i], mul) for i, (x, w, b) in enumerate(leaves)],
+                torch_fwd_ms = median_ms(lambda: [_torch_block(x, keep, w, b, gws[i], mul) for i, (x, w, b) in enumerate(leaves)],
                                           max(iters // 4, 2))
             print(json.dumps({'shape': [B, Fmax, d], 'mul': bool(mul), 'count': k, 'kernel_ms': round(kernel_ms, 4),
                               'op_ms': round(op_ms, 4), 'torch_bwd_ms': round(torch_bwd_ms, 4), 'torch_fwd_ms': round(torch_fwd_ms, 4),
@@ -154,17 +137,5 @@ def child(iters):
     return status
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--timeout', type=int, default=400)
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
-    if a.child:
-        return child(a.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--iters', str(a.iters)], timeout=a.timeout)
-    return r.returncode
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(run_child(child, 20, default_timeout=400))

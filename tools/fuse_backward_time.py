@@ -15,12 +15,12 @@ after a warm-up, the median of 5 such windows.  Per shape (N, L, H, d) one JSON 
 Before torch is timed, dx and dw of the kernel are compared with torch's; a difference above AGREE of the largest entry ends the run with
 exit status 1 and no timing line for that shape.
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
+
+from train_time import median_ms, run_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(8192, 4, 8, 512), (8192, 4, 1, 512)]
@@ -35,23 +35,6 @@ def _torch_block(x, w, b, gw, L):
     a = (c * w[None, None]).sum(3).add(b[None, None]).softmax(1)                 # (N, L, H)
     g = (a[..., None] * x).sum(1) + gw[None, :, None] * s
     return g / (g.pow(2).sum(2, keepdim=True).sqrt() + 1e-14)
-
-
-def _median_ms(fn, iters):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(5):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / iters)
-    return sorted(out)[2]
 
 
 def child(iters):
@@ -80,8 +63,8 @@ def child(iters):
         ld = (C.c_int * L)(*[L * H * d] * L)
         raw = lambda: ops.check(lib.laff_fuse_backward(ctx, xp, ld, L, N, H, d, ops._ptr(w), ops._ptr(b), ops._ptr(gw), flags, ops._ptr(dE),
                                                        H * d, dp, ld, ops._ptr(dw), ops._ptr(db), ops._ptr(ws), nbytes))      # noqa: E731
-        kernel_ms = _median_ms(raw, iters)
-        op_ms = _median_ms(lambda: ops.fuse_backward(planes, H, d, w, b, gw, flags, dE, out=out), iters)
+        kernel_ms = median_ms(raw, iters)
+        op_ms = median_ms(lambda: ops.fuse_backward(planes, H, d, w, b, gw, flags, dE, out=out), iters)
         # the same numbers from both sides, before any is trusted
         raw()
         xt, wt, bt = x.view(N, L, H, d).clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
@@ -92,9 +75,9 @@ def child(iters):
             print('laff_fuse_backward and torch autograd differ by %.3g (relative to the largest entry) at %s: nothing is timed'
                   % (agree, (N, L, H, d)), file=sys.stderr)
             return 1
-        torch_bwd_ms = _median_ms(lambda: torch.autograd.grad(E, [xt, wt, bt], dE, retain_graph=True), max(iters // 4, 2))
+        torch_bwd_ms = median_ms(lambda: torch.autograd.grad(E, [xt, wt, bt], dE, retain_graph=True), max(iters // 4, 2))
         with torch.no_grad():
-            torch_fwd_ms = _median_ms(lambda: _torch_block(xt, wt, bt, gw, L), max(iters // 4, 2))
+            torch_fwd_ms = median_ms(lambda: _torch_block(xt, wt, bt, gw, L), max(iters // 4, 2))
         nbytes = (2 * L + 1) * N * H * d * 4
         print(json.dumps({'shape': [N, L, H, d], 'kernel_ms': round(kernel_ms, 4), 'torch_bwd_ms': round(torch_bwd_ms, 4),
                           'torch_fwd_ms': round(torch_fwd_ms, 4), 'op_ms': round(op_ms, 4), 'ratio': round(torch_bwd_ms / kernel_ms, 2),
@@ -104,17 +87,5 @@ def child(iters):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--timeout', type=int, default=240)
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
-    if a.child:
-        return child(a.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--iters', str(a.iters)], timeout=a.timeout)
-    return r.returncode
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(run_child(child, 20))

@@ -16,32 +16,15 @@ Before anything is timed the kernel is held to the rule of tests/test_gpu_gru_ba
 for the output and every gradient tensor, max |device - f64| / max |f64| <= max(4 x the float32 CPU graph's error, 1.5e-6).  A miss
 ends the run with exit status 1 and no timing line.
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
+
+from train_time import median_ms, run_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, H, WE, V = 128, 1024, 500, 11286
 TOL_UNIT = 1.5e-6
-
-
-def _median_ms(fn, iters):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(5):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / iters)
-    return sorted(out)[2]
 
 
 def child(iters):
@@ -87,8 +70,8 @@ def child(iters):
             return 1
         line = {'net': net, 'N': N, 'H': H, 'we_dim': WE, 'V': V, 'tokens': int(sum(hb.batch_sizes)), 'T': len(hb.batch_sizes),
                 'largest_used_fraction_of_bound': round(max(used.values()), 3)}
-        line['ours_ms'] = round(_median_ms(ours, iters), 4)
-        line['ours_fwd_ms'] = round(_median_ms(lambda: enc.encode_batch(b), iters), 4)
+        line['ours_ms'] = round(median_ms(ours, iters), 4)
+        line['ours_fwd_ms'] = round(median_ms(lambda: enc.encode_batch(b), iters), 4)
         # the same step through torch on the device
         try:
             we = torch.nn.Embedding(V, WE).cuda()
@@ -114,7 +97,7 @@ def child(iters):
             theirs()
             torch.cuda.synchronize()
             line['max_abs_diff_dW_hh_vs_torch'] = float((rnn.weight_hh_l0.grad - enc.rnn.weight_hh_l0.grad).abs().max())
-            line['torch_ms'] = round(_median_ms(theirs, iters), 4)
+            line['torch_ms'] = round(median_ms(theirs, iters), 4)
             line['ratio'] = round(line['torch_ms'] / line['ours_ms'], 2)
         except RuntimeError as e:                       # MIOpen refuses some batch shapes outright
             line['torch_refused'] = str(e).splitlines()[0][:200]
@@ -122,17 +105,5 @@ def child(iters):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--timeout', type=int, default=240)
-    ap.add_argument('--iters', type=int, default=10)
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
-    if a.child:
-        return child(a.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--iters', str(a.iters)], timeout=a.timeout)
-    return r.returncode
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(run_child(child, 10))

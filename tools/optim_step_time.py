@@ -15,12 +15,11 @@ Before anything is timed one step of each is compared from equal state: the floa
 step's parameters have to stay within the whole-step bound of tests/test_gpu_optim.py (test_state_dict_moves_to_torch_on_the_device);
 the two fp32 results may then differ by four of them.  A miss ends the run with exit status 1 and no timing line for that set.
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
-import time
+
+from train_time import median_ms, run_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HBM_PEAK = 8.0e12
@@ -38,25 +37,6 @@ def laff_set(dk):
 
 
 SETS = [('LAFF Dk=512', laff_set(512)), ('LAFF Dk=2048', laff_set(2048)), ('small 8 x (512, 512)', [s for _ in range(8) for s in ((512, 512), (512,))])]
-
-
-def _median_ms(fn, iters):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    dev, wall = [], []
-    for _ in range(5):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        w0 = time.perf_counter()
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        wall.append((time.perf_counter() - w0) * 1e3 / iters)
-        dev.append(t0.elapsed_time(t1) / iters)
-    return sorted(dev)[2], sorted(wall)[2]
 
 
 def _gate(kind, params, grads, make_mine, make_torch):
@@ -132,7 +112,7 @@ def child(iters):
                     if clip:
                         torch.nn.utils.clip_grad_norm_(ps, 2.0)
                     opt.step()
-                return _median_ms(step, iters)
+                return median_ms(step, iters, wall=True)
             row['fused_ms'], row['fused_wall_ms'] = run(lambda ps: getattr(optim, cls)(ps, grad_clip=2.0, **kw), False)
             row['torch_foreach_ms'], row['torch_foreach_wall_ms'] = run(lambda ps: getattr(torch.optim, cls)(ps, **kw), True)
             try:
@@ -147,17 +127,5 @@ def child(iters):
     return rc
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--timeout', type=int, default=240)
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
-    if a.child:
-        return child(a.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--iters', str(a.iters)], timeout=a.timeout)
-    return r.returncode
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(run_child(child, 20))
