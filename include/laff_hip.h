@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 39
+#define LAFF_ABI_VERSION 40
 
 enum {
     LAFF_OK = 0,
@@ -573,6 +573,22 @@ int laff_fc_backward_plan(int N, int Dk, int D, int want_dx, int want_dw, int ou
 int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, const float* W, int ldw, int D, int act /*LAFF_ACT_*/,
                      const float* A, int lda, const float* dA, int ldda, float* dX, int lddx, float* dW, int lddw, float* db,
                      void* workspace, size_t workspace_bytes);
+
+/* Backward of the same projection for a SPARSE X [N, Dk] (the bag-of-words; forward laff_fc_gather_act_bn without a BatchNorm stage, or
+ * a CSR segment of laff_fc_concat_act_bn).  A [N, lda >= D] is the SAVED forward output, dA [N, ldda >= D] its gradient, dZ as above:
+ *   dW [D, lddw >= Dk]:  dW[d, v] = sum over the entries (n, v) of X of x[n, v] dZ[n, d]      (W's own layout, not the transposed one)
+ *   db [D]             = sum_n dZ[n, :]                                                        (there is no dX: counts)
+ * X comes in TRANSPOSED (CSC): colptr [Dk + 1] and rows [nnz] int32, values [nnz] fp32 or NULL for all ones; column v owns the entries
+ * [colptr[v], colptr[v + 1]), in ascending row order.  A repeated row index inside a column adds up; an entry whose row lies outside
+ * [0, N) contributes nothing; entries outside every column's range are never read.  D % 4 == 0, 4 <= D <= 8192; A and dA 16-byte aligned
+ * with lda % 4 == ldda % 4 == 0; dW and db 4-byte aligned, any lddw >= Dk.  Either output may be NULL.  The one launch writes EVERY
+ * element of the window [D, Dk] of dW and only those (+0.0 in a column without entries; no memset in front), so a call can fill a
+ * column window at any offset of a wider gradient.  dW's base and pitch 16-byte aligned and Dk % 4 == 0: 16-byte stores, else 4-byte
+ * ones, same bits.  Every element of dW is one fmaf chain over its column's entries in their order, db is summed in an order fixed by
+ * N: no atomics, two calls give the same bits.  N == 0 or nnz == 0: dW is set to zero and the pattern is not read (db is zero for
+ * N == 0, the sum otherwise).  No workspace, no allocation, no host synchronisation; ordered on the ctx's stream, capturable. */
+int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, const float* values, int nnz, int N, int Dk, int D,
+                            int act /*LAFF_ACT_*/, const float* A, int lda, const float* dA, int ldda, float* dW, int lddw, float* db);
 
 /* The optimizer step: the global L2 norm of a list of gradients, the clip by it, and Adam / RMSprop with that clip folded in.
  * A tensor list is `count` flat fp32 device tensors of n[i] >= 0 elements, each base 4-byte aligned (nothing stronger is assumed; a

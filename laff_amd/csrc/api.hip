@@ -1992,6 +1992,38 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
     return LAFF_OK;
 }
 
+int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, const float* values, int nnz, int N, int Dk, int D, int act,
+                            const float* A, int lda, const float* dA, int ldda, float* dW, int lddw, float* db) {
+    CHECK_CTX(ctx);
+    const char* fn = "laff_fc_gather_backward";
+    if (N < 0 || nnz < 0 || Dk < 1 || D < 4 || (D & 3) || D > 8192)
+        return fail(LAFF_E_SHAPE, "%s: need N>=0, nnz>=0, Dk>=1, D%%4==0, 4<=D<=8192 (N=%d nnz=%d Dk=%d D=%d)", fn, N, nnz, Dk, D);
+    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", fn, act);
+    if (dW && lddw < Dk) return fail(LAFF_E_SHAPE, "%s: lddw=%d < Dk=%d", fn, lddw, Dk);
+    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
+    if (!aligned4(dW) || !aligned4(db)) return fail(LAFF_E_ALIGN, "%s: dW / db must be 4-byte aligned", fn);
+    if (!dW && !db) return LAFF_OK;
+    const bool walk = dW && N > 0 && nnz > 0;    /* otherwise dW is the empty sum: zeros, and the pattern is not read */
+    if (walk && (!colptr || !rows)) return fail(LAFF_E_ARG, "%s: null colptr / rows", fn);
+    if (N > 0) {
+        if (!A || !dA) return fail(LAFF_E_ARG, "%s: null A / dA", fn);
+        if (lda < D || ldda < D || (lda & 3) || (ldda & 3))
+            return fail(LAFF_E_SHAPE, "%s: lda=%d and ldda=%d must be multiples of 4 and at least D=%d", fn, lda, ldda, D);
+        if (!aligned16(A) || !aligned16(dA)) return fail(LAFF_E_ALIGN, "%s: A / dA must be 16-byte aligned", fn);
+    }
+    DeviceGuard g(ctx->device);
+    if (dW && !walk) HIP_TRY(hipMemset2DAsync(dW, (size_t)lddw * sizeof(float), 0, (size_t)Dk * sizeof(float), D, ctx->stream));
+    if (N == 0) {
+        if (db) HIP_TRY(hipMemsetAsync(db, 0, (size_t)D * sizeof(float), ctx->stream));
+        return LAFF_OK;
+    }
+    laff::FcGatherBwdArgs a{};
+    a.colptr = colptr; a.rows = rows; a.values = values; a.A = A; a.dA = dA; a.dW = walk ? dW : nullptr; a.db = db;
+    a.nnz = nnz; a.N = N; a.Dk = Dk; a.D = D; a.lda = lda; a.ldda = ldda; a.lddw = lddw; a.act = act;
+    HIP_TRY(laff::launch_fc_gather_backward(a, ctx->stream));
+    return LAFF_OK;
+}
+
 static_assert(sizeof(laff_optim_tensor) == 40, "laff_optim_tensor is five 8-byte words (laff_amd/ops.py fills the host array as such)");
 
 /* the launches of the calling thread's last optimizer call, by variant */

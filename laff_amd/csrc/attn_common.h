@@ -58,12 +58,14 @@ __device__ __forceinline__ void softmax_bwd_L(const float (&a)[L], float (&da)[L
 // and threads 0..7 add the 32 group sums in group order.  (One thread per column walking all rows was a chain of rows / 8 round trips
 // on two to sixteen workgroups.)  `rows` points at the lane's four columns of the first row; a lane without columns passes rows = 0.
 // The whole block calls this (it holds a barrier); the sum is returned in the threads of group 0.
+// sum_rows_fixed_order_of is the same sum over rows that are formed on the way: row(r) gives the lane's four columns of row r.
 constexpr int DW_GROUPS = 32, DW_LANES = 8;
-__device__ __forceinline__ float4 sum_rows_fixed_order(const float* rows, int nrows, long pitch, float4 (&sh)[DW_GROUPS][DW_LANES]) {
+template <class Row>
+__device__ __forceinline__ float4 sum_rows_fixed_order_of(Row row, int nrows, float4 (&sh)[DW_GROUPS][DW_LANES]) {
     const int ln = threadIdx.x & (DW_LANES - 1), grp = threadIdx.x / DW_LANES;
     float4 acc = zero4();
 #pragma unroll 8
-    for (int r = grp; r < nrows; r += DW_GROUPS) acc = add4(acc, *(const float4*)(rows + (long)r * pitch));
+    for (int r = grp; r < nrows; r += DW_GROUPS) acc = add4(acc, row(r));
     sh[grp][ln] = acc;
     __syncthreads();
     float4 t = sh[0][ln];
@@ -72,6 +74,9 @@ __device__ __forceinline__ float4 sum_rows_fixed_order(const float* rows, int nr
         for (int k = 1; k < DW_GROUPS; ++k) t = add4(t, sh[k][ln]);
     }
     return t;
+}
+__device__ __forceinline__ float4 sum_rows_fixed_order(const float* rows, int nrows, long pitch, float4 (&sh)[DW_GROUPS][DW_LANES]) {
+    return sum_rows_fixed_order_of([=](int r) { return *(const float4*)(rows + (long)r * pitch); }, nrows, sh);
 }
 
 }  // namespace laff

@@ -28,6 +28,7 @@
 
 #include <algorithm>
 
+#include "fc_bwd_common.h"
 #include "kernels.h"
 
 namespace laff {
@@ -38,15 +39,6 @@ constexpr int KT = 32, THREADS = 256, SPLIT_LEN = 128, FILL_64 = 512, FILL_128 =
 
 typedef float bw_f32x4 __attribute__((ext_vector_type(4)));
 typedef float bw_f32x16 __attribute__((ext_vector_type(16)));
-
-// dz = da * act'(a) from the forward's output a; at most three roundings, and dact(0, 0) = 0 for every activation
-template <int ACT>
-__device__ __forceinline__ float dact(float a, float g) {
-    if constexpr (ACT == LAFF_ACT_TANH) return g * fmaf(-a, a, 1.0f);
-    else if constexpr (ACT == LAFF_ACT_SIGMOID) return g * (a * (1.0f - a));
-    else if constexpr (ACT == LAFF_ACT_RELU) return a > 0.0f ? g : 0.0f;
-    else return g;
-}
 
 // the G groups of a thread at once: one switch per step, not one per element
 template <int ACT, int G>

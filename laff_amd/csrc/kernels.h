@@ -273,6 +273,19 @@ struct FcBwdPlan {
 void fc_bwd_plan(int N, int Dk, int D, FcBwdPlan* p);
 hipError_t launch_fc_backward(const FcBwdArgs& a, hipStream_t st);
 
+// fc_gather_bwd.hip: backward of the FC projection of a sparse X, given transposed (CSC) (laff_fc_gather_backward)
+struct FcGatherBwdArgs {
+    const int* colptr;        // [Dk + 1]; column v owns the entries [colptr[v], colptr[v + 1]), ascending row order
+    const int* rows;          // [nnz] row index of an entry; one outside [0, N) contributes nothing
+    const float* values;      // [nnz] or null (all ones)
+    const float* A;           // [N, lda >= D]    the saved forward output, rows 16-byte aligned
+    const float* dA;          // [N, ldda >= D]   rows 16-byte aligned
+    float* dW;                // [D, lddw >= Dk] or null; every element of the window is written
+    float* db;                // [D] or null
+    int nnz, N, Dk, D, lda, ldda, lddw, act;
+};
+hipError_t launch_fc_gather_backward(const FcGatherBwdArgs& a, hipStream_t st);
+
 // optim.hip: global-norm clipping and the Adam / RMSprop step over a list of flat fp32 tensors (laff_grad_sqnorm, laff_grad_scale,
 // laff_optim_step)
 constexpr int OPTIM_CHUNK = 4096;        // elements of one chunk: 256 threads x 4 accesses of 16 bytes

@@ -15,7 +15,9 @@ as /root/reference/model/model.py for the symbols on the hot path (SURVEY.md sec
   get_model                            :2501-2519
 
 The towers are inference only: their training-mode forward raises.  A single TransformNet is differentiable in .train() mode
-(_FcActFn: laff_fc_act_bn forward, laff_fc_backward behind it), as the fusion blocks are (section 4.19).
+(_FcActFn: laff_fc_act_bn forward, laff_fc_backward behind it; a device CSR input through _FcGatherFn and
+laff_fc_gather_backward, a concat layer through TransformNet.concat_train and _FcConcatFn; section 4.24), as the fusion blocks are
+(section 4.19).
 Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: features arrive pre-extracted in
 `caption_feat_dict` (the reference already does this for frozen CLIP via 'CLIP_encoding', :497-498); any module
 returning {'text_features': tensor} can be plugged into `txt_net.encoder.<name>`.
@@ -208,6 +210,103 @@ class _FcActFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+def _fp32_params(weight, bias):
+    for t, nm in ((weight, 'fc1.weight'), (bias, 'fc1.bias')):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError('the differentiable projection is fp32 only, %s is %s' % (nm, t.dtype))
+
+
+def _csc_of(x):
+    """The transposed pattern of a device CSR input: the one its encoder attached (txt2vec.BoWTxtEncoder(with_csc=True)), else
+    transposed on the device now (a stable sort, no host synchronisation)."""
+    csc = getattr(x, 'laff_csc', None)
+    return tuple(csc) if csc is not None else ops.csr_transpose(x)
+
+
+class _FcGatherFn(torch.autograd.Function):
+    """a = act(x @ weight.T + bias) for a device torch.sparse_csr x: laff_fc_gather_act_bn on the layer's cached weight_t() forward,
+    ops.fc_gather_backward behind it.  Saves the transposed pattern (CSC) and the output a; dw comes back in weight's own shape,
+    contiguous, so that laff_amd.optim steps it as it is; db only where needs_input_grad asks for it; x gets no gradient (counts).
+    The forward keeps the kernel's fused activation: its output met the training tests' rule with room.
+    Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, weight_t, activation):
+        _fp32_params(weight, bias)
+        a = ops.fc_gather_act_bn(x, weight_t, None if bias is None else bias.detach(), None, None, activation)
+        ctx.save_for_backward(a, *_csc_of(x))
+        ctx.activation, ctx.has_bias, ctx.x_shape = activation, bias is not None, tuple(x.shape)
+        return a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_a):
+        a, colptr, rows, values = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dw, db = ops.fc_gather_backward((colptr, rows, values), ctx.x_shape[0], ctx.x_shape[1], a, grad_a, ctx.activation,
+                                        want_dw=need[1], want_db=ctx.has_bias and need[2])
+        return None, dw, db, None, None
+
+
+class _FcConcatFn(torch.autograd.Function):
+    """a = act(sum_s x_s @ weight[:, c_s : c_s + w_s].T + bias) over dense device fp32 segments and / or device torch.sparse_csr ones:
+    the one laff_fc_concat_act_bn launch forward (no BatchNorm stage), and behind it one call per segment on the column windows of
+    weight and of ONE (D, K) gradient buffer -- pitched views, no copies: ops.fc_backward for a dense segment (dx only where that
+    segment needs a gradient), ops.fc_gather_backward for a CSR one.  The windows cover dw, so nothing is zero-filled.  db is formed
+    exactly once, by the FIRST segment's call.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, layer, activation, weight, bias, *segments):
+        _fp32_params(weight, bias)
+        segs, wt, kinds, saved, col = [], {}, [], [], 0
+        for j, x in enumerate(segments):
+            width = x.shape[1]
+            if x.layout == torch.sparse_csr:
+                wt[j] = layer.weight_t_block(col, width)
+                kinds.append(('csr', tuple(x.shape)))
+                saved += list(_csc_of(x))
+            else:
+                if x.dtype != torch.float32:
+                    raise TypeError('the differentiable projection is fp32 only, segment %d is %s' % (j, x.dtype))
+                x = x.detach()
+                if x.dim() == 2 and x.numel() and x.stride(1) != 1:
+                    x = x.contiguous()
+                kinds.append(('dense', None))
+                saved.append(x)
+            segs.append(x)
+            col += width
+        a = ops.fc_concat_act_bn(segs, weight.detach(), None if bias is None else bias.detach(), None, None, activation, weight_t=wt)
+        ctx.save_for_backward(weight, a, *saved)
+        ctx.activation, ctx.has_bias, ctx.kinds = activation, bias is not None, kinds
+        return a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_a):
+        weight, a, *saved = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        w = weight.detach()
+        dw = torch.empty_like(w, memory_format=torch.contiguous_format) if need[2] else None
+        db = torch.empty((w.shape[0],), device=w.device, dtype=torch.float32) if ctx.has_bias and need[3] else None
+        dxs, col, at = [], 0, 0
+        for j, (kind, shape) in enumerate(ctx.kinds):
+            first_db = db if j == 0 else None
+            if kind == 'csr':
+                csc, at, width = tuple(saved[at:at + 3]), at + 3, shape[1]
+                ops.fc_gather_backward(csc, shape[0], width, a, grad_a, ctx.activation, want_dw=dw is not None,
+                                       want_db=first_db is not None, out=(None if dw is None else dw[:, col:col + width], first_db))
+                dxs.append(None)
+            else:
+                x, at = saved[at], at + 1
+                width = x.shape[1]
+                dx = ops.fc_backward(x, w[:, col:col + width], a, grad_a, ctx.activation, want_dx=need[4 + j], want_dw=dw is not None,
+                                     want_db=first_db is not None,
+                                     out=(None, None if dw is None else dw[:, col:col + width], first_db))[0]
+                dxs.append(dx)
+            col += width
+        return (None, None, dw, db) + tuple(dxs)
+
+
 class TransformNet(nn.Module):
     """fc -> activation -> dropout (identity in eval) -> BatchNorm1d, as one GEMM with a fused epilogue."""
 
@@ -320,15 +419,40 @@ class TransformNet(nn.Module):
         if self.fc1 is None:
             raise NotImplementedError('training mode: a TransformNet without fc (fc=False%s) has no differentiable path; apply its '
                                       'BatchNorm upstream as a torch op' % (', tiled over %d heads' % heads if heads > 1 else ''))
-        if x.layout != torch.strided:
-            raise NotImplementedError('training mode: a sparse (CSR) input has no backward (laff_fc_gather_act_bn is inference only)')
+        if x.layout != torch.strided and not (x.layout == torch.sparse_csr and x.is_cuda):
+            raise NotImplementedError('training mode: a sparse (CSR) input is projected on the device only (laff_fc_gather_act_bn and '
+                                      'laff_fc_gather_backward have no CPU path): move it to the device first')
         if extra_shift is not None:
             raise NotImplementedError('training mode: extra_shift (the expert embedding) is not differentiable here; add it upstream '
                                       'as a torch op')
-        y = _FcActFn.apply(x, self.fc1.weight, self.fc1.bias, self.activation_name)
+        if x.layout == torch.sparse_csr:
+            y = _FcGatherFn.apply(x, self.fc1.weight, self.fc1.bias, self.weight_t(), self.activation_name)
+        else:
+            y = _FcActFn.apply(x, self.fc1.weight, self.fc1.bias, self.activation_name)
+        return self._after_activation_train(y)
+
+    def _after_activation_train(self, y):
         if self.dropout_p is not None:
             y = F.dropout(y, self.dropout_p, training=True)
         return y if self.bn1 is None else self.bn1(y)
+
+    def concat_train(self, segments):
+        """Training mode: this layer applied to torch.cat(segments, dim=1) without forming it, under autograd (_FcConcatFn), then
+        torch's dropout and training-mode BatchNorm1d as in _forward_train.  segments: dense fp32 device matrices and / or device
+        torch.sparse_csr ones, in column order; a dense segment that requires a gradient receives one.  concat_problem stays the
+        inference path."""
+        if not self.training:
+            raise RuntimeError('concat_train is the training-mode path; in eval mode use concat_problem')
+        if self.fc1 is None:
+            raise NotImplementedError('training mode: a TransformNet without fc (fc=False) has no differentiable path')
+        segments = list(segments)
+        for j, x in enumerate(segments):
+            if not x.is_cuda or x.layout not in (torch.strided, torch.sparse_csr) or x.dim() != 2:
+                raise NotImplementedError('training mode: segment %d must be a 2-D dense or sparse (CSR) matrix on the device' % j)
+        col = sum(x.shape[1] for x in segments)
+        if col != self.fc1.in_features:
+            raise ValueError('the concatenated input has %d columns, fc1 takes %d' % (col, self.fc1.in_features))
+        return self._after_activation_train(_FcConcatFn.apply(self, self.activation_name, self.fc1.weight, self.fc1.bias, *segments))
 
     def plane(self, x, heads=1, extra_shift=None, pending=None, head_dim=None):
         """(src, tile, scale, shift) for laff_fuse.  With an FC the projection either runs now or, when `pending`

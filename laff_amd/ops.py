@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1195,6 +1195,81 @@ def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, wa
     _call('fc_backward', lib.laff_fc_backward, h, _ptr(x), N, Dk, ldx, _ptr(w), ldw, D, ACT[activation], _ptr(a), lda, _ptr(g), ldg,
           pdx, lddx, pdw, lddw, _ptr(db), _ptr(ws), nbytes)
     return dx, dw, db
+
+
+def csr_transpose(x_csr):
+    """The pattern of a torch.sparse_csr matrix (N, Dk) transposed, as laff_fc_gather_backward reads it: (colptr [Dk + 1] int32,
+    rows [nnz] int32, values [nnz] fp32) on the CSR's device.  Column v owns the entries [colptr[v], colptr[v + 1]), in the order the
+    CSR holds them (ascending row; a word that a row names twice stays twice).  The entries are sorted by column id with a stable sort
+    and colptr is searchsorted(sorted ids, arange(Dk + 1)): ids outside [0, Dk) stay in rows / values but lie in front of colptr[0] or
+    behind colptr[Dk], in no column's range -- dropped, as the forward ignores them, without a data-dependent size.  A host CSR is
+    transposed with numpy, a device CSR with torch ops and no host synchronisation."""
+    if x_csr.layout != torch.sparse_csr or x_csr.dim() != 2:
+        raise ValueError('x_csr must be a 2-D torch.sparse_csr tensor')
+    N, Dk = x_csr.shape
+    crow, col, val = x_csr.crow_indices(), x_csr.col_indices(), x_csr.values()
+    nnz = col.numel()
+    if not x_csr.is_cuda:
+        col = col.numpy().astype(np.int64)
+        row = np.repeat(np.arange(N, dtype=np.int32), np.diff(crow.numpy().astype(np.int64)))
+        order = np.argsort(col, kind='stable')
+        colptr = np.searchsorted(col[order], np.arange(Dk + 1), side='left').astype(np.int32)
+        return (torch.from_numpy(colptr), torch.from_numpy(row[order]),
+                torch.from_numpy(np.ascontiguousarray(val.numpy().astype(np.float32)[order])))
+    dev = col.device
+    # the row of entry j: the last r with crow[r] <= j
+    row = torch.searchsorted(crow.to(torch.int64), torch.arange(nnz, device=dev), right=True) - 1
+    scol, order = torch.sort(col.to(torch.int64), stable=True)
+    colptr = torch.searchsorted(scol, torch.arange(Dk + 1, device=dev), right=False).to(torch.int32)
+    return colptr, row[order].to(torch.int32), val.to(torch.float32)[order].contiguous()
+
+
+def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=True, out=None):
+    """Backward of a = act(x @ weight.T + bias) for a sparse x (N, Dk) (laff_fc_gather_backward): csc = (colptr, rows, values) as
+    csr_transpose returns them (values may be None: all ones), a (N, D) the saved forward output, grad_a (N, D) its gradient; device
+    fp32, row views whose rows are 16-byte aligned (base and pitch) are read in place, anything else is made dense first.
+    Returns (dw (D, Dk) | None, db (D,) | None); dw is in weight's own layout.  out: a (dw, db) pair of fp32 buffers (None entries are
+    allocated here; dw may be a row view with any pitch and any 4-byte aligned base, e.g. a column window of a wider gradient -- every
+    element of the window is written and nothing else; db is contiguous)."""
+    if activation not in ACT:
+        raise ValueError('unknown activation %r' % (activation,))
+    colptr, rows, values = csc
+    N, Dk = int(N), int(Dk)
+    for t, nm in ((colptr, 'colptr'), (rows, 'rows')):
+        _dev(t, nm, torch.int32)
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous vector' % nm)
+    nnz = rows.numel()
+    if colptr.numel() != Dk + 1:
+        raise ValueError('colptr has %d entries, expected Dk + 1 = %d' % (colptr.numel(), Dk + 1))
+    if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
+        raise ValueError('values must be a contiguous vector of %d' % nnz)
+    mats = []
+    for t, nm in ((a, 'a'), (grad_a, 'grad_a')):
+        _dev(t, nm)
+        if t.dim() != 2:
+            raise ValueError('%s must be 2-D, got shape %s' % (nm, tuple(t.shape)))
+        if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 4)) or t.data_ptr() % 16):
+            t = t.contiguous()
+        mats.append(_rows(t, nm))
+    (a, lda), (g, ldg) = mats
+    D, dev = a.shape[1], a.device
+    lda, ldg = (lda + 3) // 4 * 4, (ldg + 3) // 4 * 4          # a single row: no pitch of its own
+    if a.shape[0] != N or tuple(g.shape) != (N, D):
+        raise ValueError('a %s and grad_a %s do not fit N = %d' % (tuple(a.shape), tuple(g.shape), N))
+    odw, odb = out if out is not None else (None, None)
+    dw, pdw, lddw = _out_rows(odw, (D, Dk), dev, 'out dw') if want_dw else (None, None, 0)
+    db = None
+    if want_db:
+        db = torch.empty((D,), device=dev, dtype=torch.float32) if odb is None else _dev(odb, 'out db')
+        if tuple(db.shape) != (D,) or not db.is_contiguous():
+            raise ValueError('out db must be a contiguous vector of %d' % D)
+    if not (want_dw or want_db):
+        return None, None
+    lib, h = _context(dev)
+    _call('fc_gather_backward', lib.laff_fc_gather_backward, h, _ptr(colptr), _ptr(rows), _ptr(values), nnz, N, Dk, D, ACT[activation],
+          _ptr(a), lda, _ptr(g), ldg, pdw, lddw, _ptr(db))
+    return dw, db
 
 
 def optim_plan(sizes):

@@ -199,14 +199,25 @@ class W2Vec(object):
 
 class BoWTxtEncoder(nn.Module):
     """Drop-in for model.model.BoWTxtEncoder (model/model.py:399-416): `txt_net.encoder.bow_encoder = BoWTxtEncoder(t2v)`.
-    Returns the bag-of-words matrix as CSR; TransformNet projects it with the gather-sum kernel."""
+    Returns the bag-of-words matrix as CSR; TransformNet projects it with the gather-sum kernel.
 
-    def __init__(self, t2v_bow, device='cuda'):
+    with_csc=True: the transposed pattern that the projection's backward reads (ops.csr_transpose) is formed on the host next to the
+    CSR and travels as the attribute `laff_csc` of the returned tensor object: (colptr, rows, values) on the CSR's device.  A training
+    step that hands this very object to TransformNet then needs no device sort.  The attribute belongs to the Python object: any op on
+    the tensor (.to(), indexing, a collate) returns a tensor without it, and the backward transposes on the device instead."""
+
+    def __init__(self, t2v_bow, device='cuda', with_csc=False):
         super().__init__()
-        self.t2v_bow, self.device = t2v_bow, device
+        self.t2v_bow, self.device, self.with_csc = t2v_bow, device, with_csc
 
     def forward(self, caption_feat_dict, task3=False):
-        return {'text_features': self.t2v_bow.csr(caption_feat_dict['caption'], self.device)}
+        if not self.with_csc:
+            return {'text_features': self.t2v_bow.csr(caption_feat_dict['caption'], self.device)}
+        from . import ops
+        host = self.t2v_bow.csr(caption_feat_dict['caption'], 'cpu')
+        x = host.to(self.device)
+        x.laff_csc = tuple(t.to(self.device) for t in ops.csr_transpose(host))
+        return {'text_features': x}
 
 
 class W2VTxtEncoder(nn.Module):
