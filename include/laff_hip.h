@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 40
+#define LAFF_ABI_VERSION 41
 
 enum {
     LAFF_OK = 0,
@@ -589,6 +589,43 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
  * N == 0, the sum otherwise).  No workspace, no allocation, no host synchronisation; ordered on the ctx's stream, capturable. */
 int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, const float* values, int nnz, int N, int Dk, int D,
                             int act /*LAFF_ACT_*/, const float* A, int lda, const float* dA, int ldda, float* dW, int lddw, float* db);
+
+/* The stage between a projection's activation and its output in training mode (model/model.py:236-243 under .train()): dropout by a
+ * counter-based mask, then BatchNorm1d on the batch's statistics; fp32.  A [N, lda >= D] is the activation output.
+ *   m[n,c]  = keep(seed, n, c) / (1 - p)     (1 when p == 0: no generator call, seed may be NULL);   U = A (.) m
+ *   mean[c] = sum_n U / N      var[c] = sum_n (U - mean)^2 / N (biased)      invstd = 1 / sqrt(var + eps)
+ *   Y [N, ldy >= D] = gamma (U - mean) invstd + beta;     save_mean [D] = mean, save_invstd [D] = invstd
+ *   running_mean = (1 - momentum) running_mean + momentum mean;   running_var likewise with var N / (N - 1); both updated in place
+ * gamma == NULL: no BatchNorm stage, Y = U, no statistics are formed, none of beta / running_* / save_* is read or written.
+ * The mask: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (c >> 2, n, 0, 0); element (n, c) takes output word c & 3 and
+ * is kept iff word >= (uint32) floor(p * 4294967296.0).  One round: (hi0, lo0) = mulhilo32(0xD2511F53, c0), (hi1, lo1) =
+ * mulhilo32(0xCD9E8D57, c2), c = (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0), then k0 += 0x9E3779B9, k1 += 0xBB67AE85; ten rounds.  n and c are
+ * the logical row and column: pitch and base address do not enter.  seed: DEVICE pointer to one 64-bit word, read by the kernels (a
+ * captured call sees whatever the word holds at replay).  A kept element is A * fp32(1 / (1 - p)), a dropped one +0.0.
+ * The variance is the corrected two-pass form on the strip a block keeps in registers; the per-column arithmetic behind the sums runs
+ * in float64 and is rounded to fp32 once (Y is formed from the mean's fp32 head and tail; save_mean is the head).  N <= 256: one launch, A is read once.  Larger N: the rows are cut into chunks of 256, each
+ * chunk's (mean, M2) goes to `workspace` as float64 and a second launch merges them in chunk order and normalises.
+ * Backward: dY [N, lddy >= D], A, p, seed, gamma, save_mean, save_invstd as the forward had and left them; the mask is recomputed.
+ *   xhat = (U - mean) invstd      dbeta [D] = sum_n dY      dgamma [D] = sum_n dY (.) xhat
+ *   dU   = gamma invstd (dY - dbeta / N - xhat dgamma / N)      (dU = dY without a BatchNorm stage)      dA [N, ldda >= D] = dU (.) m
+ * Each of dA, dgamma, dbeta may be NULL (not formed); the others do not change by it.
+ * Any D >= 1 and any pitch >= D; bases 4-byte aligned (seed 8-byte).  Rows on 16-byte boundaries (bases, pitches, D % 4 == 0) take the
+ * kernels with 16-byte accesses, anything else the element-wise ones: same bits.  No atomics: two calls with one seed give the same
+ * bits.  No allocation, no host synchronisation; ordered on the ctx's stream, capturable.  workspace: 16-byte aligned, bytes of the plan.
+ * Refused before any GPU work (a NULL ctx is looked at last): N < 0 or D < 1 (LAFF_E_SHAPE); p outside [0, 1), p > 0 with a NULL
+ * seed, p == 0 with gamma == NULL (nothing to do), N < 2 with a BatchNorm stage (one value per channel has no variance; N == 0
+ * included), eps <= 0, momentum outside [0, 1] (LAFF_E_ARG).  N == 0 without a BatchNorm stage touches nothing.
+ * laff_dropout_bn_train_plan (host only, no ctx): out = {row chunks of the column sums (1 without a BatchNorm stage), workspace bytes,
+ * launches per direction, rows of a chunk}. */
+int laff_dropout_bn_train_plan(int N, int D, int has_bn, int out[4]);
+int laff_dropout_bn_train(laff_ctx* ctx, const float* A, int N, int D, int lda, double p, const unsigned long long* seed /*device*/,
+                          const float* gamma /*[D], nullable*/, const float* beta /*[D]*/, float* running_mean /*[D]*/,
+                          float* running_var /*[D]*/, double momentum, double eps, float* Y, int ldy, float* save_mean /*[D]*/,
+                          float* save_invstd /*[D]*/, void* workspace, size_t workspace_bytes);
+int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, const float* A, int N, int D, int lda, double p,
+                                   const unsigned long long* seed /*device*/, const float* gamma /*[D], nullable*/,
+                                   const float* save_mean /*[D]*/, const float* save_invstd /*[D]*/, float* dA /*nullable*/, int ldda,
+                                   float* dgamma /*[D], nullable*/, float* dbeta /*[D], nullable*/, void* workspace, size_t workspace_bytes);
 
 /* The optimizer step: the global L2 norm of a list of gradients, the clip by it, and Adam / RMSprop with that clip folded in.
  * A tensor list is `count` flat fp32 device tensors of n[i] >= 0 elements, each base 4-byte aligned (nothing stronger is assumed; a

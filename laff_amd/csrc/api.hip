@@ -2024,6 +2024,102 @@ int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, c
     return LAFF_OK;
 }
 
+/* what both directions of the dropout + BatchNorm stage refuse before any GPU work, a null ctx included: the tests need no GPU */
+static int dropout_bn_check(const char* fn, int N, int D, double p, const void* seed, bool has_bn) {
+    if (N < 0 || D < 1) return fail(LAFF_E_SHAPE, "%s: need N>=0, D>=1 (N=%d D=%d)", fn, N, D);
+    if (!(p >= 0.0 && p < 1.0)) return fail(LAFF_E_ARG, "%s: p=%g outside [0, 1)", fn, p);
+    if (p > 0.0 && !seed) return fail(LAFF_E_ARG, "%s: p > 0 needs a seed", fn);
+    if (p == 0.0 && !has_bn) return fail(LAFF_E_ARG, "%s: p == 0 without a BatchNorm stage (null gamma): nothing to do", fn);
+    if (has_bn && N < 2) return fail(LAFF_E_ARG, "%s: batch statistics need N >= 2 rows, got %d", fn, N);
+    if ((N + laff::BN_TRAIN_ROWS - 1) / laff::BN_TRAIN_ROWS > 65535) return fail(LAFF_E_SHAPE, "%s: N=%d beyond 65535 chunks of rows", fn, N);
+    return LAFF_OK;
+}
+
+/* the dropout side of the arguments: thresh = floor(p 2^32) and fp32(1 / (1 - p)), in double on the host */
+static void dropout_bn_mask(laff::BnTrainArgs& a, double p, const unsigned long long* seed) {
+    a.drop = p > 0.0;
+    a.seed = seed;
+    a.thresh = (unsigned)std::floor(p * 4294967296.0);
+    a.scale = (float)(1.0 / (1.0 - p));
+}
+
+int laff_dropout_bn_train_plan(int N, int D, int has_bn, int out[4]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_dropout_bn_train_plan: null out");
+    if (N < 0 || D < 1) return fail(LAFF_E_SHAPE, "laff_dropout_bn_train_plan: need N>=0, D>=1 (N=%d D=%d)", N, D);
+    laff::BnTrainPlan p;
+    laff::bn_train_plan(N, D, has_bn != 0, &p);
+    if (p.ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "laff_dropout_bn_train_plan: workspace of %zu bytes", p.ws);
+    out[0] = p.chunks; out[1] = (int)p.ws; out[2] = p.launches; out[3] = laff::BN_TRAIN_ROWS;
+    return LAFF_OK;
+}
+
+int laff_dropout_bn_train(laff_ctx* ctx, const float* A, int N, int D, int lda, double p, const unsigned long long* seed, const float* gamma,
+                          const float* beta, float* running_mean, float* running_var, double momentum, double eps, float* Y, int ldy,
+                          float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_dropout_bn_train";
+    if (int rc = dropout_bn_check(fn, N, D, p, seed, gamma != nullptr)) return rc;
+    if (gamma) {
+        if (!(eps > 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g must be positive", fn, eps);
+        if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LAFF_E_ARG, "%s: momentum=%g outside [0, 1]", fn, momentum);
+    }
+    CHECK_CTX(ctx);
+    if (N == 0) return LAFF_OK;
+    if (!A || !Y) return fail(LAFF_E_ARG, "%s: null A / Y", fn);
+    if (gamma && (!beta || !running_mean || !running_var || !save_mean || !save_invstd))
+        return fail(LAFF_E_ARG, "%s: a BatchNorm stage needs beta, running_mean, running_var, save_mean and save_invstd", fn);
+    if (lda < D || ldy < D) return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (lda=%d ldy=%d D=%d)", fn, lda, ldy, D);
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+    if (!aligned4(A) || !aligned4(Y) || !aligned4(gamma) || !aligned4(beta) || !aligned4(running_mean) || !aligned4(running_var) ||
+        !aligned4(save_mean) || !aligned4(save_invstd))
+        return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
+    if (reinterpret_cast<uintptr_t>(seed) & 7) return fail(LAFF_E_ALIGN, "%s: seed must be 8-byte aligned", fn);
+    laff::BnTrainPlan plan;
+    laff::bn_train_plan(N, D, gamma != nullptr, &plan);
+    if (plan.ws)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    laff::BnTrainArgs a{};
+    a.A = A; a.out = Y; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var;
+    a.save_mean = save_mean; a.save_invstd = save_invstd; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.N = N; a.D = D; a.lda = lda; a.ldo = ldy; a.momentum = momentum; a.eps = eps;
+    a.fast = aligned16(A) && aligned16(Y) && lda % 4 == 0 && ldy % 4 == 0 && D % 4 == 0;
+    dropout_bn_mask(a, p, seed);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_bn_train_forward(a, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, const float* A, int N, int D, int lda, double p,
+                                   const unsigned long long* seed, const float* gamma, const float* save_mean, const float* save_invstd,
+                                   float* dA, int ldda, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_dropout_bn_train_backward";
+    if (int rc = dropout_bn_check(fn, N, D, p, seed, gamma != nullptr)) return rc;
+    CHECK_CTX(ctx);
+    if (!gamma && (dgamma || dbeta)) return fail(LAFF_E_ARG, "%s: dgamma / dbeta without a BatchNorm stage (null gamma)", fn);
+    if (N == 0 || (!dA && !dgamma && !dbeta)) return LAFF_OK;
+    if (!A || !dY) return fail(LAFF_E_ARG, "%s: null A / dY", fn);
+    if (gamma && (!save_mean || !save_invstd)) return fail(LAFF_E_ARG, "%s: a BatchNorm stage needs save_mean and save_invstd", fn);
+    if (lda < D || lddy < D || (dA && ldda < D))
+        return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (lda=%d lddy=%d ldda=%d D=%d)", fn, lda, lddy, ldda, D);
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+    if (!aligned4(A) || !aligned4(dY) || !aligned4(dA) || !aligned4(gamma) || !aligned4(save_mean) || !aligned4(save_invstd) ||
+        !aligned4(dgamma) || !aligned4(dbeta))
+        return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
+    if (reinterpret_cast<uintptr_t>(seed) & 7) return fail(LAFF_E_ALIGN, "%s: seed must be 8-byte aligned", fn);
+    laff::BnTrainPlan plan;
+    laff::bn_train_plan(N, D, gamma != nullptr, &plan);
+    if (plan.ws)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    laff::BnTrainArgs a{};
+    a.A = A; a.dY = dY; a.out = dA; a.gamma = gamma; a.save_mean = const_cast<float*>(save_mean);
+    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.N = N; a.D = D; a.lda = lda; a.lddy = lddy; a.ldo = ldda;
+    a.fast = aligned16(A) && aligned16(dY) && lda % 4 == 0 && lddy % 4 == 0 && D % 4 == 0 && (!dA || (aligned16(dA) && ldda % 4 == 0));
+    dropout_bn_mask(a, p, seed);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_bn_train_backward(a, ctx->stream));
+    return LAFF_OK;
+}
+
 static_assert(sizeof(laff_optim_tensor) == 40, "laff_optim_tensor is five 8-byte words (laff_amd/ops.py fills the host array as such)");
 
 /* the launches of the calling thread's last optimizer call, by variant */

@@ -286,6 +286,39 @@ struct FcGatherBwdArgs {
 };
 hipError_t launch_fc_gather_backward(const FcGatherBwdArgs& a, hipStream_t st);
 
+// bn_train.hip: dropout by a counter-based mask and training-mode BatchNorm1d, forward and backward (laff_dropout_bn_train,
+// laff_dropout_bn_train_backward).  One struct for both directions; a direction leaves the other's fields null.
+constexpr int BN_TRAIN_ROWS = 256;       // rows of a chunk: the strip of 32 columns that a block keeps in registers
+struct BnTrainArgs {
+    const float* A;           // [N, lda >= D]    the activation output
+    const float* dY;          // backward: [N, lddy >= D]
+    float* out;               // forward: Y [N, ldo >= D]; backward: dA [N, ldo >= D] or null
+    const unsigned long long* seed;      // device; read only when drop
+    const float* gamma;       // [D], null: no BatchNorm stage
+    const float* beta;        // forward
+    float* running_mean;      // forward, updated in place, as running_var
+    float* running_var;
+    float* save_mean;         // forward: written; backward: read, as save_invstd
+    float* save_invstd;
+    float* dgamma;            // backward, [D] or null, as dbeta
+    float* dbeta;
+    double* part;             // workspace [chunks][2][D]: per chunk (mean, M2) forward, (sum dY, sum dY xhat) backward
+    int N, D, lda, lddy, ldo;
+    int drop;                 // p > 0
+    unsigned thresh;          // an element is kept iff its Philox word >= thresh
+    float scale;              // fp32(1 / (1 - p))
+    double momentum, eps;
+    int fast;                 // rows on 16-byte boundaries (bases and pitches) and D % 4 == 0
+};
+struct BnTrainPlan {
+    int chunks;               // row chunks of the column sums (1 without a BatchNorm stage: nothing is summed)
+    int launches;             // per direction: 1, or 2 when the sums are cut
+    size_t ws;                // workspace bytes (0 with one chunk)
+};
+void bn_train_plan(int N, int D, bool has_bn, BnTrainPlan* p);
+hipError_t launch_bn_train_forward(const BnTrainArgs& a, hipStream_t st);
+hipError_t launch_bn_train_backward(const BnTrainArgs& a, hipStream_t st);
+
 // optim.hip: global-norm clipping and the Adam / RMSprop step over a list of flat fp32 tensors (laff_grad_sqnorm, laff_grad_scale,
 // laff_optim_step)
 constexpr int OPTIM_CHUNK = 4096;        // elements of one chunk: 256 threads x 4 accesses of 16 bytes

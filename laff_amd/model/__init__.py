@@ -1,1 +1,1 @@
-from .model import get_model  # noqa: F401
+from .model import get_model, use_device_norm  # noqa: F401

@@ -16,8 +16,8 @@ as /root/reference/model/model.py for the symbols on the hot path (SURVEY.md sec
 
 The towers are inference only: their training-mode forward raises.  A single TransformNet is differentiable in .train() mode
 (_FcActFn: laff_fc_act_bn forward, laff_fc_backward behind it; a device CSR input through _FcGatherFn and
-laff_fc_gather_backward, a concat layer through TransformNet.concat_train and _FcConcatFn; section 4.24), as the fusion blocks are
-(section 4.19).
+laff_fc_gather_backward, a concat layer through TransformNet.concat_train and _FcConcatFn; section 4.24; with device_norm its dropout +
+BatchNorm1d stage through _DropoutBnFn and laff_dropout_bn_train; section 4.25), as the fusion blocks are (section 4.19).
 Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: features arrive pre-extracted in
 `caption_feat_dict` (the reference already does this for frozen CLIP via 'CLIP_encoding', :497-498); any module
 returning {'text_features': tensor} can be plugged into `txt_net.encoder.<name>`.
@@ -307,10 +307,49 @@ class _FcConcatFn(torch.autograd.Function):
         return (None, None, dw, db) + tuple(dxs)
 
 
-class TransformNet(nn.Module):
-    """fc -> activation -> dropout (identity in eval) -> BatchNorm1d, as one GEMM with a fused epilogue."""
+class _DropoutBnFn(torch.autograd.Function):
+    """y = BatchNorm1d(dropout(a)) in training mode on laff_dropout_bn_train, ops.dropout_bn_train_backward behind it (DESIGN.md
+    section 4.25).  The dropout mask is a function of (seed, row, column): the seed is saved, the mask and the dropped activations are
+    not, and a is the tensor that _FcActFn saved already.  running_mean / running_var are updated in place by the kernel.  weight
+    None: no BatchNorm stage.  Only the gradients that needs_input_grad asks for are formed.  Once differentiable."""
 
-    def __init__(self, fc_layers, opt=None, dropout=None, batch_norm=None, activation=None, fc=True):
+    @staticmethod
+    def forward(ctx, a, weight, bias, running_mean, running_var, p, momentum, eps):
+        a = a.detach()
+        # a fresh seed per forward from torch's device generator: torch.manual_seed governs it, nothing synchronises, and a captured
+        # step draws a new one on every replay
+        seed = torch.empty(1, dtype=torch.int64, device=a.device).random_() if p else None
+        y, mean, invstd = ops.dropout_bn_train(a, p or 0.0, seed, None if weight is None else weight.detach(),
+                                               None if bias is None else bias.detach(), running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(a, weight, seed, mean, invstd)
+        ctx.p = p or 0.0
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        a, weight, seed, mean, invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        bn = weight is not None
+        da, dgamma, dbeta = ops.dropout_bn_train_backward(grad_y, a, ctx.p, seed, weight.detach() if bn else None, mean, invstd,
+                                                          want_da=need[0], want_dgamma=bn and need[1], want_dbeta=bn and need[2])
+        return da, dgamma, dbeta, None, None, None, None, None
+
+
+def use_device_norm(module, on=True):
+    """Sets device_norm on every TransformNet under `module` (itself included): their training-mode dropout + BatchNorm1d stage then runs
+    on laff_dropout_bn_train instead of torch's F.dropout and BatchNorm1d.  Returns module."""
+    for m in module.modules():
+        if isinstance(m, TransformNet):
+            m.device_norm = bool(on)
+    return module
+
+
+class TransformNet(nn.Module):
+    """fc -> activation -> dropout (identity in eval) -> BatchNorm1d, as one GEMM with a fused epilogue.  device_norm: in training mode
+    the dropout + BatchNorm1d stage runs as one launch of this library each way (_DropoutBnFn) instead of torch's own ops."""
+
+    def __init__(self, fc_layers, opt=None, dropout=None, batch_norm=None, activation=None, fc=True, device_norm=False):
         super().__init__()
         if opt is not None:
             if batch_norm is None:
@@ -324,6 +363,7 @@ class TransformNet(nn.Module):
         self.activation_name = activation if activation in ('tanh', 'relu', 'sigmoid') else None
         self.dropout_p = dropout if (dropout is not None and dropout > 1e-3) else None
         self.out_features = fc_layers[1]
+        self.device_norm = bool(device_norm)
         self._bn_cache = None
         self.apply(_initialize_weights)
 
@@ -425,16 +465,47 @@ class TransformNet(nn.Module):
         if extra_shift is not None:
             raise NotImplementedError('training mode: extra_shift (the expert embedding) is not differentiable here; add it upstream '
                                       'as a torch op')
+        self._device_norm_supported()
         if x.layout == torch.sparse_csr:
             y = _FcGatherFn.apply(x, self.fc1.weight, self.fc1.bias, self.weight_t(), self.activation_name)
         else:
             y = _FcActFn.apply(x, self.fc1.weight, self.fc1.bias, self.activation_name)
         return self._after_activation_train(y)
 
+    def _device_norm_supported(self):
+        """device_norm: the BatchNorm1d settings that laff_dropout_bn_train does not compute are refused by name, before any launch."""
+        bn = self.bn1
+        if not self.device_norm or bn is None:
+            return
+        if bn.momentum is None:
+            raise NotImplementedError('training mode with device_norm: bn1.momentum=None (a cumulative moving average) is not '
+                                      'computed by laff_dropout_bn_train; set a momentum or device_norm=False')
+        if not bn.affine:
+            raise NotImplementedError('training mode with device_norm: bn1 with affine=False is not computed by '
+                                      'laff_dropout_bn_train; set device_norm=False')
+        if not bn.track_running_stats:
+            raise NotImplementedError('training mode with device_norm: bn1 with track_running_stats=False is not computed by '
+                                      'laff_dropout_bn_train; set device_norm=False')
+
     def _after_activation_train(self, y):
+        if self.device_norm:
+            return self._after_activation_device(y)
         if self.dropout_p is not None:
             y = F.dropout(y, self.dropout_p, training=True)
         return y if self.bn1 is None else self.bn1(y)
+
+    def _after_activation_device(self, y):
+        """The same stage as one launch each way (_DropoutBnFn).  The kernel writes bn1's running statistics through raw pointers:
+        their version counters are bumped here, or bn_affine's cache would serve the statistics of before the step to the next
+        .eval() forward.  num_batches_tracked counts the forward, as torch does."""
+        bn = self.bn1
+        if bn is None:
+            return y if self.dropout_p is None else _DropoutBnFn.apply(y, None, None, None, None, self.dropout_p, 0.0, 0.0)
+        y = _DropoutBnFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.dropout_p, bn.momentum, bn.eps)
+        torch.autograd.graph.increment_version(bn.running_mean)
+        torch.autograd.graph.increment_version(bn.running_var)
+        bn.num_batches_tracked.add_(1)
+        return y
 
     def concat_train(self, segments):
         """Training mode: this layer applied to torch.cat(segments, dim=1) without forming it, under autograd (_FcConcatFn), then
@@ -445,6 +516,7 @@ class TransformNet(nn.Module):
             raise RuntimeError('concat_train is the training-mode path; in eval mode use concat_problem')
         if self.fc1 is None:
             raise NotImplementedError('training mode: a TransformNet without fc (fc=False) has no differentiable path')
+        self._device_norm_supported()
         segments = list(segments)
         for j, x in enumerate(segments):
             if not x.is_cuda or x.layout not in (torch.strided, torch.sparse_csr) or x.dim() != 2:

@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1270,6 +1270,102 @@ def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=
     _call('fc_gather_backward', lib.laff_fc_gather_backward, h, _ptr(colptr), _ptr(rows), _ptr(values), nnz, N, Dk, D, ACT[activation],
           _ptr(a), lda, _ptr(g), ldg, pdw, lddw, _ptr(db))
     return dw, db
+
+
+def dropout_bn_train_plan(N, D, has_bn=True):
+    """laff_dropout_bn_train_plan (host only): (row chunks of the column sums -- 1 without a BatchNorm stage --, workspace bytes,
+    launches per direction, rows of a chunk)."""
+    out = (C.c_int * 4)()
+    check(_lib.load().laff_dropout_bn_train_plan(int(N), int(D), int(bool(has_bn)), out))
+    return tuple(out)
+
+
+def _bn_rows(t, name):
+    """A 2-D device fp32 operand of the dropout + BatchNorm stage as (tensor, pitch): a non-unit inner stride is made dense first."""
+    _dev(t, name)
+    if t.dim() != 2:
+        raise ValueError('%s must be 2-D, got shape %s' % (name, tuple(t.shape)))
+    if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        t = t.contiguous()
+    return _rows(t, name)
+
+
+def _bn_vec(t, D, name):
+    """A contiguous device fp32 vector of D."""
+    _dev(t, name)
+    if tuple(t.shape) != (D,) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous vector of %d, got shape %s' % (name, D, tuple(t.shape)))
+    return t
+
+
+def _bn_seed(p, seed):
+    p = float(p)
+    if p > 0.0:
+        _dev(seed, 'seed', torch.int64)
+        if seed.numel() != 1:
+            raise ValueError('seed must hold one int64, got shape %s' % (tuple(seed.shape),))
+    return p, (seed if p > 0.0 else None)
+
+
+def dropout_bn_train(a, p, seed, weight, bias, running_mean, running_var, momentum, eps, out=None):
+    """Dropout by the counter-based mask of laff_dropout_bn_train, then training-mode BatchNorm1d: a (N, D) device fp32 (a row view with
+    a pitch is read in place), p in [0, 1), seed a device int64 tensor of one element (None allowed with p == 0), weight / bias /
+    running_mean / running_var (D,) contiguous device fp32 -- the running statistics are UPDATED IN PLACE through raw pointers (their
+    version counters are the caller's to bump).  weight None: no BatchNorm stage, y = a (.) mask / (1 - p), the other vectors are
+    ignored.  Returns (y, save_mean, save_invstd), the last two None without a BatchNorm stage.  out: a y buffer, or a
+    (y, save_mean, save_invstd) triple of buffers (None entries are allocated here; y may be a row view with a pitch)."""
+    a, lda = _bn_rows(a, 'a')
+    (N, D), dev = a.shape, a.device
+    p, seed = _bn_seed(p, seed)
+    oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
+    y, py, ldy = _out_rows(oy, (N, D), dev, 'out y')
+    mean = invstd = None
+    if weight is not None:
+        weight, bias = _bn_vec(weight, D, 'weight'), _bn_vec(bias, D, 'bias')
+        running_mean, running_var = _bn_vec(running_mean, D, 'running_mean'), _bn_vec(running_var, D, 'running_var')
+        mean = _bn_vec(omean, D, 'out save_mean') if omean is not None else torch.empty((D,), device=dev, dtype=torch.float32)
+        invstd = _bn_vec(oinv, D, 'out save_invstd') if oinv is not None else torch.empty((D,), device=dev, dtype=torch.float32)
+    else:
+        bias = running_mean = running_var = None
+    nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    lib, h = _context(dev)
+    _call('dropout_bn_train', lib.laff_dropout_bn_train, h, _ptr(a), N, D, lda, p, _ptr(seed), _ptr(weight), _ptr(bias), _ptr(running_mean),
+          _ptr(running_var), float(momentum), float(eps), py, ldy, _ptr(mean), _ptr(invstd), _ptr(ws), nbytes)
+    return y, mean, invstd
+
+
+def dropout_bn_train_backward(grad_y, a, p, seed, weight, save_mean, save_invstd, want_da=True, want_dgamma=True, want_dbeta=True, out=None):
+    """Backward of dropout_bn_train (laff_dropout_bn_train_backward): grad_y and a (N, D) device fp32, p and seed as the forward had them
+    (the mask is recomputed), weight and the forward's save_mean / save_invstd (None, None, None: no BatchNorm stage, and then no
+    dgamma / dbeta).  Returns (da | None, dgamma | None, dbeta | None).  out: a (da, dgamma, dbeta) triple of buffers (None entries
+    are allocated here; da may be a row view with a pitch)."""
+    g, ldg = _bn_rows(grad_y, 'grad_y')
+    a, lda = _bn_rows(a, 'a')
+    (N, D), dev = a.shape, a.device
+    if tuple(g.shape) != (N, D):
+        raise ValueError('grad_y %s and a %s do not fit together' % (tuple(g.shape), tuple(a.shape)))
+    p, seed = _bn_seed(p, seed)
+    if weight is not None:
+        weight, save_mean = _bn_vec(weight, D, 'weight'), _bn_vec(save_mean, D, 'save_mean')
+        save_invstd = _bn_vec(save_invstd, D, 'save_invstd')
+    else:
+        save_mean = save_invstd = None
+        if want_dgamma or want_dbeta:
+            raise ValueError('dgamma / dbeta are wanted, but there is no BatchNorm stage (weight is None)')
+    oda, odg, odb = out if out is not None else (None, None, None)
+    da, pda, ldda = _out_rows(oda, (N, D), dev, 'out da') if want_da else (None, None, 0)
+    vec = lambda o, nm: _bn_vec(o, D, nm) if o is not None else torch.empty((D,), device=dev, dtype=torch.float32)
+    dgamma = vec(odg, 'out dgamma') if want_dgamma else None
+    dbeta = vec(odb, 'out dbeta') if want_dbeta else None
+    if not (want_da or want_dgamma or want_dbeta):
+        return None, None, None
+    nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    lib, h = _context(dev)
+    _call('dropout_bn_train_backward', lib.laff_dropout_bn_train_backward, h, _ptr(g), ldg, _ptr(a), N, D, lda, p, _ptr(seed), _ptr(weight),
+          _ptr(save_mean), _ptr(save_invstd), pda, ldda, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)
+    return da, dgamma, dbeta
 
 
 def optim_plan(sizes):
