@@ -14,10 +14,16 @@ as /root/reference/model/model.py for the symbols on the hot path (SURVEY.md sec
   MultiScaleTxtEncoder / MultiScaleTxtNet :552-726     the concatenated input never formed
   get_model                            :2501-2519
 
-The towers are inference only: their training-mode forward raises.  A single TransformNet is differentiable in .train() mode
-(_FcActFn: laff_fc_act_bn forward, laff_fc_backward behind it; a device CSR input through _FcGatherFn and
-laff_fc_gather_backward, a concat layer through TransformNet.concat_train and _FcConcatFn; section 4.24; with device_norm its dropout +
-BatchNorm1d stage through _DropoutBnFn and laff_dropout_bn_train; section 4.25), as the fusion blocks are (section 4.19).
+Differentiable in .train() mode (the autograd Functions live in model/autograd.py):
+  TransformNet on a dense input, plane() included       _FcActFn       DESIGN.md section 4.20
+  TransformNet on a device CSR input                     _FcGatherFn    section 4.24
+  TransformNet.concat_train (a concat layer)             _FcConcatFn    section 4.24
+  its dropout + BatchNorm1d stage with device_norm       _DropoutBnFn   section 4.25 (torch's own ops without device_norm)
+  the fusion blocks (model/Attention.py)                                section 4.19
+  VisMutiTransformNetPlusFrameFeat.frame_vector                         section 4.22
+Inference only: the towers' prepare() / forward and TransformNet.concat_problem, which raise in training mode (_eval_only), and
+W2VVPP: its forward (the training step) raises, retrieve() / predict() put the model in eval mode.
+
 Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: features arrive pre-extracted in
 `caption_feat_dict` (the reference already does this for frozen CLIP via 'CLIP_encoding', :497-498); any module
 returning {'text_features': tensor} can be plugged into `txt_net.encoder.<name>`.
@@ -31,6 +37,7 @@ import torch.nn.functional as F
 from .. import loss as _loss
 from .. import ops
 from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention
+from .autograd import _csc_of, _DropoutBnFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params  # noqa: F401  (kept importable from here)
 
 device = torch.device('cuda')
 float16 = False
@@ -182,160 +189,6 @@ def get_attention_layer(attention_type, common_space_dim, encoder_num, opt):
 # ------------------------------------------------------------------------------------------------------
 # a1/a2: TransformNet
 # ------------------------------------------------------------------------------------------------------
-class _FcActFn(torch.autograd.Function):
-    """a = act(x @ weight.T + bias) on laff_fc_act_bn (the fp32 route, whatever FC_PRECISION says) with ops.fc_backward as its backward.
-    Saves x, weight and the output a: act' is a function of a for every activation of the reference.  Only the gradients that
-    needs_input_grad asks for are formed -- no dx launch for pre-extracted features.  Once differentiable."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, activation):
-        for t, nm in ((x, 'the input'), (weight, 'fc1.weight'), (bias, 'fc1.bias')):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError('the differentiable projection is fp32 only, %s is %s' % (nm, t.dtype))
-        x = x.detach()
-        if x.dim() == 2 and x.numel() and x.stride(1) != 1:
-            x = x.contiguous()
-        a = ops.fc_act_bn(x, weight.detach(), None if bias is None else bias.detach(), None, None, activation)
-        ctx.save_for_backward(x, weight, a)
-        ctx.activation, ctx.has_bias = activation, bias is not None
-        return a
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_a):
-        x, weight, a = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dx, dw, db = ops.fc_backward(x, weight.detach(), a, grad_a, ctx.activation, want_dx=need[0], want_dw=need[1],
-                                     want_db=ctx.has_bias and need[2])
-        return dx, dw, db, None
-
-
-def _fp32_params(weight, bias):
-    for t, nm in ((weight, 'fc1.weight'), (bias, 'fc1.bias')):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError('the differentiable projection is fp32 only, %s is %s' % (nm, t.dtype))
-
-
-def _csc_of(x):
-    """The transposed pattern of a device CSR input: the one its encoder attached (txt2vec.BoWTxtEncoder(with_csc=True)), else
-    transposed on the device now (a stable sort, no host synchronisation)."""
-    csc = getattr(x, 'laff_csc', None)
-    return tuple(csc) if csc is not None else ops.csr_transpose(x)
-
-
-class _FcGatherFn(torch.autograd.Function):
-    """a = act(x @ weight.T + bias) for a device torch.sparse_csr x: laff_fc_gather_act_bn on the layer's cached weight_t() forward,
-    ops.fc_gather_backward behind it.  Saves the transposed pattern (CSC) and the output a; dw comes back in weight's own shape,
-    contiguous, so that laff_amd.optim steps it as it is; db only where needs_input_grad asks for it; x gets no gradient (counts).
-    The forward keeps the kernel's fused activation: its output met the training tests' rule with room.
-    Once differentiable."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, weight_t, activation):
-        _fp32_params(weight, bias)
-        a = ops.fc_gather_act_bn(x, weight_t, None if bias is None else bias.detach(), None, None, activation)
-        ctx.save_for_backward(a, *_csc_of(x))
-        ctx.activation, ctx.has_bias, ctx.x_shape = activation, bias is not None, tuple(x.shape)
-        return a
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_a):
-        a, colptr, rows, values = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dw, db = ops.fc_gather_backward((colptr, rows, values), ctx.x_shape[0], ctx.x_shape[1], a, grad_a, ctx.activation,
-                                        want_dw=need[1], want_db=ctx.has_bias and need[2])
-        return None, dw, db, None, None
-
-
-class _FcConcatFn(torch.autograd.Function):
-    """a = act(sum_s x_s @ weight[:, c_s : c_s + w_s].T + bias) over dense device fp32 segments and / or device torch.sparse_csr ones:
-    the one laff_fc_concat_act_bn launch forward (no BatchNorm stage), and behind it one call per segment on the column windows of
-    weight and of ONE (D, K) gradient buffer -- pitched views, no copies: ops.fc_backward for a dense segment (dx only where that
-    segment needs a gradient), ops.fc_gather_backward for a CSR one.  The windows cover dw, so nothing is zero-filled.  db is formed
-    exactly once, by the FIRST segment's call.  Once differentiable."""
-
-    @staticmethod
-    def forward(ctx, layer, activation, weight, bias, *segments):
-        _fp32_params(weight, bias)
-        segs, wt, kinds, saved, col = [], {}, [], [], 0
-        for j, x in enumerate(segments):
-            width = x.shape[1]
-            if x.layout == torch.sparse_csr:
-                wt[j] = layer.weight_t_block(col, width)
-                kinds.append(('csr', tuple(x.shape)))
-                saved += list(_csc_of(x))
-            else:
-                if x.dtype != torch.float32:
-                    raise TypeError('the differentiable projection is fp32 only, segment %d is %s' % (j, x.dtype))
-                x = x.detach()
-                if x.dim() == 2 and x.numel() and x.stride(1) != 1:
-                    x = x.contiguous()
-                kinds.append(('dense', None))
-                saved.append(x)
-            segs.append(x)
-            col += width
-        a = ops.fc_concat_act_bn(segs, weight.detach(), None if bias is None else bias.detach(), None, None, activation, weight_t=wt)
-        ctx.save_for_backward(weight, a, *saved)
-        ctx.activation, ctx.has_bias, ctx.kinds = activation, bias is not None, kinds
-        return a
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_a):
-        weight, a, *saved = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        w = weight.detach()
-        dw = torch.empty_like(w, memory_format=torch.contiguous_format) if need[2] else None
-        db = torch.empty((w.shape[0],), device=w.device, dtype=torch.float32) if ctx.has_bias and need[3] else None
-        dxs, col, at = [], 0, 0
-        for j, (kind, shape) in enumerate(ctx.kinds):
-            first_db = db if j == 0 else None
-            if kind == 'csr':
-                csc, at, width = tuple(saved[at:at + 3]), at + 3, shape[1]
-                ops.fc_gather_backward(csc, shape[0], width, a, grad_a, ctx.activation, want_dw=dw is not None,
-                                       want_db=first_db is not None, out=(None if dw is None else dw[:, col:col + width], first_db))
-                dxs.append(None)
-            else:
-                x, at = saved[at], at + 1
-                width = x.shape[1]
-                dx = ops.fc_backward(x, w[:, col:col + width], a, grad_a, ctx.activation, want_dx=need[4 + j], want_dw=dw is not None,
-                                     want_db=first_db is not None,
-                                     out=(None, None if dw is None else dw[:, col:col + width], first_db))[0]
-                dxs.append(dx)
-            col += width
-        return (None, None, dw, db) + tuple(dxs)
-
-
-class _DropoutBnFn(torch.autograd.Function):
-    """y = BatchNorm1d(dropout(a)) in training mode on laff_dropout_bn_train, ops.dropout_bn_train_backward behind it (DESIGN.md
-    section 4.25).  The dropout mask is a function of (seed, row, column): the seed is saved, the mask and the dropped activations are
-    not, and a is the tensor that _FcActFn saved already.  running_mean / running_var are updated in place by the kernel.  weight
-    None: no BatchNorm stage.  Only the gradients that needs_input_grad asks for are formed.  Once differentiable."""
-
-    @staticmethod
-    def forward(ctx, a, weight, bias, running_mean, running_var, p, momentum, eps):
-        a = a.detach()
-        # a fresh seed per forward from torch's device generator: torch.manual_seed governs it, nothing synchronises, and a captured
-        # step draws a new one on every replay
-        seed = torch.empty(1, dtype=torch.int64, device=a.device).random_() if p else None
-        y, mean, invstd = ops.dropout_bn_train(a, p or 0.0, seed, None if weight is None else weight.detach(),
-                                               None if bias is None else bias.detach(), running_mean, running_var, momentum, eps)
-        ctx.save_for_backward(a, weight, seed, mean, invstd)
-        ctx.p = p or 0.0
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_y):
-        a, weight, seed, mean, invstd = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        bn = weight is not None
-        da, dgamma, dbeta = ops.dropout_bn_train_backward(grad_y, a, ctx.p, seed, weight.detach() if bn else None, mean, invstd,
-                                                          want_da=need[0], want_dgamma=bn and need[1], want_dbeta=bn and need[2])
-        return da, dgamma, dbeta, None, None, None, None, None
-
-
 def use_device_norm(module, on=True):
     """Sets device_norm on every TransformNet under `module` (itself included): their training-mode dropout + BatchNorm1d stage then runs
     on laff_dropout_bn_train instead of torch's F.dropout and BatchNorm1d.  Returns module."""
@@ -364,8 +217,27 @@ class TransformNet(nn.Module):
         self.dropout_p = dropout if (dropout is not None and dropout > 1e-3) else None
         self.out_features = fc_layers[1]
         self.device_norm = bool(device_norm)
-        self._bn_cache = None
+        self._derived = {}
         self.apply(_initialize_weights)
+
+    def _cached(self, slot, tensors, make, extra=()):
+        """What make() returned at the last call for `slot`, as long as no tensor of `tensors` (None entries are skipped) has a new
+        data_ptr or a bumped _version and `extra` is the same; else make() now.  Every value derived from parameters is kept this way:
+        an in-place update, an optimizer step, .to(device) and load_state_dict all show in one of the two."""
+        key = tuple((t.data_ptr(), t._version) for t in tensors if t is not None) + extra
+        hit = self._derived.get(slot)
+        if hit is None or hit[0] != key:
+            hit = self._derived[slot] = (key, make())
+        return hit[1]
+
+    def _bn_tensors(self):
+        bn = self.bn1
+        return () if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
+    def _bn_fold(self):
+        bn = self.bn1
+        scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).contiguous()
+        return scale, (bn.bias.detach() - bn.running_mean * scale).contiguous()
 
     def bn_affine(self, extra_shift=None):
         """Folded eval-mode BatchNorm1d: y*scale + shift (what aten's inference kernel computes)."""
@@ -373,14 +245,7 @@ class TransformNet(nn.Module):
             if extra_shift is None:
                 return None, None
             return torch.ones_like(extra_shift), extra_shift.contiguous()
-        bn = self.bn1
-        ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._bn_cache is None or self._bn_cache[0] != key:
-            scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).contiguous()
-            shift = (bn.bias.detach() - bn.running_mean * scale).contiguous()
-            self._bn_cache = (key, scale, shift)
-        scale, shift = self._bn_cache[1:]
+        scale, shift = self._cached('bn_affine', self._bn_tensors(), self._bn_fold)
         if extra_shift is not None:
             shift = (shift + extra_shift).contiguous()
         return scale, shift
@@ -388,19 +253,13 @@ class TransformNet(nn.Module):
     def weight_t(self):
         """fc1.weight transposed ([D_k, D]: one vocabulary entry = one contiguous row), cached until the weight changes."""
         w = self.fc1.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, '_w_t', None) is None or self._w_t[0] != key:
-            self._w_t = (key, w.detach().t().contiguous())
-        return self._w_t[1]
+        return self._cached('weight_t', (w,), lambda: w.detach().t().contiguous())
 
     def weight_t_block(self, col, width):
         """Columns [col, col + width) of fc1.weight transposed ([width, D]): the block a sparse segment of a concat tower gathers from,
         cached until the weight changes."""
         w = self.fc1.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, '_w_t_blocks', None) is None or self._w_t_blocks[0] != key:
-            self._w_t_blocks = (key, {})
-        blocks = self._w_t_blocks[1]
+        blocks = self._cached('weight_t_blocks', (w,), dict)
         if (col, width) not in blocks:
             blocks[(col, width)] = w.detach()[:, col:col + width].t().contiguous()
         return blocks[(col, width)]
@@ -437,20 +296,15 @@ class TransformNet(nn.Module):
         if FC_PRECISION != 'fp16x3':
             return None
         w = self.fc1.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, '_w_split', None) is None or self._w_split[0] != key:
-            self._w_split = (key, ops.split_rows(w.detach()))
-        return self._w_split[1]
+        return self._cached('weight_split', (w,), lambda: ops.split_rows(w.detach()))
 
     def strip_weights(self):
         """fc1 + folded BatchNorm + activation packed for the strip-form FC (laff_fc_strip_pack), cached until a parameter changes."""
-        scale, shift = self.bn_affine(None)
         w, b = self.fc1.weight, self.fc1.bias
-        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version),
-               None if self.bn1 is None else self._bn_cache[0], self.activation_name, ops.fc_strip_mfma(w.device))
-        if getattr(self, '_w_strip', None) is None or self._w_strip[0] != key:
-            self._w_strip = (key, ops.fc_strip_pack(w.detach(), None if b is None else b.detach(), scale, shift, self.activation_name))
-        return self._w_strip[1]
+        return self._cached('strip_weights', (w, b) + self._bn_tensors(),
+                            lambda: ops.fc_strip_pack(w.detach(), None if b is None else b.detach(), *self.bn_affine(None),
+                                                      self.activation_name),
+                            (self.activation_name, ops.fc_strip_mfma(w.device)))
 
     def _forward_train(self, x, heads=1, extra_shift=None):
         """Training mode: fc1 + activation under autograd (_FcActFn), then torch's own dropout and training-mode BatchNorm1d (batch
@@ -722,6 +576,34 @@ ENCODER_KEYS = {'rnn_encoder': 'rnn_encoding', 'bert_encoder': 'bert_encoding', 
                 'w2v_encoder': 'w2v_encoding', 'CLIP_encoder': 'CLIP_encoding', 'NetVLAD_encoder': 'NetVLAD_encoding'}
 
 
+def _build_text_encoders(module, opt, keys=ENCODER_KEYS):
+    """What both text encoder classes hold: `space_dict` (encoder name -> feature width) in the reference's fixed order (model/model.py:
+    572-613: rnn, bert, bow, w2v, CLIP, NetVLAD), the `encoder` module of PreExtractedEncoder placeholders, `encoder_name_list` and
+    `txt_encoder_num`."""
+    te = opt.text_encoding
+    rnn = te['rnn_encoding']['name'].split('_', 1)[0]
+    module.space_dict = {}
+    if rnn == 'gru':
+        module.space_dict['rnn_encoder'] = opt.rnn_size
+    elif rnn == 'bigru':
+        module.space_dict['rnn_encoder'] = opt.rnn_size * 2
+    if te['bert_encoding']['name'] != 'noBert':
+        module.space_dict['bert_encoder'] = opt.bert_size
+    if 'no' not in te['bow_encoding']['name']:
+        module.space_dict['bow_encoder'] = opt.t2v_bow.ndims
+    if 'no' not in te['w2v_encoding']['name']:
+        module.space_dict['w2v_encoder'] = opt.t2v_w2v.ndims
+    if 'no' not in te['CLIP_encoding']['name']:
+        module.space_dict['CLIP_encoder'] = opt.clip_opt['size']
+    if 'no' not in te['NetVLAD_encoding']['name']:
+        module.space_dict['NetVLAD_encoder'] = opt.t2v_w2v.ndims * opt.NetVLAD_opt['num_clusters']
+    module.encoder = nn.Module()
+    for name in module.space_dict:
+        module.encoder.add_module(name, PreExtractedEncoder(keys[name]))
+    module.encoder_name_list = list(module.space_dict.keys())
+    module.txt_encoder_num = len(module.encoder_name_list)
+
+
 class MultiScaleTxtEncoder(nn.Module):
     """The text encoders of the W2VV++ tower (model/model.py:552-700) under `encoder.<name>`, in the reference's fixed order rnn,
     bert, bow, w2v, CLIP, NetVLAD: PreExtractedEncoder placeholders, replaced by plugging a module that returns
@@ -731,28 +613,7 @@ class MultiScaleTxtEncoder(nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        te = opt.text_encoding
-        rnn = te['rnn_encoding']['name'].split('_', 1)[0]
-        self.space_dict = {}
-        if rnn == 'gru':
-            self.space_dict['rnn_encoder'] = opt.rnn_size
-        elif rnn == 'bigru':
-            self.space_dict['rnn_encoder'] = opt.rnn_size * 2
-        if te['bert_encoding']['name'] != 'noBert':
-            self.space_dict['bert_encoder'] = opt.bert_size
-        if 'no' not in te['bow_encoding']['name']:
-            self.space_dict['bow_encoder'] = opt.t2v_bow.ndims
-        if 'no' not in te['w2v_encoding']['name']:
-            self.space_dict['w2v_encoder'] = opt.t2v_w2v.ndims
-        if 'no' not in te['CLIP_encoding']['name']:
-            self.space_dict['CLIP_encoder'] = opt.clip_opt['size']
-        if 'no' not in te['NetVLAD_encoding']['name']:
-            self.space_dict['NetVLAD_encoder'] = opt.t2v_w2v.ndims * opt.NetVLAD_opt['num_clusters']
-        self.encoder = nn.Module()
-        for name in self.space_dict:
-            self.encoder.add_module(name, PreExtractedEncoder(ENCODER_KEYS[name]))
-        self.encoder_name_list = list(self.space_dict.keys())
-        self.txt_encoder_num = len(self.encoder_name_list)
+        _build_text_encoders(self, opt)
 
     def segments(self, caption_feat_dict, task3=False):
         """The encoders' outputs in encoder order: the segments of the concatenated text feature."""
@@ -795,31 +656,7 @@ class MultiScaleTxtEncoderAttention(nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        te = opt.text_encoding
-        bow, w2v, rnn, bert, clip_, vlad = (te[k]['name'] for k in ('bow_encoding', 'w2v_encoding', 'rnn_encoding',
-                                                                     'bert_encoding', 'CLIP_encoding', 'NetVLAD_encoding'))
-        rnn = rnn.split('_', 1)[0]
-        # encoder order is fixed by the reference (model/model.py:572-613): rnn, bert, bow, w2v, CLIP, NetVLAD
-        self.space_dict = {}
-        if rnn == 'gru':
-            self.space_dict['rnn_encoder'] = opt.rnn_size
-        elif rnn == 'bigru':
-            self.space_dict['rnn_encoder'] = opt.rnn_size * 2
-        if bert != 'noBert':
-            self.space_dict['bert_encoder'] = opt.bert_size
-        if 'no' not in bow:
-            self.space_dict['bow_encoder'] = opt.t2v_bow.ndims
-        if 'no' not in w2v:
-            self.space_dict['w2v_encoder'] = opt.t2v_w2v.ndims
-        if 'no' not in clip_:
-            self.space_dict['CLIP_encoder'] = opt.clip_opt['size']
-        if 'no' not in vlad:
-            self.space_dict['NetVLAD_encoder'] = opt.t2v_w2v.ndims * opt.NetVLAD_opt['num_clusters']
-        self.encoder = nn.Module()
-        for name in self.space_dict:
-            self.encoder.add_module(name, PreExtractedEncoder(self.ENCODER_KEYS[name]))
-        self.encoder_name_list = list(self.space_dict.keys())
-        self.txt_encoder_num = len(self.encoder_name_list)
+        _build_text_encoders(self, opt, self.ENCODER_KEYS)
 
         # transform layers (model/model.py:622-681)
         D = opt.txt_fc_layers[1]
@@ -1059,6 +896,14 @@ class W2VVPP(nn.Module):
             vis_ids.extend(batch_vis_ids)
         return torch.cat(embs, dim=0), idxs_list, vis_ids
 
+    def _embed_texts(self, txt_loader):
+        """txt_net over the batches of the text loader: (the embeddings of all captions, their ids)."""
+        embs, txt_ids = [], []
+        for caption_feat_dict, _, batch_txt_ids in txt_loader:
+            embs.append(self.txt_net(caption_feat_dict))
+            txt_ids.extend(batch_txt_ids)
+        return torch.cat(embs, dim=0), txt_ids
+
     #: operand precision of retrieve() / predict() when none is given: the score matrix of the drop-in path goes to the host anyway
     #: (1.6 GB over PCIe at C4 is 40x the GEMM), so it takes the split-product GEMM whose scores are fp32-class (~2e-7) like the
     #: reference's own; bench.py / retrieval.evaluate choose their precision themselves
@@ -1130,11 +975,7 @@ class W2VVPP(nn.Module):
             else:
                 if not record_emb or self.video_all_embs is None:
                     self.video_all_embs, self.video_idxs_list, self.vis_ids = self._embed_videos(vis_loader)
-                txt_ids, txt_embs = [], []
-                for caption_feat_dict, txt_idxs, batch_txt_ids in txt_loader:
-                    txt_embs.append(self.txt_net(caption_feat_dict))
-                    txt_ids.extend(batch_txt_ids)
-                txt_all = torch.cat(txt_embs, dim=0)
+                txt_all, txt_ids = self._embed_texts(txt_loader)
             cols = np.concatenate([np.asarray(i, dtype=np.int64) for i in self.video_idxs_list])
             vis_used = self.video_all_embs
             identity = np.array_equal(cols, np.arange(len(cols)))
@@ -1232,7 +1073,7 @@ class W2VVPP(nn.Module):
         with torch.no_grad():
             Ev, idxs_list, _ = self._embed_videos(vis_loader)
             cols = np.concatenate([np.asarray(i, dtype=np.int64) for i in idxs_list])
-            Et = torch.cat([self.txt_net(caption_feat_dict) for caption_feat_dict, _, _ in txt_loader], dim=0)
+            Et, _ = self._embed_texts(txt_loader)
             out = torch.as_tensor(np.asarray(t2i_matrix), dtype=torch.float32).to(Ev.device).contiguous().clone()
             Nt, Nv = out.shape
             if Et.shape[0] != Nt or len(cols) != Nv or not np.array_equal(np.sort(cols), np.arange(Nv)):
@@ -1321,11 +1162,8 @@ class W2VVPP_MultiHeadAttention(W2VVPP_MutiVis):
         self.eval()
         with torch.no_grad():
             vis_all, idxs_list, vis_ids = self._embed_videos(vis_loader)
-            txt_ids, txt_embs = [], []
-            for caption_feat_dict, txt_idxs, batch_txt_ids in txt_loader:
-                txt_embs.append(self.txt_net(caption_feat_dict))
-                txt_ids.extend(batch_txt_ids)
-            scores = self.get_txt2vis_matrix_each_head(torch.cat(txt_embs, 0), vis_all, measure)
+            txt_all, txt_ids = self._embed_texts(txt_loader)
+            scores = self.get_txt2vis_matrix_each_head(txt_all, vis_all, measure)
         return scores.cpu().numpy(), txt_ids, vis_ids
 
 

@@ -107,6 +107,45 @@ def _rows(t, name):
     return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
 
 
+def _mat(t, name, align16=False):
+    """A 2-D device fp32 operand of a training entry point as (tensor, pitch): a row view is read in place, anything else -- a non-unit
+    inner stride, a pitch below the width (an expanded gradient) -- is made dense first.  align16: rows that are not 16-byte aligned
+    (the base, or a pitch that is no multiple of 4 floats) are made dense too."""
+    _dev(t, name)
+    if t.dim() != 2:
+        raise ValueError('%s must be 2-D, got shape %s' % (name, tuple(t.shape)))
+    if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or
+                      (align16 and (t.data_ptr() % 16 or (t.shape[0] > 1 and t.stride(0) % 4)))):
+        t = t.contiguous()
+    return _rows(t, name)
+
+
+def _vec(t, D, name):
+    """A contiguous device fp32 vector of D."""
+    _dev(t, name)
+    if tuple(t.shape) != (D,) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous vector of %d, got shape %s' % (name, D, tuple(t.shape)))
+    return t
+
+
+def _vec_out(t, D, device, name):
+    """A (D,) fp32 output: the caller's buffer through _vec, or a new one on `device`."""
+    return torch.empty((D,), device=device, dtype=torch.float32) if t is None else _vec(t, D, name)
+
+
+def _workspace(nbytes, device, floor=0):
+    """A uint8 device workspace of max(nbytes, floor) bytes; None when that is zero."""
+    if nbytes < floor:
+        nbytes = floor
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _csr_triple(x_csr):
+    """(crow_indices int32, col_indices int32, values fp32) of a torch.sparse_csr matrix, contiguous, as the kernels read them."""
+    return (x_csr.crow_indices().to(torch.int32).contiguous(), x_csr.col_indices().to(torch.int32).contiguous(),
+            x_csr.values().to(torch.float32).contiguous())
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -225,9 +264,7 @@ def fc_gather_act_bn(x_csr, weight_t, bias=None, bn_scale=None, bn_shift=None, a
     if wt.shape[0] != Dk:
         raise ValueError('weight_t is %s but x has %d columns' % (tuple(wt.shape), Dk))
     D = wt.shape[1]
-    crow = x_csr.crow_indices().to(torch.int32).contiguous()
-    col = x_csr.col_indices().to(torch.int32).contiguous()
-    val = x_csr.values().to(torch.float32).contiguous()
+    crow, col, val = _csr_triple(x_csr)
     for t, nm in ((bias, 'bias'), (bn_scale, 'bn_scale'), (bn_shift, 'bn_shift')):
         if t is not None:
             _dev(t, nm)
@@ -280,9 +317,7 @@ def fc_concat_act_bn_grouped(problems):
                 wt, ldwt = _rows(wt, 'weight_t')
                 if wt.shape[0] != Dk or wt.shape[1] != D:
                     raise ValueError('problem %d: weight_t of segment %d is %s, expected (%d, %d)' % (i, j, tuple(wt.shape), Dk, D))
-                crow = x.crow_indices().to(torch.int32).contiguous()
-                cidx = x.col_indices().to(torch.int32).contiguous()
-                val = x.values().to(torch.float32).contiguous()
+                crow, cidx, val = _csr_triple(x)
                 keep += [wt, crow, cidx, val]
                 sarr[j] = FcConcatSegment(None, 0, crow.data_ptr(), cidx.data_ptr(), val.data_ptr(), wt.data_ptr(), ldwt, Dk, col)
             else:
@@ -1022,9 +1057,7 @@ def fuse(planes, H, d, w, b, gw, flags, return_weights=False, packed_precision=N
             wt, ldwt = _rows(wt, 'weight_t')
             if wt.shape[0] != csr.shape[1] or wt.shape[1] != H * d or tile or (flags & ATT_NO_SPLIT_HEAD) or d > 512:
                 raise ValueError('gather plane %d: weight_t must be (%d, %d), split heads of d <= 512' % (i, csr.shape[1], H * d))
-            crow = csr.crow_indices().to(torch.int32).contiguous()
-            col = csr.col_indices().to(torch.int32).contiguous()
-            val = csr.values().to(torch.float32).contiguous()
+            crow, col, val = _csr_triple(csr)
             if bias is not None:
                 _dev(bias, 'bias')
             arr[i] = Plane(None, 0, 0, sp, tp, ACT[act], crow.data_ptr(), col.data_ptr(), val.data_ptr(), wt.data_ptr(), ldwt,
@@ -1141,7 +1174,7 @@ def fuse_backward(planes, H, d, w, b, gw, flags, grad_E, want_param_grads=True, 
         return dxs, dw, db
     lib, h = _context(dev)
     nbytes = _size_query('laff_fuse_backward_workspace_bytes', L, N, H, d, flags) if want else 0
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want else None
+    ws = _workspace(nbytes, dev, floor=16) if want else None
     xp = (C.c_void_p * L)(*[s.data_ptr() for s, _ in rows])
     xl = (C.c_int * L)(*[ld for _, ld in rows])
     dp = (C.c_void_p * L)(*[t.data_ptr() for t, _ in drows])
@@ -1166,15 +1199,7 @@ def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, wa
     allocated here; dx and dw may be row views with a pitch, db is contiguous) that receive the wanted outputs."""
     if activation not in ACT:
         raise ValueError('unknown activation %r' % (activation,))
-    mats = []
-    for t, nm in ((x, 'x'), (weight, 'weight'), (a, 'a'), (grad_a, 'grad_a')):
-        _dev(t, nm)
-        if t.dim() != 2:
-            raise ValueError('%s must be 2-D, got shape %s' % (nm, tuple(t.shape)))
-        if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):      # e.g. an expanded gradient
-            t = t.contiguous()
-        mats.append(_rows(t, nm))
-    (x, ldx), (w, ldw), (a, lda), (g, ldg) = mats
+    (x, ldx), (w, ldw), (a, lda), (g, ldg) = [_mat(t, nm) for t, nm in ((x, 'x'), (weight, 'weight'), (a, 'a'), (grad_a, 'grad_a'))]
     (N, Dk), D, dev = x.shape, w.shape[0], x.device
     if w.shape[1] != Dk or tuple(a.shape) != (N, D) or tuple(g.shape) != (N, D):
         raise ValueError('x %s, weight %s, a %s and grad_a %s do not fit together' % (tuple(x.shape), tuple(w.shape), tuple(a.shape),
@@ -1182,15 +1207,11 @@ def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, wa
     odx, odw, odb = out if out is not None else (None, None, None)
     dx, pdx, lddx = _out_rows(odx, (N, Dk), dev, 'out dx') if want_dx else (None, None, 0)
     dw, pdw, lddw = _out_rows(odw, (D, Dk), dev, 'out dw') if want_dw else (None, None, 0)
-    db = None
-    if want_db:
-        db = torch.empty((D,), device=dev, dtype=torch.float32) if odb is None else _dev(odb, 'out db')
-        if tuple(db.shape) != (D,) or not db.is_contiguous():
-            raise ValueError('out db must be a contiguous vector of %d' % D)
+    db = _vec_out(odb, D, dev, 'out db') if want_db else None
     if not (want_dx or want_dw or want_db):
         return None, None, None
     nbytes = fc_backward_plan(N, Dk, D, want_dx, want_dw)[1]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ws = _workspace(nbytes, dev)
     lib, h = _context(dev)
     _call('fc_backward', lib.laff_fc_backward, h, _ptr(x), N, Dk, ldx, _ptr(w), ldw, D, ACT[activation], _ptr(a), lda, _ptr(g), ldg,
           pdx, lddx, pdw, lddw, _ptr(db), _ptr(ws), nbytes)
@@ -1244,26 +1265,14 @@ def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=
         raise ValueError('colptr has %d entries, expected Dk + 1 = %d' % (colptr.numel(), Dk + 1))
     if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
         raise ValueError('values must be a contiguous vector of %d' % nnz)
-    mats = []
-    for t, nm in ((a, 'a'), (grad_a, 'grad_a')):
-        _dev(t, nm)
-        if t.dim() != 2:
-            raise ValueError('%s must be 2-D, got shape %s' % (nm, tuple(t.shape)))
-        if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 4)) or t.data_ptr() % 16):
-            t = t.contiguous()
-        mats.append(_rows(t, nm))
-    (a, lda), (g, ldg) = mats
+    (a, lda), (g, ldg) = _mat(a, 'a', align16=True), _mat(grad_a, 'grad_a', align16=True)
     D, dev = a.shape[1], a.device
     lda, ldg = (lda + 3) // 4 * 4, (ldg + 3) // 4 * 4          # a single row: no pitch of its own
     if a.shape[0] != N or tuple(g.shape) != (N, D):
         raise ValueError('a %s and grad_a %s do not fit N = %d' % (tuple(a.shape), tuple(g.shape), N))
     odw, odb = out if out is not None else (None, None)
     dw, pdw, lddw = _out_rows(odw, (D, Dk), dev, 'out dw') if want_dw else (None, None, 0)
-    db = None
-    if want_db:
-        db = torch.empty((D,), device=dev, dtype=torch.float32) if odb is None else _dev(odb, 'out db')
-        if tuple(db.shape) != (D,) or not db.is_contiguous():
-            raise ValueError('out db must be a contiguous vector of %d' % D)
+    db = _vec_out(odb, D, dev, 'out db') if want_db else None
     if not (want_dw or want_db):
         return None, None
     lib, h = _context(dev)
@@ -1278,24 +1287,6 @@ def dropout_bn_train_plan(N, D, has_bn=True):
     out = (C.c_int * 4)()
     check(_lib.load().laff_dropout_bn_train_plan(int(N), int(D), int(bool(has_bn)), out))
     return tuple(out)
-
-
-def _bn_rows(t, name):
-    """A 2-D device fp32 operand of the dropout + BatchNorm stage as (tensor, pitch): a non-unit inner stride is made dense first."""
-    _dev(t, name)
-    if t.dim() != 2:
-        raise ValueError('%s must be 2-D, got shape %s' % (name, tuple(t.shape)))
-    if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
-        t = t.contiguous()
-    return _rows(t, name)
-
-
-def _bn_vec(t, D, name):
-    """A contiguous device fp32 vector of D."""
-    _dev(t, name)
-    if tuple(t.shape) != (D,) or not t.is_contiguous():
-        raise ValueError('%s must be a contiguous vector of %d, got shape %s' % (name, D, tuple(t.shape)))
-    return t
 
 
 def _bn_seed(p, seed):
@@ -1314,21 +1305,20 @@ def dropout_bn_train(a, p, seed, weight, bias, running_mean, running_var, moment
     version counters are the caller's to bump).  weight None: no BatchNorm stage, y = a (.) mask / (1 - p), the other vectors are
     ignored.  Returns (y, save_mean, save_invstd), the last two None without a BatchNorm stage.  out: a y buffer, or a
     (y, save_mean, save_invstd) triple of buffers (None entries are allocated here; y may be a row view with a pitch)."""
-    a, lda = _bn_rows(a, 'a')
+    a, lda = _mat(a, 'a')
     (N, D), dev = a.shape, a.device
     p, seed = _bn_seed(p, seed)
     oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
     y, py, ldy = _out_rows(oy, (N, D), dev, 'out y')
     mean = invstd = None
     if weight is not None:
-        weight, bias = _bn_vec(weight, D, 'weight'), _bn_vec(bias, D, 'bias')
-        running_mean, running_var = _bn_vec(running_mean, D, 'running_mean'), _bn_vec(running_var, D, 'running_var')
-        mean = _bn_vec(omean, D, 'out save_mean') if omean is not None else torch.empty((D,), device=dev, dtype=torch.float32)
-        invstd = _bn_vec(oinv, D, 'out save_invstd') if oinv is not None else torch.empty((D,), device=dev, dtype=torch.float32)
+        weight, bias = _vec(weight, D, 'weight'), _vec(bias, D, 'bias')
+        running_mean, running_var = _vec(running_mean, D, 'running_mean'), _vec(running_var, D, 'running_var')
+        mean, invstd = _vec_out(omean, D, dev, 'out save_mean'), _vec_out(oinv, D, dev, 'out save_invstd')
     else:
         bias = running_mean = running_var = None
     nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ws = _workspace(nbytes, dev)
     lib, h = _context(dev)
     _call('dropout_bn_train', lib.laff_dropout_bn_train, h, _ptr(a), N, D, lda, p, _ptr(seed), _ptr(weight), _ptr(bias), _ptr(running_mean),
           _ptr(running_var), float(momentum), float(eps), py, ldy, _ptr(mean), _ptr(invstd), _ptr(ws), nbytes)
@@ -1340,28 +1330,27 @@ def dropout_bn_train_backward(grad_y, a, p, seed, weight, save_mean, save_invstd
     (the mask is recomputed), weight and the forward's save_mean / save_invstd (None, None, None: no BatchNorm stage, and then no
     dgamma / dbeta).  Returns (da | None, dgamma | None, dbeta | None).  out: a (da, dgamma, dbeta) triple of buffers (None entries
     are allocated here; da may be a row view with a pitch)."""
-    g, ldg = _bn_rows(grad_y, 'grad_y')
-    a, lda = _bn_rows(a, 'a')
+    g, ldg = _mat(grad_y, 'grad_y')
+    a, lda = _mat(a, 'a')
     (N, D), dev = a.shape, a.device
     if tuple(g.shape) != (N, D):
         raise ValueError('grad_y %s and a %s do not fit together' % (tuple(g.shape), tuple(a.shape)))
     p, seed = _bn_seed(p, seed)
     if weight is not None:
-        weight, save_mean = _bn_vec(weight, D, 'weight'), _bn_vec(save_mean, D, 'save_mean')
-        save_invstd = _bn_vec(save_invstd, D, 'save_invstd')
+        weight, save_mean = _vec(weight, D, 'weight'), _vec(save_mean, D, 'save_mean')
+        save_invstd = _vec(save_invstd, D, 'save_invstd')
     else:
         save_mean = save_invstd = None
         if want_dgamma or want_dbeta:
             raise ValueError('dgamma / dbeta are wanted, but there is no BatchNorm stage (weight is None)')
     oda, odg, odb = out if out is not None else (None, None, None)
     da, pda, ldda = _out_rows(oda, (N, D), dev, 'out da') if want_da else (None, None, 0)
-    vec = lambda o, nm: _bn_vec(o, D, nm) if o is not None else torch.empty((D,), device=dev, dtype=torch.float32)
-    dgamma = vec(odg, 'out dgamma') if want_dgamma else None
-    dbeta = vec(odb, 'out dbeta') if want_dbeta else None
+    dgamma = _vec_out(odg, D, dev, 'out dgamma') if want_dgamma else None
+    dbeta = _vec_out(odb, D, dev, 'out dbeta') if want_dbeta else None
     if not (want_da or want_dgamma or want_dbeta):
         return None, None, None
     nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ws = _workspace(nbytes, dev)
     lib, h = _context(dev)
     _call('dropout_bn_train_backward', lib.laff_dropout_bn_train_backward, h, _ptr(g), ldg, _ptr(a), N, D, lda, p, _ptr(seed), _ptr(weight),
           _ptr(save_mean), _ptr(save_invstd), pda, ldda, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)

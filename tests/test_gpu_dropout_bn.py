@@ -48,16 +48,11 @@ def _momentum(c):
     return 0.1 if (c[0] + c[1]) % 2 else 0.5
 
 
-def _geometry(rows, cols, layout):
-    ld = {'dense': cols, 'pitch4': (cols + 3) // 4 * 4 + 4, 'pitch3': cols + 3, 'offset': (cols + 3) // 4 * 4 + 4}[layout]
-    return ld, (1 if layout == 'offset' else 0)
-
-
 def _place(frames, t, layout):
     """A device copy of the 2-D CPU tensor t in `layout` inside a NaN frame; the pitch's slack is part of the frame's inside and is
     checked separately (_slack_intact)."""
     rows, cols = t.shape
-    ld, off = _geometry(rows, cols, layout)
+    ld, off = TR.pitch(cols, layout)
     flat = frames.floats(rows * ld + 4)
     flat.fill_(NAN)
     view = torch.as_strided(flat, (rows, cols), (ld, 1), flat.storage_offset() + off)
@@ -337,30 +332,6 @@ def test_graph_capture_replays_the_eager_bits():
 
 
 # ---- TransformNet(device_norm=True) -------------------------------------------------------------------------------------------------
-def _act(z, activation):
-    return {'tanh': torch.tanh, 'relu': torch.relu, 'sigmoid': torch.sigmoid, None: lambda t: t}[activation](z)
-
-
-def _layer_graph(dtype, W, b, x, dE, activation, bn, keep, p, eps=EPS, momentum=0.1):
-    """The reference's layer from torch modules on the CPU in `dtype`: Linear -> activation -> dropout by the given mask -> BatchNorm1d in
-    training mode.  Returns every compared tensor by name."""
-    Wt, bt = W.to(dtype).requires_grad_(True), b.to(dtype).requires_grad_(True)
-    xs = x.to(dtype).requires_grad_(True)
-    y = _act(xs @ Wt.T + bt, activation)
-    if keep is not None:
-        y = y * torch.from_numpy(keep).to(dtype) / (1.0 - p)
-    norm = None
-    if bn:
-        norm = torch.nn.BatchNorm1d(W.shape[0], eps=eps, momentum=momentum).to(dtype).train()
-        y = norm(y)
-    y.backward(dE.to(dtype))
-    out = {'y': y, 'x.grad': xs.grad, 'fc1.weight.grad': Wt.grad, 'fc1.bias.grad': bt.grad}
-    if bn:
-        out.update({'bn1.weight.grad': norm.weight.grad, 'bn1.bias.grad': norm.bias.grad, 'running_mean': norm.running_mean,
-                    'running_var': norm.running_var})
-    return {k: v.detach().double() for k, v in out.items()}
-
-
 class _SeedSpy:
     """Wraps ops.dropout_bn_train: keeps the seed tensors the module handed to it."""
 
@@ -380,15 +351,6 @@ class _SeedSpy:
 
 
 CONFIGS = [(True, 'tanh', 0.0), (True, 'relu', 0.0), (False, 'sigmoid', 0.0), (False, None, 0.0), (False, 'tanh', 0.2), (True, 'tanh', 0.2)]
-
-
-def _compare(got, ref, f32):
-    for k, g in got.items():
-        e32 = R.rel_err(f32[k], ref[k])
-        bound = max(4.0 * e32, TOL_UNIT)
-        err = R.rel_err(g.detach().cpu(), ref[k])
-        print('%-16s device %.3e  fp32 CPU %.3e  bound %.3e' % (k, err, e32, bound))
-        assert err <= bound, (k, err, bound)
 
 
 @pytest.mark.parametrize('batch_norm, activation, dropout', CONFIGS, ids=lambda v: str(v))
@@ -415,14 +377,14 @@ def test_transform_net_device_norm(batch_norm, activation, dropout, monkeypatch)
         assert abs(kept - (1.0 - dropout)) <= 5.0 * ((1.0 - dropout) * dropout / keep.size) ** 0.5, kept
         if not batch_norm:
             assert np.array_equal(y.detach().cpu().numpy() == 0, ~keep)
-    ref = _layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, keep, dropout)
-    f32 = _layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, keep, dropout)
+    ref = TR.layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, keep, dropout)
+    f32 = TR.layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, keep, dropout)
     got = {'y': y, 'x.grad': xd.grad, 'fc1.weight.grad': net.fc1.weight.grad, 'fc1.bias.grad': net.fc1.bias.grad}
     if batch_norm:
         got.update({'bn1.weight.grad': net.bn1.weight.grad, 'bn1.bias.grad': net.bn1.bias.grad, 'running_mean': net.bn1.running_mean,
                     'running_var': net.bn1.running_var})
         assert int(net.bn1.num_batches_tracked) == 1
-    _compare(got, ref, f32)
+    TR.compare(got, ref, f32)
     # plane(): the same route, plain and dense; `pending` is not used
     pending = []
     src, tile, scale, shift = net.plane(xd.detach(), heads=2, pending=pending)
@@ -472,11 +434,11 @@ def test_concat_train_passes_through_the_same_stage(monkeypatch):
     assert spy.calls == 1 and int(net.bn1.num_batches_tracked) == 1
     keep = R.keep_mask(spy.last(), N, D, 0.2)
     x = torch.cat([dense, counts], dim=1)
-    ref = _layer_graph(torch.float64, W, b, x, dE, 'tanh', True, keep, 0.2)
-    f32 = _layer_graph(torch.float32, W, b, x, dE, 'tanh', True, keep, 0.2)
+    ref = TR.layer_graph(torch.float64, W, b, x, dE, 'tanh', True, keep, 0.2)
+    f32 = TR.layer_graph(torch.float32, W, b, x, dE, 'tanh', True, keep, 0.2)
     got = {'y': y, 'fc1.weight.grad': net.fc1.weight.grad, 'fc1.bias.grad': net.fc1.bias.grad, 'bn1.weight.grad': net.bn1.weight.grad,
            'bn1.bias.grad': net.bn1.bias.grad, 'running_mean': net.bn1.running_mean, 'running_var': net.bn1.running_var}
-    _compare(got, ref, f32)
+    TR.compare(got, ref, f32)
     err = R.rel_err(xd.grad.cpu(), ref['x.grad'][:, :widths[0]])
     assert err <= max(4.0 * R.rel_err(f32['x.grad'][:, :widths[0]], ref['x.grad'][:, :widths[0]]), TOL_UNIT)
 

@@ -21,15 +21,12 @@ import pytest
 import torch
 
 import fc_bwd_ref as R
-import fuse_bwd_ref as FR
-import fuse_ref
 import train_ref as TR
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
 NAN = float('nan')
-TOL_UNIT = TR.TOL_UNIT
 
 # layouts of every operand and output: 'dense' rows on a 16-byte aligned base; 'pitch4' a wider pitch that keeps the rows 16-byte aligned
 # (the 16-byte loads, strided); 'pitch3' a wider pitch that does not (the generic loads); 'offset' a base pointer 4 bytes past a 16-byte
@@ -55,33 +52,6 @@ def _id(c):
     return 'N%d-Dk%d-D%d-%s-%s' % c
 
 
-def _geometry(rows, cols, layout):
-    ld = {'dense': cols, 'pitch4': (cols + 3) // 4 * 4 + 4, 'pitch3': cols + 3, 'offset': (cols + 3) // 4 * 4 + 4}[layout]
-    base = (ld + 3) // 4 * 4 + (1 if layout == 'offset' else 0)          # one row of canary in front
-    return ld, base, base + (rows + 1) * ld + 4
-
-
-def _place(t, layout):
-    """A device copy of the 2-D CPU tensor t in `layout`, NaN all around it: (buffer, view)."""
-    rows, cols = t.shape
-    ld, base, size = _geometry(rows, cols, layout)
-    buf = torch.full((size,), NAN, device=DEV)
-    view = torch.as_strided(buf, (rows, cols), (ld, 1), base)
-    view.copy_(t)
-    assert buf.data_ptr() % 16 == 0 and (view.data_ptr() % 16 == 4) == (layout == 'offset')
-    return buf, view
-
-
-def _out(rows, cols, layout):
-    return _place(torch.full((rows, cols), NAN), layout)
-
-
-def _out_vec(n, layout):
-    buf = torch.full((n + 8,), NAN, device=DEV)
-    lo = 1 if layout == 'offset' else 4
-    return buf, buf[lo:lo + n]
-
-
 @functools.lru_cache(maxsize=None)
 def _case(c):
     """The fp32 operands of a case on the CPU, the float64 reference and the bounds -- computed once, shared, never written."""
@@ -103,7 +73,7 @@ def _case(c):
 @functools.lru_cache(maxsize=None)
 def _device_inputs(c):
     cs = _case(c)
-    return tuple(_place(cs[k], c[4]) for k in ('x', 'w', 'a', 'da'))
+    return tuple(TR.place(cs[k], c[4]) for k in ('x', 'w', 'a', 'da'))
 
 
 def _launch(c, want=(True, True, True)):
@@ -111,7 +81,8 @@ def _launch(c, want=(True, True, True)):
     from laff_amd import ops
     N, Dk, D, act, layout = c
     (_, x), (_, w), (_, a), (_, da) = _device_inputs(c)
-    bufs = [_out(N, Dk, layout) if want[0] else None, _out(D, Dk, layout) if want[1] else None, _out_vec(D, layout) if want[2] else None]
+    bufs = [TR.pitched(N, Dk, layout) if want[0] else None, TR.pitched(D, Dk, layout) if want[1] else None,
+            TR.out_vec(D, layout != 'offset') if want[2] else None]
     res = ops.fc_backward(x, w, a, da, act, *want, out=tuple(None if b is None else b[1] for b in bufs))
     torch.cuda.synchronize()
     for name, b, r in zip(('dx', 'dw', 'db'), bufs, res):
@@ -186,7 +157,7 @@ def test_empty_batch_writes_zeros_and_nothing_else():
     Dk, D = 5, 7
     w = torch.randn(D, Dk, device=DEV)
     for layout in ('dense', 'pitch3'):
-        bdw, bdb = _out(D, Dk, layout), _out_vec(D, layout)
+        bdw, bdb = TR.pitched(D, Dk, layout), TR.out_vec(D, layout != 'offset')
         dx, dw, db = ops.fc_backward(torch.empty(0, Dk, device=DEV), w, torch.empty(0, D, device=DEV), torch.empty(0, D, device=DEV), 'tanh',
                                      out=(None, bdw[1], bdb[1]))
         torch.cuda.synchronize()
@@ -231,29 +202,6 @@ def test_graph_capture_replays_the_eager_bits():
 
 
 # ---- TransformNet in training mode --------------------------------------------------------------------------------------------------
-def _layer_graph(dtype, W, b, x, dE, activation, bn, mask, p):
-    """The reference's layer restated from torch modules on the CPU in `dtype`: Linear -> activation -> dropout by a given mask ->
-    BatchNorm1d in training mode.  Returns every compared tensor by name."""
-    lin = torch.nn.Linear(W.shape[1], W.shape[0]).to(dtype)
-    with torch.no_grad():
-        lin.weight.copy_(W)
-        lin.bias.copy_(b)
-    xs = x.to(dtype).requires_grad_(True)
-    y = a = R.forward_torch(xs, lin.weight, lin.bias, activation)
-    if mask is not None:
-        y = y * mask.to(dtype) / (1.0 - p)
-    out = {}
-    if bn:
-        norm = torch.nn.BatchNorm1d(W.shape[0]).to(dtype).train()
-        y = norm(y)
-    y.backward(dE.to(dtype))
-    out.update({'y': y, 'a': a, 'x.grad': xs.grad, 'fc1.weight.grad': lin.weight.grad, 'fc1.bias.grad': lin.bias.grad})
-    if bn:
-        out.update({'bn1.weight.grad': norm.weight.grad, 'bn1.bias.grad': norm.bias.grad, 'running_mean': norm.running_mean,
-                    'running_var': norm.running_var})
-    return {k: v.detach().double() for k, v in out.items()}
-
-
 @pytest.mark.parametrize('batch_norm, activation, dropout', [(True, 'tanh', 0.0), (True, 'relu', 0.0), (False, 'sigmoid', 0.0),
                                                              (False, None, 0.0), (False, 'tanh', 0.2)],
                          ids=lambda v: str(v))
@@ -279,18 +227,13 @@ def test_transform_net_train(batch_norm, activation, dropout):
         mask = (y.detach() != 0).cpu()
         kept = float(mask.double().mean())
         assert abs(kept - (1.0 - dropout)) <= 5.0 * ((1.0 - dropout) * dropout / mask.numel()) ** 0.5, kept
-    ref = _layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, mask, dropout)
-    f32 = _layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, mask, dropout)
+    ref = TR.layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, mask, dropout)
+    f32 = TR.layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, mask, dropout)
     got = {'y': y, 'x.grad': xd.grad, 'fc1.weight.grad': net.fc1.weight.grad, 'fc1.bias.grad': net.fc1.bias.grad}
     if batch_norm:
         got.update({'bn1.weight.grad': net.bn1.weight.grad, 'bn1.bias.grad': net.bn1.bias.grad, 'running_mean': net.bn1.running_mean,
                     'running_var': net.bn1.running_var})
-    for k, g in got.items():
-        e32 = R.rel_err(f32[k], ref[k])
-        bound = max(4.0 * e32, TOL_UNIT)
-        err = R.rel_err(g.detach().cpu(), ref[k])
-        print('%-16s device %.3e  fp32 CPU %.3e  bound %.3e' % (k, err, e32, bound))
-        assert err <= bound, (k, err, bound)
+    TR.compare(got, ref, f32)
     # plane(): the same bits, plain and dense, accepted by the training-mode fusion blocks as it is; `pending` is not used
     pending = []
     src, tile, scale, shift = net.plane(xd.detach(), heads=2, pending=pending)
@@ -326,47 +269,6 @@ def test_no_dx_launch_for_inputs_without_grad(monkeypatch):
 
 
 # ---- end to end: a LAFF tower's training step with every stage on this library's kernels -------------------------------------------
-class _Side(torch.nn.Module):
-    """One tower: L TransformNet projections (fc1 + tanh) whose plane() outputs go to the fusion block's fuse_planes."""
-
-    def __init__(self, dims, D, H):
-        super().__init__()
-        from laff_amd.model.Attention import Multi_head_MyApply_Attention
-        from laff_amd.model.model import TransformNet
-        self.proj = torch.nn.ModuleList([TransformNet((k, D), batch_norm=False, activation='tanh', dropout=0.0) for k in dims])
-        self.att = Multi_head_MyApply_Attention(D, H, D // H, with_ave=True, mul=True)
-
-    def forward(self, feats):
-        return self.att.fuse_planes([p.plane(f) for p, f in zip(self.proj, feats)])
-
-
-def _side_f64(side, feats, dtype=torch.float64):
-    """The same tower as a CPU torch graph in `dtype` with fuse_ref.attention: (E, its leaves by name)."""
-    leaves = {}
-
-    def leaf(name, t):
-        leaves[name] = t.detach().cpu().to(dtype).requires_grad_(True)
-        return leaves[name]
-    fs = [leaf('feat%d' % i, f) for i, f in enumerate(feats)]
-    planes = torch.stack([torch.tanh(f @ leaf('proj.%d.fc1.weight' % i, p.fc1.weight).T + leaf('proj.%d.fc1.bias' % i, p.fc1.bias))
-                          for i, (p, f) in enumerate(zip(side.proj, fs))], 1)
-    heads = [(leaf('att.attention_layer.%d.embedding_common.0.weight' % h, a.embedding_common[0].weight),
-              leaf('att.attention_layer.%d.embedding_common.0.bias' % h, a.embedding_common[0].bias),
-              a.global_emb_weight_net.weight.detach().cpu().to(dtype).reshape(1)) for h, a in enumerate(side.att.attention_layer)]
-    w = torch.stack([h[0].reshape(-1) for h in heads])
-    b = torch.cat([h[1].reshape(1) for h in heads])
-    gw = torch.cat([h[2].reshape(1) for h in heads])
-    H = len(heads)
-    keep = fuse_ref.F64
-    fuse_ref.F64 = dtype
-    try:
-        E = fuse_ref.attention(FR.heads_of(planes, H, planes.shape[2] // H, True), w, b, gw, with_ave=True, mul=True,
-                               l2norm_each_head=False)[0]
-    finally:
-        fuse_ref.F64 = keep
-    return E, leaves
-
-
 def test_end_to_end_two_towers_margin_loss():
     """L = 3, H = 2, d = 64, B = 16: TransformNet.train().plane() projections -> Multi_head_MyApply_Attention.train().fuse_planes on each
     side -> loss.MarginRankingLoss -> backward.  Every parameter gradient and both sides' input gradients against the same graph in
@@ -378,7 +280,7 @@ def test_end_to_end_two_towers_margin_loss():
     B, L, H, d, margin = 16, 3, 2, 64, 0.2
     dims = (24, 16, 8)
     def build():
-        txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
+        txt, vis = TR.Side(dims, H * d, H), TR.Side(dims, H * d, H)
         with torch.no_grad():
             for p in list(txt.proj) + list(vis.proj):
                 p.fc1.bias.uniform_(-0.2, 0.2)
@@ -386,15 +288,15 @@ def test_end_to_end_two_towers_margin_loss():
         ft = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            return (txt, vis, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+            return (txt, vis, ft, fv), TR.side_f64(txt, ft)[0], TR.side_f64(vis, fv)[0]
     txt, vis, ft, fv = TR.hinge_clear_seed(build, margin, 100)
     grads = {}
     for dtype in (torch.float64, torch.float32):
-        (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
+        (Et, lt), (Ev, lv) = TR.side_f64(txt, ft, dtype), TR.side_f64(vis, fv, dtype)
         TR.margin_loss_f64(Et, Ev, margin).backward()
         grads[dtype] = ({k: v.grad.double() for k, v in lt.items()}, {k: v.grad.double() for k, v in lv.items()}, Et, Ev)
     # sum_j |dT / dE_j| per side, from the float64 graph: one batched backward over the unit vectors of E
-    absjac = [TR.abs_jacobian(*_side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
+    absjac = [TR.abs_jacobian(*TR.side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
     # the device
     txt, vis = txt.to(DEV).train(), vis.to(DEV).train()
     dt = [f.to(DEV).requires_grad_(True) for f in ft]

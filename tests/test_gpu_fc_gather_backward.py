@@ -117,28 +117,12 @@ def _device_inputs(c):
     return tuple(None if t is None else t.to(DEV) for t in cs['csc']), cs['a'].to(DEV), cs['da'].to(DEV)
 
 
-def _out(rows, cols, layout):
-    """A NaN-filled device buffer and the (rows, cols) view of `layout` inside it."""
-    up = (cols + 3) // 4 * 4
-    ld, off = {'dense': (cols, 0), 'pitch4': (up + 4, 0), 'pitch3': (cols + 3, 0), 'window': (cols + 9, 3)}[layout]
-    base = (ld + 3) // 4 * 4 + off                                           # one row of canary in front
-    buf = torch.full((base + (rows + 1) * ld + 4,), NAN, device=DEV)
-    view = torch.as_strided(buf, (rows, cols), (ld, 1), base)
-    assert buf.data_ptr() % 16 == 0 and (view.data_ptr() % 16 == 0) == (layout != 'window')
-    return buf, view
-
-
-def _out_vec(n):
-    buf = torch.full((n + 8,), NAN, device=DEV)
-    return buf, buf[1:1 + n]                                                 # 4 bytes past a 16-byte boundary: db needs no more
-
-
 def _launch(c, want=(True, True), layout=None, csc=None):
     """ops.fc_gather_backward into NaN-framed buffers: (dw, db) (None where not wanted) after the frame check."""
     from laff_amd import ops
     N, Dk, D, act = c[:4]
     dcsc, a, da = _device_inputs(c)
-    bufs = [_out(D, Dk, layout or c[5]) if want[0] else None, _out_vec(D) if want[1] else None]
+    bufs = [TR.pitched(D, Dk, layout or c[5]) if want[0] else None, TR.out_vec(D) if want[1] else None]
     res = ops.fc_gather_backward(csc or dcsc, N, Dk, a, da, act, *want, out=tuple(None if b is None else b[1] for b in bufs))
     torch.cuda.synchronize()
     for name, b, r in zip(('dw', 'db'), bufs, res):
@@ -230,13 +214,13 @@ def test_empty_batch_and_empty_pattern_write_zeros_and_nothing_else():
     none = (torch.zeros(Dk + 1, dtype=torch.int32, device=DEV), torch.zeros(0, dtype=torch.int32, device=DEV), None)
     for layout in ('dense', 'pitch3', 'window'):
         # N == 0
-        bdw, bdb = _out(D, Dk, layout), _out_vec(D)
+        bdw, bdb = TR.pitched(D, Dk, layout), TR.out_vec(D)
         dw, db = ops.fc_gather_backward(none, 0, Dk, torch.empty(0, D, device=DEV), torch.empty(0, D, device=DEV), 'tanh', out=(bdw[1], bdb[1]))
         torch.cuda.synchronize()
         assert not dw.any() and not db.any() and not torch.signbit(dw).any() and TR.untouched_around(*bdw) and TR.untouched_around(*bdb)
         # nnz == 0 with rows: dW is zero, db is the column sum of dZ
         a, da = torch.tanh(torch.randn(5, D, device=DEV)), torch.randn(5, D, device=DEV)
-        bdw, bdb = _out(D, Dk, layout), _out_vec(D)
+        bdw, bdb = TR.pitched(D, Dk, layout), TR.out_vec(D)
         dw, db = ops.fc_gather_backward(none, 5, Dk, a, da, 'tanh', out=(bdw[1], bdb[1]))
         torch.cuda.synchronize()
         assert not dw.any() and not torch.signbit(dw).any() and TR.untouched_around(*bdw) and TR.untouched_around(*bdb)
@@ -330,24 +314,10 @@ def _bow(N, Dk, seed, per_row=6):
     return torch.sparse_csr_tensor(sp.crow_indices().to(torch.int32), sp.col_indices().to(torch.int32), sp.values(), size=(N, Dk)), dense
 
 
-def _compare(got, ref, f32, label):
-    """The rule of test_transform_net_train: per tensor, the larger of 4 x the float32 CPU graph's error and TOL_UNIT."""
-    worst = 0.0
-    for k, g in got.items():
-        e32 = R.rel_err(f32[k], ref[k])
-        bound = max(4.0 * e32, TR.TOL_UNIT)
-        err = R.rel_err(g.detach().cpu(), ref[k])
-        worst = max(worst, err / bound)
-        print('%s %-16s device %.3e  fp32 CPU %.3e  bound %.3e' % (label, k, err, e32, bound))
-        assert err <= bound, (k, err, bound)
-    return worst
-
-
 @pytest.mark.parametrize('batch_norm, activation, dropout', [(True, 'tanh', 0.0), (True, 'relu', 0.0), (False, 'sigmoid', 0.0),
                                                              (False, None, 0.0), (False, 'tanh', 0.2)],
                          ids=lambda v: str(v))
 def test_transform_net_train_on_a_csr_input(batch_norm, activation, dropout):
-    from test_gpu_fc_backward import _layer_graph
     from laff_amd.model.model import TransformNet
     torch.manual_seed(11)
     N = 33
@@ -368,13 +338,13 @@ def test_transform_net_train_on_a_csr_input(batch_norm, activation, dropout):
         mask = (y.detach() != 0).cpu()
         kept = float(mask.double().mean())
         assert abs(kept - (1.0 - dropout)) <= 5.0 * ((1.0 - dropout) * dropout / mask.numel()) ** 0.5, kept
-    ref = _layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, mask, dropout)
-    f32 = _layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, mask, dropout)
+    ref = TR.layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, mask, dropout)
+    f32 = TR.layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, mask, dropout)
     got = {'y': y, 'fc1.weight.grad': net.fc1.weight.grad, 'fc1.bias.grad': net.fc1.bias.grad}
     if batch_norm:
         got.update({'bn1.weight.grad': net.bn1.weight.grad, 'bn1.bias.grad': net.bn1.bias.grad, 'running_mean': net.bn1.running_mean,
                     'running_var': net.bn1.running_var})
-    _compare(got, ref, f32, 'csr')
+    TR.compare(got, ref, f32, 'csr')
     gw = net.fc1.weight.grad
     assert gw.is_contiguous() and gw.shape == net.fc1.weight.shape and gw.stride() == net.fc1.weight.stride()
     # plane(): plain and dense, accepted by the training-mode fusion blocks as it is
@@ -434,7 +404,6 @@ def test_adam_steps_the_gather_gradient_as_torch_does_and_the_attached_csc_is_us
 @pytest.mark.parametrize('kinds', [('dense', 'csr', 'dense'), ('csr', 'csr'), ('dense', 'dense', 'dense')], ids='-'.join)
 @pytest.mark.parametrize('batch_norm, activation', [(True, 'tanh'), (False, 'relu')], ids=str)
 def test_concat_train(kinds, batch_norm, activation, monkeypatch):
-    from test_gpu_fc_backward import _layer_graph
     from laff_amd import ops
     from laff_amd.model.model import TransformNet
     torch.manual_seed(17)
@@ -463,8 +432,8 @@ def test_concat_train(kinds, batch_norm, activation, monkeypatch):
     y = net.concat_train(segs)
     assert y.requires_grad and tuple(y.shape) == (N, D)
     y.backward(dE.to(DEV))
-    ref = _layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, None, 0.0)
-    f32 = _layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, None, 0.0)
+    ref = TR.layer_graph(torch.float64, W, b, x, dE, activation, batch_norm, None, 0.0)
+    f32 = TR.layer_graph(torch.float32, W, b, x, dE, activation, batch_norm, None, 0.0)
     got = {'y': y, 'fc1.weight.grad': net.fc1.weight.grad, 'fc1.bias.grad': net.fc1.bias.grad}
     if batch_norm:
         got.update({'bn1.weight.grad': net.bn1.weight.grad, 'bn1.bias.grad': net.bn1.bias.grad, 'running_mean': net.bn1.running_mean,
@@ -477,7 +446,7 @@ def test_concat_train(kinds, batch_norm, activation, monkeypatch):
         else:
             assert s.grad is None                                             # no gradient where none is required
         col += w
-    _compare(got, ref, f32, '-'.join(kinds))
+    TR.compare(got, ref, f32, '-'.join(kinds))
     assert net.fc1.weight.grad.is_contiguous() and net.fc1.weight.grad.shape == (D, K)
     # one call per segment; dx only for the segment that requires it; db formed exactly once, by the first segment's call
     assert len(calls) == kinds.count('dense') and len(gcalls) == kinds.count('csr')
@@ -499,13 +468,12 @@ def test_concat_train_refusals():
 def test_end_to_end_two_towers_with_a_bow_feature():
     """The graph of test_gpu_fc_backward.py::test_end_to_end_two_towers_margin_loss with the first text feature a CSR bag-of-words through
     TransformNet.train().plane().  Every parameter gradient and every dense input's gradient within train_ref.end_to_end_bound."""
-    from test_gpu_fc_backward import _Side, _side_f64
     from laff_amd import loss as laff_loss
     B, H, d, margin = 16, 2, 64, 0.2
     dims = (24, 16, 8)
 
     def build():
-        txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
+        txt, vis = TR.Side(dims, H * d, H), TR.Side(dims, H * d, H)
         with torch.no_grad():
             for p in list(txt.proj) + list(vis.proj):
                 p.fc1.bias.uniform_(-0.2, 0.2)
@@ -514,16 +482,16 @@ def test_end_to_end_two_towers_with_a_bow_feature():
         ft = [bow] + [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims[1:]]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            return (txt, vis, csr, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+            return (txt, vis, csr, ft, fv), TR.side_f64(txt, ft)[0], TR.side_f64(vis, fv)[0]
     txt, vis, csr, ft, fv = TR.hinge_clear_seed(build, margin, 200)
     with torch.no_grad():
-        assert TR.hinge_slack(_side_f64(txt, ft)[0], _side_f64(vis, fv)[0], margin) >= TR.HINGE_CLEAR
+        assert TR.hinge_slack(TR.side_f64(txt, ft)[0], TR.side_f64(vis, fv)[0], margin) >= TR.HINGE_CLEAR
     grads = {}
     for dtype in (torch.float64, torch.float32):
-        (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
+        (Et, lt), (Ev, lv) = TR.side_f64(txt, ft, dtype), TR.side_f64(vis, fv, dtype)
         TR.margin_loss_f64(Et, Ev, margin).backward()
         grads[dtype] = ({k: v.grad.double() for k, v in lt.items()}, {k: v.grad.double() for k, v in lv.items()}, Et, Ev)
-    absjac = [TR.abs_jacobian(*_side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
+    absjac = [TR.abs_jacobian(*TR.side_f64((txt, vis)[side], (ft, fv)[side])) for side in (0, 1)]
     txt, vis = txt.to(DEV).train(), vis.to(DEV).train()
     dt = [csr.to(DEV)] + [f.to(DEV).requires_grad_(True) for f in ft[1:]]
     dv = [f.to(DEV).requires_grad_(True) for f in fv]

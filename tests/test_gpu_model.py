@@ -480,3 +480,69 @@ def test_retrieve_walks_the_overflow_ladder(monkeypatch):
     model.retrieve(tl, vl, precision='fp16')
     assert len(calls) == 1 and calls[0][2] is False
     assert torch.equal(model.last_t2v_ranks.long(), want)
+
+
+def test_transform_net_derived_values_follow_their_parameters(monkeypatch):
+    """TransformNet's five derived values (bn_affine, weight_t, weight_t_block, weight_split, strip_weights) in eval mode: a second call
+    returns the very same objects; an in-place update of a parameter or buffer rebuilds exactly the values that read it, with the new
+    contents, and leaves the others; a bumped version counter alone (what a kernel writing through a raw pointer is followed by)
+    rebuilds too."""
+    from laff_amd import ops
+    from laff_amd.model import model as M
+    torch.manual_seed(21)
+    net = M.TransformNet((512, 64), batch_norm=True, activation='tanh').to(DEV).eval()
+    with torch.no_grad():
+        net.fc1.bias.normal_(0.0, 0.1)
+        net.bn1.running_mean.normal_()
+        net.bn1.running_var.uniform_(0.5, 1.5)
+    monkeypatch.setattr(M, 'FC_PRECISION', 'fp16x3')
+    x = torch.randn(33, 512, device=DEV)
+    assert ops.fc_strip_eligible(x, 64)
+    get = {'bn_affine': net.bn_affine, 'weight_t': net.weight_t, 'weight_t_block': lambda: net.weight_t_block(0, 8),
+           'weight_split': net.weight_split, 'strip_weights': net.strip_weights}
+
+    def objects(v):
+        return v if isinstance(v, tuple) else (v,)
+
+    def same(a, b):
+        return all(p is q for p, q in zip(objects(a), objects(b)))
+
+    def contents(name, v):
+        """What the kernels read of a value, as tensors."""
+        if name == 'weight_split':
+            return [v.buf, v.rscale]                       # K = 512: no padding, every byte is written
+        if name == 'strip_weights':
+            return ops.fc_act_bn_strip_grouped([dict(x=x, strip=v)])        # through the launch: the image's bytes that are read
+        return list(objects(v))
+
+    def from_scratch(name):
+        bn, w, b = net.bn1, net.fc1.weight.detach(), net.fc1.bias.detach()
+        scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).contiguous()
+        shift = (bn.bias.detach() - bn.running_mean * scale).contiguous()
+        return contents(name, {'bn_affine': lambda: (scale, shift), 'weight_t': lambda: w.t().contiguous(),
+                               'weight_t_block': lambda: w[:, :8].t().contiguous(), 'weight_split': lambda: ops.split_rows(w),
+                               'strip_weights': lambda: ops.fc_strip_pack(w, b, scale, shift, 'tanh')}[name]())
+
+    held = {k: g() for k, g in get.items()}
+    assert all(same(g(), held[k]) for k, g in get.items())
+    assert held['weight_split'] is not None and held['bn_affine'][0] is not None
+    readers = {'fc1.weight': {'weight_t', 'weight_t_block', 'weight_split', 'strip_weights'}, 'fc1.bias': {'strip_weights'},
+               'bn1.running_var': {'bn_affine', 'strip_weights'}}
+    for changed, rebuilt in readers.items():
+        stale = {k: [t.clone() for t in contents(k, held[k])] for k in rebuilt}
+        with torch.no_grad():
+            dict(net.state_dict(keep_vars=True))[changed].mul_(1.5)
+        now = {k: g() for k, g in get.items()}
+        for k in get:
+            assert same(now[k], held[k]) == (k not in rebuilt), (changed, k)
+            assert same(get[k](), now[k]), (changed, k)
+            if k in rebuilt:
+                new = contents(k, now[k])
+                assert all(torch.equal(p, q) for p, q in zip(new, from_scratch(k))), (changed, k)
+                assert not all(torch.equal(p, q) for p, q in zip(new, stale[k])), (changed, k)
+        held = now
+    # the version counter alone: the data is what it was, the folded affine is made again
+    torch.autograd.graph.increment_version(net.bn1.running_mean)
+    again = net.bn_affine()
+    assert not same(again, held['bn_affine']) and all(torch.equal(p, q) for p, q in zip(again, held['bn_affine']))
+    assert same(net.weight_t(), held['weight_t']) and same(net.weight_split(), held['weight_split'])

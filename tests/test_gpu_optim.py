@@ -25,8 +25,6 @@ import numpy as np
 import pytest
 import torch
 
-import fuse_bwd_ref as FR
-import fuse_ref
 import optim_ref as R
 import train_ref as TR
 
@@ -534,54 +532,13 @@ def test_state_dict_moves_to_torch_on_the_device():
 
 
 # ---- end to end: one training step with every stage on this library's kernels -------------------------------------------------------
-class _Side(torch.nn.Module):
-    """One tower: L TransformNet projections (fc1 + tanh) whose plane() outputs go to the fusion block's fuse_planes."""
-
-    def __init__(self, dims, D, H):
-        super().__init__()
-        from laff_amd.model.Attention import Multi_head_MyApply_Attention
-        from laff_amd.model.model import TransformNet
-        self.proj = torch.nn.ModuleList([TransformNet((k, D), batch_norm=False, activation='tanh', dropout=0.0) for k in dims])
-        self.att = Multi_head_MyApply_Attention(D, H, D // H, with_ave=True, mul=True)
-
-    def forward(self, feats):
-        return self.att.fuse_planes([p.plane(f) for p, f in zip(self.proj, feats)])
-
-
-def _side_f64(side, feats, dtype=torch.float64):
-    """The same tower as a CPU torch graph in `dtype` with fuse_ref.attention: (E, its leaves by name)."""
-    leaves = {}
-
-    def leaf(name, t):
-        leaves[name] = t.detach().cpu().to(dtype).clone().requires_grad_(True)     # a copy: the leaves are stepped by torch below
-        return leaves[name]
-    fs = [leaf('feat%d' % i, f) for i, f in enumerate(feats)]
-    planes = torch.stack([torch.tanh(f @ leaf('proj.%d.fc1.weight' % i, p.fc1.weight).T + leaf('proj.%d.fc1.bias' % i, p.fc1.bias))
-                          for i, (p, f) in enumerate(zip(side.proj, fs))], 1)
-    heads = [(leaf('att.attention_layer.%d.embedding_common.0.weight' % h, a.embedding_common[0].weight),
-              leaf('att.attention_layer.%d.embedding_common.0.bias' % h, a.embedding_common[0].bias),
-              a.global_emb_weight_net.weight.detach().cpu().to(dtype).reshape(1)) for h, a in enumerate(side.att.attention_layer)]
-    w = torch.stack([h[0].reshape(-1) for h in heads])
-    b = torch.cat([h[1].reshape(1) for h in heads])
-    gw = torch.cat([h[2].reshape(1) for h in heads])
-    H = len(heads)
-    keep = fuse_ref.F64
-    fuse_ref.F64 = dtype
-    try:
-        E = fuse_ref.attention(FR.heads_of(planes, H, planes.shape[2] // H, True), w, b, gw, with_ave=True, mul=True,
-                               l2norm_each_head=False)[0]
-    finally:
-        fuse_ref.F64 = keep
-    return E, leaves
-
-
 def _towers():
     """The graph of tests/test_gpu_fc_backward.py's end-to-end test: L = 3, H = 2, d = 64, B = 16, both sides, with its seed search
     (pairs 1e-4 clear of every hinge decision, in float64)."""
     B, H, d, margin = 16, 2, 64, 0.2
     dims = (24, 16, 8)
     def build():
-        txt, vis = _Side(dims, H * d, H), _Side(dims, H * d, H)
+        txt, vis = TR.Side(dims, H * d, H), TR.Side(dims, H * d, H)
         with torch.no_grad():
             for p in list(txt.proj) + list(vis.proj):
                 p.fc1.bias.uniform_(-0.2, 0.2)
@@ -589,7 +546,7 @@ def _towers():
         ft = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         fv = [z @ torch.randn(8, k) + 0.5 * torch.randn(B, k) for k in dims]
         with torch.no_grad():
-            return (txt, vis, ft, fv), _side_f64(txt, ft)[0], _side_f64(vis, fv)[0]
+            return (txt, vis, ft, fv), TR.side_f64(txt, ft, clone=True)[0], TR.side_f64(vis, fv, clone=True)[0]
     txt, vis, ft, fv = TR.hinge_clear_seed(build, margin, 100)
     return txt, vis, ft, fv, margin
 
@@ -604,7 +561,7 @@ def test_one_training_step_end_to_end():
     txt, vis, ft, fv, margin = _towers()
     stepped, norms = {}, {}
     for dtype in (torch.float64, torch.float32):
-        (Et, lt), (Ev, lv) = _side_f64(txt, ft, dtype), _side_f64(vis, fv, dtype)
+        (Et, lt), (Ev, lv) = TR.side_f64(txt, ft, dtype, clone=True), TR.side_f64(vis, fv, dtype, clone=True)
         TR.margin_loss_f64(Et, Ev, margin).backward()
         leaves = {'txt.' + k: v for k, v in lt.items() if not k.startswith('feat')}
         leaves.update({'vis.' + k: v for k, v in lv.items() if not k.startswith('feat')})
