@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 41
+#define LAFF_ABI_VERSION 42
 
 enum {
     LAFF_OK = 0,
@@ -626,6 +626,36 @@ int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, con
                                    const unsigned long long* seed /*device*/, const float* gamma /*[D], nullable*/,
                                    const float* save_mean /*[D]*/, const float* save_invstd /*[D]*/, float* dA /*nullable*/, int ldda,
                                    float* dgamma /*[D], nullable*/, float* dbeta /*[D], nullable*/, void* workspace, size_t workspace_bytes);
+
+/* Training-mode BatchNorm1d(H C) over a feature tiled H times, X.repeat(1, H): the no-transform feature of the LAFF towers
+ * (TransformNet(fc=False, batch_norm=True)); fp32.  X [N, ldx >= C]; the tiled input is never formed.  The H copies of a column share
+ * their batch statistics, which are formed once per input column:
+ *   mean[c] = sum_n X / N      var[c] = sum_n (X - mean)^2 / N (biased)      invstd = 1 / sqrt(var + eps)
+ *   Y [N, ldy >= H C]:  Y[n, hC+c] = gamma[hC+c] (X[n,c] - mean[c]) invstd[c] + beta[hC+c];   save_mean [C] = mean, save_invstd [C] = invstd
+ *   running_mean [H C], running_var [H C]: channel hC+c updated in place as laff_dropout_bn_train updates it (unbiased variance)
+ * Backward: dY [N, lddy >= H C], X, gamma, save_mean, save_invstd as the forward had and left them.
+ *   xhat = (X - mean) invstd      dbeta[hC+c] = sum_n dY[n,hC+c]      dgamma[hC+c] = sum_n dY[n,hC+c] xhat[n,c]
+ *   dU_h = gamma_h invstd (dY_h - dbeta_h / N - xhat dgamma_h / N)      dX [N, lddx >= C] = sum_h dU_h, h ascending
+ * Each of dX, dgamma, dbeta may be NULL (not formed); the others do not change by it.
+ * The arithmetic and the summation order are those of laff_dropout_bn_train: Y, running_mean, running_var, dgamma and dbeta are
+ * bit-identical to laff_dropout_bn_train / _backward with p = 0 on the materialised X.repeat(1, H), and save_mean[c] / save_invstd[c]
+ * equal that run's entries hC+c for every h.  N <= 256: one launch per direction; larger N: chunks of 256 rows, float64 partials in
+ * `workspace`, a second launch merges them in chunk order.
+ * Any C >= 1 and any pitches; bases 4-byte aligned.  Rows on 16-byte boundaries (bases, pitches, C % 4 == 0) take the kernels with
+ * 16-byte accesses, anything else the element-wise ones: same bits.  No atomics: two calls give the same bits.  No allocation, no host
+ * synchronisation; ordered on the ctx's stream, capturable.  workspace: 16-byte aligned, bytes of the plan (both directions).
+ * Refused before any GPU work (a NULL ctx is looked at last): H < 1, C < 1 or N < 0 (LAFF_E_SHAPE); N < 2, NULL gamma, eps <= 0,
+ * momentum outside [0, 1] (LAFF_E_ARG).
+ * laff_tile_bn_train_plan (host only, no ctx): out = {row chunks, workspace bytes, launches per direction, rows of a chunk}. */
+int laff_tile_bn_train_plan(int N, int C, int H, int out[4]);
+int laff_tile_bn_train(laff_ctx* ctx, const float* X /*[N, ldx >= C]*/, int N, int C, int ldx, int H, const float* gamma /*[H*C]*/,
+                       const float* beta /*[H*C]*/, float* running_mean /*[H*C]*/, float* running_var /*[H*C]*/, double momentum, double eps,
+                       float* Y /*[N, ldy >= H*C]*/, int ldy, float* save_mean /*[C]*/, float* save_invstd /*[C]*/, void* workspace,
+                       size_t workspace_bytes);
+int laff_tile_bn_train_backward(laff_ctx* ctx, const float* dY /*[N, lddy >= H*C]*/, int lddy, const float* X, int N, int C, int ldx, int H,
+                                const float* gamma, const float* save_mean, const float* save_invstd, float* dX /*[N, lddx >= C], nullable*/,
+                                int lddx, float* dgamma /*[H*C], nullable*/, float* dbeta /*[H*C], nullable*/, void* workspace,
+                                size_t workspace_bytes);
 
 /* The optimizer step: the global L2 norm of a list of gradients, the clip by it, and Adam / RMSprop with that clip folded in.
  * A tensor list is `count` flat fp32 device tensors of n[i] >= 0 elements, each base 4-byte aligned (nothing stronger is assumed; a

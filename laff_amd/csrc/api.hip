@@ -2120,6 +2120,83 @@ int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, con
     return LAFF_OK;
 }
 
+/* what the plan and both directions of the tiled BatchNorm refuse before any GPU work, a null ctx included */
+static int tile_bn_check(const char* fn, int N, int C, int H, bool has_gamma, bool batch) {
+    if (H < 1 || C < 1 || N < 0) return fail(LAFF_E_SHAPE, "%s: need N>=0, C>=1, H>=1 (N=%d C=%d H=%d)", fn, N, C, H);
+    if ((long long)H * C > INT_MAX || H > 65535) return fail(LAFF_E_SHAPE, "%s: H=%d heads of C=%d columns are out of range", fn, H, C);
+    if ((N + laff::BN_TRAIN_ROWS - 1) / laff::BN_TRAIN_ROWS > 65535) return fail(LAFF_E_SHAPE, "%s: N=%d beyond 65535 chunks of rows", fn, N);
+    if (batch && N < 2) return fail(LAFF_E_ARG, "%s: batch statistics need N >= 2 rows, got %d", fn, N);
+    if (batch && !has_gamma) return fail(LAFF_E_ARG, "%s: null gamma", fn);
+    return LAFF_OK;
+}
+
+int laff_tile_bn_train_plan(int N, int C, int H, int out[4]) {
+    if (!out) return fail(LAFF_E_ARG, "laff_tile_bn_train_plan: null out");
+    if (int rc = tile_bn_check("laff_tile_bn_train_plan", N, C, H, true, false)) return rc;
+    laff::BnTrainPlan p;
+    laff::tile_bn_train_plan(N, C, H, &p);
+    if (p.ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "laff_tile_bn_train_plan: workspace of %zu bytes", p.ws);
+    out[0] = p.chunks; out[1] = (int)p.ws; out[2] = p.launches; out[3] = laff::BN_TRAIN_ROWS;
+    return LAFF_OK;
+}
+
+int laff_tile_bn_train(laff_ctx* ctx, const float* X, int N, int C, int ldx, int H, const float* gamma, const float* beta,
+                       float* running_mean, float* running_var, double momentum, double eps, float* Y, int ldy, float* save_mean,
+                       float* save_invstd, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_tile_bn_train";
+    if (int rc = tile_bn_check(fn, N, C, H, gamma != nullptr, true)) return rc;
+    if (!(eps > 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g must be positive", fn, eps);
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LAFF_E_ARG, "%s: momentum=%g outside [0, 1]", fn, momentum);
+    CHECK_CTX(ctx);
+    if (!X || !Y || !beta || !running_mean || !running_var || !save_mean || !save_invstd)
+        return fail(LAFF_E_ARG, "%s: null X / Y / beta / running_mean / running_var / save_mean / save_invstd", fn);
+    if (ldx < C || ldy < H * C) return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (ldx=%d ldy=%d C=%d H=%d)", fn, ldx, ldy, C, H);
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+    if (!aligned4(X) || !aligned4(Y) || !aligned4(gamma) || !aligned4(beta) || !aligned4(running_mean) || !aligned4(running_var) ||
+        !aligned4(save_mean) || !aligned4(save_invstd))
+        return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
+    laff::BnTrainPlan plan;
+    laff::tile_bn_train_plan(N, C, H, &plan);
+    if (plan.ws)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    laff::TileBnTrainArgs a{};
+    a.X = X; a.Y = Y; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var;
+    a.save_mean = save_mean; a.save_invstd = save_invstd; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.N = N; a.C = C; a.H = H; a.ldx = ldx; a.ldy = ldy; a.momentum = momentum; a.eps = eps;
+    a.fast = aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && C % 4 == 0;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_tile_bn_train_forward(a, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_tile_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, const float* X, int N, int C, int ldx, int H, const float* gamma,
+                                const float* save_mean, const float* save_invstd, float* dX, int lddx, float* dgamma, float* dbeta,
+                                void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_tile_bn_train_backward";
+    if (int rc = tile_bn_check(fn, N, C, H, gamma != nullptr, true)) return rc;
+    CHECK_CTX(ctx);
+    if (!dX && !dgamma && !dbeta) return LAFF_OK;
+    if (!X || !dY || !save_mean || !save_invstd) return fail(LAFF_E_ARG, "%s: null X / dY / save_mean / save_invstd", fn);
+    if (ldx < C || lddy < H * C || (dX && lddx < C))
+        return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (ldx=%d lddy=%d lddx=%d C=%d H=%d)", fn, ldx, lddy, lddx, C, H);
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+    if (!aligned4(X) || !aligned4(dY) || !aligned4(dX) || !aligned4(gamma) || !aligned4(save_mean) || !aligned4(save_invstd) ||
+        !aligned4(dgamma) || !aligned4(dbeta))
+        return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
+    laff::BnTrainPlan plan;
+    laff::tile_bn_train_plan(N, C, H, &plan);
+    if (plan.ws)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    laff::TileBnTrainArgs a{};
+    a.X = X; a.dY = dY; a.dX = dX; a.gamma = gamma; a.save_mean = const_cast<float*>(save_mean);
+    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.N = N; a.C = C; a.H = H; a.ldx = ldx; a.lddy = lddy; a.lddx = lddx;
+    a.fast = aligned16(X) && aligned16(dY) && ldx % 4 == 0 && lddy % 4 == 0 && C % 4 == 0 && (!dX || (aligned16(dX) && lddx % 4 == 0));
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_tile_bn_train_backward(a, ctx->stream));
+    return LAFF_OK;
+}
+
 static_assert(sizeof(laff_optim_tensor) == 40, "laff_optim_tensor is five 8-byte words (laff_amd/ops.py fills the host array as such)");
 
 /* the launches of the calling thread's last optimizer call, by variant */

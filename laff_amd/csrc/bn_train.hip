@@ -24,20 +24,13 @@
 
 #include <algorithm>
 
-#include "attn_common.h"
-#include "kernels.h"
+#include "bn_train_common.h"
 
 namespace laff {
 
 namespace {
 
-constexpr int THREADS = DW_GROUPS * DW_LANES, COLS = 4 * DW_LANES, SLOTS = BN_TRAIN_ROWS / DW_GROUPS;
-enum { WHOLE = 0, PART = 1, APPLY = 2 };         // the one launch of an uncut shape; the two of a cut one
-
-struct f4a { float v[4]; };
-__device__ __forceinline__ f4a arr(float4 t) { return f4a{{t.x, t.y, t.z, t.w}}; }
-__device__ __forceinline__ float4 vec(const f4a& t) { return make_float4(t.v[0], t.v[1], t.v[2], t.v[3]); }
-__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+using namespace bn_strip;
 
 // Philox4x32-10, counter (c0, c1, 0, 0)
 __device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigned k0, unsigned k1) {
@@ -53,33 +46,6 @@ __device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigne
     }
     return make_uint4(c0, c1, c2, c3);
 }
-
-// columns [c, c + 4) of a row of D floats; FAST: one 16-byte access, else element by element and nothing past the row's end
-template <bool FAST>
-__device__ __forceinline__ float4 load4(const float* row, int c, int D) {
-    if constexpr (FAST) {
-        return *reinterpret_cast<const float4*>(row + c);
-    } else {
-        f4a v{};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (c + e < D) v.v[e] = row[c + e];
-        return vec(v);
-    }
-}
-template <bool FAST>
-__device__ __forceinline__ void store4(float* row, int c, int D, float4 t) {
-    if constexpr (FAST) {
-        *reinterpret_cast<float4*>(row + c) = t;
-    } else {
-        const f4a v = arr(t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (c + e < D) row[c + e] = v.v[e];
-    }
-}
-// the lane's four entries of a per-column vector, zeros past D (4-byte accesses: a [D] vector promises no more)
-__device__ __forceinline__ float4 cols4(const float* v, int c, int D) { return load4<false>(v, c, D); }
 
 // t (.) m for the mask bits `keep` (bit e: column c + e is kept)
 __device__ __forceinline__ float4 masked(float4 t, unsigned keep, float scale) {
@@ -111,11 +77,6 @@ __device__ __forceinline__ void load_strip(const BnTrainArgs& a, int r0, int nr,
     }
 }
 
-// the column sums of the block's chunk from each thread's own sum: the 32 group sums in group order, in the threads of group 0
-__device__ __forceinline__ float4 sum_groups(float4 own, float4 (&sh)[DW_GROUPS][DW_LANES]) {
-    return sum_rows_fixed_order_of([=](int) { return own; }, DW_GROUPS, sh);
-}
-
 template <bool FAST, int MODE>
 __global__ __launch_bounds__(THREADS) void bn_train_fwd(BnTrainArgs a) {
     __shared__ float4 sh[DW_GROUPS][DW_LANES];
@@ -130,52 +91,21 @@ __global__ __launch_bounds__(THREADS) void bn_train_fwd(BnTrainArgs a) {
     if (a.gamma) {
         double mean[4] = {0.0, 0.0, 0.0, 0.0}, m2[4] = {0.0, 0.0, 0.0, 0.0};          // of all N rows, in group 0
         if constexpr (MODE != APPLY) {
-            float4 own = zero4();
+            strip_mean_m2(u, nr, sh, bc[0], mean, m2);                                  // slots without a row hold zeros
+            if (MODE == PART && grp == 0) {
 #pragma unroll
-            for (int i = 0; i < SLOTS; ++i) own = add4(own, u[i]);                     // slots without a row hold zeros
-            const float4 s = sum_groups(own, sh);
-            if (grp == 0) bc[0][ln] = scl4(s, 1.0f / (float)nr);
-            __syncthreads();
-            const float4 mean0 = bc[0][ln];
-            float4 own1 = zero4(), own2 = zero4();
-#pragma unroll
-            for (int i = 0; i < SLOTS; ++i)
-                if (grp + i * DW_GROUPS < nr) {
-                    const float4 d = sub4(u[i], mean0);
-                    own1 = add4(own1, d);
-                    own2 = add4(own2, mul4(d, d));
-                }
-            const float4 s1 = sum_groups(own1, sh);
-            __syncthreads();
-            const float4 s2 = sum_groups(own2, sh);
-            if (grp == 0) {
-                const f4a m0 = arr(mean0), t1 = arr(s1), t2 = arr(s2);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    mean[e] = (double)m0.v[e] + (double)t1.v[e] / nr;
-                    m2[e] = fmax(0.0, (double)t2.v[e] - (double)t1.v[e] * (double)t1.v[e] / nr);
-                    if (MODE == PART && c + e < a.D) {
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < a.D) {
                         a.part[(size_t)(2 * blockIdx.y) * a.D + c + e] = mean[e];
                         a.part[(size_t)(2 * blockIdx.y + 1) * a.D + c + e] = m2[e];
                     }
-                }
             }
             if constexpr (MODE == PART) return;
         } else if (grp == 0) {
             // the chunks' (mean, M2) merged in chunk order
-            const int chunks = (a.N + BN_TRAIN_ROWS - 1) / BN_TRAIN_ROWS;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (c + e >= a.D) continue;
-                double n = 0.0;
-                for (int k = 0; k < chunks; ++k) {
-                    const double nk = (double)min(BN_TRAIN_ROWS, a.N - k * BN_TRAIN_ROWS), tot = n + nk;
-                    const double mk = a.part[(size_t)(2 * k) * a.D + c + e], delta = mk - mean[e];
-                    mean[e] += delta * (nk / tot);
-                    m2[e] += a.part[(size_t)(2 * k + 1) * a.D + c + e] + delta * delta * (n * nk / tot);
-                    n = tot;
-                }
-            }
+            for (int e = 0; e < 4; ++e)
+                if (c + e < a.D) merge_mean_m2(a.part, a.D, a.N, c + e, mean[e], m2[e]);
         }
         if (grp == 0) {
             // the mean goes to the rows as fp32 head and tail: at mean 30 and deviation 0.01 the head's rounding alone is 1e-4 of y
@@ -191,8 +121,7 @@ __global__ __launch_bounds__(THREADS) void bn_train_fwd(BnTrainArgs a) {
                 if (blockIdx.y == 0) {
                     a.save_mean[c + e] = mu.v[e];
                     a.save_invstd[c + e] = (float)invstd;
-                    a.running_mean[c + e] = (float)((1.0 - a.momentum) * a.running_mean[c + e] + a.momentum * mean[e]);
-                    a.running_var[c + e] = (float)((1.0 - a.momentum) * a.running_var[c + e] + a.momentum * (m2[e] / (a.N - 1)));
+                    update_running(a.running_mean + c + e, a.running_var + c + e, a.momentum, mean[e], m2[e], a.N);
                 }
             }
             bc[0][ln] = vec(mu);
@@ -240,12 +169,8 @@ __global__ __launch_bounds__(THREADS) void bn_train_bwd(BnTrainArgs a) {
         for (int i = 0; i < SLOTS; ++i) u[i] = grp + i * DW_GROUPS < nr ? mul4(sub4(u[i], mu), is) : zero4();      // xhat
         double tot[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};               // dbeta, dgamma over all N rows, in group 0
         if constexpr (MODE != APPLY) {
-            float4 own1 = zero4(), own2 = zero4();
-#pragma unroll
-            for (int i = 0; i < SLOTS; ++i) {
-                own1 = add4(own1, g[i]);
-                own2 = add4(own2, mul4(g[i], u[i]));
-            }
+            float4 own1, own2;
+            strip_dot(g, u, own1, own2);
             const float4 s1 = sum_groups(own1, sh);
             __syncthreads();
             const float4 s2 = sum_groups(own2, sh);
@@ -292,7 +217,7 @@ __global__ __launch_bounds__(THREADS) void bn_train_bwd(BnTrainArgs a) {
         __syncthreads();
         const float4 k1 = bc[0][ln], k2 = bc[1][ln], w = mul4(cols4(a.gamma, c, a.D), is);
 #pragma unroll
-        for (int i = 0; i < SLOTS; ++i) g[i] = mul4(w, sub4(sub4(g[i], k1), mul4(u[i], k2)));                       // dU
+        for (int i = 0; i < SLOTS; ++i) g[i] = bn_du(g[i], u[i], w, k1, k2);
     }
     if (a.out && c < a.D) {
 #pragma unroll

@@ -319,6 +319,30 @@ void bn_train_plan(int N, int D, bool has_bn, BnTrainPlan* p);
 hipError_t launch_bn_train_forward(const BnTrainArgs& a, hipStream_t st);
 hipError_t launch_bn_train_backward(const BnTrainArgs& a, hipStream_t st);
 
+// tile_bn_train.hip: training-mode BatchNorm1d(H C) over X.repeat(1, H) without forming the tiled input (laff_tile_bn_train,
+// laff_tile_bn_train_backward).  One struct for both directions, as BnTrainArgs; the statistics are per input column.
+struct TileBnTrainArgs {
+    const float* X;           // [N, ldx >= C]
+    const float* dY;          // backward: [N, lddy >= H C]
+    float* Y;                 // forward: [N, ldy >= H C]
+    float* dX;                // backward: [N, lddx >= C] or null
+    const float* gamma;       // [H C]
+    const float* beta;        // forward, [H C]
+    float* running_mean;      // forward, [H C], updated in place, as running_var
+    float* running_var;
+    float* save_mean;         // [C]; forward: written; backward: read, as save_invstd
+    float* save_invstd;
+    float* dgamma;            // backward, [H C] or null, as dbeta
+    float* dbeta;
+    double* part;             // workspace: forward [chunks][2][C] (mean, M2); backward [chunks][2][H C] (sum dY, sum dY xhat)
+    int N, C, H, ldx, ldy, lddy, lddx;
+    double momentum, eps;
+    int fast;                 // rows on 16-byte boundaries (bases and pitches) and C % 4 == 0
+};
+void tile_bn_train_plan(int N, int C, int H, BnTrainPlan* p);
+hipError_t launch_tile_bn_train_forward(const TileBnTrainArgs& a, hipStream_t st);
+hipError_t launch_tile_bn_train_backward(const TileBnTrainArgs& a, hipStream_t st);
+
 // optim.hip: global-norm clipping and the Adam / RMSprop step over a list of flat fp32 tensors (laff_grad_sqnorm, laff_grad_scale,
 // laff_optim_step)
 constexpr int OPTIM_CHUNK = 4096;        // elements of one chunk: 256 threads x 4 accesses of 16 bytes

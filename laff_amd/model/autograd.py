@@ -1,5 +1,5 @@
 """The autograd layer of the FC projection: the torch.autograd.Functions that TransformNet's training mode and the frame Linear run
-under (DESIGN.md sections 4.20, 4.24, 4.25).  Each is one forward launch of the library with its backward launches behind it, forms only
+under (DESIGN.md sections 4.20, 4.24, 4.25, 4.26).  Each is one forward launch of the library with its backward launches behind it, forms only
 the gradients that needs_input_grad asks for, and is once differentiable.
 
 The ops are reached as attributes of the `ops` module at call time: tests wrap them there and count the calls."""
@@ -169,3 +169,28 @@ class _DropoutBnFn(torch.autograd.Function):
         da, dgamma, dbeta = ops.dropout_bn_train_backward(grad_y, a, ctx.p, seed, _detached(weight), mean, invstd,
                                                           want_da=need[0], want_dgamma=bn and need[1], want_dbeta=bn and need[2])
         return da, dgamma, dbeta, None, None, None, None, None
+
+
+class _TileBnFn(torch.autograd.Function):
+    """y = BatchNorm1d(heads * C)(x.repeat(1, heads)) in training mode on laff_tile_bn_train, ops.tile_bn_train_backward behind it
+    (DESIGN.md section 4.26): the no-transform feature of the LAFF towers.  The tiled input is never formed; the statistics are saved per
+    input column.  x receives its gradient summed over the heads (the frame attention trains through it); a pre-extracted feature
+    needs none, and its launch walks no row twice.  running_mean / running_var are updated in place by the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, heads, weight, bias, running_mean, running_var, momentum, eps):
+        _fp32(x, 'the input')
+        x = _dense_input(x)
+        y, mean, invstd = ops.tile_bn_train(x, heads, weight.detach(), bias.detach(), running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(x, weight, mean, invstd)
+        ctx.heads = heads
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, mean, invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgamma, dbeta = ops.tile_bn_train_backward(grad_y, x, ctx.heads, weight.detach(), mean, invstd, want_dx=need[0],
+                                                       want_dgamma=need[2], want_dbeta=need[3])
+        return dx, None, dgamma, dbeta, None, None, None, None

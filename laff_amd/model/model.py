@@ -37,7 +37,7 @@ import torch.nn.functional as F
 from .. import loss as _loss
 from .. import ops
 from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention
-from .autograd import _csc_of, _DropoutBnFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params  # noqa: F401  (kept importable from here)
+from .autograd import _csc_of, _DropoutBnFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params, _TileBnFn  # noqa: F401  (kept importable from here)
 
 device = torch.device('cuda')
 float16 = False
@@ -309,7 +309,9 @@ class TransformNet(nn.Module):
     def _forward_train(self, x, heads=1, extra_shift=None):
         """Training mode: fc1 + activation under autograd (_FcActFn), then torch's own dropout and training-mode BatchNorm1d (batch
         statistics, running-stat updates), each a single elementwise / column pass with its own autograd.  What has no backward here
-        is refused by name."""
+        is refused by name.  Without an fc (the no-transform feature) there is a path with device_norm only: _forward_train_no_fc."""
+        if self.fc1 is None and self.device_norm:
+            return self._forward_train_no_fc(x, heads, extra_shift)
         if self.fc1 is None:
             raise NotImplementedError('training mode: a TransformNet without fc (fc=False%s) has no differentiable path; apply its '
                                       'BatchNorm upstream as a torch op' % (', tiled over %d heads' % heads if heads > 1 else ''))
@@ -325,6 +327,44 @@ class TransformNet(nn.Module):
         else:
             y = _FcActFn.apply(x, self.fc1.weight, self.fc1.bias, self.activation_name)
         return self._after_activation_train(y)
+
+    def _forward_train_no_fc(self, x, heads, extra_shift):
+        """Training mode of the no-transform feature with device_norm: BatchNorm1d on batch statistics over x, or over x tiled `heads`
+        times (x.repeat(1, heads), never formed: _TileBnFn, one launch each way, x receives its gradient summed over the heads).  An
+        input of the layer's own width -- heads == 1, or forward() on a pre-repeated input -- takes _DropoutBnFn like an fc's output."""
+        if extra_shift is not None:
+            raise NotImplementedError('training mode: extra_shift (the expert embedding) is not differentiable here; add it upstream '
+                                      'as a torch op')
+        if self.activation_name is not None:
+            raise NotImplementedError('activation without fc is never built by the reference towers')
+        self._device_norm_supported()
+        if x.layout != torch.strided or x.dim() != 2:
+            raise NotImplementedError('training mode: a TransformNet without fc takes a dense 2-D feature, got layout %s with %d '
+                                      'dimensions' % (x.layout, x.dim()))
+        if not (heads > 1 and x.shape[1] * heads == self.out_features):
+            if x.shape[1] != self.out_features:
+                raise ValueError('a TransformNet without fc of width %d takes that width, or 1 / %d of it tiled over the heads; got %d '
+                                 'columns' % (self.out_features, heads, x.shape[1]))
+            return self._after_activation_device(x)
+        bn = self.bn1
+        if bn is None:
+            raise NotImplementedError('training mode: a tiled TransformNet without fc and without BatchNorm is a plain repeat; the '
+                                      'reference towers never build it')
+        if self.dropout_p is not None:
+            raise NotImplementedError('training mode: dropout (p=%g) on a TransformNet without fc tiled over %d heads is refused: the '
+                                      'mask would differ per copy, and the reference never sets it' % (self.dropout_p, heads))
+        y = _TileBnFn.apply(x, heads, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+        self._running_stats_written()
+        return y
+
+    def _running_stats_written(self):
+        """A kernel wrote bn1's running statistics through raw pointers: their version counters are bumped here, or bn_affine's cache
+        would serve the statistics of before the step to the next .eval() forward.  num_batches_tracked counts the forward, as torch
+        does."""
+        bn = self.bn1
+        torch.autograd.graph.increment_version(bn.running_mean)
+        torch.autograd.graph.increment_version(bn.running_var)
+        bn.num_batches_tracked.add_(1)
 
     def _device_norm_supported(self):
         """device_norm: the BatchNorm1d settings that laff_dropout_bn_train does not compute are refused by name, before any launch."""
@@ -349,16 +389,12 @@ class TransformNet(nn.Module):
         return y if self.bn1 is None else self.bn1(y)
 
     def _after_activation_device(self, y):
-        """The same stage as one launch each way (_DropoutBnFn).  The kernel writes bn1's running statistics through raw pointers:
-        their version counters are bumped here, or bn_affine's cache would serve the statistics of before the step to the next
-        .eval() forward.  num_batches_tracked counts the forward, as torch does."""
+        """The same stage as one launch each way (_DropoutBnFn)."""
         bn = self.bn1
         if bn is None:
             return y if self.dropout_p is None else _DropoutBnFn.apply(y, None, None, None, None, self.dropout_p, 0.0, 0.0)
         y = _DropoutBnFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.dropout_p, bn.momentum, bn.eps)
-        torch.autograd.graph.increment_version(bn.running_mean)
-        torch.autograd.graph.increment_version(bn.running_var)
-        bn.num_batches_tracked.add_(1)
+        self._running_stats_written()
         return y
 
     def concat_train(self, segments):

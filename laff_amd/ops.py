@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1355,6 +1355,60 @@ def dropout_bn_train_backward(grad_y, a, p, seed, weight, save_mean, save_invstd
     _call('dropout_bn_train_backward', lib.laff_dropout_bn_train_backward, h, _ptr(g), ldg, _ptr(a), N, D, lda, p, _ptr(seed), _ptr(weight),
           _ptr(save_mean), _ptr(save_invstd), pda, ldda, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)
     return da, dgamma, dbeta
+
+
+def tile_bn_train_plan(N, C_in, H):
+    """laff_tile_bn_train_plan (host only) for N rows of C_in columns tiled over H heads: (row chunks of the column sums, workspace bytes
+    of either direction, launches per direction, rows of a chunk)."""
+    out = (C.c_int * 4)()
+    check(_lib.load().laff_tile_bn_train_plan(int(N), int(C_in), int(H), out))
+    return tuple(out)
+
+
+def tile_bn_train(x, heads, weight, bias, running_mean, running_var, momentum, eps, out=None):
+    """Training-mode BatchNorm1d(heads * W) over x.repeat(1, heads) on laff_tile_bn_train, the tiled input never formed: x (N, W) device
+    fp32 (a row view with a pitch is read in place), weight / bias / running_mean / running_var (heads * W,) contiguous device fp32 --
+    the running statistics are UPDATED IN PLACE through raw pointers (their version counters are the caller's to bump).  Returns
+    (y (N, heads * W), save_mean (W,), save_invstd (W,)): the statistics are per input column.  out: a y buffer, or a
+    (y, save_mean, save_invstd) triple of buffers (None entries are allocated here; y may be a row view with a pitch)."""
+    x, ldx = _mat(x, 'x')
+    (N, W), dev, H = x.shape, x.device, int(heads)
+    oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
+    weight, bias = _vec(weight, H * W, 'weight'), _vec(bias, H * W, 'bias')
+    running_mean, running_var = _vec(running_mean, H * W, 'running_mean'), _vec(running_var, H * W, 'running_var')
+    y, py, ldy = _out_rows(oy, (N, H * W), dev, 'out y')
+    mean, invstd = _vec_out(omean, W, dev, 'out save_mean'), _vec_out(oinv, W, dev, 'out save_invstd')
+    nbytes = tile_bn_train_plan(N, W, H)[1]
+    ws = _workspace(nbytes, dev)
+    lib, h = _context(dev)
+    _call('tile_bn_train', lib.laff_tile_bn_train, h, _ptr(x), N, W, ldx, H, _ptr(weight), _ptr(bias), _ptr(running_mean),
+          _ptr(running_var), float(momentum), float(eps), py, ldy, _ptr(mean), _ptr(invstd), _ptr(ws), nbytes)
+    return y, mean, invstd
+
+
+def tile_bn_train_backward(grad_y, x, heads, weight, save_mean, save_invstd, want_dx=True, want_dgamma=True, want_dbeta=True, out=None):
+    """Backward of tile_bn_train (laff_tile_bn_train_backward): grad_y (N, heads * W) and x (N, W) device fp32, weight and the forward's
+    save_mean / save_invstd.  Returns (dx (N, W) | None -- the heads' contributions summed in ascending order --, dgamma | None,
+    dbeta | None, both (heads * W,)).  out: a (dx, dgamma, dbeta) triple of buffers (None entries are allocated here; dx may be a row
+    view with a pitch)."""
+    g, ldg = _mat(grad_y, 'grad_y')
+    x, ldx = _mat(x, 'x')
+    (N, W), dev, H = x.shape, x.device, int(heads)
+    if tuple(g.shape) != (N, H * W):
+        raise ValueError('grad_y %s does not fit x %s tiled over %d heads' % (tuple(g.shape), tuple(x.shape), H))
+    weight, save_mean, save_invstd = _vec(weight, H * W, 'weight'), _vec(save_mean, W, 'save_mean'), _vec(save_invstd, W, 'save_invstd')
+    odx, odg, odb = out if out is not None else (None, None, None)
+    dx, pdx, lddx = _out_rows(odx, (N, W), dev, 'out dx') if want_dx else (None, None, 0)
+    dgamma = _vec_out(odg, H * W, dev, 'out dgamma') if want_dgamma else None
+    dbeta = _vec_out(odb, H * W, dev, 'out dbeta') if want_dbeta else None
+    if not (want_dx or want_dgamma or want_dbeta):
+        return None, None, None
+    nbytes = tile_bn_train_plan(N, W, H)[1]
+    ws = _workspace(nbytes, dev)
+    lib, h = _context(dev)
+    _call('tile_bn_train_backward', lib.laff_tile_bn_train_backward, h, _ptr(g), ldg, _ptr(x), N, W, ldx, H, _ptr(weight), _ptr(save_mean),
+          _ptr(save_invstd), pdx, lddx, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)
+    return dx, dgamma, dbeta
 
 
 def optim_plan(sizes):
