@@ -84,6 +84,7 @@ int metrics_read_back(laff_ctx* ctx, double out7[7], const char* flagged) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }                       // floats: every region of a float workspace starts on 16 bytes
 size_t round256(size_t b) { return (b + 255) / 256 * 256; }                 // bytes: every region of a byte workspace starts on 256 bytes
 
@@ -1967,7 +1968,6 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
     if (int rc = fc_backward_shape(fn, N, Dk, D)) return rc;
     if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", fn, act);
     if (dW && lddw < Dk) return fail(LAFF_E_SHAPE, "%s: lddw=%d < Dk=%d", fn, lddw, Dk);
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
     if (!aligned4(dW) || !aligned4(db)) return fail(LAFF_E_ALIGN, "%s: dW / db must be 4-byte aligned", fn);
     DeviceGuard g(ctx->device);
     if (N == 0) {                                /* the empty sum: zeros in dW and db, nothing else is read or written */
@@ -2000,7 +2000,6 @@ int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, c
         return fail(LAFF_E_SHAPE, "%s: need N>=0, nnz>=0, Dk>=1, D%%4==0, 4<=D<=8192 (N=%d nnz=%d Dk=%d D=%d)", fn, N, nnz, Dk, D);
     if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", fn, act);
     if (dW && lddw < Dk) return fail(LAFF_E_SHAPE, "%s: lddw=%d < Dk=%d", fn, lddw, Dk);
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
     if (!aligned4(dW) || !aligned4(db)) return fail(LAFF_E_ALIGN, "%s: dW / db must be 4-byte aligned", fn);
     if (!dW && !db) return LAFF_OK;
     const bool walk = dW && N > 0 && nnz > 0;    /* otherwise dW is the empty sum: zeros, and the pattern is not read */
@@ -2024,15 +2023,40 @@ int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, c
     return LAFF_OK;
 }
 
+/* The refusals and steps that the plain and the tiled BatchNorm entry points share; a layer of D columns is planned as
+   bn_train_plan(N, D, has_bn), the tiled one with D = H C.  The first three come before CHECK_CTX: the tests call them without a GPU. */
+static int bn_plan_out(const char* fn, int N, int D, bool has_bn, int out[4]) {
+    laff::BnTrainPlan p;
+    laff::bn_train_plan(N, D, has_bn, &p);
+    if (p.ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "%s: workspace of %zu bytes", fn, p.ws);
+    out[0] = p.chunks; out[1] = (int)p.ws; out[2] = p.launches; out[3] = laff::BN_TRAIN_ROWS;
+    return LAFF_OK;
+}
+static int bn_rows_check(const char* fn, int N, bool batch) {             /* at most one of the two can hold */
+    if ((N + laff::BN_TRAIN_ROWS - 1) / laff::BN_TRAIN_ROWS > 65535) return fail(LAFF_E_SHAPE, "%s: N=%d beyond 65535 chunks of rows", fn, N);
+    if (batch && N < 2) return fail(LAFF_E_ARG, "%s: batch statistics need N >= 2 rows, got %d", fn, N);
+    return LAFF_OK;
+}
+static int bn_eps_momentum_check(const char* fn, double eps, double momentum) {
+    if (!(eps > 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g must be positive", fn, eps);
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LAFF_E_ARG, "%s: momentum=%g outside [0, 1]", fn, momentum);
+    return LAFF_OK;
+}
+/* the float64 partials of a call in its checked workspace; null where the plan needs none */
+static int bn_part(const char* fn, int N, int D, bool has_bn, void* workspace, size_t workspace_bytes, double** part) {
+    laff::BnTrainPlan plan;
+    laff::bn_train_plan(N, D, has_bn, &plan);
+    *part = plan.ws ? (double*)workspace : nullptr;
+    return plan.ws ? need_workspace(fn, workspace, workspace_bytes, plan.ws) : LAFF_OK;
+}
+
 /* what both directions of the dropout + BatchNorm stage refuse before any GPU work, a null ctx included: the tests need no GPU */
 static int dropout_bn_check(const char* fn, int N, int D, double p, const void* seed, bool has_bn) {
     if (N < 0 || D < 1) return fail(LAFF_E_SHAPE, "%s: need N>=0, D>=1 (N=%d D=%d)", fn, N, D);
     if (!(p >= 0.0 && p < 1.0)) return fail(LAFF_E_ARG, "%s: p=%g outside [0, 1)", fn, p);
     if (p > 0.0 && !seed) return fail(LAFF_E_ARG, "%s: p > 0 needs a seed", fn);
     if (p == 0.0 && !has_bn) return fail(LAFF_E_ARG, "%s: p == 0 without a BatchNorm stage (null gamma): nothing to do", fn);
-    if (has_bn && N < 2) return fail(LAFF_E_ARG, "%s: batch statistics need N >= 2 rows, got %d", fn, N);
-    if ((N + laff::BN_TRAIN_ROWS - 1) / laff::BN_TRAIN_ROWS > 65535) return fail(LAFF_E_SHAPE, "%s: N=%d beyond 65535 chunks of rows", fn, N);
-    return LAFF_OK;
+    return bn_rows_check(fn, N, has_bn);
 }
 
 /* the dropout side of the arguments: thresh = floor(p 2^32) and fp32(1 / (1 - p)), in double on the host */
@@ -2042,15 +2066,14 @@ static void dropout_bn_mask(laff::BnTrainArgs& a, double p, const unsigned long 
     a.thresh = (unsigned)std::floor(p * 4294967296.0);
     a.scale = (float)(1.0 / (1.0 - p));
 }
+static int dropout_bn_seed_check(const char* fn, const unsigned long long* seed) {
+    return (reinterpret_cast<uintptr_t>(seed) & 7) ? fail(LAFF_E_ALIGN, "%s: seed must be 8-byte aligned", fn) : LAFF_OK;
+}
 
 int laff_dropout_bn_train_plan(int N, int D, int has_bn, int out[4]) {
     if (!out) return fail(LAFF_E_ARG, "laff_dropout_bn_train_plan: null out");
     if (N < 0 || D < 1) return fail(LAFF_E_SHAPE, "laff_dropout_bn_train_plan: need N>=0, D>=1 (N=%d D=%d)", N, D);
-    laff::BnTrainPlan p;
-    laff::bn_train_plan(N, D, has_bn != 0, &p);
-    if (p.ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "laff_dropout_bn_train_plan: workspace of %zu bytes", p.ws);
-    out[0] = p.chunks; out[1] = (int)p.ws; out[2] = p.launches; out[3] = laff::BN_TRAIN_ROWS;
-    return LAFF_OK;
+    return bn_plan_out("laff_dropout_bn_train_plan", N, D, has_bn != 0, out);
 }
 
 int laff_dropout_bn_train(laff_ctx* ctx, const float* A, int N, int D, int lda, double p, const unsigned long long* seed, const float* gamma,
@@ -2058,28 +2081,22 @@ int laff_dropout_bn_train(laff_ctx* ctx, const float* A, int N, int D, int lda, 
                           float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes) {
     const char* fn = "laff_dropout_bn_train";
     if (int rc = dropout_bn_check(fn, N, D, p, seed, gamma != nullptr)) return rc;
-    if (gamma) {
-        if (!(eps > 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g must be positive", fn, eps);
-        if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LAFF_E_ARG, "%s: momentum=%g outside [0, 1]", fn, momentum);
-    }
+    if (gamma)
+        if (int rc = bn_eps_momentum_check(fn, eps, momentum)) return rc;
     CHECK_CTX(ctx);
     if (N == 0) return LAFF_OK;
     if (!A || !Y) return fail(LAFF_E_ARG, "%s: null A / Y", fn);
     if (gamma && (!beta || !running_mean || !running_var || !save_mean || !save_invstd))
         return fail(LAFF_E_ARG, "%s: a BatchNorm stage needs beta, running_mean, running_var, save_mean and save_invstd", fn);
     if (lda < D || ldy < D) return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (lda=%d ldy=%d D=%d)", fn, lda, ldy, D);
-    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     if (!aligned4(A) || !aligned4(Y) || !aligned4(gamma) || !aligned4(beta) || !aligned4(running_mean) || !aligned4(running_var) ||
         !aligned4(save_mean) || !aligned4(save_invstd))
         return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
-    if (reinterpret_cast<uintptr_t>(seed) & 7) return fail(LAFF_E_ALIGN, "%s: seed must be 8-byte aligned", fn);
-    laff::BnTrainPlan plan;
-    laff::bn_train_plan(N, D, gamma != nullptr, &plan);
-    if (plan.ws)
-        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    if (int rc = dropout_bn_seed_check(fn, seed)) return rc;
     laff::BnTrainArgs a{};
+    if (int rc = bn_part(fn, N, D, gamma != nullptr, workspace, workspace_bytes, &a.part)) return rc;
     a.A = A; a.out = Y; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var;
-    a.save_mean = save_mean; a.save_invstd = save_invstd; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.save_mean = save_mean; a.save_invstd = save_invstd;
     a.N = N; a.D = D; a.lda = lda; a.ldo = ldy; a.momentum = momentum; a.eps = eps;
     a.fast = aligned16(A) && aligned16(Y) && lda % 4 == 0 && ldy % 4 == 0 && D % 4 == 0;
     dropout_bn_mask(a, p, seed);
@@ -2100,18 +2117,14 @@ int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, con
     if (gamma && (!save_mean || !save_invstd)) return fail(LAFF_E_ARG, "%s: a BatchNorm stage needs save_mean and save_invstd", fn);
     if (lda < D || lddy < D || (dA && ldda < D))
         return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (lda=%d lddy=%d ldda=%d D=%d)", fn, lda, lddy, ldda, D);
-    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     if (!aligned4(A) || !aligned4(dY) || !aligned4(dA) || !aligned4(gamma) || !aligned4(save_mean) || !aligned4(save_invstd) ||
         !aligned4(dgamma) || !aligned4(dbeta))
         return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
-    if (reinterpret_cast<uintptr_t>(seed) & 7) return fail(LAFF_E_ALIGN, "%s: seed must be 8-byte aligned", fn);
-    laff::BnTrainPlan plan;
-    laff::bn_train_plan(N, D, gamma != nullptr, &plan);
-    if (plan.ws)
-        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
+    if (int rc = dropout_bn_seed_check(fn, seed)) return rc;
     laff::BnTrainArgs a{};
+    if (int rc = bn_part(fn, N, D, gamma != nullptr, workspace, workspace_bytes, &a.part)) return rc;
     a.A = A; a.dY = dY; a.out = dA; a.gamma = gamma; a.save_mean = const_cast<float*>(save_mean);
-    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta;
     a.N = N; a.D = D; a.lda = lda; a.lddy = lddy; a.ldo = ldda;
     a.fast = aligned16(A) && aligned16(dY) && lda % 4 == 0 && lddy % 4 == 0 && D % 4 == 0 && (!dA || (aligned16(dA) && ldda % 4 == 0));
     dropout_bn_mask(a, p, seed);
@@ -2124,8 +2137,7 @@ int laff_dropout_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, con
 static int tile_bn_check(const char* fn, int N, int C, int H, bool has_gamma, bool batch) {
     if (H < 1 || C < 1 || N < 0) return fail(LAFF_E_SHAPE, "%s: need N>=0, C>=1, H>=1 (N=%d C=%d H=%d)", fn, N, C, H);
     if ((long long)H * C > INT_MAX || H > 65535) return fail(LAFF_E_SHAPE, "%s: H=%d heads of C=%d columns are out of range", fn, H, C);
-    if ((N + laff::BN_TRAIN_ROWS - 1) / laff::BN_TRAIN_ROWS > 65535) return fail(LAFF_E_SHAPE, "%s: N=%d beyond 65535 chunks of rows", fn, N);
-    if (batch && N < 2) return fail(LAFF_E_ARG, "%s: batch statistics need N >= 2 rows, got %d", fn, N);
+    if (int rc = bn_rows_check(fn, N, batch)) return rc;
     if (batch && !has_gamma) return fail(LAFF_E_ARG, "%s: null gamma", fn);
     return LAFF_OK;
 }
@@ -2133,11 +2145,7 @@ static int tile_bn_check(const char* fn, int N, int C, int H, bool has_gamma, bo
 int laff_tile_bn_train_plan(int N, int C, int H, int out[4]) {
     if (!out) return fail(LAFF_E_ARG, "laff_tile_bn_train_plan: null out");
     if (int rc = tile_bn_check("laff_tile_bn_train_plan", N, C, H, true, false)) return rc;
-    laff::BnTrainPlan p;
-    laff::tile_bn_train_plan(N, C, H, &p);
-    if (p.ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "laff_tile_bn_train_plan: workspace of %zu bytes", p.ws);
-    out[0] = p.chunks; out[1] = (int)p.ws; out[2] = p.launches; out[3] = laff::BN_TRAIN_ROWS;
-    return LAFF_OK;
+    return bn_plan_out("laff_tile_bn_train_plan", N, H * C, true, out);
 }
 
 int laff_tile_bn_train(laff_ctx* ctx, const float* X, int N, int C, int ldx, int H, const float* gamma, const float* beta,
@@ -2145,23 +2153,18 @@ int laff_tile_bn_train(laff_ctx* ctx, const float* X, int N, int C, int ldx, int
                        float* save_invstd, void* workspace, size_t workspace_bytes) {
     const char* fn = "laff_tile_bn_train";
     if (int rc = tile_bn_check(fn, N, C, H, gamma != nullptr, true)) return rc;
-    if (!(eps > 0.0)) return fail(LAFF_E_ARG, "%s: eps=%g must be positive", fn, eps);
-    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LAFF_E_ARG, "%s: momentum=%g outside [0, 1]", fn, momentum);
+    if (int rc = bn_eps_momentum_check(fn, eps, momentum)) return rc;
     CHECK_CTX(ctx);
     if (!X || !Y || !beta || !running_mean || !running_var || !save_mean || !save_invstd)
         return fail(LAFF_E_ARG, "%s: null X / Y / beta / running_mean / running_var / save_mean / save_invstd", fn);
     if (ldx < C || ldy < H * C) return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (ldx=%d ldy=%d C=%d H=%d)", fn, ldx, ldy, C, H);
-    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     if (!aligned4(X) || !aligned4(Y) || !aligned4(gamma) || !aligned4(beta) || !aligned4(running_mean) || !aligned4(running_var) ||
         !aligned4(save_mean) || !aligned4(save_invstd))
         return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
-    laff::BnTrainPlan plan;
-    laff::tile_bn_train_plan(N, C, H, &plan);
-    if (plan.ws)
-        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
     laff::TileBnTrainArgs a{};
+    if (int rc = bn_part(fn, N, H * C, true, workspace, workspace_bytes, &a.part)) return rc;
     a.X = X; a.Y = Y; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var;
-    a.save_mean = save_mean; a.save_invstd = save_invstd; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.save_mean = save_mean; a.save_invstd = save_invstd;
     a.N = N; a.C = C; a.H = H; a.ldx = ldx; a.ldy = ldy; a.momentum = momentum; a.eps = eps;
     a.fast = aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && C % 4 == 0;
     DeviceGuard g(ctx->device);
@@ -2179,17 +2182,13 @@ int laff_tile_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, const 
     if (!X || !dY || !save_mean || !save_invstd) return fail(LAFF_E_ARG, "%s: null X / dY / save_mean / save_invstd", fn);
     if (ldx < C || lddy < H * C || (dX && lddx < C))
         return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (ldx=%d lddy=%d lddx=%d C=%d H=%d)", fn, ldx, lddy, lddx, C, H);
-    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     if (!aligned4(X) || !aligned4(dY) || !aligned4(dX) || !aligned4(gamma) || !aligned4(save_mean) || !aligned4(save_invstd) ||
         !aligned4(dgamma) || !aligned4(dbeta))
         return fail(LAFF_E_ALIGN, "%s: every fp32 pointer must be 4-byte aligned", fn);
-    laff::BnTrainPlan plan;
-    laff::tile_bn_train_plan(N, C, H, &plan);
-    if (plan.ws)
-        if (int rc = need_workspace(fn, workspace, workspace_bytes, plan.ws)) return rc;
     laff::TileBnTrainArgs a{};
+    if (int rc = bn_part(fn, N, H * C, true, workspace, workspace_bytes, &a.part)) return rc;
     a.X = X; a.dY = dY; a.dX = dX; a.gamma = gamma; a.save_mean = const_cast<float*>(save_mean);
-    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta; a.part = plan.ws ? (double*)workspace : nullptr;
+    a.save_invstd = const_cast<float*>(save_invstd); a.dgamma = dgamma; a.dbeta = dbeta;
     a.N = N; a.C = C; a.H = H; a.ldx = ldx; a.lddy = lddy; a.lddx = lddx;
     a.fast = aligned16(X) && aligned16(dY) && ldx % 4 == 0 && lddy % 4 == 0 && C % 4 == 0 && (!dX || (aligned16(dX) && lddx % 4 == 0));
     DeviceGuard g(ctx->device);

@@ -339,7 +339,7 @@ struct TileBnTrainArgs {
     double momentum, eps;
     int fast;                 // rows on 16-byte boundaries (bases and pitches) and C % 4 == 0
 };
-void tile_bn_train_plan(int N, int C, int H, BnTrainPlan* p);
+// its plan is bn_train_plan(N, H C, true): the backward's partials; the forward's are 1 / H of them
 hipError_t launch_tile_bn_train_forward(const TileBnTrainArgs& a, hipStream_t st);
 hipError_t launch_tile_bn_train_backward(const TileBnTrainArgs& a, hipStream_t st);
 

@@ -209,12 +209,6 @@ hipError_t launch(const TileBnTrainArgs& a, int row_blocks, int head_blocks, int
 
 }  // namespace
 
-void tile_bn_train_plan(int N, int C, int H, BnTrainPlan* p) {
-    p->chunks = std::max(1, (N + BN_TRAIN_ROWS - 1) / BN_TRAIN_ROWS);
-    p->launches = p->chunks > 1 ? 2 : 1;
-    p->ws = p->chunks > 1 ? (size_t)p->chunks * 2 * H * C * sizeof(double) : 0;       // the backward's partials; the forward's are 1 / H
-}
-
 hipError_t launch_tile_bn_train_forward(const TileBnTrainArgs& a, hipStream_t st) {
     const int row_blocks = (a.N + BN_TRAIN_ROWS - 1) / BN_TRAIN_ROWS;
     if (row_blocks == 1) return launch<true, WHOLE>(a, 1, a.H, 1, st);

@@ -157,6 +157,13 @@ def _size_query(symbol_name, *ints):
     return n.value
 
 
+def _plan_query(symbol_name, n, *ints):
+    """A laff_*_plan style query: symbol(ints..., int out[n]) -> out as a tuple."""
+    out = (C.c_int * n)()
+    check(getattr(_lib.load(), symbol_name)(*[int(i) for i in ints], out))
+    return tuple(out)
+
+
 def _offsets(off, off_host, name):
     """The offsets of a ragged batch (laff_amd/ragged.py): off [N+1] int32 on the device and off_host, the same on the host.
     Returns (off, off_host as a contiguous int32 array, N)."""
@@ -1187,9 +1194,7 @@ def fuse_backward(planes, H, d, w, b, gw, flags, grad_E, want_param_grads=True, 
 def fc_backward_plan(N, Dk, D, want_dx=True, want_dw=True):
     """laff_fc_backward_plan (host only): (chunks of dW's and db's sum over N, workspace bytes for the wanted outputs -- db's always
     counted --, chunks of dX's sum over D, tile variants: bit 0 dW and bit 1 dX on 128 x 128 tiles, else 64 x 64)."""
-    out = (C.c_int * 4)()
-    check(_lib.load().laff_fc_backward_plan(int(N), int(Dk), int(D), int(bool(want_dx)), int(bool(want_dw)), out))
-    return tuple(out)
+    return _plan_query('laff_fc_backward_plan', 4, N, Dk, D, bool(want_dx), bool(want_dw))
 
 
 def fc_backward(x, weight, a, grad_a, activation, want_dx=True, want_dw=True, want_db=True, out=None):
@@ -1284,9 +1289,25 @@ def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=
 def dropout_bn_train_plan(N, D, has_bn=True):
     """laff_dropout_bn_train_plan (host only): (row chunks of the column sums -- 1 without a BatchNorm stage --, workspace bytes,
     launches per direction, rows of a chunk)."""
-    out = (C.c_int * 4)()
-    check(_lib.load().laff_dropout_bn_train_plan(int(N), int(D), int(bool(has_bn)), out))
-    return tuple(out)
+    return _plan_query('laff_dropout_bn_train_plan', 4, N, D, bool(has_bn))
+
+
+def _bn_fwd_out(out, shape, width, dev, has_bn=True):
+    """((y, its pointer, its pitch), save_mean, save_invstd) from `out`, a y buffer or a triple; the statistics are (width,) or None."""
+    oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
+    y = _out_rows(oy, shape, dev, 'out y')
+    if not has_bn:
+        return y, None, None
+    return y, _vec_out(omean, width, dev, 'out save_mean'), _vec_out(oinv, width, dev, 'out save_invstd')
+
+
+def _bn_bwd_out(out, shape, width, dev, name, want_dx, want_dgamma, want_dbeta):
+    """((d_input, its pointer, its pitch), dgamma, dbeta) from `out`, a triple or None; the last two are (width,), the unwanted None."""
+    odx, odg, odb = out if out is not None else (None, None, None)
+    dx = _out_rows(odx, shape, dev, 'out ' + name) if want_dx else (None, None, 0)
+    dgamma = _vec_out(odg, width, dev, 'out dgamma') if want_dgamma else None
+    dbeta = _vec_out(odb, width, dev, 'out dbeta') if want_dbeta else None
+    return dx, dgamma, dbeta
 
 
 def _bn_seed(p, seed):
@@ -1308,15 +1329,12 @@ def dropout_bn_train(a, p, seed, weight, bias, running_mean, running_var, moment
     a, lda = _mat(a, 'a')
     (N, D), dev = a.shape, a.device
     p, seed = _bn_seed(p, seed)
-    oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
-    y, py, ldy = _out_rows(oy, (N, D), dev, 'out y')
-    mean = invstd = None
     if weight is not None:
         weight, bias = _vec(weight, D, 'weight'), _vec(bias, D, 'bias')
         running_mean, running_var = _vec(running_mean, D, 'running_mean'), _vec(running_var, D, 'running_var')
-        mean, invstd = _vec_out(omean, D, dev, 'out save_mean'), _vec_out(oinv, D, dev, 'out save_invstd')
     else:
         bias = running_mean = running_var = None
+    (y, py, ldy), mean, invstd = _bn_fwd_out(out, (N, D), D, dev, weight is not None)
     nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
     ws = _workspace(nbytes, dev)
     lib, h = _context(dev)
@@ -1343,10 +1361,7 @@ def dropout_bn_train_backward(grad_y, a, p, seed, weight, save_mean, save_invstd
         save_mean = save_invstd = None
         if want_dgamma or want_dbeta:
             raise ValueError('dgamma / dbeta are wanted, but there is no BatchNorm stage (weight is None)')
-    oda, odg, odb = out if out is not None else (None, None, None)
-    da, pda, ldda = _out_rows(oda, (N, D), dev, 'out da') if want_da else (None, None, 0)
-    dgamma = _vec_out(odg, D, dev, 'out dgamma') if want_dgamma else None
-    dbeta = _vec_out(odb, D, dev, 'out dbeta') if want_dbeta else None
+    (da, pda, ldda), dgamma, dbeta = _bn_bwd_out(out, (N, D), D, dev, 'da', want_da, want_dgamma, want_dbeta)
     if not (want_da or want_dgamma or want_dbeta):
         return None, None, None
     nbytes = dropout_bn_train_plan(N, D, weight is not None)[1]
@@ -1360,9 +1375,7 @@ def dropout_bn_train_backward(grad_y, a, p, seed, weight, save_mean, save_invstd
 def tile_bn_train_plan(N, C_in, H):
     """laff_tile_bn_train_plan (host only) for N rows of C_in columns tiled over H heads: (row chunks of the column sums, workspace bytes
     of either direction, launches per direction, rows of a chunk)."""
-    out = (C.c_int * 4)()
-    check(_lib.load().laff_tile_bn_train_plan(int(N), int(C_in), int(H), out))
-    return tuple(out)
+    return _plan_query('laff_tile_bn_train_plan', 4, N, C_in, H)
 
 
 def tile_bn_train(x, heads, weight, bias, running_mean, running_var, momentum, eps, out=None):
@@ -1373,11 +1386,9 @@ def tile_bn_train(x, heads, weight, bias, running_mean, running_var, momentum, e
     (y, save_mean, save_invstd) triple of buffers (None entries are allocated here; y may be a row view with a pitch)."""
     x, ldx = _mat(x, 'x')
     (N, W), dev, H = x.shape, x.device, int(heads)
-    oy, omean, oinv = out if isinstance(out, (tuple, list)) else (out, None, None)
     weight, bias = _vec(weight, H * W, 'weight'), _vec(bias, H * W, 'bias')
     running_mean, running_var = _vec(running_mean, H * W, 'running_mean'), _vec(running_var, H * W, 'running_var')
-    y, py, ldy = _out_rows(oy, (N, H * W), dev, 'out y')
-    mean, invstd = _vec_out(omean, W, dev, 'out save_mean'), _vec_out(oinv, W, dev, 'out save_invstd')
+    (y, py, ldy), mean, invstd = _bn_fwd_out(out, (N, H * W), W, dev)
     nbytes = tile_bn_train_plan(N, W, H)[1]
     ws = _workspace(nbytes, dev)
     lib, h = _context(dev)
@@ -1397,10 +1408,7 @@ def tile_bn_train_backward(grad_y, x, heads, weight, save_mean, save_invstd, wan
     if tuple(g.shape) != (N, H * W):
         raise ValueError('grad_y %s does not fit x %s tiled over %d heads' % (tuple(g.shape), tuple(x.shape), H))
     weight, save_mean, save_invstd = _vec(weight, H * W, 'weight'), _vec(save_mean, W, 'save_mean'), _vec(save_invstd, W, 'save_invstd')
-    odx, odg, odb = out if out is not None else (None, None, None)
-    dx, pdx, lddx = _out_rows(odx, (N, W), dev, 'out dx') if want_dx else (None, None, 0)
-    dgamma = _vec_out(odg, H * W, dev, 'out dgamma') if want_dgamma else None
-    dbeta = _vec_out(odb, H * W, dev, 'out dbeta') if want_dbeta else None
+    (dx, pdx, lddx), dgamma, dbeta = _bn_bwd_out(out, (N, W), H * W, dev, 'dx', want_dx, want_dgamma, want_dbeta)
     if not (want_dx or want_dgamma or want_dbeta):
         return None, None, None
     nbytes = tile_bn_train_plan(N, W, H)[1]
@@ -1541,9 +1549,7 @@ def frame_fuse(frames, lens, w, b, gw, flags, out=None):
 def frame_fuse_backward_plan(count, B, Fmax, d, want_dw=True):
     """laff_frame_fuse_backward_plan (host only): (workspace bytes, kernel variant -- the 256-column chunks a lane owns: 1 / 2 / 4 for
     d <= 256 / 512 / 1024 --, launches of the main kernel, partial rows of dw per feature)."""
-    out = (C.c_int * 4)()
-    check(_lib.load().laff_frame_fuse_backward_plan(int(count), int(B), int(Fmax), int(d), int(bool(want_dw)), out))
-    return tuple(out)
+    return _plan_query('laff_frame_fuse_backward_plan', 4, count, B, Fmax, d, bool(want_dw))
 
 
 def frame_fuse_backward(frames_list, lens, params, flags, grad_list, want_param_grads=True, out=None):
