@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 42
+#define LAFF_ABI_VERSION 43
 
 enum {
     LAFF_OK = 0,
@@ -656,6 +656,34 @@ int laff_tile_bn_train_backward(laff_ctx* ctx, const float* dY /*[N, lddy >= H*C
                                 const float* gamma, const float* save_mean, const float* save_invstd, float* dX /*[N, lddx >= C], nullable*/,
                                 int lddx, float* dgamma /*[H*C], nullable*/, float* dbeta /*[H*C], nullable*/, void* workspace,
                                 size_t workspace_bytes);
+
+/* The expert stage of a LAFF tower in training mode (model/model.py:1848-1873, :1653-1694 of the reference): the expert embedding added
+ * to each of the L projected planes and `l2norm(local_embs, dim=2)` after it, written as the stacked tensor the fusion reads in place.
+ * One launch for all L planes; fp32.  x: HOST array of L device pointers, x[l] [N, ldx[l] >= D] (ldx a HOST array), D = H d columns.
+ * expert [L, lde >= D] or NULL; l2norm 0 / 1; both off is refused (the towers never ask for a plain copy).
+ *   v = x[l][n, :] + expert[l, :]   (x without expert)        r = 1 / (sqrt(sum_c v^2) + 1e-13 + 1e-14)   (as laff_plane_row_norms)
+ *   Y: element (n, l, c) at n ldn + l ldl + c:  v r, or v without l2norm;      rnorm [L][N] = r  (only with l2norm)
+ * Backward: dY in Y's layout (the fusion backward's gradient of the stacked tensor, in place), x, expert, rnorm as the forward had and
+ * left them.  With s = sqrt(sum_c v^2) and g = dY[n, l, :]:
+ *   dv = r g - v (r^2 / s) (v . g), the second term 0 where s == 0;  dv = g without l2norm
+ *   dx[l] [N, lddx[l] >= D] = dv  (every plane, HOST arrays as x / ldx)      d_expert [L, D] dense, or NULL = sum_n dv
+ * d_expert is a two-stage sum: each block of the backward launch adds the dv of its 16 rows in ascending order and stores the partial
+ * to `workspace` ([blocks][L][D] floats), a second small launch adds the partials in block order.  The block count depends on N only.
+ * No atomics: two calls give the same bits.  No allocation, no host synchronisation; ordered on the ctx's stream, capturable (the
+ * pointer and pitch arrays are read on the host at the call).  N == 0 touches nothing, except d_expert = 0.
+ * Refused before any GPU work (a NULL ctx is looked at last): L outside [1, 8], D % 4 != 0, D < 4, D > 8192, N < 0, a pitch below D,
+ * stacked pitches that overlap (LAFF_E_SHAPE); no expert and no l2norm, a NULL array / plane / stacked tensor, l2norm without rnorm,
+ * d_expert without expert, a workspace below the plan's bytes when d_expert is asked (LAFF_E_ARG); a base that is not 16-byte aligned
+ * or a pitch that is no multiple of 4 floats (LAFF_E_ALIGN).
+ * laff_expert_stage_train_plan (host only, no ctx): out = {blocks of the backward launch per plane, workspace bytes}. */
+int laff_expert_stage_train_plan(int N, int L, int D, int out[2]);
+int laff_expert_stage_train(laff_ctx* ctx, const float* const* x /*host [L]*/, const int* ldx /*host [L]*/, int N, int L, int D,
+                            const float* expert /*[L, lde >= D], nullable*/, int lde, int l2norm, float* Y, int ldn, int ldl,
+                            float* rnorm /*[L][N], with l2norm*/);
+int laff_expert_stage_train_backward(laff_ctx* ctx, const float* dY, int ldn, int ldl, const float* const* x /*host [L]*/,
+                                     const int* ldx /*host [L]*/, int N, int L, int D, const float* expert, int lde, int l2norm,
+                                     const float* rnorm, float* const* dx /*host [L]*/, const int* lddx /*host [L]*/,
+                                     float* d_expert /*[L, D], nullable*/, void* workspace, size_t workspace_bytes);
 
 /* The optimizer step: the global L2 norm of a list of gradients, the clip by it, and Adam / RMSprop with that clip folded in.
  * A tensor list is `count` flat fp32 device tensors of n[i] >= 0 elements, each base 4-byte aligned (nothing stronger is assumed; a

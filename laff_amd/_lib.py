@@ -11,7 +11,7 @@ ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 
 class Plane(C.Structure):
@@ -173,6 +173,10 @@ SIGNATURES = {
     'laff_tile_bn_train_plan': (C.c_int, [_I, _I, _I, C.POINTER(_I)]),
     'laff_tile_bn_train': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, C.c_double, C.c_double, _P, _I, _P, _P, _P, C.c_size_t]),
     'laff_tile_bn_train_backward': (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, C.c_size_t]),
+    'laff_expert_stage_train_plan': (C.c_int, [_I, _I, _I, C.POINTER(_I)]),
+    'laff_expert_stage_train': (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(_I), _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
+    'laff_expert_stage_train_backward': (C.c_int, [_P, _P, _I, _I, C.POINTER(C.c_void_p), C.POINTER(_I), _I, _I, _I, _P, _I, _I, _P,
+                                                   C.POINTER(C.c_void_p), C.POINTER(_I), _P, _P, C.c_size_t]),
     'laff_optim_plan': (C.c_int, [_I, C.POINTER(C.c_longlong), C.POINTER(_I)]),
     'laff_optim_last_launches': (C.c_int, [C.POINTER(_I)]),
     'laff_grad_sqnorm': (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _P, C.c_size_t]),

@@ -61,6 +61,18 @@ class config(object):
     vis_frame_addFC = False
     t2v_bow = T2V(0)
     t2v_w2v = T2V(0)
+    # what enable_training() reads, at the reference's defaults (configs/base_config.py:84-100, :167, :245)
+    loss = 'mrl'
+    margin = 0.2
+    direction = 't2i'
+    max_violation = True
+    cost_style = 'sum'
+    optimizer = 'rmsprop'
+    lr = 0.0001
+    lr_decay_rate = 0.99
+    grad_clip = 2
+    multi_space = True
+    negative = False
 
 
 def make_config(vid_dims, txt_dims, D=4096, heads=8, model_name='LAFF', vis_no_transform=(), txt_no_transform=(),

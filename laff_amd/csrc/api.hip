@@ -2196,6 +2196,93 @@ int laff_tile_bn_train_backward(laff_ctx* ctx, const float* dY, int lddy, const 
     return LAFF_OK;
 }
 
+/* what the plan and both directions of the expert stage refuse before any GPU work, a null ctx included: the tests need no GPU */
+static int expert_stage_shape(const char* fn, int N, int L, int D) {
+    if (L < 1 || L > laff::EXPERT_MAX_PLANES) return fail(LAFF_E_SHAPE, "%s: need 1 <= L <= %d planes, got %d", fn, laff::EXPERT_MAX_PLANES, L);
+    if (D < 4 || D % 4 != 0 || D > 8192) return fail(LAFF_E_SHAPE, "%s: need D %% 4 == 0 and 4 <= D <= 8192, got %d", fn, D);
+    if (N < 0) return fail(LAFF_E_SHAPE, "%s: need N >= 0, got %d", fn, N);
+    return LAFF_OK;
+}
+static int expert_stage_check(const char* fn, int N, int L, int D, const float* const* x, const int* ldx, const char* xname,
+                              const float* expert, int lde, int l2norm, const float* stacked, int ldn, int ldl, const char* sname,
+                              const float* rnorm) {
+    if (int rc = expert_stage_shape(fn, N, L, D)) return rc;
+    if (!expert && !l2norm) return fail(LAFF_E_ARG, "%s: neither an expert table nor l2norm: a plain copy is not provided", fn);
+    if (N == 0) return LAFF_OK;                    /* no rows: nothing is addressed (torch hands null pointers for empty tensors) */
+    if (!x || !ldx || !stacked) return fail(LAFF_E_ARG, "%s: null %s / its pitches / %s", fn, xname, sname);
+    if (l2norm && !rnorm) return fail(LAFF_E_ARG, "%s: l2norm needs rnorm", fn);
+    for (int l = 0; l < L; ++l) {
+        if (!x[l]) return fail(LAFF_E_ARG, "%s: null %s[%d]", fn, xname, l);
+        if (ldx[l] < D) return fail(LAFF_E_SHAPE, "%s: the row pitch of %s[%d] is below D (%d < %d)", fn, xname, l, ldx[l], D);
+        if (ldx[l] % 4 != 0 || !aligned16(x[l]))
+            return fail(LAFF_E_ALIGN, "%s: the rows of %s[%d] must be 16-byte aligned (base and pitch %d)", fn, xname, l, ldx[l]);
+    }
+    if (expert && lde < D) return fail(LAFF_E_SHAPE, "%s: the row pitch of expert is below D (%d < %d)", fn, lde, D);
+    if (expert && (lde % 4 != 0 || !aligned16(expert))) return fail(LAFF_E_ALIGN, "%s: the rows of expert must be 16-byte aligned (base and pitch %d)", fn, lde);
+    if (ldn < D || ldl < D || !((long long)ldn >= (long long)(L - 1) * ldl + D || (long long)ldl >= (long long)(N > 0 ? N - 1 : 0) * ldn + D))
+        return fail(LAFF_E_SHAPE, "%s: the pitches of %s (row %d, plane %d) do not hold [N=%d, L=%d, D=%d] without overlap", fn, sname, ldn, ldl, N, L, D);
+    if (ldn % 4 != 0 || ldl % 4 != 0 || !aligned16(stacked))
+        return fail(LAFF_E_ALIGN, "%s: the rows of %s must be 16-byte aligned (base, row pitch %d, plane pitch %d)", fn, sname, ldn, ldl);
+    if (rnorm && !aligned4(rnorm)) return fail(LAFF_E_ALIGN, "%s: rnorm must be 4-byte aligned", fn);
+    return LAFF_OK;
+}
+
+int laff_expert_stage_train_plan(int N, int L, int D, int out[2]) {
+    const char* fn = "laff_expert_stage_train_plan";
+    if (!out) return fail(LAFF_E_ARG, "%s: null out", fn);
+    if (int rc = expert_stage_shape(fn, N, L, D)) return rc;
+    int chunks;
+    size_t ws;
+    laff::expert_stage_plan(N, L, D, &chunks, &ws);
+    if (ws > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "%s: workspace of %zu bytes", fn, ws);
+    out[0] = chunks; out[1] = (int)ws;
+    return LAFF_OK;
+}
+
+int laff_expert_stage_train(laff_ctx* ctx, const float* const* x, const int* ldx, int N, int L, int D, const float* expert, int lde,
+                            int l2norm, float* Y, int ldn, int ldl, float* rnorm) {
+    const char* fn = "laff_expert_stage_train";
+    if (int rc = expert_stage_check(fn, N, L, D, x, ldx, "x", expert, lde, l2norm, Y, ldn, ldl, "Y", rnorm)) return rc;
+    CHECK_CTX(ctx);
+    if (N == 0) return LAFF_OK;
+    laff::ExpertStageArgs a{};
+    for (int l = 0; l < L; ++l) { a.x[l] = x[l]; a.ldx[l] = ldx[l]; }
+    a.expert = expert; a.lde = lde; a.Y = Y; a.rnorm = l2norm ? rnorm : nullptr; a.N = N; a.L = L; a.D = D; a.l2norm = l2norm != 0;
+    a.ldn = ldn; a.ldl = ldl;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_expert_stage_forward(a, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_expert_stage_train_backward(laff_ctx* ctx, const float* dY, int ldn, int ldl, const float* const* x, const int* ldx, int N, int L,
+                                     int D, const float* expert, int lde, int l2norm, const float* rnorm, float* const* dx, const int* lddx,
+                                     float* d_expert, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_expert_stage_train_backward";
+    if (int rc = expert_stage_check(fn, N, L, D, x, ldx, "x", expert, lde, l2norm, dY, ldn, ldl, "dY", rnorm)) return rc;
+    if (N > 0 && (!dx || !lddx)) return fail(LAFF_E_ARG, "%s: null dx / its pitches", fn);
+    for (int l = 0; l < L && N > 0; ++l) {
+        if (!dx[l]) return fail(LAFF_E_ARG, "%s: null dx[%d]", fn, l);
+        if (lddx[l] < D) return fail(LAFF_E_SHAPE, "%s: the row pitch of dx[%d] is below D (%d < %d)", fn, l, lddx[l], D);
+        if (lddx[l] % 4 != 0 || !aligned16(dx[l]))
+            return fail(LAFF_E_ALIGN, "%s: the rows of dx[%d] must be 16-byte aligned (base and pitch %d)", fn, l, lddx[l]);
+    }
+    if (d_expert && !expert) return fail(LAFF_E_ARG, "%s: d_expert without an expert table", fn);
+    if (d_expert && !aligned16(d_expert)) return fail(LAFF_E_ALIGN, "%s: d_expert must be 16-byte aligned", fn);
+    int chunks;
+    size_t ws;
+    laff::expert_stage_plan(N, L, D, &chunks, &ws);
+    if (d_expert && ws)
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, ws)) return rc;
+    CHECK_CTX(ctx);
+    laff::ExpertStageArgs a{};
+    for (int l = 0; l < L && N > 0; ++l) { a.x[l] = x[l]; a.ldx[l] = ldx[l]; a.dx[l] = dx[l]; a.lddx[l] = lddx[l]; }
+    a.expert = expert; a.lde = lde; a.dY = dY; a.rnorm = l2norm ? const_cast<float*>(rnorm) : nullptr; a.N = N; a.L = L; a.D = D;
+    a.l2norm = l2norm != 0; a.ldn = ldn; a.ldl = ldl; a.d_expert = d_expert; a.part = d_expert && ws ? (float*)workspace : nullptr;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_expert_stage_backward(a, ctx->stream));
+    return LAFF_OK;
+}
+
 static_assert(sizeof(laff_optim_tensor) == 40, "laff_optim_tensor is five 8-byte words (laff_amd/ops.py fills the host array as such)");
 
 /* the launches of the calling thread's last optimizer call, by variant */

@@ -343,6 +343,28 @@ struct TileBnTrainArgs {
 hipError_t launch_tile_bn_train_forward(const TileBnTrainArgs& a, hipStream_t st);
 hipError_t launch_tile_bn_train_backward(const TileBnTrainArgs& a, hipStream_t st);
 
+// expert_train.hip: the expert stage of the towers in training mode (laff_expert_stage_train, laff_expert_stage_train_backward): the
+// expert embedding added to each plane and the row norm over all D columns, into / out of the stacked [N, L, D] tensor of the fusion.
+// One struct for both directions.
+constexpr int EXPERT_MAX_PLANES = 8;
+constexpr int EXPERT_ROWS = 16;           // rows of one block of the backward: one partial column sum of d_expert per block
+struct ExpertStageArgs {
+    const float* x[EXPERT_MAX_PLANES];    // [N, ldx[l] >= D] each
+    float* dx[EXPERT_MAX_PLANES];         // backward: [N, lddx[l] >= D] each
+    int ldx[EXPERT_MAX_PLANES], lddx[EXPERT_MAX_PLANES];
+    const float* expert;                  // [L, lde >= D] or null
+    float* Y;                             // forward: element (n, l, c) at n ldn + l ldl + c
+    const float* dY;                      // backward: the same layout
+    float* rnorm;                         // [L][N]; forward: written, backward: read; null without l2norm
+    float* part;                          // backward: [chunks][L][D] partial column sums, or null (d_expert not formed)
+    float* d_expert;                      // backward: [L, D] dense, or null
+    int N, L, D, lde, l2norm;
+    long ldn, ldl;
+};
+void expert_stage_plan(int N, int L, int D, int* chunks, size_t* ws);
+hipError_t launch_expert_stage_forward(const ExpertStageArgs& a, hipStream_t st);
+hipError_t launch_expert_stage_backward(const ExpertStageArgs& a, hipStream_t st);
+
 // optim.hip: global-norm clipping and the Adam / RMSprop step over a list of flat fp32 tensors (laff_grad_sqnorm, laff_grad_scale,
 // laff_optim_step)
 constexpr int OPTIM_CHUNK = 4096;        // elements of one chunk: 256 threads x 4 accesses of 16 bytes

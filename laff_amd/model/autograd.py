@@ -1,5 +1,5 @@
 """The autograd layer of the FC projection: the torch.autograd.Functions that TransformNet's training mode and the frame Linear run
-under (DESIGN.md sections 4.20, 4.24, 4.25, 4.26).  Each is one forward launch of the library with its backward launches behind it, forms only
+under (DESIGN.md sections 4.20, 4.24, 4.25, 4.26, 4.27).  Each is one forward launch of the library with its backward launches behind it, forms only
 the gradients that needs_input_grad asks for, and is once differentiable.
 
 The ops are reached as attributes of the `ops` module at call time: tests wrap them there and count the calls."""
@@ -194,3 +194,34 @@ class _TileBnFn(torch.autograd.Function):
         dx, dgamma, dbeta = ops.tile_bn_train_backward(grad_y, x, ctx.heads, weight.detach(), mean, invstd, want_dx=need[0],
                                                        want_dgamma=need[2], want_dbeta=need[3])
         return dx, None, dgamma, dbeta, None, None, None, None
+
+
+class _ExpertStageFn(torch.autograd.Function):
+    """The expert stage of a tower in training mode on laff_expert_stage_train, ops.expert_stage_train_backward behind it (DESIGN.md
+    section 4.27): stacked[n, l, :] = l2norm(planes[l][n, :] + expert[l, :]) over all columns, either part optional, one launch each way
+    for all planes.  Returns the stacked (N, L, D) tensor that the fusion reads in place.  Every plane receives its gradient (one
+    launch writes them all), the expert table its column sums when it asks for them.  Saves the planes and the row norms, not the
+    output."""
+
+    @staticmethod
+    def forward(ctx, l2norm, expert, *planes):
+        for i, t in enumerate(planes):
+            _fp32(t, 'plane %d' % i)
+        _fp32(expert, 'the expert table')
+        planes = [_dense_input(t) for t in planes]
+        e = None if expert is None else expert.detach()
+        stacked, rnorm = ops.expert_stage_train(planes, e, l2norm)
+        ctx.save_for_backward(*[t for t in (e, rnorm) if t is not None], *planes)
+        ctx.meta = (bool(l2norm), e is not None)
+        return stacked
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stacked):
+        l2norm, has_expert = ctx.meta
+        saved = list(ctx.saved_tensors)
+        e = saved.pop(0) if has_expert else None
+        rnorm = saved.pop(0) if l2norm else None
+        dxs, d_expert = ops.expert_stage_train_backward(grad_stacked, saved, e, l2norm, rnorm,
+                                                        want_d_expert=has_expert and ctx.needs_input_grad[1])
+        return (None, d_expert) + tuple(dxs)

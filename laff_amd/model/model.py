@@ -21,8 +21,11 @@ Differentiable in .train() mode (the autograd Functions live in model/autograd.p
   its dropout + BatchNorm1d stage with device_norm       _DropoutBnFn   section 4.25 (torch's own ops without device_norm)
   the fusion blocks (model/Attention.py)                                section 4.19
   VisMutiTransformNetPlusFrameFeat.frame_vector                         section 4.22
-Inference only: the towers' prepare() / forward and TransformNet.concat_problem, which raise in training mode (_eval_only), and
-W2VVPP: its forward (the training step) raises, retrieve() / predict() put the model in eval mode.
+  the expert stage of the LAFF towers (expert embedding + l2norm)  _ExpertStageFn section 4.27
+  the LAFF and FrameLAFF towers' prepare() / forward and the model's training step (enable_training, forward)   section 4.27
+Inference only (_eval_only raises in training mode): the concat towers of plain 'W2VVPP' (TransformNet.concat_problem), and the
+FrameLAFF video tower's prepare() / forward until its model's enable_training() has armed it; retrieve() / predict() put the model in
+eval mode.
 
 Text encoders (GRU / BoW / W2V / CLIP, :311-549) are upstream of the path: features arrive pre-extracted in
 `caption_feat_dict` (the reference already does this for frozen CLIP via 'CLIP_encoding', :497-498); any module
@@ -36,8 +39,10 @@ import torch.nn.functional as F
 
 from .. import loss as _loss
 from .. import ops
+from .. import optim as _optim
 from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention
-from .autograd import _csc_of, _DropoutBnFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params, _TileBnFn  # noqa: F401  (kept importable from here)
+from .autograd import (_csc_of, _DropoutBnFn, _ExpertStageFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params,  # noqa: F401  (kept importable from here)
+                       _TileBnFn)
 
 device = torch.device('cuda')
 float16 = False
@@ -508,6 +513,25 @@ def _fuse(attention_layer, planes, heads, l2norm_planes=False):
     raise NotImplementedError('attention layer %s is outside the LAFF hot path' % type(attention_layer).__name__)
 
 
+def _train_on_device(module):
+    """The towers' training routes run on the device only: a model on the CPU is refused by name before its first layer is reached."""
+    p = next(module.parameters(), None)
+    if p is not None and not p.is_cuda:
+        raise NotImplementedError('training mode: the towers train on the device only (laff_amd has no CPU path); move the model to the '
+                                  'GPU, or call .eval()')
+
+
+def _fuse_train(attention_layer, planes, heads, expert_embedding, l2norm):
+    """Training mode: the planes of a tower (plain and dense, as plane() hands them over under autograd) through its fusion block.
+    Without experts and without l2norm they go to fuse_planes; with either they pass the expert stage in one launch each way
+    (_ExpertStageFn: the expert table receives its gradient) and the block reads the stacked result in place."""
+    if expert_embedding is None and not l2norm:
+        return _fuse(attention_layer, planes, heads)
+    srcs = [ops.dense_plane(p, i) for i, p in enumerate(planes)]
+    expert = None if expert_embedding is None else expert_embedding.weight[:len(srcs)]
+    return attention_layer(_ExpertStageFn.apply(bool(l2norm), expert, *srcs))
+
+
 def _materialise(plane, heads, D):
     src, tile, scale, shift = plane[:4]
     act = plane[4] if len(plane) > 4 else None
@@ -572,8 +596,14 @@ class VisMutiTransformNetAddAttnetion(nn.Module):
             self.expert_l2Norm = True          # l2norm(local_embs, dim=2) before the attention (model/model.py:1855-1856, 1872-1873)
 
     def prepare(self, vis_input, vis_frame_feat_dict_input=None, pending=None):
-        """Queue this tower's FC projections on `pending`; returns the closure that fuses once they have run."""
-        _eval_only(self)
+        """Queue this tower's FC projections on `pending`; returns the closure that fuses once they have run.  In training mode the
+        projections run at once under autograd (`pending` is not used) and the closure holds the differentiable embeddings."""
+        heads = self.opt.multi_head_attention['heads']
+        if self.training:
+            _train_on_device(self)
+            emb = _fuse_train(self.attention_layer, self.VisMutiTransformNet.planes(vis_input), heads, self.expert_embedding,
+                              self.expert_l2Norm)
+            return lambda: emb
         planes = self.VisMutiTransformNet.planes(vis_input, _expert_rows(self.expert_embedding, len(self.vis_net_space_dict)),
                                                  pending)
         return lambda: _fuse(self.attention_layer, planes, self.opt.multi_head_attention['heads'], self.expert_l2Norm)
@@ -721,8 +751,26 @@ class MultiScaleTxtEncoderAttention(nn.Module):
             self.expert_embedding = nn.Embedding(len(self.space_dict), D)
         self.txt_expert_l2Norm = bool(opt.txt_expert_embedding['l2norm'])      # model/model.py:1660-1661, 1693-1694
 
+    def _prepare_train(self, caption_feat_dict, task3):
+        """Training mode: every encoder's feature through its transform layer under autograd (a device CSR feature takes the gather
+        route, an encoder that is itself differentiable receives its gradient), then the fusion through _fuse_train."""
+        heads = self.opt.multi_head_attention['heads']
+        planes = []
+        for name in self.encoder_name_list:
+            feats = getattr(self.encoder, name)(caption_feat_dict, task3=task3)['text_features']
+            if feats.layout != torch.sparse_csr:
+                feats = to_device_and_float16(feats)
+            elif not feats.is_cuda:                         # (a device CSR is handed on as the object it is: it may carry its laff_csc)
+                feats = feats.to(device)
+            h = heads if name in self.opt.txt_no_transform else 1
+            planes.append(getattr(self.transform_layer, name + '_transform').plane(feats, h))
+        return _fuse_train(self.attention_layer, planes, heads, self.expert_embedding, self.txt_expert_l2Norm)
+
     def prepare(self, caption_feat_dict, pending=None, task3=False):
-        _eval_only(self)
+        if self.training:
+            _train_on_device(self)
+            emb = self._prepare_train(caption_feat_dict, task3)
+            return lambda: emb
         heads = self.opt.multi_head_attention['heads']
         expert = _expert_rows(self.expert_embedding, len(self.encoder_name_list))
         planes = []
@@ -814,14 +862,22 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
         return finish()
 
     def prepare(self, vis_input, vis_frame_feat_dict_input=None, pending=None):
-        _eval_only(self)
+        """In training mode the route is open only once the owning model's enable_training() has armed the tower (training_armed): a
+        tower built on its own keeps the inference-only refusal.  Armed, every frame feature goes through frame_vector (differentiable),
+        the projections run at once under autograd (`pending` is not used) and the closure holds the differentiable embeddings."""
+        train = self.training
+        if train and not getattr(self, 'training_armed', False):
+            _eval_only(self)
+        if train:
+            _train_on_device(self)
+            pending = None
         if self.opt.frame_feat_with_video_feat is False:
             vis_input = {}
         names = [k for k in vis_frame_feat_dict_input if k != 'mask_tensor']
         for feat_name in names:
             vis_frame_feat_dict_input[feat_name] = to_device_and_float16(vis_frame_feat_dict_input[feat_name])
         shapes = {tuple(vis_frame_feat_dict_input[k].shape) for k in names}
-        if len(names) > 1 and len(shapes) == 1 and not self.opt.vis_frame_addFC:
+        if not train and len(names) > 1 and len(shapes) == 1 and not self.opt.vis_frame_addFC:
             # every frame feature of the tower in ONE launch (same shape, same attention type, shared lens)
             frames = [vis_frame_feat_dict_input[k].contiguous() for k in names]
             mask = vis_frame_feat_dict_input['mask_tensor'].to(device=frames[0].device)
@@ -848,6 +904,9 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
             vis_input[name] = to_device_and_float16(vis_input[name])
             h = heads if name in self.opt.vis_no_transform else 1
             planes.append(module_dict[name].plane(vis_input[name], h, None, pending))
+        if train:
+            emb = _fuse(self.vis_attention_layer, planes, heads)
+            return lambda: emb
         return lambda: _fuse(self.vis_attention_layer, planes, heads)
 
     def get_attention_weight(self, vis_input, vis_frame_feat_dict_input):
@@ -860,7 +919,8 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
 # a9-a11: the cross-modal model
 # ------------------------------------------------------------------------------------------------------
 class W2VVPP(nn.Module):
-    """Inference surface of the reference's W2VVPP family (model/model.py:791-1128)."""
+    """The reference's W2VVPP family (model/model.py:791-1128): the inference surface, and for the LAFF towers the training step
+    (enable_training, forward)."""
 
     #: operand precision of the similarity GEMM ('fp32' | 'fp16' | 'bf16' | 'fp16x3' | 'bf16x3')
     sim_precision = None
@@ -881,8 +941,86 @@ class W2VVPP(nn.Module):
         self._init_vis_net(opt)
         self._init_txt_net(opt)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError('training step (model/model.py:964-1001) is out of scope; use predict()')
+    # -- the training step (model/model.py:791-1001, :1975-2048) ------------------------------------
+    def _training_refusals(self):
+        """What the step does not cover, by name, before any launch."""
+        opt = self.opt
+        if isinstance(self.vis_net, VisTransformNet) or isinstance(self.txt_net, MultiScaleTxtNet):
+            raise NotImplementedError('training step (model/model.py:964-1001) is out of scope for the concat towers of W2VVPP; use predict()')
+        if getattr(opt, 'negative', False):
+            raise NotImplementedError('training step: opt.negative (cal_foward_neg and Margin2Loss, model/model.py:889-962) is not '
+                                      'provided; set negative=False')
+        if not getattr(opt, 'multi_space', True):
+            raise NotImplementedError('training step: multi_space=False scores the heads through get_txt2vis_matrix, which is not '
+                                      'differentiable here; set multi_space=True')
+        if globals()['float16']:
+            raise NotImplementedError('training step: float16 (autocast + GradScaler, model/model.py:970-989) has no counterpart here; '
+                                      'the step is fp32')
+
+    def enable_training(self, device_norm=True):
+        """Everything the reference's constructor builds for training (model/model.py:1984-2030), kept out of __init__ so that a model
+        built for inference allocates none of it: criterion, criterion_with_score, optimizer and lr_schedulers (laff_amd.optim: the clip
+        by opt.grad_clip runs inside optimizer.step()), params, grad_clip, iters = 0.  device_norm: every TransformNet's training-mode
+        dropout + BatchNorm1d stage runs on this library's kernels (use_device_norm); the no-transform feature trains only that way.
+        Returns self."""
+        self._training_refusals()
+        opt = self.opt
+        self.criterion = _loss.criterion_for(opt)
+        self.criterion_with_score = _loss.MarginRankingLossWithScore(margin=opt.margin, max_violation=opt.max_violation,
+                                                                     cost_style=opt.cost_style, direction=opt.direction)
+        self.optimizer, self.lr_schedulers = _optim.optimizer_for(opt, self)
+        self.params = list(self.parameters())
+        self.grad_clip = opt.grad_clip
+        self.iters = 0
+        use_device_norm(self, device_norm)
+        if isinstance(self.vis_net, VisMutiTransformNetPlusFrameFeat):
+            self.vis_net.training_armed = True             # the FrameLAFF tower's training route opens for this model only
+        return self
+
+    def compute_loss(self, vis_embs, txt_embs, *unused):
+        """(loss, {'triplet_loss': loss}) of a batch of embeddings, 2-D or (B, H, d) for the per-head sum (model/model.py:840-865,
+        :2032-2048 with multi_space): loss.compute_loss on self.criterion.  The reference's trailing arguments are accepted and unused."""
+        return _loss.compute_loss(self.criterion, vis_embs, txt_embs)
+
+    def cal_foward(self, train_data):
+        """Both towers and the loss of one batch (model/model.py:867-887): reads train_data['vis_feats'], ['captions'] and
+        ['vis_frame_feat_dict'] (an empty dict means None), calls optimizer.zero_grad() where the reference does.  Returns
+        (loss, loss_items).  The input dicts are written to, as in the reference: hand over fresh ones every step."""
+        frames = train_data.get('vis_frame_feat_dict')
+        if frames == {}:
+            frames = None
+        txt_embs = self.txt_net(train_data['captions'])
+        vis_embs = self.vis_net(train_data['vis_feats'], txt_emb=txt_embs, vis_frame_feat_dict_input=frames)
+        self.optimizer.zero_grad()
+        return self.compute_loss(vis_embs, txt_embs, 0, 0, 0)
+
+    def forward(self, train_data, epoch=None):
+        """One training step (model/model.py:964-1001): iters += 1, cal_foward, loss.backward(), optimizer.step(); returns loss_items.
+        fp32 only: the reference's float16 / autocast / GradScaler branch has no counterpart here.  The clip by grad_clip runs INSIDE
+        optimizer.step() (laff_amd.optim): after a step .grad still holds the UNCLIPPED gradients and optimizer.total_norm their global
+        norm, where the reference's clip_grad_norm_ scales .grad in place -- parameters and optimizer state are the reference's."""
+        if getattr(self, 'optimizer', None) is None:
+            self._training_refusals()
+            raise NotImplementedError('training step: this model was built for inference; call enable_training() first (it builds the '
+                                      'criterion and the optimizer)')
+        self._training_refusals()
+        if not self.training:
+            raise RuntimeError('training step: the model is in eval mode; call .train() first')
+        self.iters += 1
+        loss, loss_items = self.cal_foward(train_data)
+        loss.backward()
+        self.optimizer.step()
+        return loss_items
+
+    @property
+    def learning_rate(self):
+        """The learning rate of every parameter group (model/model.py:1580-1586)."""
+        return [group['lr'] for group in self.optimizer.param_groups]
+
+    def lr_step(self, val_value):
+        """StepLR once, ReduceLROnPlateau on val_value (model/model.py:1588-1595)."""
+        self.lr_schedulers[0].step()
+        self.lr_schedulers[1].step(val_value)
 
     # -- towers ---------------------------------------------------------------------------------------------
     def encode_video(self, vis_input, vis_frame_feat_dict=None):

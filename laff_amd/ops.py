@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1417,6 +1417,107 @@ def tile_bn_train_backward(grad_y, x, heads, weight, save_mean, save_invstd, wan
     _call('tile_bn_train_backward', lib.laff_tile_bn_train_backward, h, _ptr(g), ldg, _ptr(x), N, W, ldx, H, _ptr(weight), _ptr(save_mean),
           _ptr(save_invstd), pdx, lddx, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)
     return dx, dgamma, dbeta
+
+
+def expert_stage_train_plan(N, L, D):
+    """laff_expert_stage_train_plan (host only) for L planes of N rows and D columns: (blocks of the backward launch per plane -- one
+    partial column sum of d_expert each --, workspace bytes of the backward when d_expert is asked)."""
+    return _plan_query('laff_expert_stage_train_plan', 2, N, L, D)
+
+
+def _stacked3(t, N, L, D, name):
+    """An (N, L, D) device fp32 tensor as the expert stage addresses it: (tensor, row pitch, plane pitch).  Unit inner stride, 16-byte
+    aligned rows; anything else is refused (an output) -- the callers make their inputs so."""
+    _dev(t, name)
+    if tuple(t.shape) != (N, L, D):
+        raise ValueError('%s must be (%d, %d, %d), got %s' % (name, N, L, D, tuple(t.shape)))
+    if t.numel() and (t.stride(2) != 1 or t.stride(0) % 4 or t.stride(1) % 4 or t.data_ptr() % 16):
+        raise ValueError('%s must have unit inner stride and 16-byte aligned rows, got strides %s' % (name, t.stride()))
+    ldn = t.stride(0) if N > 1 else max(t.stride(0), (L - 1) * max(t.stride(1), D) + D)
+    ldl = t.stride(1) if L > 1 else max(t.stride(1), D)
+    return t, ldn, ldl
+
+
+def _plane_arrays(planes, name, N, D):
+    """L (N, D) device fp32 row views as the host arrays of the expert stage: (tensors kept alive, pointer array, pitch array).  A plane
+    whose rows are not 16-byte aligned is made dense first."""
+    kept, L = [], len(planes)
+    ptrs, lds = (C.c_void_p * L)(), (C.c_int * L)()
+    for l, t in enumerate(planes):
+        t, ld = _mat(t, '%s[%d]' % (name, l), align16=True)
+        if tuple(t.shape) != (N, D):
+            raise ValueError('%s[%d] must be (%d, %d), got %s' % (name, l, N, D, tuple(t.shape)))
+        kept.append(t)
+        ptrs[l], lds[l] = t.data_ptr(), (ld + 3) // 4 * 4 if t.shape[0] <= 1 else ld
+    return kept, ptrs, lds
+
+
+def expert_stage_train(planes, expert, l2norm, out=None):
+    """The expert stage of a tower in training mode on laff_expert_stage_train, one launch for all planes: planes L device fp32 (N, D)
+    matrices (row views with 16-byte aligned rows are read in place), expert (L, D) device fp32 or None, added row l to plane l; with
+    l2norm every row of every plane is then divided by its norm over all D columns (+ 1e-13 + 1e-14).  Returns (stacked (N, L, D),
+    rnorm (L, N) or None without l2norm).  out: a (stacked, rnorm) pair of buffers (None entries are allocated here; stacked may have
+    pitches)."""
+    L = len(planes)
+    N, D = planes[0].shape
+    kept, ptrs, lds = _plane_arrays(planes, 'planes', N, D)
+    dev = kept[0].device
+    if expert is not None:
+        expert, lde = _mat(expert, 'expert', align16=True)
+        if tuple(expert.shape) != (L, D):
+            raise ValueError('expert must be (%d, %d), got %s' % (L, D, tuple(expert.shape)))
+    else:
+        lde = 0
+    oy, orn = out if out is not None else (None, None)
+    if oy is None:
+        oy = torch.empty((N, L, D), device=dev, dtype=torch.float32)
+    oy, ldn, ldl = _stacked3(oy, N, L, D, 'out stacked')
+    rnorm = None
+    if l2norm:
+        rnorm = torch.empty((L, N), device=dev, dtype=torch.float32) if orn is None else _dev(orn, 'out rnorm')
+        if tuple(rnorm.shape) != (L, N) or not rnorm.is_contiguous():
+            raise ValueError('out rnorm must be a contiguous (%d, %d), got %s' % (L, N, tuple(rnorm.shape)))
+    lib, h = _context(dev)
+    _call('expert_stage_train', lib.laff_expert_stage_train, h, ptrs, lds, N, L, D, _ptr(expert), lde, int(bool(l2norm)), _ptr(oy), ldn, ldl,
+          _ptr(rnorm))
+    return oy, rnorm
+
+
+def expert_stage_train_backward(grad_stacked, planes, expert, l2norm, rnorm, want_d_expert=True, out=None):
+    """Backward of expert_stage_train (laff_expert_stage_train_backward): grad_stacked (N, L, D) device fp32 (read in place when its
+    rows are 16-byte aligned), the forward's planes, expert and rnorm.  Returns (list of L dx (N, D), d_expert (L, D) | None).
+    out: a (list of dx buffers or None, d_expert buffer or None) pair."""
+    L = len(planes)
+    N, D = planes[0].shape
+    kept, ptrs, lds = _plane_arrays(planes, 'planes', N, D)
+    dev = kept[0].device
+    g = _dev(grad_stacked, 'grad_stacked')
+    if g.dim() == 3 and g.numel() and (g.stride(2) != 1 or g.stride(0) % 4 or g.stride(1) % 4 or g.data_ptr() % 16 or
+                                       (N > 1 and g.stride(0) < D) or (L > 1 and g.stride(1) < D)):
+        g = g.contiguous()
+    g, ldn, ldl = _stacked3(g, N, L, D, 'grad_stacked')
+    if expert is not None:
+        expert, lde = _mat(expert, 'expert', align16=True)
+    else:
+        lde = 0
+    odx, ode = out if out is not None else (None, None)
+    dxs = [torch.empty((N, D), device=dev, dtype=torch.float32) for _ in range(L)] if odx is None else list(odx)
+    dkept, dptrs, dlds = _plane_arrays(dxs, 'out dx', N, D)
+    if any(a is not b for a, b in zip(dkept, dxs)):
+        raise ValueError('out dx must be row views with 16-byte aligned rows')
+    d_expert = None
+    if want_d_expert:
+        if expert is None:
+            raise ValueError('d_expert was asked without an expert table')
+        d_expert = torch.empty((L, D), device=dev, dtype=torch.float32) if ode is None else _dev(ode, 'out d_expert')
+        if tuple(d_expert.shape) != (L, D) or not d_expert.is_contiguous():
+            raise ValueError('out d_expert must be a contiguous (%d, %d), got %s' % (L, D, tuple(d_expert.shape)))
+    nbytes = expert_stage_train_plan(N, L, D)[1] if want_d_expert else 0
+    ws = _workspace(nbytes, dev)
+    lib, h = _context(dev)
+    _call('expert_stage_train_backward', lib.laff_expert_stage_train_backward, h, _ptr(g), ldn, ldl, ptrs, lds, N, L, D, _ptr(expert), lde,
+          int(bool(l2norm)), _ptr(rnorm), dptrs, dlds, _ptr(d_expert), _ptr(ws), nbytes)
+    return dxs, d_expert
 
 
 def optim_plan(sizes):

@@ -176,6 +176,9 @@ class _StepOptimizer(Optimizer):
                                [st[1] for _, _, st in items] if len(self._states) > 1 else None, step=step,
                                max_norm=self.grad_clip if clip else 0.0, workspace=self._ws if clip else None, partials=partials,
                                total_norm_out=self.total_norm if clip else None, checked=True, **self._hyper(group))
+                # the kernel wrote through raw pointers: the version counters are bumped here (no launch), as an in-place torch op would,
+                # or whatever a module derived from a parameter (TransformNet._cached, the packed attention weights) would outlive the step
+                torch.autograd.graph.increment_version([p for p, _, _ in items] + [t for _, _, st in items for t in st])
         return loss
 
 

@@ -1,0 +1,252 @@
+"""The 'LAFF' model's training graph restated as a CPU torch graph in float64 or float32, built from a case of the training-step fixture
+(tests/golden/train_step.<case>.<n>.npz, tools/gen_golden_train.py) -- its config and a state dict: both towers (TransformNet layers in
+training mode, the tiled no-transform feature, the expert stage, the multi-head attention through fuse_ref.attention) and the per-head
+margin ranking loss with max_violation and direction.  In the style of train_ref.Side / side_f64; it gives the device tests the
+absolute Jacobian of train_ref.end_to_end_bound and the host tests a float64 value for everything the fixture records.
+
+Also here: load_case (the shards of a case as one dict), device_model (this library's model built from a case) and train_data (fresh
+input dicts of a step)."""
+import glob
+import json
+import os
+
+import numpy as np
+import torch
+
+import fuse_bwd_ref
+import fuse_ref
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+CASES = ('a', 'b', 'c', 'd', 'e')
+L2_EPS = 1e-13 + 1e-14
+_cache = {}
+
+
+def load_case(key):
+    """({array name: array} over every shard of the case, its meta dict).  Cached: the arrays are shared and must stay unchanged."""
+    if key not in _cache:
+        arrays = {}
+        paths = sorted(glob.glob(os.path.join(GOLDEN, 'train_step.%s.*.npz' % key)))
+        assert paths, 'no fixture shards for case %s' % key
+        for p in paths:
+            with np.load(p) as z:
+                for k in z.files:
+                    arrays[k] = z[k]
+        meta = json.loads(str(arrays.pop('meta')))
+        _cache[key] = (arrays, meta)
+    return _cache[key]
+
+
+def sub(arrays, prefix):
+    return {k[len(prefix):]: v for k, v in arrays.items() if k.startswith(prefix)}
+
+
+def param_names(sd):
+    """The trainable tensors of a state dict of the model: everything but the BatchNorm buffers."""
+    return [k for k in sd if not k.endswith(('running_mean', 'running_var', 'num_batches_tracked'))]
+
+
+def _l2norm(x, dim):
+    return x / (x.pow(2).sum(dim, keepdim=True).sqrt() + L2_EPS)
+
+
+def _transform(P, prefix, x, heads, stats, cols=None):
+    """One TransformNet in training mode with dropout 0: fc1 + tanh where the layer has an fc, the feature tiled over the heads where it
+    has none, then BatchNorm1d on batch statistics.  stats[prefix] = (batch mean, unbiased batch variance).  cols: only these output
+    columns (one head's slice; a tiled feature's copy for that head is the feature itself)."""
+    pick = (lambda t: t) if cols is None else (lambda t: t[cols])
+    if prefix + 'fc1.weight' in P:
+        y = torch.tanh(x @ pick(P[prefix + 'fc1.weight']).T + pick(P[prefix + 'fc1.bias']))
+    else:
+        y = x.repeat(1, heads) if cols is None else x
+    if prefix + 'bn1.weight' in P:
+        if cols is None:
+            stats[prefix] = (y.detach().mean(0), y.detach().var(0, unbiased=True))
+        # (written out: torch's fused batch_norm has no batching rule for abs_jacobian's batched backward and falls back to a loop)
+        y = (y - y.mean(0)) / torch.sqrt(y.var(0, unbiased=False) + 1e-5) * pick(P[prefix + 'bn1.weight']) + pick(P[prefix + 'bn1.bias'])
+    return y
+
+
+def _fusion(P, prefix, planes, meta, dtype, layer='attention_layer', head=None):
+    """stack -> expert embedding -> l2norm(dim=2) -> Multi_head_MyApply_Attention (split heads).  head: the planes are that head's
+    columns only and so is the result (N, 1, d) -- without l2norm over all columns a head's embedding depends on nothing else."""
+    H, D = meta['H'], meta['D']
+    d = D // H
+    local = torch.stack(planes, 1)
+    if meta['expert']:
+        e = P[prefix + 'expert_embedding.weight'][None, :len(planes)]
+        local = local + (e if head is None else e[:, :, head * d:(head + 1) * d])
+    if meta['l2norm']:
+        assert head is None, 'l2norm over all columns couples the heads'
+        local = _l2norm(local, 2)
+    att = prefix + layer + '.attention_layer.%d.'
+    hs = range(H) if head is None else [head]
+    w = torch.stack([P[att % h + 'embedding_common.0.weight'].reshape(-1) for h in hs])
+    b = torch.cat([P[att % h + 'embedding_common.0.bias'].reshape(1) for h in hs])
+    gw = torch.cat([P[att % h + 'global_emb_weight_net.weight'].detach().reshape(1) for h in hs])
+    keep = fuse_ref.F64
+    fuse_ref.F64 = dtype
+    try:
+        return fuse_ref.attention(fuse_bwd_ref.heads_of(local, len(hs), d, True), w, b, gw, with_ave=meta['with_ave'], mul=meta['mul'],
+                                  l2norm_each_head=False)[0]
+    finally:
+        fuse_ref.F64 = keep
+
+
+TXT_KEYS = {'bow_encoder': 'bow_feature', 'w2v_encoder': 'w2v_feature', 'CLIP_encoder': 'CLIP_encoding'}
+
+
+def _frame_vector(P, name, frames, mask, meta, dtype):
+    """The frame attention of the FrameLAFF tower without a frame FC (Attention_1 over a video's frames, padded frames exact zeros that
+    take part in the softmax): fuse_ref.frame_attention on leaves of `dtype`."""
+    kind = {'attention_noAveNoAverageMul': (False, False), 'attention_noAverageMul_Ave': (True, False),
+            'attention_averageMul': (True, True), 'average_AverageMul_noAve': (False, True)}[meta['vis_frame_attention']]
+    pre = 'vis_net.frame_attention.%s.0.' % name
+    keep = fuse_ref.F64
+    fuse_ref.F64 = dtype
+    try:
+        bias = P[pre + 'embedding_common.0.bias']
+        out = fuse_ref.frame_attention(frames, P[pre + 'embedding_common.0.weight'], bias.detach(),
+                                       P[pre + 'global_emb_weight_net.weight'].detach(), with_ave=kind[0], mul=kind[1], mask=mask)
+        return out + 0.0 * bias.sum()      # softmax ignores the shift: the bias is reached, its gradient is zero (fuse_ref reads it as a float)
+    finally:
+        fuse_ref.F64 = keep
+
+
+def side_embedding(meta, P, side, inputs, dtype=torch.float64, stats=None, head=None):
+    """One tower's embedding (N, H, d) -- or, with head, that head's (N, 1, d) from a graph that holds the head's columns only -- on
+    inputs = (vis {feature: array}, txt {key: array}, frames {frame feature: (B, Fmax, d), 'mask_tensor': (B, Fmax)} or None)."""
+    vis, txt, frames = inputs
+    H, stats = meta['H'], {} if stats is None else stats
+    cols = None if head is None else slice(head * (meta['D'] // H), (head + 1) * (meta['D'] // H))
+    t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)        # noqa: E731
+    if side == 'txt':
+        planes = [_transform(P, 'txt_net.transform_layer.%s_transform.' % name, t(txt[TXT_KEYS[name]]), H, stats, cols)
+                  for name in meta['encoder_name_list']]
+        return _fusion(P, 'txt_net.', planes, meta, dtype, head=head)
+    if meta.get('model', 'LAFF') == 'FrameLAFF':
+        feats = {name: t(vis[name]) for name in meta['vid_dims']}
+        for name in meta['frame_feats']:
+            feats[name] = _frame_vector(P, name, t(frames[name]), t(frames['mask_tensor']), meta, dtype)
+        planes = [_transform(P, 'vis_net.%s.' % name, x, H, stats, cols) for name, x in feats.items()]
+        return _fusion(P, 'vis_net.', planes, meta, dtype, 'vis_attention_layer', head)
+    planes = [_transform(P, 'vis_net.VisMutiTransformNet.%s.' % name, t(vis[name]), H, stats, cols) for name in meta['vid_dims']]
+    return _fusion(P, 'vis_net.', planes, meta, dtype, head=head)
+
+
+def embeddings(meta, P, vis, txt, dtype=torch.float64, frames=None):
+    """(txt_emb, vis_emb, stats) of the two towers; P: {state-dict name: tensor of dtype}."""
+    stats = {}
+    inputs = (vis, txt, frames)
+    return side_embedding(meta, P, 'txt', inputs, dtype, stats), side_embedding(meta, P, 'vis', inputs, dtype, stats), stats
+
+
+def margin_loss(txt_emb, vis_emb, meta):
+    """MarginRankingLoss(margin, 'cosine', max_violation, 'sum', direction)(s = txt, im = vis) per head, summed."""
+    B = txt_emb.shape[0]
+    eye = torch.eye(B, dtype=torch.bool)
+    total = 0.0
+    for h in range(txt_emb.shape[1]):
+        S = _l2norm(vis_emb[:, h], 1) @ _l2norm(txt_emb[:, h], 1).T
+        dg = torch.diag(S)
+        if meta['direction'] in ('i2t', 'bidir'):
+            cost = torch.clamp(meta['margin'] + S - dg[:, None], min=0).masked_fill(eye, 0)
+            total = total + (cost.max(1)[0] if meta['max_violation'] else cost).sum()
+        if meta['direction'] in ('t2i', 'bidir'):
+            cost = torch.clamp(meta['margin'] + S - dg[None, :], min=0).masked_fill(eye, 0)
+            total = total + (cost.max(0)[0] if meta['max_violation'] else cost).sum()
+    return total
+
+
+def leaves_of(sd, dtype=torch.float64):
+    """{name: tensor of dtype}: the trainable ones are leaves that require a gradient."""
+    train = set(param_names(sd))
+    return {k: torch.as_tensor(np.asarray(v)).to(dtype).requires_grad_(k in train) for k, v in sd.items()
+            if not k.endswith('num_batches_tracked')}
+
+
+def step_graph(key, step, dtype=torch.float64, sd=None):
+    """The graph of step `step` (1 or 2) of a case from the state the fixture's float64 run had before it (or from `sd`): a dict with the
+    leaves P, txt_emb, vis_emb, loss, the BatchNorm batch statistics, and grads {name: d loss / d leaf, None where unreached}."""
+    return step_graph_of(*load_case(key), step, dtype, sd)
+
+
+def step_graph_of(arrays, meta, step, dtype=torch.float64, sd=None):
+    """step_graph on the arrays and meta of a case that is not on disk yet (tools/gen_golden_train.py)."""
+    if sd is None:
+        sd = sub(arrays, 'sd0/') if step == 1 else sub(arrays, 's%d/sd/' % (step - 1))
+    P = leaves_of(sd, dtype)
+    pre = 's%d/in/' % step
+    inputs = (sub(arrays, pre + 'vis/'), sub(arrays, pre + 'txt/'), sub(arrays, pre + 'frame/'))
+    txt_emb, vis_emb, stats = embeddings(meta, P, inputs[0], inputs[1], dtype, inputs[2])
+    loss = margin_loss(txt_emb, vis_emb, meta)
+    names = [k for k in P if P[k].requires_grad]
+    gs = torch.autograd.grad(loss, [P[k] for k in names], retain_graph=True, allow_unused=True)
+    return dict(P=P, txt_emb=txt_emb, vis_emb=vis_emb, loss=loss, stats=stats, grads=dict(zip(names, gs)), meta=meta, inputs=inputs,
+                dtype=dtype)
+
+
+def abs_jacobian(graph):
+    """{name: sum_j |d (d loss / d leaf) / d (d loss / d E_j)|} = sum_j |d E_j / d leaf| over the elements of both embeddings, for every
+    leaf with a gradient: the second term of train_ref.end_to_end_bound.  Several seconds of CPU time per step of a case: the device tests compute
+    it once per session (a cache) and share it."""
+    acc, meta = {}, graph['meta']
+    for side in ('txt', 'vis'):                            # a tower's embedding moves with its own leaves only
+        names = [k for k, g in graph['grads'].items() if g is not None and k.startswith(side + '_net.')]
+        leaves = [graph['P'][k] for k in names]
+        acc.update({k: torch.zeros_like(v) for k, v in zip(names, leaves)})
+        if meta['l2norm']:
+            parts = [graph[side + '_emb']]
+        else:                                              # ... and a head's with its own columns: H graphs of 1 / H the width, same sums
+            parts = [side_embedding(meta, graph['P'], side, graph['inputs'], graph['dtype'], head=h) for h in range(meta['H'])]
+        for E in parts:
+            E = E.reshape(-1)
+            eye = torch.eye(E.numel(), dtype=E.dtype)
+            for lo in range(0, E.numel(), 1024):
+                js = torch.autograd.grad(E, leaves, eye[lo:lo + 1024], retain_graph=True, is_grads_batched=True, allow_unused=True)
+                for k, j in zip(names, js):
+                    if j is not None:
+                        acc[k] += j.abs().sum(0)
+    return acc
+
+
+# ---- this library's model built from a case -----------------------------------------------------------------------------------------
+def make_cfg(meta, **overrides):
+    from laff_amd.config import make_config
+    e = {'expert': meta['expert'], 'l2norm': meta['l2norm']}
+    kw = dict(vis_no_transform=meta['vis_no_transform'], txt_no_transform=meta['txt_no_transform'], batch_norm=meta['batch_norm'],
+              with_ave=meta['with_ave'], mul=meta['mul'], dropout=meta['dropout'], vis_expert_embedding=dict(e), txt_expert_embedding=dict(e),
+              max_violation=meta['max_violation'], direction=meta['direction'], margin=meta['margin'], loss=meta['loss'],
+              optimizer=meta['optimizer'], lr=meta['lr'], grad_clip=meta['grad_clip'])
+    if meta.get('model', 'LAFF') == 'FrameLAFF':
+        kw.update(vis_frame_attention=meta['vis_frame_attention'], vis_frame_addFC=False, frame_feat_with_video_feat=True,
+                  max_frame=meta['max_frame'], frame_feats=meta['frame_feats'])
+    kw.update(overrides)
+    return make_config(meta['vid_dims'], meta['txt_dims'], meta['D'], meta['H'], meta.get('model', 'LAFF'), **kw)
+
+
+def device_model(key, device='cuda', sd=None, **overrides):
+    """get_model('LAFF') from the case's config with the fixture's initial state (or `sd`, float64 arrays are rounded to fp32) loaded,
+    in training mode."""
+    from laff_amd.model.model import get_model
+    arrays, meta = load_case(key)
+    model = get_model(meta.get('model', 'LAFF'), device, make_cfg(meta, **overrides))
+    sd = sub(arrays, 'sd0/') if sd is None else sd
+    own = model.state_dict()
+    state = {k: torch.as_tensor(np.asarray(v)).to(own[k].dtype) for k, v in sd.items()}
+    assert set(state) == set(own), (set(state) ^ set(own))
+    model.load_state_dict(state)
+    return model.train()
+
+
+ENCODING_KEYS = {'bow_feature': 'bow_encoding', 'w2v_feature': 'w2v_encoding', 'CLIP_encoding': 'CLIP_encoding'}
+
+
+def train_data(key, step, device='cuda'):
+    """Fresh input dicts of a step, as W2VVPP.cal_foward reads them."""
+    arrays, meta = load_case(key)
+    pre = 's%d/in/' % step
+    cap = {'caption': ['%d' % i for i in range(meta['N'])]}
+    cap.update({ENCODING_KEYS[k]: torch.from_numpy(v.copy()).to(device) for k, v in sub(arrays, pre + 'txt/').items()})
+    return {'vis_feats': {k: torch.from_numpy(sub(arrays, pre + 'vis/')[k].copy()).to(device) for k in meta['vid_dims']},
+            'captions': cap, 'vis_frame_feat_dict': {k: torch.from_numpy(v.copy()).to(device) for k, v in sub(arrays, pre + 'frame/').items()}}
