@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 43
+#define LAFF_ABI_VERSION 44
 
 enum {
     LAFF_OK = 0,
@@ -490,6 +490,31 @@ int laff_netvlad_workspace_bytes(int R, int K, size_t* out);
 int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off, const int* row_off_host,
                         const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, float* out, int ldo,
                         void* workspace, size_t workspace_bytes);
+
+/* ---- the NetVLAD text encoder, differentiable: the saving forward and the gradients of fc1_weight and centroids (fp32) ----------
+ * The arguments up to ldo are laff_netvlad_encode's, with its limits and error codes; the word2vec table gets no gradient.
+ * laff_netvlad_encode_train: the same out, bit for bit, and reserve (laff_netvlad_train_reserve_bytes(N, R, K) bytes, 16-byte
+ *   aligned): the soft assignments [R, K], 1 / max(|x|, eps) [R], per caption max(|u_k|, eps) for every cluster and max(|v|, eps)
+ *   [N, K + 1], and which of those norms were clamped [N, K + 1] int32.  The assignments go straight into the reserve, so workspace
+ *   is not used: NULL / 0 is fine, a pointer must be 16-byte aligned.
+ * laff_netvlad_backward: from out [N, ldo] (the forward's), d_out [N, ldg] (its gradient; ldg % 4 == 0, at least K*D, 16-byte aligned)
+ *   and the reserve: d_fc1 [K, D] = sum_r dz_r (x) xh_r and d_centroids [K, D] = - sum_i s_ik du_ik, contiguous and 16-byte aligned;
+ *   either may be NULL (not wanted: not formed, not touched).  The clamped norms follow torch: below eps a norm passes no gradient, the
+ *   derivative is d / eps.  Every element of a wanted output is written exactly once, zeros included; N = 0 or R = 0 is legal (zeros).
+ *   Sums run over token rows / captions in ascending order inside chunks whose boundaries depend on (N, R) alone, then over the chunks in
+ *   ascending order: no atomics, two calls give the same bits.  An id outside [0, V) is never read past the table and makes both
+ *   gradients NaN.  workspace: laff_netvlad_backward_workspace_bytes(N, R, K, D) bytes, 16-byte aligned.  Three launches.
+ * Buffers that are too small are refused by name before any launch.  No allocation, no host synchronisation: capturable. */
+int laff_netvlad_train_reserve_bytes(int N, int R, int K, size_t* out);
+int laff_netvlad_backward_workspace_bytes(int N, int R, int K, int D, size_t* out);
+int laff_netvlad_encode_train(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off,
+                              const int* row_off_host, const int* zero_rows, int N, int R, const float* fc1_weight,
+                              const float* centroids, int K, float* out, int ldo, void* reserve, size_t reserve_bytes, void* workspace,
+                              size_t workspace_bytes);
+int laff_netvlad_backward(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off, const int* row_off_host,
+                          const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, const float* out,
+                          int ldo, const float* d_out, int ldg, const void* reserve, size_t reserve_bytes, float* d_fc1,
+                          float* d_centroids, void* workspace, size_t workspace_bytes);
 
 /* ---- a2-a6: stack + Multi_head_MyApply_Attention / Attention_1 / JustAverage ----------------------------
  * (model/model.py:1858-1876, :1663-1705; model/Attention.py:508-531, :78-105)

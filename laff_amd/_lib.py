@@ -11,7 +11,7 @@ ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 
 class Plane(C.Structure):
@@ -241,6 +241,12 @@ SIGNATURES = {
     'laff_bert_encode': (C.c_int, [_P, _P, _P, C.POINTER(_I), _I, _I, C.POINTER(BertText), _I, _P, _I, _P, C.c_size_t]),
     'laff_netvlad_workspace_bytes': (C.c_int, [_I, _I, C.POINTER(C.c_size_t)]),
     'laff_netvlad_encode': (C.c_int, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _I, _I, _P, _P, _I, _P, _I, _P, C.c_size_t]),
+    'laff_netvlad_train_reserve_bytes': (C.c_int, [_I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_netvlad_backward_workspace_bytes': (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'laff_netvlad_encode_train': (C.c_int, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _I, _I, _P, _P, _I, _P, _I, _P, C.c_size_t, _P,
+                                            C.c_size_t]),
+    'laff_netvlad_backward': (C.c_int, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, C.c_size_t,
+                                        _P, _P, _P, C.c_size_t]),
     'laff_rerank_workspace_bytes': (C.c_int, [C.POINTER(RerankProblem), _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_rerank_run': (C.c_int, [_P, C.POINTER(RerankProblem), _I, _I, _I, _F, _P, C.c_size_t]),
     'laff_rerank_tkb': (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I]),

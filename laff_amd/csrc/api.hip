@@ -1322,6 +1322,60 @@ int netvlad_check_k(const char* fn, int K) {
         return fail(LAFF_E_UNSUPPORTED, "%s: K=%d: the number of clusters must be in [1, %d]", fn, K, laff::NETVLAD_MAX_K);
     return LAFF_OK;
 }
+// what laff_netvlad_encode, laff_netvlad_encode_train and laff_netvlad_backward check alike, in two steps around the empty problem
+int netvlad_check_sizes(const char* fn, int V, int D, int N, int R, int K) {
+    if (int rc = netvlad_check_k(fn, K)) return rc;
+    if (D < 4 || D > laff::NETVLAD_MAX_D || D % 4)
+        return fail(LAFF_E_UNSUPPORTED, "%s: D=%d: the word-vector width must be a multiple of 4 in [4, %d]", fn, D, laff::NETVLAD_MAX_D);
+    if (N < 0 || R < 0 || V < 1) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d V=%d", fn, N, R, V);
+    return LAFF_OK;
+}
+// other_null: one of the caller's own pointers is missing
+int netvlad_check_batch(const char* fn, const float* table, const int* ids, const int* row_off, const int* row_off_host,
+                        const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, int D,
+                        const float* out, int ldo, bool other_null) {
+    if (!table || (R && !ids) || !row_off || !row_off_host || !zero_rows || !fc1_weight || !centroids || !out || other_null)
+        return fail(LAFF_E_ARG, "%s: null argument", fn);
+    if (int rc = check_offsets(fn, "row_off", "caption", "NR", row_off_host, N, R, 0, INT_MAX, nullptr)) return rc;
+    if (ldo < K * D || ldo % 4) return fail(LAFF_E_SHAPE, "%s: ldo=%d: at least K*D=%d and a multiple of 4", fn, ldo, K * D);
+    return LAFF_OK;
+}
+// the training reserve: the forward's workspace (assignments, 1 / max(|x|, eps)) | den [N, K + 1] fp32 | clamped [N, K + 1] int32
+struct NetvladReserve {
+    size_t rnorm, den, clamped, total;
+};
+NetvladReserve netvlad_reserve(int N, int R, int K) {
+    NetvladReserve s;
+    s.rnorm = netvlad_rnorm_offset(R, K);
+    s.den = netvlad_ws_bytes(R, K);
+    s.clamped = s.den + round256((size_t)N * (K + 1) * sizeof(float));
+    s.total = s.clamped + round256((size_t)N * (K + 1) * sizeof(int));
+    return s;
+}
+// the backward's workspace: DU [N, K, D] | s [N, K] | dz [R, K] | the chunk sums of d_fc1 and of d_centroids [chunks, K, D], fp32,
+// each region on 256 bytes.  At most 128 chunks each, of at least 64 token rows / 16 captions: a function of (N, R) alone
+struct NetvladBwdWs {
+    size_t mass, dz, part_fc1, part_cent, total;
+    int rows_per_chunk, chunks_r, caps_per_chunk, chunks_n;
+};
+NetvladBwdWs netvlad_bwd_ws(int N, int R, int K, int D) {
+    NetvladBwdWs s;
+    s.rows_per_chunk = std::max(64, (R + 127) / 128);
+    s.chunks_r = (R + s.rows_per_chunk - 1) / s.rows_per_chunk;
+    s.caps_per_chunk = std::max(16, (N + 127) / 128);
+    s.chunks_n = (N + s.caps_per_chunk - 1) / s.caps_per_chunk;
+    const size_t kd = (size_t)K * D * sizeof(float);
+    s.mass = round256((size_t)N * kd);
+    s.dz = s.mass + round256((size_t)N * K * sizeof(float));
+    s.part_fc1 = s.dz + round256((size_t)R * K * sizeof(float));
+    s.part_cent = s.part_fc1 + round256((size_t)s.chunks_r * kd);
+    s.total = s.part_cent + round256((size_t)s.chunks_n * kd);
+    return s;
+}
+int check_reserve(const char* fn, size_t reserve_bytes, size_t need) {
+    if (reserve_bytes < need) return fail(LAFF_E_ARG, "%s: reserve too small (%zu < %zu bytes)", fn, reserve_bytes, need);
+    return LAFF_OK;
+}
 }  // namespace
 
 int laff_netvlad_workspace_bytes(int R, int K, size_t* out) {
@@ -1336,15 +1390,11 @@ int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const i
                         void* workspace, size_t workspace_bytes) {
     const char* fn = "laff_netvlad_encode";
     // every argument is checked before any GPU work
-    if (int rc = netvlad_check_k(fn, K)) return rc;
-    if (D < 4 || D > laff::NETVLAD_MAX_D || D % 4)
-        return fail(LAFF_E_UNSUPPORTED, "%s: D=%d: the word-vector width must be a multiple of 4 in [4, %d]", fn, D, laff::NETVLAD_MAX_D);
-    if (N < 0 || R < 0 || V < 1) return fail(LAFF_E_SHAPE, "%s: bad shape N=%d R=%d V=%d", fn, N, R, V);
+    if (int rc = netvlad_check_sizes(fn, V, D, N, R, K)) return rc;
     if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch */
-    if (!table || (R && !ids) || !row_off || !row_off_host || !zero_rows || !fc1_weight || !centroids || !out || (R && !workspace))
-        return fail(LAFF_E_ARG, "%s: null argument", fn);
-    if (int rc = check_offsets(fn, "row_off", "caption", "NR", row_off_host, N, R, 0, INT_MAX, nullptr)) return rc;
-    if (ldo < K * D || ldo % 4) return fail(LAFF_E_SHAPE, "%s: ldo=%d: at least K*D=%d and a multiple of 4", fn, ldo, K * D);
+    if (int rc = netvlad_check_batch(fn, table, ids, row_off, row_off_host, zero_rows, N, R, fc1_weight, centroids, K, D, out, ldo,
+                                     R && !workspace))
+        return rc;
     if (int rc = check_workspace(fn, workspace, workspace_bytes, netvlad_ws_bytes(R, K),
                                  aligned16(table) && aligned16(centroids) && aligned16(fc1_weight) && aligned16(out),
                                  "table / fc1_weight / centroids / out / workspace"))
@@ -1355,6 +1405,93 @@ int laff_netvlad_encode(laff_ctx* ctx, const float* table, int V, int D, const i
     laff::NetvladArgs a{table, V, D, K, ids, row_off, zero_rows, N, R, fc1_weight, centroids, ws,
                         (float*)((char*)workspace + netvlad_rnorm_offset(R, K)), out, ldo};
     HIP_TRY(laff::launch_netvlad_encode(a, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_netvlad_train_reserve_bytes(int N, int R, int K, size_t* out) {
+    if (!out || N < 0 || R < 0) return fail(LAFF_E_ARG, "laff_netvlad_train_reserve_bytes: bad args");
+    if (int rc = netvlad_check_k("laff_netvlad_train_reserve_bytes", K)) return rc;
+    *out = netvlad_reserve(N, R, K).total;
+    return LAFF_OK;
+}
+
+int laff_netvlad_backward_workspace_bytes(int N, int R, int K, int D, size_t* out) {
+    const char* fn = "laff_netvlad_backward_workspace_bytes";
+    if (!out) return fail(LAFF_E_ARG, "%s: bad args", fn);
+    if (int rc = netvlad_check_sizes(fn, 1, D, N, R, K)) return rc;
+    *out = netvlad_bwd_ws(N, R, K, D).total;
+    return LAFF_OK;
+}
+
+int laff_netvlad_encode_train(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off,
+                              const int* row_off_host, const int* zero_rows, int N, int R, const float* fc1_weight,
+                              const float* centroids, int K, float* out, int ldo, void* reserve, size_t reserve_bytes, void* workspace,
+                              size_t workspace_bytes) {
+    const char* fn = "laff_netvlad_encode_train";
+    if (int rc = netvlad_check_sizes(fn, V, D, N, R, K)) return rc;
+    if (N == 0) return LAFF_OK;                 /* empty problem: nothing to launch, nothing to save */
+    if (int rc = netvlad_check_batch(fn, table, ids, row_off, row_off_host, zero_rows, N, R, fc1_weight, centroids, K, D, out, ldo,
+                                     !reserve))
+        return rc;
+    const NetvladReserve rs = netvlad_reserve(N, R, K);
+    if (int rc = check_reserve(fn, reserve_bytes, rs.total)) return rc;
+    /* the assignments go straight into the reserve: the workspace is not used, it may be null */
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, 0,
+                                 aligned16(table) && aligned16(centroids) && aligned16(fc1_weight) && aligned16(out) && aligned16(reserve),
+                                 "table / fc1_weight / centroids / out / reserve / workspace"))
+        return rc;
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    char* r = (char*)reserve;
+    laff::NetvladArgs a{table, V, D, K, ids, row_off, zero_rows, N, R, fc1_weight, centroids, (float*)r, (float*)(r + rs.rnorm), out, ldo};
+    HIP_TRY(laff::launch_netvlad_encode_train(a, (float*)(r + rs.den), (int*)(r + rs.clamped), ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_netvlad_backward(laff_ctx* ctx, const float* table, int V, int D, const int* ids, const int* row_off, const int* row_off_host,
+                          const int* zero_rows, int N, int R, const float* fc1_weight, const float* centroids, int K, const float* out,
+                          int ldo, const float* d_out, int ldg, const void* reserve, size_t reserve_bytes, float* d_fc1,
+                          float* d_centroids, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_netvlad_backward";
+    if (int rc = netvlad_check_sizes(fn, V, D, N, R, K)) return rc;
+    if (N > 0) {
+        if (int rc = netvlad_check_batch(fn, table, ids, row_off, row_off_host, zero_rows, N, R, fc1_weight, centroids, K, D, out, ldo,
+                                         !d_out || !reserve || !workspace))
+            return rc;
+        if (ldg < K * D || ldg % 4) return fail(LAFF_E_SHAPE, "%s: ldg=%d: at least K*D=%d and a multiple of 4", fn, ldg, K * D);
+        if (int rc = check_reserve(fn, reserve_bytes, netvlad_reserve(N, R, K).total)) return rc;
+    }
+    if (!d_fc1 && !d_centroids) return LAFF_OK; /* nothing wanted: nothing to launch */
+    const NetvladBwdWs L = netvlad_bwd_ws(N, R, K, D);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, N > 0 ? L.total : 0,
+                                 aligned16(table) && aligned16(centroids) && aligned16(out) && aligned16(d_out) && aligned16(reserve) &&
+                                     aligned16(d_fc1) && aligned16(d_centroids),
+                                 "table / centroids / out / d_out / reserve / d_fc1 / d_centroids / workspace"))
+        return rc;
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    const NetvladReserve rs = netvlad_reserve(N, R, K);
+    char* r = (char*)const_cast<void*>(reserve);
+    char* w = (char*)workspace;
+    laff::NetvladBwdArgs p{};
+    p.f = laff::NetvladArgs{table, V, D, K, ids, row_off, zero_rows, N, R, fc1_weight, centroids, (float*)r, (float*)(r + rs.rnorm),
+                            const_cast<float*>(out), ldo};
+    p.den = (const float*)(r + rs.den);
+    p.clamped = (const int*)(r + rs.clamped);
+    p.g = d_out;
+    p.ldg = ldg;
+    p.du = (float*)w;
+    p.mass = (float*)(w + L.mass);
+    p.dz = (float*)(w + L.dz);
+    p.part_fc1 = (float*)(w + L.part_fc1);
+    p.part_cent = (float*)(w + L.part_cent);
+    p.rows_per_chunk = L.rows_per_chunk;
+    p.chunks_r = L.chunks_r;
+    p.caps_per_chunk = L.caps_per_chunk;
+    p.chunks_n = L.chunks_n;
+    p.d_fc1 = d_fc1;
+    p.d_cent = d_centroids;
+    HIP_TRY(laff::launch_netvlad_backward(p, ctx->stream));
     return LAFF_OK;
 }
 

@@ -690,7 +690,28 @@ struct NetvladArgs {
     float* out;
     long ldo;
 };
+hipError_t launch_netvlad_assign(const NetvladArgs& a, hipStream_t st);      // the first of its two launches alone (R > 0)
 hipError_t launch_netvlad_encode(const NetvladArgs& a, hipStream_t st);
+
+// netvlad_bwd.hip: the saving forward and the backward of the NetVLAD encoder (laff_netvlad_encode_train, laff_netvlad_backward)
+struct NetvladBwdArgs {
+    NetvladArgs f;            // the forward's arguments: assign and rnorm are the reserve's, out the forward's output
+    const float* den;         // reserve: [N, K + 1] max(|u_k|, eps) for k < K, then max(|v|, eps)
+    const int* clamped;       // reserve: [N, K + 1] 1 where that norm was not above eps
+    const float* g;           // [N, ldg] the gradient of out
+    long ldg;
+    float* du;                // workspace: [N, K, D]
+    float* mass;              // workspace: [N, K] s_k
+    float* dz;                // workspace: [R, K] the gradient of the logits
+    float* part_fc1;          // workspace: [chunks_r, K, D] the sums of d_fc1 over rows_per_chunk token rows each
+    float* part_cent;         // workspace: [chunks_n, K, D] the sums of d_centroids over caps_per_chunk captions each
+    int rows_per_chunk, chunks_r, caps_per_chunk, chunks_n;
+    float* d_fc1;             // [K, D] or null
+    float* d_cent;            // [K, D] or null
+};
+// a.assign / a.rnorm are written (the reserve's regions); den / clamped [N, K + 1] as NetvladBwdArgs reads them
+hipError_t launch_netvlad_encode_train(const NetvladArgs& a, float* den, int* clamped, hipStream_t st);
+hipError_t launch_netvlad_backward(const NetvladBwdArgs& p, hipStream_t st);
 
 // rerank.hip: k-reciprocal re-ranking (laff_rerank_run) and the neighbour-count re-ranking (laff_rerank_tkb)
 constexpr int RERANK_MAX_K1 = 32;

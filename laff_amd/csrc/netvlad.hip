@@ -1,4 +1,4 @@
-// netvlad.hip -- the NetVLAD caption encoder of the text tower, inference only
+// netvlad.hip -- the NetVLAD caption encoder of the text tower, the inference forward (training: netvlad_bwd.hip)
 // (reference model/model.py:529-549 NetVLADTxtEncoder over model/Attention.py:862-918 NetVLAD.forward).
 //
 // Per caption, over its M word2vec rows x_m (the distinct known words; or Z zero rows when no word is known):
@@ -216,15 +216,19 @@ __global__ __launch_bounds__(VLAD_THREADS) void netvlad_vlad_kernel(NetvladArgs 
         }
 }
 
+// the soft assignments and 1 / max(|x|, eps) of the R > 0 token rows; the saving forward (netvlad_bwd.hip) starts with it as well
+hipError_t launch_netvlad_assign(const NetvladArgs& a, hipStream_t st) {
+    const unsigned blocks = (unsigned)((a.R + 255) / 256);
+    if (a.K <= 8) netvlad_assign_kernel<8><<<blocks, 256, 0, st>>>(a);
+    else if (a.K <= 16) netvlad_assign_kernel<16><<<blocks, 256, 0, st>>>(a);
+    else if (a.K <= 32) netvlad_assign_kernel<32><<<blocks, 256, 0, st>>>(a);
+    else netvlad_assign_kernel<64><<<blocks, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t launch_netvlad_encode(const NetvladArgs& a, hipStream_t st) {
-    if (a.R > 0) {
-        const unsigned blocks = (unsigned)((a.R + 255) / 256);
-        if (a.K <= 8) netvlad_assign_kernel<8><<<blocks, 256, 0, st>>>(a);
-        else if (a.K <= 16) netvlad_assign_kernel<16><<<blocks, 256, 0, st>>>(a);
-        else if (a.K <= 32) netvlad_assign_kernel<32><<<blocks, 256, 0, st>>>(a);
-        else netvlad_assign_kernel<64><<<blocks, 256, 0, st>>>(a);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
+    if (a.R > 0)
+        if (hipError_t e = launch_netvlad_assign(a, st); e != hipSuccess) return e;
     netvlad_vlad_kernel<<<a.N, VLAD_THREADS, 0, st>>>(a);
     return hipGetLastError();
 }

@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -686,11 +686,17 @@ def netvlad_workspace_bytes(R, K):
     return _size_query('laff_netvlad_workspace_bytes', R, K)
 
 
-def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, out=None, workspace=None):
-    """laff_netvlad_encode.  table [V, D] fp32 (word2vec rows), ids [R] int32, row_off [N+1] int32 and zero_rows [N] int32 on the
-    device, row_off_host: the same offsets as a host int32 array; fc1_weight / centroids [K, D] fp32.  Returns out [N, K*D] fp32.
-    workspace: a uint8 device tensor of netvlad_workspace_bytes(R, K) bytes, or None to allocate one here (pass one for HIP-graph
-    capture)."""
+def netvlad_train_reserve_bytes(N, R, K):
+    return _size_query('laff_netvlad_train_reserve_bytes', N, R, K)
+
+
+def netvlad_backward_workspace_bytes(N, R, K, D):
+    return _size_query('laff_netvlad_backward_workspace_bytes', N, R, K, D)
+
+
+def _netvlad_args(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids):
+    """What netvlad_encode, netvlad_encode_train and netvlad_backward check alike.  Returns the arguments table .. K that their C calls
+    share after the context, (V, D, K, R, N) and the tensors that have to outlive the call."""
     table, fc1_weight, centroids = _dev(table, 'table'), _dev(fc1_weight, 'fc1_weight'), _dev(centroids, 'centroids')
     ids, row_off = _dev(ids, 'ids', torch.int32), _dev(row_off, 'row_off', torch.int32)
     zero_rows = _dev(zero_rows, 'zero_rows', torch.int32)
@@ -709,12 +715,72 @@ def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, cen
     if zero_rows.numel() != N:
         raise ValueError('zero_rows has %d entries for %d captions' % (zero_rows.numel(), N))
     row_off, roh, N = _offsets(row_off, row_off_host, 'row_off')
-    workspace, out, o, ldo = _ws_out(workspace, lambda: netvlad_workspace_bytes(R, K), out, (N, K * D), table.device)
-    lib, h = _context(table.device)
-    _call('netvlad_encode', lib.laff_netvlad_encode, h, _ptr(table), V, D, _ptr(ids), _ptr(row_off),
-          roh.ctypes.data_as(C.POINTER(C.c_int)), _ptr(zero_rows), N, R, _ptr(fc1_weight), _ptr(centroids), K, o, ldo,
-          _ptr(workspace), workspace.numel())
+    keep = (table, ids, row_off, roh, zero_rows, fc1_weight, centroids)
+    head = (_ptr(table), V, D, _ptr(ids), _ptr(row_off), roh.ctypes.data_as(C.POINTER(C.c_int)), _ptr(zero_rows), N, R,
+            _ptr(fc1_weight), _ptr(centroids), K)
+    return head, (V, D, K, R, N), keep
+
+
+def netvlad_encode(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, out=None, workspace=None):
+    """laff_netvlad_encode.  table [V, D] fp32 (word2vec rows), ids [R] int32, row_off [N+1] int32 and zero_rows [N] int32 on the
+    device, row_off_host: the same offsets as a host int32 array; fc1_weight / centroids [K, D] fp32.  Returns out [N, K*D] fp32.
+    workspace: a uint8 device tensor of netvlad_workspace_bytes(R, K) bytes, or None to allocate one here (pass one for HIP-graph
+    capture)."""
+    head, (V, D, K, R, N), keep = _netvlad_args(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids)
+    workspace, out, o, ldo = _ws_out(workspace, lambda: netvlad_workspace_bytes(R, K), out, (N, K * D), keep[0].device)
+    lib, h = _context(keep[0].device)
+    _call('netvlad_encode', lib.laff_netvlad_encode, h, *head, o, ldo, _ptr(workspace), workspace.numel())
     return out
+
+
+def _byte_buffer(buf, name, nbytes, device):
+    """A caller's uint8 device buffer of at least nbytes, or a fresh one."""
+    if buf is None:
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    _dev(buf, name, torch.uint8)
+    if buf.numel() < nbytes:
+        raise ValueError('%s has %d bytes, %d are needed' % (name, buf.numel(), nbytes))
+    return buf
+
+
+def netvlad_encode_train(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, out=None, reserve=None):
+    """laff_netvlad_encode_train: netvlad_encode (the same bits) that also fills reserve, a uint8 device tensor of
+    netvlad_train_reserve_bytes(N, R, K) bytes (allocated here when None), for netvlad_backward.  It needs no workspace: the
+    assignments go straight into the reserve.  Returns (out, reserve)."""
+    head, (V, D, K, R, N), keep = _netvlad_args(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids)
+    dev = keep[0].device
+    reserve = _byte_buffer(reserve, 'reserve', netvlad_train_reserve_bytes(N, R, K), dev)
+    out, o, ldo = _out_rows(out, (N, K * D), dev)
+    lib, h = _context(dev)
+    _call('netvlad_encode_train', lib.laff_netvlad_encode_train, h, *head, o, ldo, _ptr(reserve), reserve.numel(), None, 0)
+    return out, reserve
+
+
+def netvlad_backward(grad_out, out, reserve, table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids, want=(True, True),
+                     d_fc1=None, d_centroids=None, workspace=None):
+    """laff_netvlad_backward.  grad_out [N, K*D] the gradient of out (the forward's output, with its reserve from
+    netvlad_encode_train on the same batch and parameters).  want = (d_fc1, d_centroids): which gradients to form; d_fc1 /
+    d_centroids: contiguous [K, D] fp32 buffers to write into (allocated here when wanted and None); workspace: a uint8 device
+    tensor of netvlad_backward_workspace_bytes(N, R, K, D) bytes, or None to allocate one.  Returns (d_fc1 | None, d_centroids | None)."""
+    head, (V, D, K, R, N), keep = _netvlad_args(table, ids, row_off, row_off_host, zero_rows, fc1_weight, centroids)
+    dev = keep[0].device
+    g, ldg = _mat(grad_out, 'grad_out', align16=True)
+    o, ldo = _rows(out, 'out')
+    if tuple(g.shape) != (N, K * D) or tuple(o.shape) != (N, K * D):
+        raise ValueError('grad_out and out must both be (%d, %d), got %s and %s' % (N, K * D, tuple(g.shape), tuple(o.shape)))
+    reserve = _byte_buffer(_dev(reserve, 'reserve', torch.uint8), 'reserve', netvlad_train_reserve_bytes(N, R, K), dev)
+    grads = []
+    for flag, t, nm in ((want[0], d_fc1, 'd_fc1'), (want[1], d_centroids, 'd_centroids')):
+        if flag and t is None:
+            t = torch.empty((K, D), device=dev, dtype=torch.float32)
+        if flag and (tuple(_dev(t, nm).shape) != (K, D) or not t.is_contiguous()):
+            raise ValueError('%s must be a contiguous (%d, %d) matrix' % (nm, K, D))
+        grads.append(t if flag else None)
+    workspace = _byte_buffer(workspace, 'workspace', netvlad_backward_workspace_bytes(N, R, K, D), dev)
+    lib, h = _context(dev)
+    _call('netvlad_backward', lib.laff_netvlad_backward, h, *head, _ptr(o), ldo, _ptr(g), ldg, _ptr(reserve), reserve.numel(),
+          _ptr(grads[0]), _ptr(grads[1]), _ptr(workspace), workspace.numel())
+    return grads[0], grads[1]
 
 
 def clip_image_kpad(patch_size, precision='fp16'):

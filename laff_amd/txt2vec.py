@@ -11,7 +11,8 @@ Stop words are DATA of the deployment (the reference ships `stopwords_en.txt`); 
 `set(open('stopwords_en.txt').read().split())`.
 
 The NetVLAD encoder (`NetVLADTxtEncoder`) shares the W2Vec object and its device table: the host maps captions to table rows
-(`W2Vec.ragged`), the soft assignment and the residual pooling run on the GPU (`laff_netvlad_encode`).
+(`W2Vec.ragged`), the soft assignment and the residual pooling run on the GPU (`laff_netvlad_encode`; with differentiable=True
+in training `laff_netvlad_encode_train` and `laff_netvlad_backward`).
 
 The GRU encoder (`GruTxtEncoder`) keeps the same split: the host maps captions to token ids and lays the batch out the way the
 step kernel walks it (`IdxVec.batch`); the recurrence runs on the GPU (`laff_gru_encode`).
@@ -244,15 +245,43 @@ class _NetVLAD(nn.Module):
         self.fc1.weight = nn.Parameter(init_sc * torch.randn(self.num_clusters, self.dim))
 
 
+class _NetvladEncodeFn(torch.autograd.Function):
+    """The saving forward (laff_netvlad_encode_train) with laff_netvlad_backward behind it.  Saves out, the reserve and the batch
+    arrays; forms only the gradients that needs_input_grad asks for (the word2vec table gets none: the reference feeds its rows
+    without a graph).  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, table, batch, fc1_weight, centroids):
+        from . import ops
+        out, reserve = ops.netvlad_encode_train(table, *batch, fc1_weight.detach(), centroids.detach())
+        ctx.save_for_backward(out, reserve, table, fc1_weight, centroids)
+        ctx.batch = batch
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import ops
+        out, reserve, table, fc1_weight, centroids = ctx.saved_tensors
+        want = (bool(ctx.needs_input_grad[2]), bool(ctx.needs_input_grad[3]))
+        d_fc1, d_cent = ops.netvlad_backward(grad_out, out, reserve, table, *ctx.batch, fc1_weight.detach(), centroids.detach(),
+                                             want=want)
+        return None, None, d_fc1, d_cent
+
+
 class NetVLADTxtEncoder(nn.Module):
-    """Drop-in for model.model.NetVLADTxtEncoder (model/model.py:529-549), inference:
+    """Drop-in for model.model.NetVLADTxtEncoder (model/model.py:529-549):
     `txt_net.encoder.NetVLAD_encoder = NetVLADTxtEncoder(t2v_w2v, num_clusters, alpha)`, sharing the W2Vec (and its device table)
     with W2VTxtEncoder.  State-dict keys are the reference's (netvlad.fc1.weight, netvlad.centeroids), so its checkpoints load with
     strict=True.  Output: {'text_features': (N, K * D)}.  The kernel reads the parameters as they are, so every change of them
-    (load_state_dict, copy_, a new Parameter) is seen by the next call."""
+    (load_state_dict, copy_, a new Parameter) is seen by the next call.
+    Training: with differentiable=True, .train() and enabled gradients, forward / encode_batch run the saving forward
+    (laff_netvlad_encode_train, fp32; the same bits) under autograd, and its backward gives the gradients of netvlad.fc1.weight and
+    netvlad.centeroids (laff_netvlad_backward).  The switch is explicit: without it .train() changes nothing."""
 
-    def __init__(self, t2v_w2v, num_clusters=32, alpha=100, device='cuda'):
+    def __init__(self, t2v_w2v, num_clusters=32, alpha=100, device='cuda', differentiable=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         K, D = int(num_clusters), int(t2v_w2v.ndims)
         if not 1 <= K <= 64:
             raise NotImplementedError('NetVLADTxtEncoder: num_clusters=%d; the kernel takes 1 to 64 clusters' % K)
@@ -269,8 +298,20 @@ class NetVLADTxtEncoder(nn.Module):
         """The device half of forward(): W2Vec.ragged's arrays, ids / row_off / zero_rows already on the device."""
         from . import ops
         v = self.netvlad
+        if self.differentiable and self.training and torch.is_grad_enabled():
+            return self._encode_train((ids, row_off, row_off_host, zero_rows))
         return ops.netvlad_encode(self.t2v_w2v.device_table(self.device), ids, row_off, row_off_host, zero_rows,
                                   v.fc1.weight.detach(), v.centeroids.detach(), out=out, workspace=workspace)
+
+    def _encode_train(self, batch):
+        v = self.netvlad
+        for p_, nm in ((v.fc1.weight, 'netvlad.fc1.weight'), (v.centeroids, 'netvlad.centeroids')):
+            if p_.dtype != torch.float32:
+                raise TypeError('the differentiable NetVLAD encoder is fp32 only, %s is %s' % (nm, p_.dtype))
+            if not p_.is_cuda:
+                raise RuntimeError('the differentiable NetVLAD encoder runs on the device only, %s is a CPU tensor: laff_amd has no '
+                                   'CPU path' % nm)
+        return _NetvladEncodeFn.apply(self.t2v_w2v.device_table(self.device), batch, v.fc1.weight, v.centeroids)
 
     def forward(self, caption_feat_dict, task3=False):
         b = self.to_device(*self.t2v_w2v.ragged(caption_feat_dict['caption']))

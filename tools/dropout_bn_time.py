@@ -22,7 +22,7 @@ import json
 import os
 import sys
 
-from train_time import median_ms, run_child
+from train_time import median_ms, run_child, torch_launches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(128, 512), (128, 2048), (128, 4096), (8192, 512)]
@@ -31,21 +31,6 @@ HBM_PEAK = 8.0e12
 TOL_UNIT = 1.5e-6
 SEED = 0x0123456789abcdef
 EPS, MOMENTUM = 1e-5, 0.1
-
-
-def _torch_launches(fn):
-    """Device kernels of one call of fn, counted by torch.profiler; None when it sees none."""
-    import torch
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and 'memcpy' not in e.name.lower())
-        return n or None
-    except Exception:
-        return None
 
 
 def child(iters):
@@ -127,7 +112,7 @@ def child(iters):
             leaves = [ag] + ([norm.weight, norm.bias] if bn else [])
             t_bwd = lambda: torch.autograd.grad(yt, leaves, dy, retain_graph=True)       # noqa: E731
             row = {'shape': [N, D], 'stage': name, 'chunks': chunks,
-                   'launches': {'fwd': launches, 'bwd': launches, 'torch_fwd': _torch_launches(t_fwd), 'torch_bwd': _torch_launches(t_bwd)}}
+                   'launches': {'fwd': launches, 'bwd': launches, 'torch_fwd': torch_launches(t_fwd), 'torch_bwd': torch_launches(t_bwd)}}
             times = {'fwd_ms': median_ms(fwd, iters), 'bwd_ms': median_ms(bwd, iters),
                      'op_fwd_ms': median_ms(lambda: ops.dropout_bn_train(a, p, seed if p else None, gamma if bn else None, beta, rm, rv,
                                                                          MOMENTUM, EPS), iters),

@@ -1,5 +1,5 @@
-"""What the training-path timing tools (tools/*_backward_time.py, tools/optim_step_time.py) share: the timed window and the
-parent / child process scaffold."""
+"""What the training-path timing tools (tools/*_backward_time.py, tools/optim_step_time.py) share: the timed window, the count of
+torch's launches and the parent / child process scaffold."""
 import argparse
 import os
 import subprocess
@@ -26,6 +26,21 @@ def median_ms(fn, iters, wall=False):
         host.append((time.perf_counter() - w0) * 1e3 / iters)
         dev.append(t0.elapsed_time(t1) / iters)
     return (sorted(dev)[2], sorted(host)[2]) if wall else sorted(dev)[2]
+
+
+def torch_launches(fn):
+    """Device kernels of one call of fn, counted by torch.profiler; None when it sees none."""
+    import torch
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and 'memcpy' not in e.name.lower())
+        return n or None
+    except Exception:
+        return None
 
 
 def run_child(child, default_iters, default_timeout=240):
