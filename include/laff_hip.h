@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 44
+#define LAFF_ABI_VERSION 45
 
 enum {
     LAFF_OK = 0,
@@ -1028,6 +1028,54 @@ int laff_rank_metrics(laff_ctx* ctx, const int* r, int Nq, int base, int* ranks_
  * The device writes a pinned (device-addressable) buffer directly from the kernel; any other host pointer gets a 64-byte copy queued
  * behind the launch. */
 int laff_rank_metrics_async(laff_ctx* ctx, const int* r, int Nq, int base, int* ranks_out, double* out8_pinned_host);
+
+/* ---- t: a training batch gathered from a device-resident training set in ONE launch (no counterpart in the reference: its
+ * PairDataset / collate_pair, data_provider.py:92-152, :621-698, read and stack a batch item by item on the host) -----------------
+ * Runs 1 .. LAFF_ASSEMBLE_MAX_JOBS copy jobs over the same B batch rows.  Sources are resident device arrays of 4-byte elements.
+ * Every per-batch integer sits in ONE int32 control block [control_len], passed TWICE: on the device for the kernel and in HOST
+ * memory for the checks (the same values; the caller uploads it once per batch).  A job names where in the block its integers start.
+ *   LAFF_ASSEMBLE_ROWS    dst[b, 0:w] = src[row[b], 0:w]: src [n_src, ld_src >= w], dst [B, ld_dst >= w], row = control + rows_at [B],
+ *                         every row[b] in [0, n_src) (a source row may repeat).  Any w >= 1.
+ *   LAFF_ASSEMBLE_RAGGED  src [n_items, ld_src >= w] holds n_src segments, segment g the rows [off_src[g], off_src[g + 1]) (off_src
+ *                         [n_src + 1] int32 on the device); seg = control + rows_at [B] in [0, n_src).  dst [B, fmax, w] contiguous:
+ *                         the first min(len, fmax) rows of segment seg[b], then zeros up to fmax >= 1; a padded row is not read from the
+ *                         source.  mask (nullable) [B, fmax] fp32: 1 for a copied row, 0 for a padded one.  Several jobs over the same
+ *                         segments give the same mask: pass it to the first and NULL to the others.
+ *   LAFF_ASSEMBLE_CSR     the source CSR has n_src rows and n_items entries: off_src = crow_src [n_src + 1], col_src (int32), src =
+ *                         val_src (4-byte values).  row = control + rows_at [B]; crow_dst = control + crow_at [B + 1], non-decreasing from
+ *                         crow_dst[0] >= 0 with crow_dst[B] <= cap_dst (the entries col_dst and dst = val_dst hold).  The entries of source
+ *                         row row[b] go to [crow_dst[b], crow_dst[b + 1]); a range longer than the source row is filled with zeros, a
+ *                         shorter one takes the row's first entries.  Empty rows and crow_dst[B] == 0 are legal.
+ * The job chooses its access width: 16 bytes a lane where src, dst and both pitches are 16-byte aligned (ragged: w % 4 == 0 too),
+ * with the last w % 4 elements of a row copied one by one; 4 bytes a lane otherwise (any 4-byte aligned window of a wider matrix).
+ * Every destination element is written exactly once, plain loads and stores, no atomics: two calls give the same bits.  An index read
+ * from DEVICE memory (the device copy of control, off_src) that points outside its source is never followed: that row comes out as
+ * zeros.  Limits: 1 <= B <= 4096; at most LAFF_ASSEMBLE_MAX_JOBS jobs; a destination of 2^31 elements or more (B * ld_dst,
+ * B * fmax * w) is refused by name (LAFF_E_SHAPE); sources are addressed in 64 bits.  All refusals come before the launch, the NULL ctx
+ * last.  No allocation, no host synchronisation: capturable in a HIP graph. */
+enum { LAFF_ASSEMBLE_ROWS = 0, LAFF_ASSEMBLE_RAGGED = 1, LAFF_ASSEMBLE_CSR = 2 };
+#define LAFF_ASSEMBLE_MAX_JOBS 16
+#define LAFF_ASSEMBLE_MAX_BATCH 4096
+typedef struct laff_assemble_job {
+    int kind;               /* LAFF_ASSEMBLE_* */
+    int rows_at;            /* index in control of this job's B source indices */
+    int crow_at;            /* CSR: index in control of crow_dst [B + 1] */
+    int w;                  /* rows, ragged: elements of a row */
+    int ld_src;             /* rows, ragged: pitch of src in elements */
+    int ld_dst;             /* rows: pitch of dst in elements */
+    int n_src;              /* rows: rows of src; ragged: segments; CSR: rows of the source */
+    int n_items;            /* ragged: rows of src; CSR: entries of the source */
+    int fmax;               /* ragged: rows of a padded batch row */
+    int cap_dst;            /* CSR: entries that col_dst / dst hold */
+    const void* src;        /* device; CSR: val_src */
+    const int* off_src;     /* device; ragged: seg_off; CSR: crow_src */
+    const int* col_src;     /* device; CSR */
+    void* dst;              /* device; CSR: val_dst */
+    int* col_dst;           /* device; CSR */
+    float* mask;            /* device; ragged, nullable */
+} laff_assemble_job;
+int laff_batch_assemble(laff_ctx* ctx, const laff_assemble_job* jobs, int count, int B, const int* control /*device*/,
+                        const int* control_host, int control_len);
 
 /* ---- e: the collectives of the sharded path for a host that is not Python (laff_amd/dist.py issues the same three through
  * torch.distributed).  One process per GPU; RCCL is looked up at the first call (a copy already loaded into

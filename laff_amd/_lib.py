@@ -11,7 +11,7 @@ ATT_WITH_AVE, ATT_MUL, ATT_L2NORM_EACH_HEAD, ATT_NO_SPLIT_HEAD, ATT_JUST_AVERAGE
 GRU_POOLING = {'mean': 0, 'last': 1, 'mean_last': 2}
 OPT_KIND = {'adam': 0, 'rmsprop': 1}
 PREC = {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4}
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 
 class Plane(C.Structure):
@@ -119,6 +119,14 @@ class RerankProblem(C.Structure):
     _fields_ = [('qq', C.c_void_p), ('ldqq', C.c_longlong), ('qg', C.c_void_p), ('ldqg', C.c_longlong), ('gg', C.c_void_p),
                 ('ldgg', C.c_longlong), ('out', C.c_void_p), ('ldo', C.c_longlong), ('Q', C.c_int), ('G', C.c_int)]
 
+
+class AssembleJob(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('kind', 'rows_at', 'crow_at', 'w', 'ld_src', 'ld_dst', 'n_src', 'n_items', 'fmax', 'cap_dst')] + \
+               [(n, C.c_void_p) for n in ('src', 'off_src', 'col_src', 'dst', 'col_dst', 'mask')]
+
+
+ASSEMBLE_KIND = {'rows': 0, 'ragged': 1, 'csr': 2}
+ASSEMBLE_MAX_JOBS, ASSEMBLE_MAX_BATCH = 16, 4096
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -247,6 +255,7 @@ SIGNATURES = {
                                             C.c_size_t]),
     'laff_netvlad_backward': (C.c_int, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, C.c_size_t,
                                         _P, _P, _P, C.c_size_t]),
+    'laff_batch_assemble': (C.c_int, [_P, C.POINTER(AssembleJob), _I, _I, _P, _P, _I]),
     'laff_rerank_workspace_bytes': (C.c_int, [C.POINTER(RerankProblem), _I, _I, _I, C.POINTER(C.c_size_t)]),
     'laff_rerank_run': (C.c_int, [_P, C.POINTER(RerankProblem), _I, _I, _I, _F, _P, C.c_size_t]),
     'laff_rerank_tkb': (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I]),

@@ -1496,6 +1496,87 @@ int laff_netvlad_backward(laff_ctx* ctx, const float* table, int V, int D, const
 }
 
 namespace {
+// B entries of the host control block from `at`, each in [0, n): the source indices of job i
+int assemble_indices(const char* fn, int i, const int* control_host, int control_len, int at, int B, int n, const char* what) {
+    if (at < 0 || (long long)at + B > control_len)
+        return fail(LAFF_E_ARG, "%s: job %d: %s [%d, %d) lie outside the control block of %d", fn, i, what, at, at + B, control_len);
+    for (int b = 0; b < B; ++b)
+        if (control_host[at + b] < 0 || control_host[at + b] >= n)
+            return fail(LAFF_E_ARG, "%s: job %d: %s[%d] = %d is outside [0, %d)", fn, i, what, b, control_host[at + b], n);
+    return LAFF_OK;
+}
+}  // namespace
+
+int laff_batch_assemble(laff_ctx* ctx, const laff_assemble_job* jobs, int count, int B, const int* control, const int* control_host,
+                        int control_len) {
+    const char* fn = "laff_batch_assemble";
+    if (count < 1 || count > LAFF_ASSEMBLE_MAX_JOBS)
+        return fail(LAFF_E_SHAPE, "%s: %d jobs; a launch takes 1 to %d", fn, count, LAFF_ASSEMBLE_MAX_JOBS);
+    if (B < 1 || B > LAFF_ASSEMBLE_MAX_BATCH) return fail(LAFF_E_SHAPE, "%s: B=%d; a batch has 1 to %d rows", fn, B, LAFF_ASSEMBLE_MAX_BATCH);
+    if (!jobs || !control || !control_host || control_len < 1) return fail(LAFF_E_ARG, "%s: null jobs / control / control_host", fn);
+    if (!aligned4(control)) return fail(LAFF_E_ALIGN, "%s: control must be 4-byte aligned", fn);
+    laff::AssembleTable t{};
+    t.count = count;
+    t.B = B;
+    t.control = control;
+    for (int i = 0; i < count; ++i) {
+        const laff_assemble_job& q = jobs[i];
+        laff::AssembleJob& j = t.j[i];
+        if (q.kind < LAFF_ASSEMBLE_ROWS || q.kind > LAFF_ASSEMBLE_CSR) return fail(LAFF_E_ARG, "%s: job %d: bad kind %d", fn, i, q.kind);
+        if (!q.src || !q.dst) return fail(LAFF_E_ARG, "%s: job %d: null src / dst", fn, i);
+        if (!aligned4(q.src) || !aligned4(q.dst)) return fail(LAFF_E_ALIGN, "%s: job %d: src / dst must be 4-byte aligned", fn, i);
+        j.kind = q.kind;
+        j.rows_at = q.rows_at;
+        j.src = q.src;
+        j.dst = q.dst;
+        if (q.kind == LAFF_ASSEMBLE_CSR) {
+            if (q.n_src < 1 || q.n_items < 0 || q.cap_dst < 0)
+                return fail(LAFF_E_SHAPE, "%s: job %d: bad CSR sizes n_src=%d n_items=%d cap_dst=%d", fn, i, q.n_src, q.n_items, q.cap_dst);
+            if (!q.off_src || !q.col_src || !q.col_dst) return fail(LAFF_E_ARG, "%s: job %d: null crow_src / col_src / col_dst", fn, i);
+            if (int rc = assemble_indices(fn, i, control_host, control_len, q.rows_at, B, q.n_src, "row")) return rc;
+            if (q.crow_at < 0 || (long long)q.crow_at + B + 1 > control_len)
+                return fail(LAFF_E_ARG, "%s: job %d: crow_dst [%d, %d] lies outside the control block of %d", fn, i, q.crow_at,
+                            q.crow_at + B, control_len);
+            const int* cd = control_host + q.crow_at;
+            if (cd[0] < 0) return fail(LAFF_E_ARG, "%s: job %d: crow_dst[0] = %d is negative", fn, i, cd[0]);
+            for (int b = 0; b < B; ++b)
+                if (cd[b + 1] < cd[b]) return fail(LAFF_E_ARG, "%s: job %d: crow_dst decreases at %d (%d -> %d)", fn, i, b, cd[b], cd[b + 1]);
+            if (cd[B] > q.cap_dst) return fail(LAFF_E_ARG, "%s: job %d: crow_dst[B] = %d entries, col_dst / val_dst hold %d", fn, i, cd[B], q.cap_dst);
+            j.crow_at = q.crow_at;
+            j.n_src = q.n_src;
+            j.n_items = q.n_items;
+            j.off_src = q.off_src;
+            j.col_src = q.col_src;
+            j.col_dst = q.col_dst;
+            continue;
+        }
+        const bool ragged = q.kind == LAFF_ASSEMBLE_RAGGED;
+        if (q.w < 1 || q.ld_src < q.w || q.n_src < 1 || (!ragged && q.ld_dst < q.w) || (ragged && (q.fmax < 1 || q.n_items < 0)))
+            return fail(LAFF_E_SHAPE, "%s: job %d: bad shape w=%d ld_src=%d ld_dst=%d n_src=%d n_items=%d fmax=%d", fn, i, q.w, q.ld_src,
+                        q.ld_dst, q.n_src, q.n_items, q.fmax);
+        if (ragged && !q.off_src) return fail(LAFF_E_ARG, "%s: job %d: null seg_off", fn, i);
+        const long long dst_elems = ragged ? (long long)B * q.fmax * q.w : (long long)B * q.ld_dst;
+        if (dst_elems > INT_MAX)
+            return fail(LAFF_E_SHAPE, "%s: job %d: a destination of %lld elements overflows 32-bit indexing (%s)", fn, i, dst_elems,
+                        ragged ? "B * fmax * w" : "B * ld_dst");
+        if (int rc = assemble_indices(fn, i, control_host, control_len, q.rows_at, B, q.n_src, ragged ? "seg" : "row")) return rc;
+        j.w = q.w;
+        j.ld_src = q.ld_src;
+        j.ld_dst = ragged ? q.w : q.ld_dst;
+        j.n_src = q.n_src;
+        j.n_items = q.n_items;
+        j.fmax = ragged ? q.fmax : 1;
+        j.off_src = q.off_src;
+        j.mask = ragged ? q.mask : nullptr;
+        j.vec = aligned16(q.src) && aligned16(q.dst) && q.ld_src % 4 == 0 && j.ld_dst % 4 == 0 && q.w >= 4;
+    }
+    CHECK_CTX(ctx);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_batch_assemble(t, ctx->stream));
+    return LAFF_OK;
+}
+
+namespace {
 int rr_round_half_even(int k1) { return (k1 & 1) ? ((k1 / 2) & 1 ? k1 / 2 + 1 : k1 / 2) : k1 / 2; }
 // checks k1 / k2 and one problem's sizes; lays the problem's workspace out from `base` (may be null: sizes only); returns the bytes
 int rerank_layout(const char* fn, int i, int Q, int G, int k1, int k2, char* base, laff::RerankProblem* d, size_t* bytes) {

@@ -755,4 +755,33 @@ struct SimHistArgs {
 bool sim_hist_tiles(int Nt, int Nv, unsigned* tilesV, unsigned* tiles);    // false: more tiles than a grid holds
 hipError_t launch_sim_hist(const SimHistArgs& a, unsigned tiles, hipStream_t st);
 
+// batch_assemble.hip: a training batch gathered from the resident set in one launch (laff_batch_assemble)
+constexpr int ASSEMBLE_JOBS = 16;             // jobs of one launch: the table travels in the launch arguments (16 x 96 bytes)
+constexpr int ASSEMBLE_THREADS = 256;
+constexpr int ASSEMBLE_ITEMS_PER_THREAD = 4;  // a job gets a block per 1024 items ...
+constexpr int ASSEMBLE_BLOCK_CAP = 512;       // ... up to this many, which then stride
+struct AssembleJob {
+    int kind;                 // LAFF_ASSEMBLE_*
+    int vec;                  // rows, ragged: 16-byte pieces (bases and pitches allow it); else one element a piece
+    int rows_at, crow_at;     // in the control block: the B source indices; CSR: crow_dst [B + 1]
+    int w, ld_src, ld_dst;
+    int n_src;                // rows of src (rows), segments (ragged), rows of the source CSR
+    int n_items;              // ragged: rows of src; CSR: entries of the source
+    int fmax;
+    int first_block, blocks;  // filled by launch_batch_assemble
+    const void* src;          // CSR: val_src
+    const int* off_src;       // ragged: seg_off [n_src + 1]; CSR: crow_src [n_src + 1]
+    const int* col_src;
+    void* dst;                // CSR: val_dst
+    int* col_dst;
+    float* mask;
+};
+struct AssembleTable {
+    int count, B;
+    const int* control;
+    AssembleJob j[ASSEMBLE_JOBS];
+};
+long long assemble_items(const AssembleJob& j, int B);
+hipError_t launch_batch_assemble(AssembleTable& t, hipStream_t st);
+
 }  // namespace laff

@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'batch_assemble', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -517,6 +517,105 @@ def gru_gather_rows(table, ids, out=None):
     lib, h = _context(tb.device)
     _call('gru_gather_rows', lib.laff_gru_gather_rows, h, _ptr(tb), V, D, _ptr(ix), M, _ptr(out))
     return out
+
+
+def _assemble_view(t, name, dims):
+    """A device operand of batch_assemble with 4-byte elements (fp32 or int32) and unit inner stride, read or written IN PLACE (no copy
+    of a resident array is ever made here); `dims`-dimensional.  Returns its row pitch in elements."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError('%s must be a CUDA (ROCm) tensor: laff_amd has no CPU path' % name)
+    if t.dtype not in (torch.float32, torch.int32):
+        raise TypeError('%s must be float32 or int32, got %s' % (name, t.dtype))
+    if t.dim() != dims:
+        raise ValueError('%s must be %d-D, got shape %s' % (name, dims, tuple(t.shape)))
+    if dims == 1:
+        if t.numel() > 1 and t.stride(0) != 1:
+            raise ValueError('%s must be a contiguous vector' % name)
+        return 1
+    if dims == 3:
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous, got shape %s strides %s' % (name, tuple(t.shape), t.stride()))
+        return t.shape[2]
+    if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise ValueError('%s must have contiguous rows, got shape %s strides %s' % (name, tuple(t.shape), t.stride()))
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def batch_assemble(jobs, control, control_host, B):
+    """laff_batch_assemble: up to 16 gather jobs over the same B batch rows in one launch.  Every tensor is a device
+    tensor of float32 or int32 that is read or written in place; `control` is the batch's int32 control block on the device and
+    `control_host` the same values on the host (a numpy int32 array, e.g. the pinned block it was uploaded from).  A job is a tuple:
+        ('rows', src, rows_at, dst)                      dst[b] = src[control[rows_at + b]]; src (Nsrc, w) and dst (B, w) row views
+        ('ragged', src, seg_off, rows_at, dst, mask)     src (Nrows, w) row view, seg_off (Nseg + 1,) int32, dst (B, Fmax, w) contiguous,
+                                                         mask (B, Fmax) fp32 contiguous or None; rows past a segment's end are zeros
+        ('csr', (crow, col, val), rows_at, crow_at, (col_dst, val_dst))
+                                                         the entries of row control[rows_at + b] to [control[crow_at + b], control[crow_at + b + 1])
+    src and dst of a job have the same dtype.  Returns nothing: the destinations are the result."""
+    B = int(B)
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= _lib.ASSEMBLE_MAX_JOBS:
+        raise ValueError('batch_assemble takes 1 to %d jobs, got %d' % (_lib.ASSEMBLE_MAX_JOBS, len(jobs)))
+    if not 1 <= B <= _lib.ASSEMBLE_MAX_BATCH:
+        raise ValueError('batch_assemble takes 1 to %d batch rows, got %d' % (_lib.ASSEMBLE_MAX_BATCH, B))
+    _dev(control, 'control', torch.int32)
+    if control.dim() != 1 or not control.is_contiguous():
+        raise ValueError('control must be a contiguous vector')
+    host = control_host
+    if not isinstance(host, np.ndarray) or host.dtype != np.int32 or host.ndim != 1 or not host.flags.c_contiguous:
+        raise TypeError('control_host must be a contiguous 1-D numpy int32 array')
+    if host.size != control.numel():
+        raise ValueError('control_host has %d entries, control %d' % (host.size, control.numel()))
+    dev = control.device
+    arr = (_lib.AssembleJob * len(jobs))()
+
+    def same(i, nm, t, dtype=None):
+        if t.device != dev:
+            raise ValueError('job %d: %s is on %s, control on %s' % (i, nm, t.device, dev))
+        if dtype is not None and t.dtype != dtype:
+            raise TypeError('job %d: %s must be %s, got %s' % (i, nm, dtype, t.dtype))
+
+    for i, job in enumerate(jobs):
+        kind = job[0]
+        if kind not in _lib.ASSEMBLE_KIND:
+            raise ValueError("job %d: unknown kind %r (one of 'rows', 'ragged', 'csr')" % (i, kind))
+        q = arr[i]
+        q.kind = _lib.ASSEMBLE_KIND[kind]
+        if kind == 'rows':
+            _, src, rows_at, dst = job
+            q.ld_src, q.ld_dst = _assemble_view(src, 'job %d: src' % i, 2), _assemble_view(dst, 'job %d: dst' % i, 2)
+            same(i, 'src', src), same(i, 'dst', dst, src.dtype)
+            if dst.shape[0] != B or dst.shape[1] != src.shape[1]:
+                raise ValueError('job %d: dst %s does not fit B = %d rows of src %s' % (i, tuple(dst.shape), B, tuple(src.shape)))
+            q.w, q.n_src, q.rows_at = src.shape[1], src.shape[0], int(rows_at)
+            q.src, q.dst = src.data_ptr(), dst.data_ptr()
+        elif kind == 'ragged':
+            _, src, seg_off, rows_at, dst, mask = job
+            q.ld_src = _assemble_view(src, 'job %d: src' % i, 2)
+            _assemble_view(dst, 'job %d: dst' % i, 3), _assemble_view(seg_off, 'job %d: seg_off' % i, 1)
+            same(i, 'src', src), same(i, 'dst', dst, src.dtype), same(i, 'seg_off', seg_off, torch.int32)
+            if dst.shape[0] != B or dst.shape[2] != src.shape[1] or seg_off.numel() < 2:
+                raise ValueError('job %d: dst %s does not fit B = %d, src %s' % (i, tuple(dst.shape), B, tuple(src.shape)))
+            if mask is not None:
+                _assemble_view(mask, 'job %d: mask' % i, 2), same(i, 'mask', mask, torch.float32)
+                if tuple(mask.shape) != tuple(dst.shape[:2]) or not mask.is_contiguous():
+                    raise ValueError('job %d: mask must be a contiguous %s, got %s' % (i, tuple(dst.shape[:2]), tuple(mask.shape)))
+                q.mask = mask.data_ptr()
+            q.w, q.n_items, q.n_src, q.fmax, q.rows_at = src.shape[1], src.shape[0], seg_off.numel() - 1, dst.shape[1], int(rows_at)
+            q.src, q.dst, q.off_src = src.data_ptr(), dst.data_ptr(), seg_off.data_ptr()
+        else:
+            _, (crow, col, val), rows_at, crow_at, (col_dst, val_dst) = job
+            for nm, t, dt in (('crow', crow, torch.int32), ('col', col, torch.int32), ('val', val, None), ('col_dst', col_dst, torch.int32),
+                              ('val_dst', val_dst, val.dtype)):
+                _assemble_view(t, 'job %d: %s' % (i, nm), 1), same(i, nm, t, dt)
+            if crow.numel() < 2 or col.numel() != val.numel() or col_dst.numel() != val_dst.numel():
+                raise ValueError('job %d: crow has %d entries, col %d, val %d, col_dst %d, val_dst %d' %
+                                 (i, crow.numel(), col.numel(), val.numel(), col_dst.numel(), val_dst.numel()))
+            q.n_src, q.n_items, q.cap_dst, q.rows_at, q.crow_at = crow.numel() - 1, col.numel(), col_dst.numel(), int(rows_at), int(crow_at)
+            # (an empty tensor has no storage: any aligned non-null address stands for it, nothing is read or written there)
+            q.src, q.col_src = val.data_ptr() or control.data_ptr(), col.data_ptr() or control.data_ptr()
+            q.dst, q.col_dst, q.off_src = val_dst.data_ptr() or control.data_ptr(), col_dst.data_ptr() or control.data_ptr(), crow.data_ptr()
+    lib, h = _context(dev)
+    _call('batch_assemble', lib.laff_batch_assemble, h, arr, len(jobs), B, _ptr(control), host.ctypes.data_as(C.c_void_p), host.size)
 
 
 def _batch_sizes(batch_sizes):

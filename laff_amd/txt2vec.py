@@ -29,6 +29,21 @@ from .ragged import _Weights, ragged_batch
 
 _NON_ALNUM = re.compile(r"[^A-Za-z0-9]")
 
+#: key of a caption dict under which data.PairProvider hands every encoder its batch input, prepared from the token ids it stored at
+#: build: {encoder object: prepared input}.  An encoder whose object is in there uses that input and does no string work; without
+#: the key (or without its own entry) it tokenises caption_feat_dict['caption'] as before.  The two ways give the same bits.
+#:   BoWTxtEncoder      the batch CSR on the device (with `laff_csc` attached when the provider formed it)
+#:   W2VTxtEncoder      the (B, ndims) mean-pooled matrix on the device
+#:   GruTxtEncoder      a GruBatch / GruTrainBatch on the device (its own to_device of IdxVec.batch_ids)
+#:   NetVLADTxtEncoder  the tuple its own to_device returns (W2Vec.ragged_rows)
+PREPARED_KEY = 'laff_prepared'
+
+
+def prepared_input(caption_feat_dict, encoder):
+    """The prepared batch input of `encoder` in a caption dict, or None."""
+    prepared = caption_feat_dict.get(PREPARED_KEY) if hasattr(caption_feat_dict, 'get') else None
+    return None if prepared is None else prepared.get(encoder)
+
 
 def tokenize(text, clean=True, remove_stopword=False, stopwords=()):
     """textlib.TextTool.tokenize(language='en') (textlib.py:27-45)."""
@@ -171,9 +186,13 @@ class W2Vec(object):
     def ragged(self, captions):
         """The captions as laff_netvlad_encode takes them: ids [R] int32 (raw_ids concatenated), row_off [N+1] int32 and zero_rows
         [N] int32 (the token count of a caption without known words, else 0)."""
-        rows = [self.raw_ids(c) for c in captions]
+        return self.ragged_rows([self.raw_ids(c) for c in captions])
+
+    @staticmethod
+    def ragged_rows(rows):
+        """ragged() from the captions' raw_ids results, e.g. ones kept from an earlier pass."""
         b = ragged_batch([r for r, _ in rows])
-        return b.ids, b.row_off, np.array([0 if r else n for r, n in rows], np.int32)
+        return b.ids, b.row_off, np.array([0 if len(r) else n for r, n in rows], np.int32)
 
     def encoding(self, caption):
         ids, _ = self._ids(caption)
@@ -212,6 +231,9 @@ class BoWTxtEncoder(nn.Module):
         self.t2v_bow, self.device, self.with_csc = t2v_bow, device, with_csc
 
     def forward(self, caption_feat_dict, task3=False):
+        x = prepared_input(caption_feat_dict, self)
+        if x is not None:
+            return {'text_features': x}
         if not self.with_csc:
             return {'text_features': self.t2v_bow.csr(caption_feat_dict['caption'], self.device)}
         from . import ops
@@ -229,6 +251,9 @@ class W2VTxtEncoder(nn.Module):
         self.t2v_w2v, self.device = t2v_w2v, device
 
     def forward(self, caption_feat_dict, task3=False):
+        x = prepared_input(caption_feat_dict, self)
+        if x is not None:
+            return {'text_features': x}
         return {'text_features': self.t2v_w2v.encode(caption_feat_dict['caption'], self.device)}
 
 
@@ -314,7 +339,9 @@ class NetVLADTxtEncoder(nn.Module):
         return _NetvladEncodeFn.apply(self.t2v_w2v.device_table(self.device), batch, v.fc1.weight, v.centeroids)
 
     def forward(self, caption_feat_dict, task3=False):
-        b = self.to_device(*self.t2v_w2v.ragged(caption_feat_dict['caption']))
+        b = prepared_input(caption_feat_dict, self)
+        if b is None:
+            b = self.to_device(*self.t2v_w2v.ragged(caption_feat_dict['caption']))
         return {'text_features': self.encode_batch(*b)}
 
 
@@ -361,7 +388,11 @@ class IdxVec(object):
         return np.array([self.vocab(w) for w in words])
 
     def batch(self, captions):
-        ids = [self.encoding(c) for c in captions]
+        return self.batch_ids([self.encoding(c) for c in captions])
+
+    @staticmethod
+    def batch_ids(ids):
+        """batch() from the captions' encoding() arrays, e.g. ones kept from an earlier pass."""
         lens = np.array([len(v) for v in ids], dtype=np.int64)
         perm = np.argsort(-lens, kind='stable').astype(np.int32)
         T = int(lens.max()) if len(ids) else 0
@@ -498,5 +529,7 @@ class GruTxtEncoder(nn.Module):
         return GruTrainBatch(*base, *[torch.from_numpy(a).to(dev) for a in gru_train_arrays(b.tokens, b.batch_sizes)])
 
     def forward(self, caption_feat_dict, task3=False):
-        b = self.t2v_idx.batch(caption_feat_dict['caption'])
-        return {'text_features': self.encode_batch(self.to_device(b))}
+        b = prepared_input(caption_feat_dict, self)
+        if b is None:
+            b = self.to_device(self.t2v_idx.batch(caption_feat_dict['caption']))
+        return {'text_features': self.encode_batch(b)}
