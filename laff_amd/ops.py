@@ -344,7 +344,7 @@ def fc_concat_act_bn_grouped(problems):
     return outs
 
 
-LOSS_FLAGS = {'max_violation': 1, 'mean': 2, 'i2t': 4, 't2i': 8}
+LOSS_FLAGS = {k: _lib.K['LAFF_LOSS_' + c] for k, c in (('max_violation', 'MAX_VIOLATION'), ('mean', 'COST_MEAN'), ('i2t', 'DIR_I2T'), ('t2i', 'DIR_T2I'))}
 
 
 def margin_loss(s, im, margin, max_violation=True, cost_style='sum', direction='t2i', want_grad=True):
@@ -1060,8 +1060,8 @@ def fc_act_bn_fused_grouped(problems):
 #: the kernels behind the FC projections (LAFF_FC_KERNEL_* of include/laff_hip.h, in that order).  The first six are what
 #: fc_act_bn_grouped / fc_act_bn_split_grouped / fc_act_bn_fused_grouped choose between; fc_act_bn_strip_grouped, fc_gather_act_bn and
 #: fc_concat_act_bn_grouped each have a kernel family of their own.
-FC_ROUTES = ('F32_REG', 'F32_TAIL', 'F32_GLDS', 'F16_128', 'X3', 'X3_FUSED', 'STRIP', 'GATHER', 'CONCAT')
-_FC_FAMILIES = {'fp32': 0, 'split': 1, 'fused': 2}
+FC_ROUTES = _lib.enum_names('LAFF_FC_KERNEL_')[:_lib.K['LAFF_FC_KERNEL_CONCAT'] + 1]      # F16_256, behind it, is no FC entry point's kernel
+_FC_FAMILIES = {k: _lib.K['LAFF_FC_FAMILY_' + c] for k, c in (('fp32', 'F32'), ('split', 'SPLIT'), ('fused', 'FUSED'))}
 _FC_OWN_KERNEL = {'strip': 'STRIP', 'gather': 'GATHER', 'concat': 'CONCAT'}
 
 
@@ -2020,7 +2020,7 @@ def sim_hist(T, V, heads=1, eps=1e-14, out=None):
 
 
 #: the kernels laff_sim_gemm / laff_sim_gemm_banded choose between (LAFF_ROUTE_* of include/laff_hip.h, in that order)
-SIM_ROUTES = ('TILED128_REG', 'TILED128_TAIL', 'TILED128', 'TILED256', 'TILED256_LONGK', 'X3', 'STRIP')
+SIM_ROUTES = _lib.enum_names('LAFF_ROUTE_')
 _COUNT_MODES = {None: 0, 'approx': 1, 'banded': 2}
 
 

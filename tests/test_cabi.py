@@ -54,6 +54,194 @@ def test_argument_errors_do_not_need_a_gpu():
     assert lib.laff_v2t_count_exact(None, None, 1, 1, 1, None, None, 1, None, None, 1, 4, None, None, None, None, None, 4) == -1
 
 
+# ---- the binding is derived from the header (laff_amd/_lib.py): the C++ compiler checks the derivation -----------------------------
+_PROBE = r'''
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+#include "laff_hip.h"
+template <class T> void one() {
+    if constexpr (std::is_void_v<T>) std::printf(" v0");
+    else std::printf(" %c%zu", std::is_pointer_v<T> ? 'p' : std::is_floating_point_v<T> ? 'f' : std::is_signed_v<T> ? 'i' : 'u', sizeof(T));
+}
+template <class F> struct sig;
+template <class R, class... A> struct sig<R(A...)> {
+    static void print(const char* name) { std::printf("%s", name); one<R>(); std::printf(" <-"); (one<A>(), ...); std::printf("\n"); }
+};
+int main() {
+@BODY@
+    return 0;
+}
+'''
+
+
+def _kind(ctype):
+    """'p8', 'f4', 'i4', 'u8', ...: class and size of a ctypes type, as the probe prints them for the C type."""
+    code = ctype._type_ if isinstance(ctype._type_, str) else 'P'            # POINTER(struct): a pointer
+    cls = 'p' if code in 'Pz' else 'f' if code in 'fd' else 'i' if code in 'bhilq' else 'u' if code in 'BHILQ' else '?'
+    return '%s%d' % (cls, ctypes.sizeof(ctype))
+
+
+@pytest.fixture(scope='module')
+def probe(tmp_path_factory):
+    """What the host C++ compiler says about every declaration of the header: {function: 'i4 <- p8 i4 ...'} and {struct or struct.field:
+    numbers}.  Nothing of the library is referenced: the program is built from the header alone and is not linked against it."""
+    import shutil
+    import subprocess
+    from laff_amd import _lib, build
+    lines = ['    sig<decltype(%s)>::print("%s");' % (s, s) for s in sorted(_lib.SIGNATURES)]
+    for cname, cls in _lib.STRUCTS.items():
+        lines.append('    std::printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        lines += ['    std::printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, f, cname, f, cname, f)
+                  for f, _ in cls._fields_]
+    out = tmp_path_factory.mktemp('probe')
+    src, exe = str(out / 'probe.cpp'), str(out / 'probe')
+    with open(src, 'w') as fh:
+        fh.write(_PROBE.replace('@BODY@', '\n'.join(lines)))
+    cxx = shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
+    cmd = [cxx] if cxx else [build.hipcc(), '-x', 'c++']                     # hipcc's host side when there is no system compiler
+    r = subprocess.run(cmd + ['-std=c++17', '-I' + os.path.join(ROOT, 'include'), src, '-o', exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return dict(line.split(' ', 1) for line in r.stdout.splitlines())
+
+
+def test_signatures_agree_with_the_compiler(probe):
+    """Return type and every parameter of every entry point: class (pointer, floating, signed, unsigned) and size, as the C++ compiler
+    reads the header against what the binding passes.  A dropped, swapped or mis-sized argument shows here."""
+    from laff_amd import _lib
+    assert len(_lib.SIGNATURES) >= 115
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert probe[name] == ' '.join([_kind(res), '<-'] + [_kind(a) for a in args]), name
+
+
+def test_structures_agree_with_the_compiler(probe):
+    """sizeof, and offset and size of every field, of every struct of the header against the ctypes classes (a lost field shows as a
+    sizeof mismatch)."""
+    from laff_amd import _lib
+    assert len(_lib.STRUCTS) >= 20
+    for cname, cls in _lib.STRUCTS.items():
+        assert probe[cname] == '%d' % ctypes.sizeof(cls), cname
+        for f, _ in cls._fields_:
+            assert probe['%s.%s' % (cname, f)] == '%d %d' % (getattr(cls, f).offset, getattr(cls, f).size), (cname, f)
+
+
+def test_pointer_rule_and_typed_struct_pointers():
+    """Every pointer parameter is c_void_p, `const char*` is c_char_p; inside structs a pointer to another struct of the header is typed
+    (the encoders assign ctypes arrays to `blocks` / `segments`).  A struct instance given for a pointer parameter goes by reference."""
+    from laff_amd import _lib
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert res in (ctypes.c_int, ctypes.c_char_p), name
+        assert all(a in (ctypes.c_void_p, ctypes.c_char_p) or _kind(a)[0] in 'fiu' for a in args), name
+    assert _lib.SIGNATURES['laff_last_error'] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES['laff_match_ids'][1] == [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int,
+                                                    ctypes.c_void_p]
+    assert _lib.SIGNATURES['laff_comm_init'][1][3] is ctypes.c_void_p                       # const unsigned char*: bytes, not a string
+    assert _lib.SIGNATURES['laff_device_info'][1] == [ctypes.c_void_p, ctypes.c_void_p]      # int out[4]
+    assert dict(_lib.ClipText._fields_)['blocks'] is ctypes.POINTER(_lib.ClipBlock)
+    assert dict(_lib.ClipVisual._fields_)['blocks'] is ctypes.POINTER(_lib.ClipBlock)
+    assert dict(_lib.BertText._fields_)['blocks'] is ctypes.POINTER(_lib.BertBlock)
+    assert dict(_lib.FcConcatProblem._fields_)['segments'] is ctypes.POINTER(_lib.FcConcatSegment)
+    assert dict(_lib.FrameDesc._fields_)['reserved'] is ctypes.c_int32 * 2
+    assert all(t is ctypes.c_void_p for n, t in _lib.Plane._fields_ if n in ('src', 'indptr', 'wt', 'row_scale'))
+    lib = _lib.load()
+    side = _lib.RankSide(2, None, 0, None, 0, None, 4096, None, None, None, None, None)
+    assert lib.laff_fuse_packed_rank(None, None, 1, 1, 1, 4, None, None, None, 0, None, None, None, 1, 1.0, side) == -1
+    assert b'null ctx' in lib.laff_last_error()
+
+
+def test_public_values_are_pinned():
+    """The derivation renames and renumbers nothing: the constants the package publishes, as literals."""
+    from laff_amd import _lib, ops
+    assert _lib.ACT == {None: 0, False: 0, '': 0, 'none': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
+    assert _lib.PREC == {'fp32': 0, 'fp16': 1, 'bf16': 2, 'fp16x3': 3, 'bf16x3': 4} and ops.PREC is _lib.PREC
+    assert _lib.GRU_POOLING == {'mean': 0, 'last': 1, 'mean_last': 2}
+    assert _lib.OPT_KIND == {'adam': 0, 'rmsprop': 1}
+    assert _lib.ASSEMBLE_KIND == {'rows': 0, 'ragged': 1, 'csr': 2}
+    assert (_lib.ATT_WITH_AVE, _lib.ATT_MUL, _lib.ATT_L2NORM_EACH_HEAD, _lib.ATT_NO_SPLIT_HEAD, _lib.ATT_JUST_AVERAGE) == (1, 2, 4, 8, 16)
+    assert (_lib.ASSEMBLE_MAX_JOBS, _lib.ASSEMBLE_MAX_BATCH) == (16, 4096)
+    assert ops.LOSS_FLAGS == {'max_violation': 1, 'mean': 2, 'i2t': 4, 't2i': 8}
+    assert ops.FC_ROUTES == ('F32_REG', 'F32_TAIL', 'F32_GLDS', 'F16_128', 'X3', 'X3_FUSED', 'STRIP', 'GATHER', 'CONCAT')
+    assert ops.SIM_ROUTES == ('TILED128_REG', 'TILED128_TAIL', 'TILED128', 'TILED256', 'TILED256_LONGK', 'X3', 'STRIP')
+    assert ops._FC_FAMILIES == {'fp32': 0, 'split': 1, 'fused': 2}
+    names = ['FcProblem', 'FcConcatSegment', 'FcConcatProblem', 'FcSplitProblem', 'FcFusedProblem', 'FcShape', 'FcLaunch', 'FcStripProblem',
+             'ClipBlock', 'ClipText', 'ClipVisual', 'FrameDesc', 'BertBlock', 'BertText', 'Plane', 'OptimTensor', 'OptimHyper', 'RankSide',
+             'RerankProblem', 'AssembleJob']
+    assert [cls.__name__ for cls in _lib.STRUCTS.values()] == names                        # in the header's order
+    assert all(getattr(_lib, n) is cls and issubclass(cls, ctypes.Structure) for n, cls in zip(names, _lib.STRUCTS.values()))
+    assert _lib.STRUCTS['laff_fc_concat_segment'] is _lib.FcConcatSegment and _lib.STRUCTS['laff_plane'] is _lib.Plane
+    assert _lib.HEADER_PATH in __import__('laff_amd.build', fromlist=['HEADERS']).HEADERS       # the file the library is built from
+
+
+_MINI = 'typedef struct laff_ctx laff_ctx;\nint laff_ok(laff_ctx* ctx, const float* x /*device*/, size_t n);\n%s\n'
+
+
+@pytest.mark.parametrize('decl, named', [
+    ('int laff_f(laff_ctx* ctx, short x);', "unknown type 'short'.*laff_f"),                       # an unknown type word
+    ('typedef struct { int a; wchar_t* b; } laff_s;', "unknown type 'wchar_t'.*wchar_t\\* b"),
+    ('int laff_f(laff_other* p);', "unknown type 'laff_other'.*laff_f"),                            # neither a struct nor opaque
+    ('int (*laff_cb)(int);', r'cannot parse the declaration.*laff_cb'),                             # not a declaration of the header's kinds
+    ('typedef union { int a; float b; } laff_u;', r'cannot parse the declaration.*laff_u'),
+    ('static inline int laff_g(int a) { return a; }', r'cannot parse the declaration.*laff_g'),
+    ('typedef struct { int* a, b; } laff_s;', r'cannot parse.*int\* a, b'),
+    ('enum { LAFF_X = 1, LAFF_Y };', r"cannot parse the enumerator 'LAFF_Y'"),
+    ('int laff_f(laff_ctx*);', r'laff_f'),                                                          # a parameter without a name
+    ('#define laff_m(x) laff_ok(0, x, 1)', r'without a parsed prototype.*laff_m'),                  # a name the symbol regex sees
+])
+def test_parser_refuses_what_it_does_not_understand(decl, named):
+    from laff_amd import _lib
+    wrap = 'extern "C" {\n%s}\n'
+    structs, sigs, consts = _lib.parse_header(wrap % (_MINI % 'enum { LAFF_A = -3 };\n#define LAFF_N 7'))
+    assert sigs == {'laff_ok': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t])} and consts == {'LAFF_A': -3, 'LAFF_N': 7}
+    with pytest.raises(ValueError, match=named):
+        _lib.parse_header(wrap % (_MINI % decl))
+    with pytest.raises(ValueError, match='extern "C"'):
+        _lib.parse_header(_MINI % '')
+
+
+# ---- one table for what every feature's host test used to assert one copy each: the entry point is in the header, the library and the
+# binding, with this many arguments, at an ABI version of at least this ------------------------------------------------------------
+ENTRY_POINTS = [          # (symbol, argument count or None where none was asserted, minimum ABI or 0)
+    ('laff_dropout_bn_train_plan', 4, 41), ('laff_dropout_bn_train', 19, 41), ('laff_dropout_bn_train_backward', 18, 41),
+    ('laff_batch_assemble', None, 45),
+    ('laff_bert_workspace_bytes', None, 0), ('laff_bert_encode', None, 0), ('laff_clip_pack_weight', None, 0),
+    ('laff_frame_fuse_backward_plan', None, 38), ('laff_frame_fuse_backward', None, 38),
+    ('laff_rerank_workspace_bytes', None, 32), ('laff_rerank_run', None, 32), ('laff_rerank_tkb', None, 32),
+    ('laff_sim_hist', 12, 33),
+    ('laff_fc_gather_backward', 16, 40),
+    ('laff_expert_stage_train_plan', 4, 43), ('laff_expert_stage_train', 13, 43), ('laff_expert_stage_train_backward', 18, 43),
+    ('laff_gru_pack_whh_t', None, 0), ('laff_gru_gather_rows', None, 0), ('laff_gru_train_reserve_bytes', None, 0),
+    ('laff_gru_encode_train', None, 0), ('laff_gru_backward_plan', None, 0), ('laff_gru_backward_workspace_bytes', None, 0),
+    ('laff_gru_backward', None, 0),
+    ('laff_clip_workspace_bytes', None, 0), ('laff_clip_encode', None, 0),
+    ('laff_netvlad_train_reserve_bytes', None, 44), ('laff_netvlad_backward_workspace_bytes', None, 44),
+    ('laff_netvlad_encode_train', None, 44), ('laff_netvlad_backward', None, 44),
+    ('laff_clip_pack_weight_padded', None, 26), ('laff_clip_image_kpad', None, 26), ('laff_clip_image_workspace_bytes', None, 26),
+    ('laff_clip_image_encode', None, 26),
+    ('laff_dsl_loss_workspace_bytes', None, 0), ('laff_dsl_loss', None, 0), ('laff_margin_loss_scores', None, 0),
+    ('laff_netvlad_workspace_bytes', None, 28), ('laff_netvlad_encode', None, 28),
+    ('laff_fc_concat_act_bn', None, 29), ('laff_fc_concat_act_bn_grouped', None, 29),
+    ('laff_tile_bn_train_plan', 4, 42), ('laff_tile_bn_train', 18, 42), ('laff_tile_bn_train_backward', 17, 42),
+]
+
+
+@pytest.mark.parametrize('name, nargs, min_abi', ENTRY_POINTS)
+def test_entry_point_in_header_library_and_binding_at_the_header_abi(name, nargs, min_abi):
+    from laff_amd import _lib
+    header = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    assert re.search(r'^int %s\(' % name, header, flags=re.M) and re.search(r'\b%s\s*\(' % name, header)
+    assert hasattr(raw, name) and getattr(raw, name) is not None              # AttributeError if the built library does not export it
+    assert name in _lib.SIGNATURES
+    if nargs is not None:
+        assert len(_lib.SIGNATURES[name][1]) == nargs
+    fn = getattr(_lib.load(), name)
+    assert fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.SIGNATURES[name][1]
+    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', header, flags=re.M)
+    assert len(abi) == 1 and raw.laff_abi_version() == _lib.load().laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= min_abi
+
+
 def test_coalesce_batches_concatenates_what_a_loader_yields():
     """model.retrieve() runs each tower once over the concatenated batches of any loader (laff_amd/model/model.py, coalesce_batches)."""
     import numpy as np

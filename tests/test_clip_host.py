@@ -167,17 +167,10 @@ def test_c_entry_points_refuse_bad_arguments_without_a_gpu():
 
 
 def test_clip_entry_points_in_header_library_and_binding_at_the_header_abi():
-    """The CLIP entry points and structs are in the header, the library and the binding, and all three carry the header's
-    LAFF_ABI_VERSION (read from the header, so that a later ABI bump does not have to edit this test)."""
+    """The CLIP structs are in the header and the binding (the entry points and the ABI version: test_cabi.py, ENTRY_POINTS)."""
     from laff_amd import _lib
     text = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    lib = C.CDLL(_lib.LIB_PATH)
-    for s in ('laff_clip_pack_weight', 'laff_clip_workspace_bytes', 'laff_clip_encode'):
-        assert re.search(r'\b%s\s*\(' % s, text) and hasattr(lib, s) and s in _lib.SIGNATURES
     assert 'typedef struct laff_clip_text' in text and 'typedef struct laff_clip_block' in text
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', text, flags=re.M)
-    assert len(abi) == 1
-    assert lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0])
     assert C.sizeof(_lib.ClipBlock) == 12 * 8 and C.sizeof(_lib.ClipText) == 6 * 4 + 6 * 8
 
 

@@ -2,8 +2,6 @@
 against the generator's known-answer vectors and a scalar evaluation, the float64 formulas against float64 torch autograd, the plan, the
 refusals of the two entry points (which need no GPU), the ABI, and the module's opt-in keyword."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import torch
 
 import dropout_bn_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 0x0123456789abcdef
 
 
@@ -124,14 +121,8 @@ def test_ops_refuse_host_and_non_fp32_tensors():
 
 
 def test_header_binding_and_library_agree_on_the_abi_and_the_new_symbols():
-    from laff_amd import _lib, ops
-    header = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', header, flags=re.M)
-    lib = _lib.load()
-    assert len(abi) == 1 and lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= 41
-    for name, nargs in (('laff_dropout_bn_train_plan', 4), ('laff_dropout_bn_train', 19), ('laff_dropout_bn_train_backward', 18)):
-        assert re.search(r'\bint %s\(' % name, header) and hasattr(lib, name)
-        assert len(_lib.SIGNATURES[name][1]) == nargs
+    """(The entry points themselves: test_cabi.py, ENTRY_POINTS.)"""
+    from laff_amd import ops
     assert 'bn_train.hip' in __import__('laff_amd.build', fromlist=['SOURCES']).SOURCES
     for name in ('dropout_bn_train', 'dropout_bn_train_backward', 'dropout_bn_train_plan'):
         assert callable(getattr(ops, name)) and name in ops.__all__

@@ -3,8 +3,6 @@ the plan and the argument checks of laff_frame_fuse_backward, and what Attention
 mode.  All on the CPU."""
 import ctypes as C
 import itertools
-import os
-import re
 
 import pytest
 import torch
@@ -91,11 +89,7 @@ def test_plan_and_argument_errors_do_not_need_a_gpu():
 
 
 def test_abi_version():
-    from laff_amd import _lib
-    lib = _lib.load()
-    text = open(os.path.join(os.path.dirname(__file__), '..', 'include', 'laff_hip.h')).read()
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', text, flags=re.M)
-    assert len(abi) == 1 and lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= 38
+    """(The ABI version itself: test_cabi.py, ENTRY_POINTS.)"""
     assert 'frame_fuse_backward' in __import__('laff_amd.ops', fromlist=['x']).__all__
     assert 'frame_fuse_backward_plan' in __import__('laff_amd.ops', fromlist=['x']).__all__
 

@@ -2,8 +2,6 @@
 float64 restatement (tests/loss_ref.py) against the golden vectors, central differences and float64 autograd, the inputs and the
 derived gradient bound of the embedding margin test (tests/test_gpu_losses.py), and the routing of loss.criterion_for."""
 import ctypes as C
-import os
-import re
 import types
 
 import numpy as np
@@ -11,28 +9,12 @@ import pytest
 
 import loss_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ('laff_dsl_loss_workspace_bytes', 'laff_dsl_loss', 'laff_margin_loss_scores')
 F64_NOISE = 1e-12          # float64 rounding of the restatement itself (a BLAS that sums in another order), far below any e_ref > 0
 
 
 # ------------------------------------------------------------------------------------------------ C ABI
-@pytest.mark.parametrize('name', NEW_SYMBOLS)
-def test_header_declares_the_symbol(name):
-    text = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    assert re.search(r'^int %s\(' % name, text, flags=re.M), name
-
-
-@pytest.mark.parametrize('name', NEW_SYMBOLS)
-def test_library_exports_and_lib_binds_the_symbol(name):
-    from laff_amd import _lib
-    assert name in _lib.SIGNATURES
-    raw = C.CDLL(_lib.LIB_PATH)
-    assert getattr(raw, name) is not None            # AttributeError if the built library does not export it
-    fn = getattr(_lib.load(), name)
-    assert fn.restype is C.c_int and list(fn.argtypes) == _lib.SIGNATURES[name][1]
-
-
+# (the three entry points in the header, the library and the binding: test_cabi.py, ENTRY_POINTS)
 def test_argument_errors_without_a_gpu():
     from laff_amd import _lib
     lib = _lib.load()

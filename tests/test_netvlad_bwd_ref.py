@@ -85,14 +85,10 @@ def test_differentiable_switch_constructs_on_the_cpu_with_the_reference_keys():
 
 
 def test_new_entry_points_in_header_library_and_binding():
-    from laff_amd import _lib, ops
-    text = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    lib = C.CDLL(_lib.LIB_PATH)
+    """(Header, library and binding: test_cabi.py, ENTRY_POINTS.)"""
+    from laff_amd import ops
     for s in NEW_SYMBOLS:
-        assert re.search(r'\b%s\s*\(' % s, text) and hasattr(lib, s) and s in _lib.SIGNATURES, s
         assert hasattr(ops, s[len('laff_'):])
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', text, flags=re.M)
-    assert len(abi) == 1 and lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= 44
 
 
 def test_c_entry_points_refuse_bad_arguments_without_a_gpu():

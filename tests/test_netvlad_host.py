@@ -9,7 +9,6 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from netvlad_ref import netvlad_features
 from laff_amd import txt2vec as T
 
@@ -148,16 +147,6 @@ def test_c_entry_points_refuse_bad_arguments_without_a_gpu():
     assert enc() == -1 and b'null ctx' in lib.laff_last_error()         # valid arguments: only then the ctx
     assert enc(ro=(0,)) == 0                                            # the empty problem
     assert enc(ro=(0, 0, 0), ids=None, ws=None, ws_bytes=0) == -1 and b'null ctx' in lib.laff_last_error()   # no ids: none read
-
-
-def test_netvlad_entry_points_in_header_library_and_binding_at_the_header_abi():
-    from laff_amd import _lib
-    text = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    lib = C.CDLL(_lib.LIB_PATH)
-    for s in ('laff_netvlad_workspace_bytes', 'laff_netvlad_encode'):
-        assert re.search(r'\b%s\s*\(' % s, text) and hasattr(lib, s) and s in _lib.SIGNATURES
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', text, flags=re.M)
-    assert len(abi) == 1 and lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= 28
 
 
 def test_netvlad_hip_kernels_have_no_scratch(tmp_path):

@@ -187,8 +187,6 @@ def test_abi_refusals_come_before_the_ctx():
     from laff_amd import _lib
     lib = _lib.load()
     header = open(os.path.join(ROOT, 'include', 'laff_hip.h')).read()
-    abi = re.findall(r'^#define LAFF_ABI_VERSION (\d+)$', header, flags=re.M)
-    assert len(abi) == 1 and lib.laff_abi_version() == _lib.ABI_VERSION == int(abi[0]) >= 45
     assert 'LAFF_ASSEMBLE_MAX_JOBS %d' % _lib.ASSEMBLE_MAX_JOBS in header and 'LAFF_ASSEMBLE_MAX_BATCH %d' % _lib.ASSEMBLE_MAX_BATCH in header
     buf = np.zeros(64, np.float32)
     ctl = np.array([0, 1, 2, 0, 0, 2, 2, 5], np.int32)         # rows 0 1 2 | - | crow_dst 0 2 2 5
