@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 45
+#define LAFF_ABI_VERSION 46
 
 enum {
     LAFF_OK = 0,
@@ -614,6 +614,40 @@ int laff_fc_backward(laff_ctx* ctx, const float* X, int N, int Dk, int ldx, cons
  * N == 0, the sum otherwise).  No workspace, no allocation, no host synchronisation; ordered on the ctx's stream, capturable. */
 int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, const float* values, int nnz, int N, int Dk, int D,
                             int act /*LAFF_ACT_*/, const float* A, int lda, const float* dA, int ldda, float* dW, int lddw, float* db);
+
+/* Backward of the concat layer A = act(sum_s X_s . W[:, col_s : col_s + Dk_s]^T + bias), the forward laff_fc_concat_act_bn computes
+ * without a BatchNorm stage; fp32.  A [N, lda >= D] is the SAVED forward output, dA [N, ldda >= D] its gradient, dZ as above.  W is
+ * [D, ldw >= K] and dW ONE gradient [D, lddw >= K]; each may be NULL, as may db and every dX:
+ *   dW[:, col_s : col_s + Dk_s] = dZ^T X_s     every DENSE segment in ONE launch, X_s read in place, the window written in place: every
+ *                                              element of a window exactly once, nothing outside the windows
+ *   db [D] = sum_n dZ[n, :]                    once per call: by the dense launch, or by the first CSR segment's when all are CSR
+ *   dX_s [N, lddx >= Dk_s] = dZ W[:, window]   every dense segment with dX != NULL in ONE launch, W read in place at the window
+ * The segments come as parallel host arrays of nseg entries, segment s being dense (nnz[s] < 0) or sparse (nnz[s] >= 0 entries):
+ *   widths[s] = Dk_s, cols[s] = col_s                         both kinds
+ *   X[s] [N, ldx[s] >= Dk_s], dX[s] [N, lddx[s] >= Dk_s]      dense (dX[s] NULL: not wanted; X[s] is read for dW only)
+ *   colptr[s], rows[s], values[s] (NULL = ones), nnz[s]       sparse: the TRANSPOSED pattern, exactly as laff_fc_gather_backward takes
+ *                                                             it; that kernel is issued on the segment's window, one launch each.  A
+ *                                                             dX on a sparse segment is refused (counts).
+ * (one array per field and no struct: the header's structs are a pinned list, tests/test_cabi.py.)  An array whose kind of segment
+ * does not occur may be NULL.  The dense products run laff_fc_backward's tile body on v_mfma_f32_32x32x2_f32: an element is one fmaf
+ * chain in k order, and with the same cut it has the bits of laff_fc_backward on the window.  The sum over N of dW and db is not cut at
+ * N <= 128; beyond that, and for the sum over D of dX, the cut depends on (N, D, the dense widths) only; partial tiles go to
+ * `workspace` (16-byte aligned) and are added in chunk order.  No atomics: two calls give the same bits.  No allocation, no host
+ * synchronisation; ordered on the ctx's stream, capturable.
+ * Limits, refused by name before any GPU work (a NULL ctx is looked at last): 1 <= nseg <= 8, Dk >= 1, windows inside [0, K) and pairwise
+ * disjoint, D % 4 == 0, 4 <= D <= 8192, lddw >= K, a workspace of at least the plan's bytes; pointers 4-byte aligned, and with a sparse
+ * segment A / dA 16-byte aligned with lda % 4 == ldda % 4 == 0.  N == 0: the windows of dW and db are set to zero, nothing else is touched.
+ * laff_fc_concat_backward_plan (host only, no ctx): widths[s] = Dk_s, kinds[s] = bit 0 sparse | bit 1 dX wanted;
+ * out = {chunks of the dW / db sum, workspace bytes, chunks of the dX sum, tile variants: bit 0 dW and bit 1 dX on 128 x 128 tiles}.
+ * The bytes come back as an int: a shape whose workspace exceeds INT_MAX bytes is refused by the plan (LAFF_E_SHAPE). */
+int laff_fc_concat_backward_plan(int N, int D, const int* widths /*host*/, const int* kinds /*host*/, int nseg, int want_dw, int out[4]);
+int laff_fc_concat_backward(laff_ctx* ctx, int nseg, const int* widths /*host*/, const int* cols /*host*/, const int* nnz /*host*/,
+                            const float* const* X /*host array of device pointers*/, const int* ldx /*host*/,
+                            float* const* dX /*host array of device pointers*/, const int* lddx /*host*/,
+                            const int* const* colptr /*host array*/, const int* const* rows /*host array*/,
+                            const float* const* values /*host array*/, int N, const float* W, int K, int ldw, int D, int act /*LAFF_ACT_*/,
+                            const float* A, int lda, const float* dA, int ldda, float* dW, int lddw, float* db, void* workspace,
+                            size_t workspace_bytes);
 
 /* The stage between a projection's activation and its output in training mode (model/model.py:236-243 under .train()): dropout by a
  * counter-based mask, then BatchNorm1d on the batch's statistics; fp32.  A [N, lda >= D] is the activation output.

@@ -2241,6 +2241,125 @@ int laff_fc_gather_backward(laff_ctx* ctx, const int* colptr, const int* rows, c
     return LAFF_OK;
 }
 
+/* what the plan and the call of a concat layer's backward refuse first: the number of segments, N and D */
+static int fc_concat_backward_shape(const char* fn, int N, int D, int nseg) {
+    if (nseg < 1 || nseg > laff::CONCAT_MAX_SEG)
+        return fail(LAFF_E_ARG, "%s: need 1 <= nseg <= %d segments (nseg=%d)", fn, laff::CONCAT_MAX_SEG, nseg);
+    if (N < 0 || D < 4 || (D & 3) || D > 8192)
+        return fail(LAFF_E_SHAPE, "%s: need N >= 0, D %% 4 == 0, 4 <= D <= 8192 (N=%d D=%d)", fn, N, D);
+    return LAFF_OK;
+}
+
+/* the workspace bytes of the dense launches: dX's partial rows, dW's with db's, or db's alone */
+static size_t fc_concat_backward_ws(const laff::FcBwdPlan& p, bool dense, bool dx, bool want_dw) {
+    return dense ? std::max(dx ? p.ws_dx : (size_t)0, want_dw ? p.ws_dw : p.ws_db) : 0;
+}
+
+int laff_fc_concat_backward_plan(int N, int D, const int* widths, const int* kinds, int nseg, int want_dw, int out[4]) {
+    const char* fn = "laff_fc_concat_backward_plan";
+    if (!out || !widths || !kinds) return fail(LAFF_E_ARG, "%s: null widths / kinds / out", fn);
+    if (int rc = fc_concat_backward_shape(fn, N, D, nseg)) return rc;
+    int dk[laff::CONCAT_MAX_SEG], n = 0, dx_cols = 0;
+    for (int s = 0; s < nseg; ++s) {
+        if (widths[s] < 1) return fail(LAFF_E_SHAPE, "%s: segment %d has width Dk=%d", fn, s, widths[s]);
+        if ((kinds[s] & 3) == 3) return fail(LAFF_E_ARG, "%s: segment %d: a CSR segment has no dX", fn, s);
+        if (kinds[s] & 1) continue;
+        dk[n++] = widths[s];
+        if (kinds[s] & 2) dx_cols += widths[s];
+    }
+    laff::FcBwdPlan p;
+    laff::fc_concat_bwd_plan(N, D, dk, n, dx_cols, &p);
+    const size_t bytes = fc_concat_backward_ws(p, n > 0, dx_cols > 0, want_dw != 0);
+    if (bytes > (size_t)INT_MAX) return fail(LAFF_E_SHAPE, "%s: workspace of %zu bytes", fn, bytes);
+    out[0] = p.chunks; out[1] = (int)bytes; out[2] = p.chunks_dx; out[3] = (p.tile_dw == 128 ? 1 : 0) | (p.tile_dx == 128 ? 2 : 0);
+    return LAFF_OK;
+}
+
+int laff_fc_concat_backward(laff_ctx* ctx, int nseg, const int* widths, const int* cols, const int* nnz, const float* const* X, const int* ldx,
+                            float* const* dX, const int* lddx, const int* const* colptr, const int* const* rows, const float* const* values,
+                            int N, const float* W, int K, int ldw, int D, int act, const float* A, int lda, const float* dA, int ldda,
+                            float* dW, int lddw, float* db, void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_fc_concat_backward";
+    if (int rc = fc_concat_backward_shape(fn, N, D, nseg)) return rc;
+    if (!widths || !cols || !nnz) return fail(LAFF_E_ARG, "%s: null widths / cols / nnz", fn);
+    if (K < 1) return fail(LAFF_E_SHAPE, "%s: K=%d", fn, K);
+    if (act < LAFF_ACT_NONE || act > LAFF_ACT_SIGMOID) return fail(LAFF_E_ARG, "%s: bad act %d", fn, act);
+    /* the call's arrays go straight into the two launchers' forms: the dense segments into a.seg, a sparse one into its gather launch */
+    laff::FcConcatBwdArgs a{};
+    laff::FcGatherBwdArgs csr[laff::CONCAT_MAX_SEG];
+    int csr_col[laff::CONCAT_MAX_SEG], ncsr = 0, dk[laff::CONCAT_MAX_SEG], dx_cols = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const int w = widths[s], c = cols[s];
+        float* const dx = dX ? dX[s] : nullptr;
+        if (w < 1) return fail(LAFF_E_SHAPE, "%s: segment %d has width Dk=%d", fn, s, w);
+        if (c < 0 || (long long)c + w > K)
+            return fail(LAFF_E_SHAPE, "%s: segment %d: columns [%d, %lld) are outside W's K=%d", fn, s, c, (long long)c + w, K);
+        for (int t = 0; t < s; ++t)
+            if (c < cols[t] + widths[t] && cols[t] < c + w) return fail(LAFF_E_SHAPE, "%s: segments %d and %d overlap in W's columns", fn, t, s);
+        if (nnz[s] >= 0) {
+            if (dx) return fail(LAFF_E_ARG, "%s: segment %d: a CSR segment has no dX (counts)", fn, s);
+            laff::FcGatherBwdArgs& q = csr[ncsr];
+            q = laff::FcGatherBwdArgs{};
+            q.colptr = colptr ? colptr[s] : nullptr; q.rows = rows ? rows[s] : nullptr; q.values = values ? values[s] : nullptr;
+            q.nnz = nnz[s]; q.N = N; q.Dk = w; q.D = D; q.lda = lda; q.ldda = ldda; q.lddw = lddw; q.act = act; q.A = A; q.dA = dA;
+            if (dW && N > 0 && q.nnz > 0 && (!q.colptr || !q.rows)) return fail(LAFF_E_ARG, "%s: segment %d: null colptr / rows", fn, s);
+            csr_col[ncsr++] = c;
+        } else {
+            laff::FcConcatBwdSeg& f = a.seg[a.nseg];
+            f.X = X ? X[s] : nullptr; f.ldx = ldx ? ldx[s] : 0; f.dX = N > 0 ? dx : nullptr; f.lddx = lddx ? lddx[s] : 0; f.dk = w; f.col = c;
+            if (N > 0 && ((dW && f.ldx < w) || (dx && f.lddx < w)))
+                return fail(LAFF_E_SHAPE, "%s: segment %d: a row pitch is below Dk=%d (ldx=%d lddx=%d)", fn, s, w, f.ldx, f.lddx);
+            if (N > 0 && dW && !f.X) return fail(LAFF_E_ARG, "%s: segment %d: null X (read for dW)", fn, s);
+            if (!aligned4(f.X) || !aligned4(dx)) return fail(LAFF_E_ALIGN, "%s: segment %d: X / dX must be 4-byte aligned", fn, s);
+            dk[a.nseg++] = w;
+            if (dx) dx_cols += w;
+        }
+    }
+    if (dW && lddw < K) return fail(LAFF_E_SHAPE, "%s: lddw=%d < K=%d", fn, lddw, K);
+    if (!aligned4(dW) || !aligned4(db) || !aligned4(W)) return fail(LAFF_E_ALIGN, "%s: W / dW / db must be 4-byte aligned", fn);
+    laff::FcBwdPlan p;
+    laff::fc_concat_bwd_plan(N, D, dk, a.nseg, dx_cols, &p);
+    const size_t need = N > 0 ? fc_concat_backward_ws(p, a.nseg > 0, dx_cols > 0, dW != nullptr) : 0;
+    if (need && (dW || db || dx_cols))
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, need)) return rc;
+    if (N > 0 && (dW || db || dx_cols)) {
+        if (!A || !dA || (dx_cols && !W)) return fail(LAFF_E_ARG, "%s: null A / dA, or W (read for dX)", fn);
+        if (lda < D || ldda < D || (dx_cols && ldw < K))
+            return fail(LAFF_E_SHAPE, "%s: a row pitch is below the row width (lda=%d ldda=%d D=%d; ldw=%d K=%d)", fn, lda, ldda, D, ldw, K);
+        if (!aligned4(A) || !aligned4(dA)) return fail(LAFF_E_ALIGN, "%s: A / dA must be 4-byte aligned", fn);
+        if (ncsr && (!aligned16(A) || !aligned16(dA) || (lda & 3) || (ldda & 3)))
+            return fail(LAFF_E_ALIGN, "%s: with a CSR segment A / dA must be 16-byte aligned and lda=%d, ldda=%d multiples of 4", fn, lda, ldda);
+    }
+    CHECK_CTX(ctx);
+    if (!dW && !db && !dx_cols) return LAFF_OK;
+    DeviceGuard g(ctx->device);
+    if (N == 0) {                                /* the empty sum: zeros in dW's windows and db, nothing else is read or written */
+        if (dW)
+            for (int s = 0; s < nseg; ++s)
+                HIP_TRY(hipMemset2DAsync(dW + cols[s], (size_t)lddw * sizeof(float), 0, (size_t)widths[s] * sizeof(float), D, ctx->stream));
+        if (db) HIP_TRY(hipMemsetAsync(db, 0, (size_t)D * sizeof(float), ctx->stream));
+        return LAFF_OK;
+    }
+    /* the dense segments: one launch for dW (with db), one for dX */
+    a.W = W; a.A = A; a.dA = dA; a.dW = dW; a.db = db;
+    a.N = N; a.D = D; a.ldw = ldw; a.lda = lda; a.ldda = ldda; a.lddw = lddw; a.act = act;
+    a.part = need ? (float*)workspace : nullptr;
+    HIP_TRY(laff::launch_fc_concat_backward(a, ctx->stream));
+    /* the CSR segments: laff_fc_gather_backward's launch on each window; db from the first one when no dense launch formed it */
+    for (int i = 0; i < ncsr; ++i) {
+        laff::FcGatherBwdArgs& q = csr[i];
+        q.db = a.nseg == 0 && i == 0 ? db : nullptr;
+        if (!dW && !q.db) continue;
+        float* window = dW ? dW + csr_col[i] : nullptr;
+        const bool walk = window && q.nnz > 0;   /* otherwise the window is the empty sum: zeros, and the pattern is not read */
+        if (window && !walk) HIP_TRY(hipMemset2DAsync(window, (size_t)lddw * sizeof(float), 0, (size_t)q.Dk * sizeof(float), D, ctx->stream));
+        if (!walk && !q.db) continue;
+        q.dW = walk ? window : nullptr;
+        HIP_TRY(laff::launch_fc_gather_backward(q, ctx->stream));
+    }
+    return LAFF_OK;
+}
+
 /* The refusals and steps that the plain and the tiled BatchNorm entry points share; a layer of D columns is planned as
    bn_train_plan(N, D, has_bn), the tiled one with D = H C.  The first three come before CHECK_CTX: the tests call them without a GPU. */
 static int bn_plan_out(const char* fn, int N, int D, bool has_bn, int out[4]) {

@@ -286,6 +286,29 @@ struct FcGatherBwdArgs {
 };
 hipError_t launch_fc_gather_backward(const FcGatherBwdArgs& a, hipStream_t st);
 
+// fc_concat_bwd.hip: backward of the concat layer's dense segments, all of them in one launch per product (laff_fc_concat_backward;
+// the CSR segments go through launch_fc_gather_backward on their windows)
+struct FcConcatBwdSeg {
+    const float* X;           // [N, ldx >= dk]   read for dW, in place
+    float* dX;                // [N, lddx >= dk] or null
+    int ldx, lddx, dk, col;   // col: first column of the segment's window in W and dW
+};
+struct FcConcatBwdArgs {
+    const float* W;           // [D, ldw >= K]    read for dX, in place at every window
+    const float* A;           // [N, lda >= D]    the saved forward output
+    const float* dA;          // [N, ldda >= D]
+    float* dW;                // [D, lddw >= K] or null; only the dense segments' windows are written
+    float* db;                // [D] or null
+    int N, D, ldw, lda, ldda, lddw, act;
+    int nseg;                 // dense segments, in list order
+    FcConcatBwdSeg seg[CONCAT_MAX_SEG];
+    float* part;              // workspace, as FcBwdArgs::part with the segments' columns side by side in a partial row
+};
+// how the dense segments of widths dk[0 .. n) are cut, from (N, D, the widths) alone: as FcBwdPlan, with the products' tiles counted
+// over all segments; ws_dx counts the dx_cols columns of the segments that want a dX
+void fc_concat_bwd_plan(int N, int D, const int* dk, int n, int dx_cols, FcBwdPlan* p);
+hipError_t launch_fc_concat_backward(const FcConcatBwdArgs& a, hipStream_t st);
+
 // bn_train.hip: dropout by a counter-based mask and training-mode BatchNorm1d, forward and backward (laff_dropout_bn_train,
 // laff_dropout_bn_train_backward).  One struct for both directions; a direction leaves the other's fields null.
 constexpr int BN_TRAIN_ROWS = 256;       // rows of a chunk: the strip of 32 columns that a block keeps in registers

@@ -142,6 +142,31 @@ class _FcConcatFn(torch.autograd.Function):
         return (None, None, dw, db) + tuple(dxs)
 
 
+class _FcConcatGroupedFn(_FcConcatFn):
+    """_FcConcatFn's forward with ONE ops.fc_concat_backward call behind it: a launch writes the column
+    windows of dw for all dense segments and db, a launch the dx of every dense segment that needs a gradient, and a CSR segment's
+    window is one gather launch inside the same call.  The training route of the W2VV++ video tower (TransformNet.concat_train with
+    grouped=True); _FcConcatFn stays what concat_train runs by default, what the text tower takes and what this one is compared with."""
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_a):
+        weight, a, *saved = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        segs, want_dx, at = [], [], 0
+        for j, shape in enumerate(ctx.csr_shapes):           # a CSR segment's (N, width), None for a dense one
+            if shape is not None:
+                segs.append(tuple(saved[at:at + 3]))
+                at += 3
+            else:
+                segs.append(saved[at])
+                at += 1
+            want_dx.append(shape is None and need[4 + j])
+        dxs, dw, db = ops.fc_concat_backward(segs, weight.detach(), a, grad_a, ctx.activation, want_dx=want_dx, want_dw=need[2],
+                                             want_db=ctx.has_bias and need[3])
+        return (None, None, dw, db) + tuple(dxs)
+
+
 class _DropoutBnFn(torch.autograd.Function):
     """y = BatchNorm1d(dropout(a)) in training mode on laff_dropout_bn_train, ops.dropout_bn_train_backward behind it (DESIGN.md
     section 4.25).  The dropout mask is a function of (seed, row, column): the seed is saved, the mask and the dropped activations are

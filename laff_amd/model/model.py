@@ -23,7 +23,7 @@ Differentiable in .train() mode (the autograd Functions live in model/autograd.p
   VisMutiTransformNetPlusFrameFeat.frame_vector                         section 4.22
   the expert stage of the LAFF towers (expert embedding + l2norm)  _ExpertStageFn section 4.27
   the LAFF and FrameLAFF towers' prepare() / forward and the model's training step (enable_training, forward)   section 4.27
-Inference only (_eval_only raises in training mode): the concat towers of plain 'W2VVPP' (TransformNet.concat_problem), and the
+Inference only (_eval_only raises in training mode): TransformNet.concat_problem and a concat tower that no enable_training() armed, and the
 FrameLAFF video tower's prepare() / forward until its model's enable_training() has armed it; retrieve() / predict() put the model in
 eval mode.
 
@@ -41,7 +41,7 @@ from .. import loss as _loss
 from .. import ops
 from .. import optim as _optim
 from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention
-from .autograd import (_csc_of, _DropoutBnFn, _ExpertStageFn, _FcActFn, _FcConcatFn, _FcGatherFn, _fp32_params,  # noqa: F401  (kept importable from here)
+from .autograd import (_csc_of, _DropoutBnFn, _ExpertStageFn, _FcActFn, _FcConcatFn, _FcConcatGroupedFn, _FcGatherFn, _fp32_params,  # noqa: F401  (kept importable from here)
                        _TileBnFn)
 
 device = torch.device('cuda')
@@ -402,11 +402,12 @@ class TransformNet(nn.Module):
         self._running_stats_written()
         return y
 
-    def concat_train(self, segments):
+    def concat_train(self, segments, grouped=False):
         """Training mode: this layer applied to torch.cat(segments, dim=1) without forming it, under autograd (_FcConcatFn), then
         torch's dropout and training-mode BatchNorm1d as in _forward_train.  segments: dense fp32 device matrices and / or device
         torch.sparse_csr ones, in column order; a dense segment that requires a gradient receives one.  concat_problem stays the
-        inference path."""
+        inference path.  grouped: the backward is one ops.fc_concat_backward call (_FcConcatGroupedFn) instead of one call per
+        segment -- the route of the W2VV++ towers."""
         if not self.training:
             raise RuntimeError('concat_train is the training-mode path; in eval mode use concat_problem')
         if self.fc1 is None:
@@ -419,7 +420,8 @@ class TransformNet(nn.Module):
         col = sum(x.shape[1] for x in segments)
         if col != self.fc1.in_features:
             raise ValueError('the concatenated input has %d columns, fc1 takes %d' % (col, self.fc1.in_features))
-        return self._after_activation_train(_FcConcatFn.apply(self, self.activation_name, self.fc1.weight, self.fc1.bias, *segments))
+        fn = _FcConcatGroupedFn if grouped else _FcConcatFn
+        return self._after_activation_train(fn.apply(self, self.activation_name, self.fc1.weight, self.fc1.bias, *segments))
 
     def plane(self, x, heads=1, extra_shift=None, pending=None, head_dim=None):
         """(src, tile, scale, shift) for laff_fuse.  With an FC the projection either runs now or, when `pending`
@@ -473,13 +475,34 @@ class VisTransformNet(TransformNet):
         super().__init__((int(np.sum(list(opt.vis_fc_layers[0].values()))), opt.vis_fc_layers[1]), opt)
 
     def prepare(self, vis_input, vis_frame_feat_dict_input=None, pending=None):
-        """Queue the projection on `pending`; returns the closure that hands the embeddings over once run_fc() has run."""
+        """Queue the projection on `pending`; returns the closure that hands the embeddings over once run_fc() has run.  In training
+        mode the route is open only once the owning model's enable_training() has armed the tower (training_armed): the projection then
+        runs at once under autograd (_concat_tower_train) and the closure holds the differentiable embeddings."""
         segments = list(vis_input.values()) if isinstance(vis_input, dict) else [vis_input]     # dict order, as torch.cat(list(...))
+        if self.training and getattr(self, 'training_armed', False):
+            emb = _concat_tower_train(self, self, segments, grouped=True)
+            return lambda: emb
         out = self.concat_problem(segments, pending)
         return lambda: out
 
     def forward(self, vis_input, txt_emb=None, vis_frame_feat_dict_input=None):
         return self.prepare(vis_input)()
+
+
+def _concat_tower_train(tower, layer, segments, grouped):
+    """The training route of a W2VV++ concat tower: its segments through layer.concat_train.  Dense segments
+    go to the device as fp32; a CSR one that is on the device already is handed on as the object it is (it may carry its laff_csc).
+    grouped: the backward is the one laff_fc_concat_backward call.  The video tower takes it; the text tower keeps the per-segment
+    calls, which measured faster at its mix of a wide aligned segment, a CSR one and a narrow unaligned one (section 4.30)."""
+    _train_on_device(tower)
+    segs = []
+    for x in segments:
+        if x.layout != torch.sparse_csr:
+            x = to_device_and_float16(x)
+        elif not x.is_cuda:
+            x = x.to(device)
+        segs.append(x)
+    return layer.concat_train(segs, grouped=grouped)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -709,6 +732,12 @@ class MultiScaleTxtNet(nn.Module):
         self.transformer = TransformNet(opt.txt_fc_layers, opt, opt.dropout, opt.batch_norm, opt.activation)
 
     def prepare(self, caption_feat_dict, pending=None, task3=False):
+        """As VisTransformNet.prepare; an armed tower in training mode hands the encoders' segments to the layer's training route (the
+        per-segment backward, _concat_tower_train): a device CSR bag of words stays sparse (with its laff_csc), a differentiable
+        encoder's output receives its gradient."""
+        if self.training and getattr(self, 'training_armed', False):
+            emb = _concat_tower_train(self, self.transformer, self.encoder.segments(caption_feat_dict, task3), grouped=False)
+            return lambda: emb
         out = self.transformer.concat_problem(self.encoder.segments(caption_feat_dict, task3), pending)
         return lambda: out
 
@@ -919,8 +948,8 @@ class VisMutiTransformNetPlusFrameFeat(nn.Module):
 # a9-a11: the cross-modal model
 # ------------------------------------------------------------------------------------------------------
 class W2VVPP(nn.Module):
-    """The reference's W2VVPP family (model/model.py:791-1128): the inference surface, and for the LAFF towers the training step
-    (enable_training, forward)."""
+    """The reference's W2VVPP family (model/model.py:791-1128): the inference surface, and the training step (enable_training, forward)
+    for the LAFF towers and for the W2VV++ concat towers (section 4.30)."""
 
     #: operand precision of the similarity GEMM ('fp32' | 'fp16' | 'bf16' | 'fp16x3' | 'bf16x3')
     sim_precision = None
@@ -945,8 +974,16 @@ class W2VVPP(nn.Module):
     def _training_refusals(self):
         """What the step does not cover, by name, before any launch."""
         opt = self.opt
-        if isinstance(self.vis_net, VisTransformNet) or isinstance(self.txt_net, MultiScaleTxtNet):
-            raise NotImplementedError('training step (model/model.py:964-1001) is out of scope for the concat towers of W2VVPP; use predict()')
+        if self._concat_towers():
+            # the base class's compute_loss on 2-D embeddings (model/model.py:840-865): class W2VVPP, or W2VVPP_MutiVis with both concat
+            if isinstance(self.vis_net, VisTransformNet) != isinstance(self.txt_net, MultiScaleTxtNet):
+                raise NotImplementedError('training step: one concat tower beside one attention tower gives 2-D embeddings on one side and '
+                                          'per-head ones on the other; the reference raises on the rank mismatch.  Make both towers '
+                                          "'concat' or neither")
+            if isinstance(self, W2VVPP_MultiHeadAttention):
+                raise NotImplementedError("training step: key 'LAFF' with the concat towers scores its 2-D embeddings through "
+                                          'get_txt2vis_matrix and criterion_with_score (model/model.py:2040-2042), and that score matrix '
+                                          "is not differentiable here; train them under 'W2VVPP' or 'w2vpp_mutivis_attention'")
         if getattr(opt, 'negative', False):
             raise NotImplementedError('training step: opt.negative (cal_foward_neg and Margin2Loss, model/model.py:889-962) is not '
                                       'provided; set negative=False')
@@ -956,6 +993,14 @@ class W2VVPP(nn.Module):
         if globals()['float16']:
             raise NotImplementedError('training step: float16 (autocast + GradScaler, model/model.py:970-989) has no counterpart here; '
                                       'the step is fp32')
+        if self._concat_towers():
+            p = next(self.parameters(), None)
+            if p is not None and not p.is_cuda:
+                raise NotImplementedError('training step: the concat towers train on the device only (laff_amd has no CPU path); move '
+                                          'the model to the GPU, or use predict()')
+
+    def _concat_towers(self):
+        return isinstance(self.vis_net, VisTransformNet) or isinstance(self.txt_net, MultiScaleTxtNet)
 
     def enable_training(self, device_norm=True):
         """Everything the reference's constructor builds for training (model/model.py:1984-2030), kept out of __init__ so that a model
@@ -968,13 +1013,16 @@ class W2VVPP(nn.Module):
         self.criterion = _loss.criterion_for(opt)
         self.criterion_with_score = _loss.MarginRankingLossWithScore(margin=opt.margin, max_violation=opt.max_violation,
                                                                      cost_style=opt.cost_style, direction=opt.direction)
-        self.optimizer, self.lr_schedulers = _optim.optimizer_for(opt, self)
+        # the concat towers train under the reference's base class: Adam(params, lr) with torch's default eps (model/model.py:825), not
+        # the multi-head class's eps=1e-4 (:2022)
+        self.optimizer, self.lr_schedulers = _optim.optimizer_for(opt, self, **({'adam_eps': 1e-8} if self._concat_towers() else {}))
         self.params = list(self.parameters())
         self.grad_clip = opt.grad_clip
         self.iters = 0
         use_device_norm(self, device_norm)
-        if isinstance(self.vis_net, VisMutiTransformNetPlusFrameFeat):
-            self.vis_net.training_armed = True             # the FrameLAFF tower's training route opens for this model only
+        for net in (self.vis_net, self.txt_net):           # the towers whose training route opens for an armed model only
+            if isinstance(net, (VisMutiTransformNetPlusFrameFeat, VisTransformNet, MultiScaleTxtNet)):
+                net.training_armed = True
         return self
 
     def compute_loss(self, vis_embs, txt_embs, *unused):

@@ -16,7 +16,7 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcProblem, FcSplitProblem, FcStripProblem, Plane, check, FcFusedProblem, RankSide, FcConcatProblem, FcConcatSegment,
                    FcLaunch, FcShape, RerankProblem)
 
-__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'batch_assemble', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
+__all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'batch_assemble', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'fc_concat_backward', 'fc_concat_backward_plan', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
            'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
 
 _ctx = {}
@@ -1449,6 +1449,103 @@ def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=
     _call('fc_gather_backward', lib.laff_fc_gather_backward, h, _ptr(colptr), _ptr(rows), _ptr(values), nnz, N, Dk, D, ACT[activation],
           _ptr(a), lda, _ptr(g), ldg, pdw, lddw, _ptr(db))
     return dw, db
+
+
+def _concat_kinds(segments, want_dx):
+    """(widths, kinds) of a concat layer's segments as laff_fc_concat_backward_plan takes them: a segment is a dense (N, Dk) matrix (or
+    just its width, for a plan) or a transposed pattern (colptr, rows, values); kinds = bit 0 CSR | bit 1 dX wanted."""
+    want_dx = list(want_dx) if want_dx is not None else [False] * len(segments)
+    if len(want_dx) != len(segments):
+        raise ValueError('want_dx has %d entries for %d segments' % (len(want_dx), len(segments)))
+    widths, kinds = [], []
+    for j, (x, wdx) in enumerate(zip(segments, want_dx)):
+        csr = isinstance(x, (tuple, list))
+        if csr and wdx:
+            raise ValueError('segment %d is sparse (counts): it has no dx' % j)
+        widths.append(x[0].numel() - 1 if csr else int(x) if isinstance(x, int) else x.shape[1])
+        kinds.append((1 if csr else 0) | (2 if wdx else 0))
+    return widths, kinds, want_dx
+
+
+def fc_concat_backward_plan(N, D, segments, want_dx=None, want_dw=True):
+    """laff_fc_concat_backward_plan (host only): (chunks of dW's and db's sum over N, workspace bytes, chunks of dX's sum over D, tile
+    variants: bit 0 dW and bit 1 dX on 128 x 128 tiles).  segments: as fc_concat_backward takes them, a dense one also as its width."""
+    widths, kinds, _ = _concat_kinds(segments, want_dx)
+    n = len(widths)
+    out = (C.c_int * 4)()
+    check(_lib.load().laff_fc_concat_backward_plan(int(N), int(D), (C.c_int * n)(*widths), (C.c_int * n)(*kinds), n, bool(want_dw), out))
+    return tuple(out)
+
+
+def fc_concat_backward(segments, weight, a, grad_a, activation, want_dx=None, want_dw=True, want_db=True, out=None, columns=None):
+    """Backward of a = act(cat(segments, dim 1) @ weight.T + bias) without the concatenation (laff_fc_concat_backward): one launch
+    writes the column windows of ONE (D, K) dw for all dense segments (and db), one launch the dx of every dense segment that wants
+    one, and each sparse segment's window is one laff_fc_gather_backward launch.  segments: dense (N, Dk) device fp32 matrices (row
+    views with a pitch are read in place) and / or transposed patterns (colptr, rows, values) as csr_transpose returns them, in the
+    order their columns have in weight (D, K); a (N, D) the saved forward output, grad_a (N, D) its gradient.  want_dx: one flag per
+    segment (default: none).  columns: the first column of every segment's window in weight where the windows do not simply follow
+    each other (they may then leave columns of weight out: those columns of dw are not written).
+    Returns (dxs -- a list with None where no dx was asked for --, dw (D, K) | None, db (D,) | None).
+    out: a (dxs, dw, db) triple of fp32 buffers; dxs a list (None entries are allocated here), dw may be a row view with a pitch."""
+    if activation not in ACT:
+        raise ValueError('unknown activation %r' % (activation,))
+    segments = list(segments)
+    widths, kinds, want_dx = _concat_kinds(segments, want_dx)
+    sparse = any(k & 1 for k in kinds)
+    (w, ldw) = _mat(weight, 'weight')
+    (a, lda), (g, ldg) = _mat(a, 'a', align16=sparse), _mat(grad_a, 'grad_a', align16=sparse)
+    (N, D), K, dev = a.shape, w.shape[1], a.device
+    if sparse:
+        lda, ldg = (lda + 3) // 4 * 4, (ldg + 3) // 4 * 4      # a single row: no pitch of its own
+    free = columns is not None
+    if not free:
+        columns = [sum(widths[:j]) for j in range(len(widths))]
+    if len(columns) != len(widths):
+        raise ValueError('columns has %d entries for %d segments' % (len(columns), len(widths)))
+    if w.shape[0] != D or tuple(g.shape) != (N, D) or (
+            max(c + k for c, k in zip(columns, widths)) > K if free else sum(widths) != K):
+        raise ValueError('weight %s, a %s, grad_a %s and segments of %d columns do not fit together' % (
+            tuple(w.shape), tuple(a.shape), tuple(g.shape), sum(widths)))
+    odx, odw, odb = out if out is not None else (None, None, None)
+    odx = list(odx) if odx is not None else [None] * len(segments)
+    dw, pdw, lddw = _out_rows(odw, (D, K), dev, 'out dw') if want_dw else (None, None, 0)
+    db = _vec_out(odb, D, dev, 'out db') if want_db else None
+    n = len(segments)
+    ints = {k: (C.c_int * n)() for k in ('cols', 'nnz', 'ldx', 'lddx')}
+    ptrs = {k: (C.c_void_p * n)() for k in ('x', 'dx', 'colptr', 'rows', 'values')}
+    dxs, keep = [], []
+    for j, x in enumerate(segments):
+        ints['cols'][j], ints['nnz'][j] = int(columns[j]), -1
+        if kinds[j] & 1:
+            colptr, rows, values = x
+            for t, nm in ((colptr, 'colptr'), (rows, 'rows')):
+                _dev(t, nm, torch.int32)
+                if t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError('segment %d: %s must be a contiguous vector' % (j, nm))
+            nnz = rows.numel()
+            if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
+                raise ValueError('segment %d: values must be a contiguous vector of %d' % (j, nnz))
+            ints['nnz'][j] = nnz
+            ptrs['colptr'][j], ptrs['rows'][j] = colptr.data_ptr(), rows.data_ptr()
+            ptrs['values'][j] = values.data_ptr() if values is not None else None
+            dxs.append(None)
+        else:
+            x, ints['ldx'][j] = _mat(x, 'segment %d' % j)
+            if x.shape[0] != N:
+                raise ValueError('segment %d is %s, expected %d rows' % (j, tuple(x.shape), N))
+            dx, _, ints['lddx'][j] = _out_rows(odx[j], (N, widths[j]), dev, 'out dx %d' % j) if want_dx[j] else (None, None, 0)
+            ptrs['x'][j], ptrs['dx'][j] = x.data_ptr(), dx.data_ptr() if dx is not None else None
+            keep.append(x)
+            dxs.append(dx)
+    if not (any(want_dx) or want_dw or want_db):
+        return dxs, None, None
+    nbytes = fc_concat_backward_plan(N, D, segments, want_dx, want_dw)[1]
+    ws = _workspace(nbytes, dev)
+    lib, h = _context(dev)
+    _call('fc_concat_backward', lib.laff_fc_concat_backward, h, n, (C.c_int * n)(*widths), ints['cols'], ints['nnz'], ptrs['x'], ints['ldx'],
+          ptrs['dx'], ints['lddx'], ptrs['colptr'], ptrs['rows'], ptrs['values'], N, _ptr(w), K, ldw, D, ACT[activation], _ptr(a), lda,
+          _ptr(g), ldg, pdw, lddw, _ptr(db), _ptr(ws), nbytes)
+    return dxs, dw, db
 
 
 def dropout_bn_train_plan(N, D, has_bn=True):

@@ -240,9 +240,10 @@ class RMSprop(_StepOptimizer):
         return dict(lr=group['lr'], beta2=group['alpha'], eps=group['eps'], weight_decay=group['weight_decay'])
 
 
-def optimizer_for(opt, model):
+def optimizer_for(opt, model, adam_eps=1e-4):
     """The reference's optimizer and schedulers (model/model.py:2008-2028) for `model`: parameters whose name contains 'BertModel',
-    'csn_model' or 'ClipModel' form a second group at opt.lr / 20; opt.optimizer 'adam' -> Adam(lr, eps=1e-4), 'rmsprop' ->
+    'csn_model' or 'ClipModel' form a second group at opt.lr / 20; opt.optimizer 'adam' -> Adam(lr, eps=adam_eps: the multi-head
+    class's 1e-4, :2022; the base class keeps torch's 1e-8, :825), 'rmsprop' ->
     RMSprop(lr), both clipping at opt.grad_clip inside the step.  Returns (optimizer, [StepLR(step_size=1, gamma=opt.lr_decay_rate),
     ReduceLROnPlateau(mode='max', factor=0.5, patience=2)])."""
     special, usual = [], []
@@ -250,7 +251,7 @@ def optimizer_for(opt, model):
         (special if ('BertModel' in name or 'csn_model' in name or 'ClipModel' in name) else usual).append(p)
     params = [{'params': usual}, {'params': special, 'lr': opt.lr / 20}]
     if opt.optimizer == 'adam':
-        optimizer = Adam(params, lr=opt.lr, eps=1e-4, grad_clip=opt.grad_clip)
+        optimizer = Adam(params, lr=opt.lr, eps=adam_eps, grad_clip=opt.grad_clip)
     elif opt.optimizer == 'rmsprop':
         optimizer = RMSprop(params, lr=opt.lr, grad_clip=opt.grad_clip)
     else:
