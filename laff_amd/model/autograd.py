@@ -87,6 +87,16 @@ class _FcGatherFn(torch.autograd.Function):
         return None, dw, db, None, None
 
 
+def _saved_segments(csr_shapes, saved):
+    """(shape, segment) per segment of a concat layer from what its forward saved: a CSR segment's (N, width) with its
+    (colptr, rows, values) -- 3 saved tensors --, None with the dense matrix -- 1 saved tensor -- for a dense one."""
+    at = 0
+    for shape in csr_shapes:
+        n = 1 if shape is None else 3
+        yield shape, saved[at] if shape is None else tuple(saved[at:at + 3])
+        at += n
+
+
 class _FcConcatFn(torch.autograd.Function):
     """a = act(sum_s x_s @ weight[:, c_s : c_s + w_s].T + bias) over dense device fp32 segments and / or device torch.sparse_csr ones:
     the one laff_fc_concat_act_bn launch forward (no BatchNorm stage), and behind it one call per segment on the column windows of
@@ -124,18 +134,16 @@ class _FcConcatFn(torch.autograd.Function):
         w = weight.detach()
         dw = torch.empty_like(w, memory_format=torch.contiguous_format) if need[2] else None
         db = torch.empty((w.shape[0],), device=w.device, dtype=torch.float32) if ctx.has_bias and need[3] else None
-        dxs, col, at = [], 0, 0
-        for j, shape in enumerate(ctx.csr_shapes):           # a CSR segment's (N, width), None for a dense one
+        dxs, col = [], 0
+        for j, (shape, x) in enumerate(_saved_segments(ctx.csr_shapes, saved)):
             first_db = db if j == 0 else None
-            width = saved[at].shape[1] if shape is None else shape[1]
+            width = x.shape[1] if shape is None else shape[1]
             window = None if dw is None else dw[:, col:col + width]
             if shape is not None:
-                csc, at = tuple(saved[at:at + 3]), at + 3
-                ops.fc_gather_backward(csc, shape[0], width, a, grad_a, ctx.activation, want_dw=dw is not None,
+                ops.fc_gather_backward(x, shape[0], width, a, grad_a, ctx.activation, want_dw=dw is not None,
                                        want_db=first_db is not None, out=(window, first_db))
                 dxs.append(None)
             else:
-                x, at = saved[at], at + 1
                 dxs.append(ops.fc_backward(x, w[:, col:col + width], a, grad_a, ctx.activation, want_dx=need[4 + j],
                                            want_dw=dw is not None, want_db=first_db is not None, out=(None, window, first_db))[0])
             col += width
@@ -153,14 +161,9 @@ class _FcConcatGroupedFn(_FcConcatFn):
     def backward(ctx, grad_a):
         weight, a, *saved = ctx.saved_tensors
         need = ctx.needs_input_grad
-        segs, want_dx, at = [], [], 0
-        for j, shape in enumerate(ctx.csr_shapes):           # a CSR segment's (N, width), None for a dense one
-            if shape is not None:
-                segs.append(tuple(saved[at:at + 3]))
-                at += 3
-            else:
-                segs.append(saved[at])
-                at += 1
+        segs, want_dx = [], []
+        for j, (shape, x) in enumerate(_saved_segments(ctx.csr_shapes, saved)):
+            segs.append(x)
             want_dx.append(shape is None and need[4 + j])
         dxs, dw, db = ops.fc_concat_backward(segs, weight.detach(), a, grad_a, ctx.activation, want_dx=want_dx, want_dw=need[2],
                                              want_db=ctx.has_bias and need[3])

@@ -146,6 +146,23 @@ def _csr_triple(x_csr):
             x_csr.values().to(torch.float32).contiguous())
 
 
+def _csc_triple(csc, where='', Dk=None):
+    """(colptr, rows, values, nnz) of a transposed pattern as csr_transpose returns it, checked: colptr and rows contiguous int32 device
+    vectors (colptr of Dk + 1 entries where Dk is given), values None (all ones) or a contiguous fp32 device vector of nnz.  where:
+    a prefix of the error texts ('segment %d: ')."""
+    colptr, rows, values = csc
+    for t, nm in ((colptr, 'colptr'), (rows, 'rows')):
+        _dev(t, nm, torch.int32)
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError('%s%s must be a contiguous vector' % (where, nm))
+    nnz = rows.numel()
+    if Dk is not None and colptr.numel() != Dk + 1:
+        raise ValueError('%scolptr has %d entries, expected Dk + 1 = %d' % (where, colptr.numel(), Dk + 1))
+    if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
+        raise ValueError('%svalues must be a contiguous vector of %d' % (where, nnz))
+    return colptr, rows, values, nnz
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -1424,17 +1441,8 @@ def fc_gather_backward(csc, N, Dk, a, grad_a, activation, want_dw=True, want_db=
     element of the window is written and nothing else; db is contiguous)."""
     if activation not in ACT:
         raise ValueError('unknown activation %r' % (activation,))
-    colptr, rows, values = csc
     N, Dk = int(N), int(Dk)
-    for t, nm in ((colptr, 'colptr'), (rows, 'rows')):
-        _dev(t, nm, torch.int32)
-        if t.dim() != 1 or not t.is_contiguous():
-            raise ValueError('%s must be a contiguous vector' % nm)
-    nnz = rows.numel()
-    if colptr.numel() != Dk + 1:
-        raise ValueError('colptr has %d entries, expected Dk + 1 = %d' % (colptr.numel(), Dk + 1))
-    if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
-        raise ValueError('values must be a contiguous vector of %d' % nnz)
+    colptr, rows, values, nnz = _csc_triple(csc, Dk=Dk)
     (a, lda), (g, ldg) = _mat(a, 'a', align16=True), _mat(grad_a, 'grad_a', align16=True)
     D, dev = a.shape[1], a.device
     lda, ldg = (lda + 3) // 4 * 4, (ldg + 3) // 4 * 4          # a single row: no pitch of its own
@@ -1517,15 +1525,7 @@ def fc_concat_backward(segments, weight, a, grad_a, activation, want_dx=None, wa
     for j, x in enumerate(segments):
         ints['cols'][j], ints['nnz'][j] = int(columns[j]), -1
         if kinds[j] & 1:
-            colptr, rows, values = x
-            for t, nm in ((colptr, 'colptr'), (rows, 'rows')):
-                _dev(t, nm, torch.int32)
-                if t.dim() != 1 or not t.is_contiguous():
-                    raise ValueError('segment %d: %s must be a contiguous vector' % (j, nm))
-            nnz = rows.numel()
-            if values is not None and (_dev(values, 'values').dim() != 1 or values.numel() != nnz or not values.is_contiguous()):
-                raise ValueError('segment %d: values must be a contiguous vector of %d' % (j, nnz))
-            ints['nnz'][j] = nnz
+            colptr, rows, values, ints['nnz'][j] = _csc_triple(x, 'segment %d: ' % j)
             ptrs['colptr'][j], ptrs['rows'][j] = colptr.data_ptr(), rows.data_ptr()
             ptrs['values'][j] = values.data_ptr() if values is not None else None
             dxs.append(None)

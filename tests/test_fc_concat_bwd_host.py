@@ -106,76 +106,26 @@ def test_the_plan_is_a_pure_function_of_the_shapes():
         ops.fc_concat_backward_plan(9, 6, [4])
 
 
-# ---- the fixture of the reference's own steps (tools/gen_golden_train_w2vvpp.py) ----------------------------------------------------
-def _rel(a, b):
-    import numpy as np
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    top = float(np.abs(b).max())
-    return float(np.abs(a - b).max()) / top if top else float(np.abs(a - b).max())
-
-
+# ---- the fixture of the reference's own steps (tools/gen_golden_train.py) -----------------------------------------------------------
 @pytest.mark.parametrize('key', ['i', 'ii'])
 def test_concat_tower_ref_reproduces_the_reference_in_float64(key):
     """Embeddings, loss and every gradient of both steps to 1e-12."""
-    import concat_tower_ref as CT
-    arrays, meta = CT.load_case(key)
+    import tower_ref
+    arrays, meta = tower_ref.load_case(key)
     assert meta['model'] == {'i': 'W2VVPP', 'ii': 'w2vpp_mutivis_attention'}[key] and meta['N'] == 12 and meta['D'] == 64
     assert list(meta['vid_dims'].values()) == [96, 48, 40] and list(meta['txt_dims'].values()) == [30, 50, 64]
     assert (meta['optimizer'], meta['max_violation'], meta['direction']) == {'i': ('rmsprop', True, 't2i'), 'ii': ('adam', False, 'bidir')}[key]
-    for s in (1, 2):
-        graph = CT.step_graph(key, s)
-        pre = 's%d/' % s
-        assert _rel(graph['txt_emb'].detach().numpy(), arrays[pre + 'txt_emb']) <= 1e-12
-        assert _rel(graph['vis_emb'].detach().numpy(), arrays[pre + 'vis_emb']) <= 1e-12
-        want = meta['steps'][s - 1]['loss']
-        assert abs(float(graph['loss'].detach()) - want) <= 1e-12 * abs(want)
-        grads = CT.tower_ref.sub(arrays, pre + 'grad/')
-        assert sorted(grads) == sorted(k for k, g in graph['grads'].items() if g is not None) == sorted(CT.tower_ref.param_names(
-            CT.tower_ref.sub(arrays, 'sd0/')))
-        for k, v in grads.items():
-            assert _rel(graph['grads'][k].numpy(), v) <= 1e-12, (s, k)
-        assert meta['steps'][s - 1]['slack'] >= CT.train_ref.HINGE_CLEAR
-
-
-def _optim_ref_steps(key, eps=None):
-    """The largest relative distance, over both steps, of optim_ref's parameters and optimizer state from the fixture's."""
-    import numpy as np
-    import concat_tower_ref as CT
-    import optim_ref
-    arrays, meta = CT.load_case(key)
-    sub = CT.tower_ref.sub
-    eps = meta['eps'] if eps is None else eps
-    worst = 0.0
-    for s in (1, 2):
-        grads = sub(arrays, 's%d/grad/' % s)
-        names = sorted(grads)
-        before = sub(arrays, 'sd0/') if s == 1 else sub(arrays, 's%d/sd/' % (s - 1))
-        prev = {} if s == 1 else sub(arrays, 's%d/state/' % (s - 1))
-        after, state = sub(arrays, 's%d/sd/' % s), sub(arrays, 's%d/state/' % s)
-        g = [grads[k] for k in names]
-        total = optim_ref.total_norm(g)
-        assert abs(total - meta['steps'][s - 1]['total_norm']) <= 1e-12 * total
-        c = optim_ref.clip_coef(total, meta['grad_clip'])
-        old = lambda n: [prev[n + '/' + k] if prev else np.zeros_like(grads[k]) for k in names]      # noqa: E731
-        if meta['optimizer'] == 'rmsprop':
-            p2, s2 = optim_ref.rmsprop([before[k] for k in names], g, old('square_avg'), meta['lr'], meta['alpha'], eps, 0.0, c)
-            new = {'square_avg': s2}
-        else:
-            p2, m2, v2 = optim_ref.adam([before[k] for k in names], g, old('exp_avg'), old('exp_avg_sq'), meta['lr'], *meta['betas'], eps,
-                                        0.0, s, c)
-            new = {'exp_avg': m2, 'exp_avg_sq': v2}
-        assert meta['steps'][s - 1]['opt_step'] == s
-        for i, k in enumerate(names):
-            worst = max(worst, _rel(p2[i], after[k]), *[_rel(v[i], state[n + '/' + k]) for n, v in new.items()])
-    return worst
+    assert tower_ref.REL == 1e-12 and all(rec['none'] == [] for rec in meta['steps'])     # every parameter has a gradient
+    tower_ref.check_restatement(arrays, meta)
 
 
 def test_optim_ref_reproduces_the_reference_optimizers_and_adam_only_with_the_default_eps():
-    assert _optim_ref_steps('i') <= 1e-12
-    assert _optim_ref_steps('ii') <= 1e-12
-    import concat_tower_ref as CT
-    assert CT.load_case('ii')[1]['eps'] == 1e-8 and CT.load_case('ii')[1]['betas'] == [0.9, 0.999]
-    assert _optim_ref_steps('ii', eps=1e-4) > 1e-6                         # the multi-head class's eps is not what the base class steps with
+    import tower_ref
+    for key in ('i', 'ii'):
+        tower_ref.check_replay(*tower_ref.load_case(key))
+    arrays, meta = tower_ref.load_case('ii')
+    assert meta['eps'] == 1e-8 and meta['betas'] == [0.9, 0.999]
+    assert max(tower_ref.replay_steps(arrays, meta, eps=1e-4).values()) > 1e-6      # the multi-head class's eps is not what the base class steps with
 
 
 # ---- the towers and the step -------------------------------------------------------------------------------------------------------

@@ -1,32 +1,24 @@
 """The W2VV++ concat towers in training mode and the model's training step on the MI355X, against float64 and against
-the fixture of the reference's own steps (tests/golden/train_step_w2vvpp.<case>.<n>.npz, tools/gen_golden_train_w2vvpp.py).
+the fixture of the reference's own steps (tests/golden/train_step_w2vvpp.<case>.<n>.npz, tools/gen_golden_train.py).
 
-Rules, all of tests/train_ref.py and tests/test_gpu_train_step.py, constants unchanged:
+Rules, all of tests/train_ref.py, constants unchanged:
     module level         train_ref.compare: max |device - float64| / max |float64| within max(4 x the float32 CPU graph's, TOL_UNIT)
-    embeddings, loss     max |device - float64| <= max(4 e32, TOL_UNIT) max |float64|, e32 the fixture's recorded error of the
-                         reference's own float32 run for that tensor
-    raw gradients        element by element under end_to_end_bound, the absolute Jacobian from tests/concat_tower_ref.py
-    the step             parameters and optimizer state against tests/optim_ref.py applied to this model's OWN device gradients, under
-                         the bounds of tests/test_gpu_optim.py; not compared with the fixture element by element (the
-                         first update is +-lr-sized whatever |g|; tests/test_fc_concat_bwd_host.py ties the optimizer to the reference)
+    the step             tests/train_step_check.py, shared with tests/test_gpu_train_step.py: embeddings, loss, raw gradients, total
+                         norm, the optimizer on the device's own gradients, running statistics
 """
 import copy
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-import concat_tower_ref as CT
-import fuse_bwd_ref
-import optim_ref
+import tower_ref
 import train_ref as TR
+import train_step_check as SC
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
-rel_err = fuse_bwd_ref.rel_err
-sub = CT.tower_ref.sub
+DEV = SC.DEV
 
 
 # ---- the armed towers against float64 and against the per-segment route -------------------------------------------------------------
@@ -128,188 +120,33 @@ def test_armed_tower_against_float64_and_the_per_segment_route(side, batch_norm,
 
 
 # ---- both fixture cases on the device ----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _refs(key, step):
-    g64 = CT.step_graph(key, step)
-    absjac = {k: v.numpy() for k, v in CT.abs_jacobian(g64).items()}
-    return g64, absjac, CT.step_graph(key, step, torch.float32)
-
-
-def _state_before(key, step):
-    arrays, _ = CT.load_case(key)
-    return sub(arrays, 'sd0/') if step == 1 else sub(arrays, 's%d/sd/' % (step - 1))
-
-
-def _state_names(meta):
-    return ('square_avg',) if meta['optimizer'] == 'rmsprop' else ('exp_avg', 'exp_avg_sq')
-
-
-def _model(key, step=1, **overrides):
-    """The model in the state the fixture's run had before `step`, enable_training() called; for step 2 the optimizer state of the
-    fixture's step 1 is loaded through optimizer.load_state_dict."""
-    arrays, meta = CT.load_case(key)
-    model = CT.device_model(key, DEV, sd=_state_before(key, step), **overrides).enable_training()
-    assert model.vis_net.training_armed and model.txt_net.training_armed
-    assert model.optimizer.param_groups[0]['eps'] == 1e-8                    # both cases: the base class's optimizers, torch's default eps
-    if step == 2:
-        state = model.optimizer.state_dict()
-        names = [k for k, _ in model.named_parameters()]
-        assert state['param_groups'][0]['params'] == list(range(len(names)))
-        state['state'] = {i: dict({'step': torch.tensor(float(meta['steps'][0]['opt_step']))},
-                                  **{n: torch.as_tensor(arrays['s1/state/%s/%s' % (n, k)]).float().to(DEV) for n in _state_names(meta)})
-                          for i, k in enumerate(names)}
-        model.optimizer.load_state_dict(state)
-    return model
-
-
-def _grad_bounds(key, step):
-    """{name: (float64 gradient, element bound)} for every gradient of a fixture step (the rule of test_gpu_train_step.py)."""
-    arrays, meta = CT.load_case(key)
-    _, absjac, _ = _refs(key, step)
-    e32 = meta['steps'][step - 1]['e32']
-    out = {}
-    for name, r64 in sub(arrays, 's%d/grad/' % step).items():
-        # end_to_end_bound takes the float32 CPU gradient to form e32; the fixture keeps that figure of the reference's float32 run, not
-        # the tensor, so the rule is handed a tensor with exactly that error: r64 with its largest element moved by e32 max |r64|
-        r64_t = torch.as_tensor(r64)
-        r32_t = r64_t.clone()
-        r32_t.view(-1)[r64_t.abs().argmax()] += e32['grad/' + name] * r64_t.abs().max()
-        bound, e, _ = TR.end_to_end_bound(r64_t, r32_t, torch.as_tensor(absjac[name]))
-        assert abs(e - e32['grad/' + name]) <= 1e-6 * e32['grad/' + name] + 1e-300
-        out[name] = (r64, bound.numpy())
-    return out
-
-
-def _check_step(key, step):
-    arrays, meta = CT.load_case(key)
-    rec, pre = meta['steps'][step - 1], 's%d/' % step
-    e32 = rec['e32']
-    # ---- embeddings, on a model of their own (a training-mode forward moves the running statistics)
-    probe = _model(key, step)
-    data = CT.train_data(key, step, DEV)
-    txt, vis = probe.txt_net(data['captions']), probe.vis_net(data['vis_feats'])
-    assert txt.requires_grad and vis.requires_grad and txt.dim() == vis.dim() == 2
-    for name, got in (('txt_emb', txt), ('vis_emb', vis)):
-        err, bound = rel_err(got.detach().cpu(), arrays[pre + name]), max(4.0 * e32[name], TR.TOL_UNIT)
-        print('case %s step %d %-8s device %.2e  reference fp32 %.2e  bound %.2e' % (key, step, name, err, e32[name], bound))
-        assert err <= bound, (name, err, bound)
-    # ---- loss and raw gradients: cal_foward + backward
-    model = _model(key, step)
-    loss, items = model.cal_foward(CT.train_data(key, step, DEV))
-    loss.backward()
-    torch.cuda.synchronize()
-    bound = max(4.0 * e32['loss'], TR.TOL_UNIT) * abs(rec['loss'])
-    print('case %s step %d loss     device %.9g  float64 %.9g  bound %.2e' % (key, step, float(loss.detach()), rec['loss'], bound))
-    assert abs(float(loss.detach()) - rec['loss']) <= bound
-    grads = {k: p.grad for k, p in model.named_parameters()}
-    assert all(g is not None for g in grads.values()) and sorted(grads) == sorted(sub(arrays, pre + 'grad/'))
-    worst = 0.0
-    for name, (r64, b) in _grad_bounds(key, step).items():
-        err = np.abs(grads[name].cpu().double().numpy() - r64)
-        worst = max(worst, float((err / b).max()))
-        assert np.all(err <= b), (name, float((err / b).max()))
-    print('case %s step %d: %d gradients, worst err / bound %.3f' % (key, step, len(grads), worst))
-    # ---- the step itself, on a fresh model: optim_ref on the device's own gradients, the bounds of test_gpu_optim.py
-    stepped = _model(key, step)
-    params = dict(stepped.named_parameters())
-    names = sorted(params)
-    before = {k: p.detach().cpu().double().numpy().copy() for k, p in params.items()}
-    old = {n: [stepped.optimizer.state[params[k]][n].cpu().double().numpy().copy() if params[k] in stepped.optimizer.state
-               else np.zeros_like(before[k]) for k in names] for n in _state_names(meta)}
-    items = stepped(CT.train_data(key, step, DEV))
-    torch.cuda.synchronize()
-    assert stepped.iters == 1 and float(items['triplet_loss'].detach()) == float(loss.detach())
-    assert all(torch.equal(params[k].grad, grads[k]) for k in names)
-    g_own = [params[k].grad.cpu().double().numpy() for k in names]
-    norm = optim_ref.total_norm(g_own)
-    total = float(stepped.optimizer.total_norm)
-    assert abs(total - norm) <= 2.0 ** -23 * norm
-    # | |g| - |g64| | <= |g - g64| <= sqrt(sum of the squared element bounds), plus TOL_UNIT |g64| for the sum itself
-    tol = float(np.sqrt(sum(float((b * b).sum()) for _, b in _grad_bounds(key, step).values()))) + TR.TOL_UNIT * rec['total_norm']
-    assert abs(total - rec['total_norm']) <= tol, (total, rec['total_norm'], tol)
-    c = optim_ref.clip_coef(norm, meta['grad_clip'])
-    p0 = [before[k] for k in names]
-    G = optim_ref.gmag(p0, g_own, c, 0.0)
-    new = {n: [stepped.optimizer.state[params[k]][n].cpu().numpy() for k in names] for n in _state_names(meta)}
-    p_dev = [params[k].detach().cpu().numpy() for k in names]
-    lr, eps = meta['lr'], meta['eps']
-    if meta['optimizer'] == 'rmsprop':
-        _, s_ref = optim_ref.rmsprop(p0, g_own, old['square_avg'], lr, meta['alpha'], eps, 0.0, c)
-        checks = [('square_avg', new['square_avg'], s_ref, optim_ref.bound_v(old['square_avg'], G, meta['alpha']))]
-        p_ref = optim_ref.rmsprop_param(p0, optim_ref.clipped(g_own, c), new['square_avg'], lr, eps)
-        checks.append(('parameter', p_dev, p_ref, optim_ref.bound_p_rmsprop(p_ref, G, new['square_avg'], lr, eps)))
-    else:
-        b1, b2 = meta['betas']
-        t = step                                           # the fixture's optimizer is at step 1 before step 2
-        _, m_ref, v_ref = optim_ref.adam(p0, g_own, old['exp_avg'], old['exp_avg_sq'], lr, b1, b2, eps, 0.0, t, c)
-        checks = [('exp_avg', new['exp_avg'], m_ref, optim_ref.bound_m(old['exp_avg'], G, b1)),
-                  ('exp_avg_sq', new['exp_avg_sq'], v_ref, optim_ref.bound_v(old['exp_avg_sq'], G, b2))]
-        p_ref = optim_ref.adam_param(p0, new['exp_avg'], new['exp_avg_sq'], lr, b1, b2, eps, t)
-        checks.append(('parameter', p_dev, p_ref, optim_ref.bound_p_adam(p_ref, new['exp_avg'], new['exp_avg_sq'], lr, b1, b2, eps, t)))
-    for what, dev, ref, bounds in checks:
-        for k, a, r, bd in zip(names, dev, ref, bounds):
-            assert np.all(np.abs(a.astype(np.float64) - r) <= bd), (what, k)
-    assert any(not np.array_equal(a.astype(np.float64), before[k]) for k, a in zip(names, p_dev))
-    # ---- BatchNorm statistics after the step
-    g64, _, g32 = _refs(key, step)
-    sd_before, sd_after, sd_dev = _state_before(key, step), sub(arrays, pre + 'sd/'), stepped.state_dict()
-    for prefix, (m64, v64) in g64['stats'].items():
-        bn = prefix + 'bn1.'
-        m32, v32 = g32['stats'][prefix]
-        for stat, s32 in (('running_mean', m32), ('running_var', v32)):
-            prev = torch.as_tensor(sd_before[bn + stat]).double()
-            want = torch.as_tensor(sd_after[bn + stat]).double()
-            bound = max(4.0 * rel_err(0.9 * prev + 0.1 * s32.double(), want), TR.TOL_UNIT)
-            err = rel_err(sd_dev[bn + stat].cpu(), want)
-            assert err <= bound, (bn + stat, err, bound)
-        assert int(sd_dev[bn + 'num_batches_tracked']) == int(sd_after[bn + 'num_batches_tracked'])
-    return stepped
-
-
-@pytest.mark.parametrize('key', CT.CASES)
+@pytest.mark.parametrize('key', tower_ref.CONCAT_CASES)
 def test_step_one_against_the_fixture(key):
-    _check_step(key, 1)
+    SC.check_step(key, 1)
 
 
-@pytest.mark.parametrize('key', CT.CASES)
+@pytest.mark.parametrize('key', tower_ref.CONCAT_CASES)
 def test_teacher_forced_step_two(key):
     """From the fixture's parameters and optimizer state after step 1 (rounded to fp32), on the step-2 inputs."""
-    _check_step(key, 2)
+    SC.check_step(key, 2)
 
 
-@pytest.mark.parametrize('key', CT.CASES)
+@pytest.mark.parametrize('key', tower_ref.CONCAT_CASES)
 def test_back_to_inference_after_a_step(key):
     """After one step and .eval() the embeddings change and are, bit for bit, those of a fresh model loaded with this one's
     state_dict(): no stale weight_t_block or bn_affine survives the step; eval mode runs the one-launch forward as before."""
-    from laff_amd.model.model import get_model
-    arrays, meta = CT.load_case(key)
-    model = _model(key)
-    with torch.no_grad():                                  # fill the eval-mode caches first
-        model.eval()
-        data = CT.train_data(key, 2, DEV)
-        stale_t, stale_v = model.txt_net(data['captions']), model.vis_net(data['vis_feats'])
-        model.train()
-    model(CT.train_data(key, 1, DEV))
-    model.eval()
-    fresh = get_model(meta['model'], DEV, CT.make_cfg(meta)).eval()
-    fresh.load_state_dict(model.state_dict())
-    with torch.no_grad():
-        got = [model.txt_net(CT.train_data(key, 2, DEV)['captions']), model.vis_net(CT.train_data(key, 2, DEV)['vis_feats'])]
-        want = [fresh.txt_net(CT.train_data(key, 2, DEV)['captions']), fresh.vis_net(CT.train_data(key, 2, DEV)['vis_feats'])]
-    assert not got[0].requires_grad and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-    assert not torch.equal(got[0], stale_t) and not torch.equal(got[1], stale_v)
+    SC.back_to_inference_after_a_step(key)
 
 
 def test_step_refusals_on_the_device():
     from laff_amd.model.model import get_model
-    _, meta = CT.load_case('i')
+    _, meta = tower_ref.load_case('i')
     with pytest.raises(NotImplementedError, match="key 'LAFF' with the concat towers"):
-        get_model('LAFF', DEV, CT.make_cfg(dict(meta, model='LAFF'))).enable_training()
+        get_model('LAFF', DEV, tower_ref.make_cfg(dict(meta, model='LAFF'))).enable_training()
     for field, value, text in (('negative', True, 'opt.negative'), ('multi_space', False, 'multi_space=False')):
         with pytest.raises(NotImplementedError, match=text):
-            CT.device_model('i', DEV, **{field: value}).enable_training()
+            tower_ref.device_model('i', DEV, **{field: value}).enable_training()
     # the per-head Adam keeps its eps where the towers are not concat: nothing changes for the models that trained before
-    import tower_ref
     assert tower_ref.device_model('a', DEV, optimizer='adam').enable_training().optimizer.param_groups[0]['eps'] == 1e-4
 
 

@@ -1,38 +1,63 @@
-"""The 'LAFF' model's training graph restated as a CPU torch graph in float64 or float32, built from a case of the training-step fixture
-(tests/golden/train_step.<case>.<n>.npz, tools/gen_golden_train.py) -- its config and a state dict: both towers (TransformNet layers in
-training mode, the tiled no-transform feature, the expert stage, the multi-head attention through fuse_ref.attention) and the per-head
-margin ranking loss with max_violation and direction.  In the style of train_ref.Side / side_f64; it gives the device tests the
+"""The training graph of a model that trains here, restated as a CPU torch graph in float64 or float32 and built from a case of the
+training-step fixture (tools/gen_golden_train.py) -- its config and a state dict.  Cases a-e (tests/golden/train_step.<case>.<n>.npz)
+are 'LAFF' and 'FrameLAFF': both towers (TransformNet layers in training mode, the tiled no-transform feature, the expert stage, the
+multi-head attention through fuse_ref.attention) and the per-head margin ranking loss with max_violation and direction.  Cases i and
+ii (tests/golden/train_step_w2vvpp.<case>.<n>.npz) are the W2VV++ concat towers: one TransformNet per side over the concatenated
+features and the same loss on 2-D embeddings, one head.  In the style of train_ref.Side / side_f64; it gives the device tests the
 absolute Jacobian of train_ref.end_to_end_bound and the host tests a float64 value for everything the fixture records.
 
-Also here: load_case (the shards of a case as one dict), device_model (this library's model built from a case) and train_data (fresh
-input dicts of a step)."""
+Also here: load_case (the shards of a case as one dict in one layout), replay_steps (tests/optim_ref.py applied to the fixture's own
+gradients), device_model (this library's model built from a case) and train_data (fresh input dicts of a step)."""
 import glob
 import json
 import os
+import re
 
 import numpy as np
 import torch
 
 import fuse_bwd_ref
 import fuse_ref
+import optim_ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 CASES = ('a', 'b', 'c', 'd', 'e')
+CONCAT_CASES = ('i', 'ii')
+STEMS = dict({k: 'train_step' for k in CASES}, **{k: 'train_step_w2vvpp' for k in CONCAT_CASES})
+STATE_NAMES = {'rmsprop': ('square_avg',), 'adam': ('exp_avg', 'exp_avg_sq')}
 L2_EPS = 1e-13 + 1e-14
+REL = 1e-12                               # a float64 restatement against the float64 run of the reference
+rel_err = fuse_bwd_ref.rel_err
 _cache = {}
 
 
+def with_defaults(meta):
+    """The meta of a case with the fields that older fixtures were written without.  The concat cases i and ii carry no H (and
+    nothing else of the attention blocks): that is how an older meta tells which towers it has."""
+    meta.setdefault('attention', 'Multi_head_MyApply_Attention' if 'H' in meta else 'concat')
+    meta.setdefault('H', 1)
+    meta.setdefault('model', 'LAFF')
+    meta.setdefault('betas', [])
+    for rec in meta['steps']:
+        rec.setdefault('none', [])
+    return meta
+
+
 def load_case(key):
-    """({array name: array} over every shard of the case, its meta dict).  Cached: the arrays are shared and must stay unchanged."""
+    """({array name: array} over the file or the shards of the case, its meta dict), the optimizer state under
+    s<n>/state/<state name>/<param> whatever is on disk.  Cached: the arrays are shared and must stay unchanged."""
     if key not in _cache:
         arrays = {}
-        paths = sorted(glob.glob(os.path.join(GOLDEN, 'train_step.%s.*.npz' % key)))
-        assert paths, 'no fixture shards for case %s' % key
+        stem = os.path.join(GOLDEN, '%s.%s' % (STEMS[key], key))
+        paths = sorted(glob.glob(stem + '.npz') + glob.glob(stem + '.*.npz'))
+        assert paths, 'no fixture for case %s' % key
         for p in paths:
             with np.load(p) as z:
                 for k in z.files:
-                    arrays[k] = z[k]
-        meta = json.loads(str(arrays.pop('meta')))
+                    # the committed cases a-e predate the common layout and keep RMSprop's state as s<n>/sq/<param>; a regenerated
+                    # case no longer needs the rename
+                    arrays[re.sub(r'^(s\d+)/sq/', r'\1/state/square_avg/', k)] = z[k]
+        meta = with_defaults(json.loads(str(arrays.pop('meta'))))
         _cache[key] = (arrays, meta)
     return _cache[key]
 
@@ -115,16 +140,22 @@ def _frame_vector(P, name, frames, mask, meta, dtype):
 
 def side_embedding(meta, P, side, inputs, dtype=torch.float64, stats=None, head=None):
     """One tower's embedding (N, H, d) -- or, with head, that head's (N, 1, d) from a graph that holds the head's columns only -- on
-    inputs = (vis {feature: array}, txt {key: array}, frames {frame feature: (B, Fmax, d), 'mask_tensor': (B, Fmax)} or None)."""
+    inputs = (vis {feature: array}, txt {key: array}, frames {frame feature: (B, Fmax, d), 'mask_tensor': (B, Fmax)} or None).
+    A concat tower's is (N, D): one TransformNet over the concatenated features."""
     vis, txt, frames = inputs
     H, stats = meta['H'], {} if stats is None else stats
     cols = None if head is None else slice(head * (meta['D'] // H), (head + 1) * (meta['D'] // H))
     t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)        # noqa: E731
+    if meta['attention'] == 'concat':
+        assert head is None
+        if side == 'txt':
+            return _transform(P, 'txt_net.transformer.', torch.cat([t(txt[TXT_KEYS[n]]) for n in meta['encoder_name_list']], 1), 1, stats)
+        return _transform(P, 'vis_net.', torch.cat([t(vis[n]) for n in meta['vid_dims']], 1), 1, stats)
     if side == 'txt':
         planes = [_transform(P, 'txt_net.transform_layer.%s_transform.' % name, t(txt[TXT_KEYS[name]]), H, stats, cols)
                   for name in meta['encoder_name_list']]
         return _fusion(P, 'txt_net.', planes, meta, dtype, head=head)
-    if meta.get('model', 'LAFF') == 'FrameLAFF':
+    if meta['model'] == 'FrameLAFF':
         feats = {name: t(vis[name]) for name in meta['vid_dims']}
         for name in meta['frame_feats']:
             feats[name] = _frame_vector(P, name, t(frames[name]), t(frames['mask_tensor']), meta, dtype)
@@ -142,7 +173,10 @@ def embeddings(meta, P, vis, txt, dtype=torch.float64, frames=None):
 
 
 def margin_loss(txt_emb, vis_emb, meta):
-    """MarginRankingLoss(margin, 'cosine', max_violation, 'sum', direction)(s = txt, im = vis) per head, summed."""
+    """MarginRankingLoss(margin, 'cosine', max_violation, 'sum', direction)(s = txt, im = vis) per head, summed; 2-D embeddings are
+    one head."""
+    if txt_emb.dim() == 2:
+        txt_emb, vis_emb = txt_emb[:, None], vis_emb[:, None]
     B = txt_emb.shape[0]
     eye = torch.eye(B, dtype=torch.bool)
     total = 0.0
@@ -165,6 +199,11 @@ def leaves_of(sd, dtype=torch.float64):
             if not k.endswith('num_batches_tracked')}
 
 
+def state_before(arrays, step):
+    """The state dict the fixture's float64 run had before `step`."""
+    return sub(arrays, 'sd0/') if step == 1 else sub(arrays, 's%d/sd/' % (step - 1))
+
+
 def step_graph(key, step, dtype=torch.float64, sd=None):
     """The graph of step `step` (1 or 2) of a case from the state the fixture's float64 run had before it (or from `sd`): a dict with the
     leaves P, txt_emb, vis_emb, loss, the BatchNorm batch statistics, and grads {name: d loss / d leaf, None where unreached}."""
@@ -173,9 +212,7 @@ def step_graph(key, step, dtype=torch.float64, sd=None):
 
 def step_graph_of(arrays, meta, step, dtype=torch.float64, sd=None):
     """step_graph on the arrays and meta of a case that is not on disk yet (tools/gen_golden_train.py)."""
-    if sd is None:
-        sd = sub(arrays, 'sd0/') if step == 1 else sub(arrays, 's%d/sd/' % (step - 1))
-    P = leaves_of(sd, dtype)
+    P = leaves_of(state_before(arrays, step) if sd is None else sd, dtype)
     pre = 's%d/in/' % step
     inputs = (sub(arrays, pre + 'vis/'), sub(arrays, pre + 'txt/'), sub(arrays, pre + 'frame/'))
     txt_emb, vis_emb, stats = embeddings(meta, P, inputs[0], inputs[1], dtype, inputs[2])
@@ -195,10 +232,10 @@ def abs_jacobian(graph):
         names = [k for k, g in graph['grads'].items() if g is not None and k.startswith(side + '_net.')]
         leaves = [graph['P'][k] for k in names]
         acc.update({k: torch.zeros_like(v) for k, v in zip(names, leaves)})
-        if meta['l2norm']:
-            parts = [graph[side + '_emb']]
-        else:                                              # ... and a head's with its own columns: H graphs of 1 / H the width, same sums
+        if meta['H'] > 1 and not meta['l2norm']:           # ... and a head's with its own columns: H graphs of 1 / H the width, same sums
             parts = [side_embedding(meta, graph['P'], side, graph['inputs'], graph['dtype'], head=h) for h in range(meta['H'])]
+        else:
+            parts = [graph[side + '_emb']]
         for E in parts:
             E = E.reshape(-1)
             eye = torch.eye(E.numel(), dtype=E.dtype)
@@ -210,27 +247,114 @@ def abs_jacobian(graph):
     return acc
 
 
+# ---- the restatement and the optimizer against what a case records --------------------------------------------------------------------
+BIAS = 'embedding_common.0.bias'          # softmax ignores a shift: the reference's gradient there is rounding noise, ours exact zeros
+
+
+def check_restatement(arrays, meta):
+    """step_graph_of in float64 reproduces both steps of the case to REL: embeddings, loss, which parameters have no gradient, every
+    gradient, and the running statistics the step leaves (momentum 0.1 on the batch's mean and unbiased variance).  Every recorded
+    hinge decision is train_ref.HINGE_CLEAR from flipping."""
+    import train_ref
+    for step in (1, 2):
+        g = step_graph_of(arrays, meta, step)
+        pre, rec = 's%d/' % step, meta['steps'][step - 1]
+        for name in ('txt_emb', 'vis_emb'):
+            e = rel_err(g[name].detach(), arrays[pre + name])
+            print('case %s step %d %-8s %.2e' % (meta['key'], step, name, e))
+            assert e <= REL, (name, e)
+        assert abs(float(g['loss'].detach()) - rec['loss']) <= REL * abs(rec['loss'])
+        assert sorted(k for k, t in g['grads'].items() if t is None) == rec['none']
+        grads = sub(arrays, pre + 'grad/')
+        assert sorted(grads) == sorted(k for k, t in g['grads'].items() if t is not None)
+        worst = 0.0
+        for name, want in grads.items():
+            got = g['grads'][name]
+            if name.endswith(BIAS):
+                assert float(got.abs().max()) <= 1e-12 and float(np.abs(want).max()) <= 1e-12        # noise on both sides, no more
+                continue
+            e = rel_err(got, want)
+            worst = max(worst, e)
+            assert e <= REL, (name, e)
+        print('case %s step %d: %d gradients, worst %.2e' % (meta['key'], step, len(g['grads']), worst))
+        before, after = state_before(arrays, step), sub(arrays, pre + 'sd/')
+        for prefix, (mean, var) in g['stats'].items():
+            bn = prefix + 'bn1.'
+            assert rel_err(0.9 * torch.as_tensor(before[bn + 'running_mean']).double() + 0.1 * mean, after[bn + 'running_mean']) <= REL
+            assert rel_err(0.9 * torch.as_tensor(before[bn + 'running_var']).double() + 0.1 * var, after[bn + 'running_var']) <= REL
+            assert int(after[bn + 'num_batches_tracked']) == step
+        assert rec['slack'] >= train_ref.HINGE_CLEAR
+
+
+def replay_steps(arrays, meta, eps=None):
+    """Both steps of a case through tests/optim_ref.py: clip_grad_norm_(grad_clip), then RMSprop or Adam (meta['optimizer']) with the
+    case's lr, alpha / betas and eps (or `eps`), each step from the fixture's float64 gradients and its parameters and optimizer state
+    before that step.  {(step, 'parameter' or a state name, param): rel_err from what the fixture holds after the step}.  Asserted on
+    the way: the recorded total norm, the optimizer's step count, that the parameters without a gradient are the recorded ones and
+    stay as they were, and that every stepped parameter has its state."""
+    out = {}
+    eps = meta['eps'] if eps is None else eps
+    for step in (1, 2):
+        pre, rec = 's%d/' % step, meta['steps'][step - 1]
+        grads, before, prev = sub(arrays, pre + 'grad/'), state_before(arrays, step), sub(arrays, 's%d/state/' % (step - 1))
+        after, state = sub(arrays, pre + 'sd/'), sub(arrays, pre + 'state/')
+        names = sorted(grads)
+        assert sorted(set(param_names(before)) - set(names)) == rec['none'] and rec['opt_step'] == step
+        g, p0 = [grads[k] for k in names], [before[k] for k in names]
+        total = optim_ref.total_norm(g)
+        assert abs(total - rec['total_norm']) <= REL * total
+        c = optim_ref.clip_coef(total, meta['grad_clip'])
+        old = {n: [prev.get(n + '/' + k, np.zeros_like(grads[k])) for k in names] for n in STATE_NAMES[meta['optimizer']]}
+        if meta['optimizer'] == 'rmsprop':
+            new = dict(zip(('parameter', 'square_avg'), optim_ref.rmsprop(p0, g, old['square_avg'], meta['lr'], meta['alpha'], eps, 0.0, c)))
+        else:
+            new = dict(zip(('parameter', 'exp_avg', 'exp_avg_sq'), optim_ref.adam(p0, g, old['exp_avg'], old['exp_avg_sq'], meta['lr'],
+                                                                                  *meta['betas'], eps, 0.0, step, c)))
+        assert sorted(state) == sorted(n + '/' + k for n in STATE_NAMES[meta['optimizer']] for k in names)
+        for what, values in new.items():
+            for k, v in zip(names, values):
+                out[step, what, k] = rel_err(v, after[k] if what == 'parameter' else state[what + '/' + k])
+        for k in rec['none']:
+            assert np.array_equal(after[k], before[k])     # no gradient: the step leaves them alone
+    return out
+
+
+def check_replay(arrays, meta):
+    """replay_steps reproduces the case's parameters and optimizer state after both steps to REL: clip coefficient, eps, alpha / betas
+    and the learning rate are the reference's."""
+    for (step, what, k), e in replay_steps(arrays, meta).items():
+        if what == 'square_avg' and k.endswith(BIAS):
+            # the gradient there is rounding noise (1e-19 in float64) and differs from run to run: its square is no more than noise either,
+            # and moves nothing (eps = 1e-8)
+            assert float(np.abs(arrays['s%d/state/%s/%s' % (step, what, k)]).max()) <= 1e-30
+        else:
+            assert e <= REL, (step, what, k, e)
+
+
 # ---- this library's model built from a case -----------------------------------------------------------------------------------------
 def make_cfg(meta, **overrides):
     from laff_amd.config import make_config
-    e = {'expert': meta['expert'], 'l2norm': meta['l2norm']}
-    kw = dict(vis_no_transform=meta['vis_no_transform'], txt_no_transform=meta['txt_no_transform'], batch_norm=meta['batch_norm'],
-              with_ave=meta['with_ave'], mul=meta['mul'], dropout=meta['dropout'], vis_expert_embedding=dict(e), txt_expert_embedding=dict(e),
-              max_violation=meta['max_violation'], direction=meta['direction'], margin=meta['margin'], loss=meta['loss'],
-              optimizer=meta['optimizer'], lr=meta['lr'], grad_clip=meta['grad_clip'])
-    if meta.get('model', 'LAFF') == 'FrameLAFF':
+    kw = dict(batch_norm=meta['batch_norm'], dropout=meta['dropout'], max_violation=meta['max_violation'], direction=meta['direction'],
+              margin=meta['margin'], loss=meta['loss'], optimizer=meta['optimizer'], lr=meta['lr'], grad_clip=meta['grad_clip'])
+    if meta['attention'] == 'concat':
+        kw.update(txt_attention='concat', vis_attention='concat')
+    else:
+        e = {'expert': meta['expert'], 'l2norm': meta['l2norm']}
+        kw.update(vis_no_transform=meta['vis_no_transform'], txt_no_transform=meta['txt_no_transform'], with_ave=meta['with_ave'],
+                  mul=meta['mul'], vis_expert_embedding=dict(e), txt_expert_embedding=dict(e))
+    if meta['model'] == 'FrameLAFF':
         kw.update(vis_frame_attention=meta['vis_frame_attention'], vis_frame_addFC=False, frame_feat_with_video_feat=True,
                   max_frame=meta['max_frame'], frame_feats=meta['frame_feats'])
     kw.update(overrides)
-    return make_config(meta['vid_dims'], meta['txt_dims'], meta['D'], meta['H'], meta.get('model', 'LAFF'), **kw)
+    return make_config(meta['vid_dims'], meta['txt_dims'], meta['D'], meta['H'], meta['model'], **kw)
 
 
 def device_model(key, device='cuda', sd=None, **overrides):
-    """get_model('LAFF') from the case's config with the fixture's initial state (or `sd`, float64 arrays are rounded to fp32) loaded,
-    in training mode."""
+    """get_model(the case's registry key) from the case's config with the fixture's initial state (or `sd`, float64 arrays are rounded
+    to fp32) loaded, in training mode."""
     from laff_amd.model.model import get_model
     arrays, meta = load_case(key)
-    model = get_model(meta.get('model', 'LAFF'), device, make_cfg(meta, **overrides))
+    model = get_model(meta['model'], device, make_cfg(meta, **overrides))
     sd = sub(arrays, 'sd0/') if sd is None else sd
     own = model.state_dict()
     state = {k: torch.as_tensor(np.asarray(v)).to(own[k].dtype) for k, v in sd.items()}
