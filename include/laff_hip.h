@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAFF_ABI_VERSION 46
+#define LAFF_ABI_VERSION 47
 
 enum {
     LAFF_OK = 0,
@@ -577,6 +577,47 @@ int laff_fuse_backward(laff_ctx* ctx, const float* const* x /*host array of L de
                        unsigned flags /*LAFF_ATT_*/, const float* dE /*[N, lde >= H*d]*/, int lde,
                        float* const* dx /*host array of L device pointers*/, const int* lddx /*host, L pitches*/,
                        float* dw /*[H,d], nullable*/, float* db /*[H], nullable*/, void* workspace, size_t workspace_bytes);
+
+/* ---- multi-head self-attention fusion (Multi_head_MyApply_selfAttention, model/Attention.py:317-470) ------------------------- */
+/* the token list of a group (row n, head h): the L planes' head slices, optionally with one token in front (T = L + 1) */
+enum { LAFF_SA_PREPEND_NONE = 0, LAFF_SA_PREPEND_MAX = 1 /* elementwise max over l */, LAFF_SA_PREPEND_MEAN = 2 /* mean over l */ };
+/* what is returned of the T outputs o_i */
+enum {
+    LAFF_SA_POOL_MEAN = 0,   /* mean over i */
+    LAFF_SA_POOL_MAX = 1,    /* elementwise max over i */
+    LAFF_SA_POOL_TOKEN = 2,  /* o_token, 0 <= token < T: first / last / second / third and the prepending types */
+    LAFF_SA_POOL_ALL = 3     /* every o_i, a stacked (N, L, H*d) tensor (the Attention_1 output type); no prepended token */
+};
+
+/* The block over PLAIN DENSE planes, fp32.  x: HOST array of L device pointers with row pitches ldx (elements): plane l holds
+ * x_l[n, h*d + c], so the slices of a stacked (N, L, H*d) tensor are read in place.  Per group (n, h), with the tokens u_i of the
+ * `prepend` rule:
+ *   t_i = u_i / (|u_i| + 1e-13 + 1e-14)  with LAFF_ATT_L2NORM_EACH_HEAD (the only flag read), else u_i
+ *   A = softmax_j(s t_i . t_j),  s = (d / H) ^ -0.5 with the INTEGER quotient (Attention.py:402), so d >= H
+ *   r_i = sum_j A_ij t_j + t_i;   o_i = gamma (.) (r_i - mean r_i) / sqrt(var r_i + 1e-5) + beta   (biased variance; gamma, beta [d]
+ *   are shared by all heads)
+ * and E [N, lde >= H*d] receives the pooled rows, or, with LAFF_SA_POOL_ALL, O receives o_l at O[n * ldon + l * ldol + h*d + c].
+ * Maxima (LAFF_SA_PREPEND_MAX, LAFF_SA_POOL_MAX): the LOWEST index wins a tie -- a `>` comparison in ascending index; the backward
+ * routes the gradient to that index.
+ * Backward: recomputes the forward from the planes (nothing else is saved); dE [N, lde] is the gradient of E, or dO that of O in the
+ * same stacked layout.  Writes
+ *   dx_l [N, lddx_l]    the gradient of every plane, always (through the prepended token and the normalisation as well);
+ *   dgamma, dbeta [d]   each on request (NULL: not formed): a deterministic two-stage sum over rows and heads through the workspace.
+ * No atomics: two calls give the same bits.  No allocation, no host synchronisation; ordered on the ctx's stream, capturable.
+ * workspace: caller-owned device scratch of out[0] bytes of laff_selfattn_fuse_backward_plan, 16-byte aligned, only used when dgamma
+ * or dbeta is given.  laff_selfattn_fuse_backward_plan (host only, no ctx): out = {workspace bytes, partial rows = blocks of the launch}.
+ * Limits: 1 <= L <= 8, d % 4 == 0, 4 <= d <= 512, H >= 1, H*d <= 8192, d >= H, 16-byte aligned bases, pitches % 4 == 0.  N == 0
+ * touches nothing, except zeros to dgamma / dbeta when they are given. */
+int laff_selfattn_fuse_backward_plan(int N, int H, int d, int out[2]);
+int laff_selfattn_fuse(laff_ctx* ctx, const float* const* x /*host array of L device pointers*/, const int* ldx /*host, L row pitches*/,
+                       int L, int N, int H, int d, const float* gamma /*[d]*/, const float* beta /*[d]*/, int prepend /*LAFF_SA_PREPEND_*/,
+                       int pool /*LAFF_SA_POOL_*/, int token, unsigned flags, float* E /*[N, lde], pooled*/, int lde,
+                       float* O /*stacked, LAFF_SA_POOL_ALL*/, int ldon, int ldol);
+int laff_selfattn_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int L, int N, int H, int d, const float* gamma,
+                                const float* beta, int prepend, int pool, int token, unsigned flags, const float* dE, int lde,
+                                const float* dO, int ldon, int ldol, float* const* dx /*host array of L device pointers*/,
+                                const int* lddx /*host, L pitches*/, float* dgamma /*[d], nullable*/, float* dbeta /*[d], nullable*/,
+                                void* workspace, size_t workspace_bytes);
 
 /* Backward of the FC projection A = act(X W^T + bias), the forward laff_fc_act_bn computes without a BatchNorm stage; fp32 MFMA.
  * X [N, ldx >= Dk], W [D, ldw >= Dk], A [N, lda >= D] the SAVED forward output, dA [N, ldda >= D] its gradient.  With

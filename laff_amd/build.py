@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'liblaff_hip.so')
-SOURCES = ['gemm_nt.hip', 'sim_strip.hip', 'fc_strip.hip', 'fc_strip16.hip', 'fc_concat.hip', 'fuse.hip', 'fuse_bwd.hip', 'frame_bwd.hip', 'fc_bwd.hip', 'fc_gather_bwd.hip', 'fc_concat_bwd.hip', 'bn_train.hip', 'tile_bn_train.hip', 'expert_train.hip', 'optim.hip', 'rank.hip', 'loss.hip', 'loss_dsl.hip', 'gru.hip', 'gru_bwd.hip', 'clip.hip', 'clip_image.hip', 'frame_prep.hip', 'bert.hip', 'netvlad.hip', 'netvlad_bwd.hip', 'batch_assemble.hip', 'rerank.hip', 'sim_hist.hip', 'comm.hip', 'api.hip']
+SOURCES = ['gemm_nt.hip', 'sim_strip.hip', 'fc_strip.hip', 'fc_strip16.hip', 'fc_concat.hip', 'fuse.hip', 'fuse_bwd.hip', 'selfattn_fuse.hip', 'frame_bwd.hip', 'fc_bwd.hip', 'fc_gather_bwd.hip', 'fc_concat_bwd.hip', 'bn_train.hip', 'tile_bn_train.hip', 'expert_train.hip', 'optim.hip', 'rank.hip', 'loss.hip', 'loss_dsl.hip', 'gru.hip', 'gru_bwd.hip', 'clip.hip', 'clip_image.hip', 'frame_prep.hip', 'bert.hip', 'netvlad.hip', 'netvlad_bwd.hip', 'batch_assemble.hip', 'rerank.hip', 'sim_hist.hip', 'comm.hip', 'api.hip']
 HEADERS = [os.path.join(CSRC, 'kernels.h'), os.path.join(CSRC, 'clip_core.h'), os.path.join(CSRC, 'exact_cos.h'), os.path.join(CSRC, 'strip_util.h'), os.path.join(CSRC, 'fc_strip_common.h'), os.path.join(CSRC, 'wave_reduce.h'), os.path.join(CSRC, 'attn_common.h'), os.path.join(CSRC, 'fc_bwd_common.h'), os.path.join(CSRC, 'fc_bwd_tile.h'), os.path.join(CSRC, 'bn_train_common.h'), os.path.join(os.path.dirname(HERE), 'include', 'laff_hip.h')]
 ARCH = 'gfx950'
 FLAGS = ['-O3', '-std=c++20', '-fPIC', '--offload-arch=' + ARCH, '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']

@@ -50,6 +50,7 @@ class config(object):
     txt_fc_same_with_vis_fc = False
     multi_head_attention = {'dropout': 0.0, 'heads': 8, 'embed_dim_qkv': 512}
     attention_param_each_head = {'with_ave': False, 'mul': False, 'split_head': True}
+    my_self_attention_output_type = 'mean'          # configs/base_config.py:133-136 of the reference
     txt_attention_global_decay_rate = 0.8
     vis_attention_global_decay_rate = 0.8
     vid_feats = []

@@ -2161,6 +2161,115 @@ int laff_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int
     return LAFF_OK;
 }
 
+// the shape and mode of laff_selfattn_fuse, its backward and the plan: plain integers, checked before anything else
+static int selfattn_shape(const char* fn, int N, int H, int d) {
+    if (N < 0 || H < 1) return fail(LAFF_E_SHAPE, "%s: need N>=0, H>=1 (N=%d H=%d)", fn, N, H);
+    if (d < 4 || d > 512 || (d & 3)) return fail(LAFF_E_SHAPE, "%s: d=%d per head outside [4,512] or not a multiple of 4", fn, d);
+    if ((long long)H * d > 8192) return fail(LAFF_E_SHAPE, "%s: H * d = %lld columns (at most 8192)", fn, (long long)H * d);
+    if (d < H) return fail(LAFF_E_SHAPE, "%s: d=%d < H=%d: the scale (d / H) ^ -0.5 divides by zero", fn, d, H);
+    if ((long long)N * H > INT_MAX) return fail(LAFF_E_SHAPE, "%s: N * H = %lld groups", fn, (long long)N * H);
+    return LAFF_OK;
+}
+
+// everything of the two launches but the ctx: fills `a`.  g: E / dE (pooled) and S: O / dO (stacked) are the output of the forward and
+// the incoming gradient of the backward.
+static int selfattn_check(const char* fn, const float* const* x, const int* ldx, int L, int N, int H, int d, const float* gamma,
+                          const float* beta, int prepend, int pool, int token, unsigned flags, const float* g, int lde, const float* S,
+                          int ldon, int ldol, const char* gname, const char* sname, laff::SelfAttnArgs& a) {
+    if (L < 1 || L > laff::MAX_L) return fail(LAFF_E_SHAPE, "%s: L=%d outside [1,%d]", fn, L, laff::MAX_L);
+    if (int rc = selfattn_shape(fn, N, H, d)) return rc;
+    if (flags & ~(unsigned)LAFF_ATT_L2NORM_EACH_HEAD) return fail(LAFF_E_ARG, "%s: unknown flags 0x%x", fn, flags);
+    if (prepend < LAFF_SA_PREPEND_NONE || prepend > LAFF_SA_PREPEND_MEAN) return fail(LAFF_E_ARG, "%s: unknown prepend %d", fn, prepend);
+    if (pool < LAFF_SA_POOL_MEAN || pool > LAFF_SA_POOL_ALL) return fail(LAFF_E_ARG, "%s: unknown pool %d", fn, pool);
+    const int T = L + (prepend != LAFF_SA_PREPEND_NONE);
+    if (pool == LAFF_SA_POOL_TOKEN && (token < 0 || token >= T)) return fail(LAFF_E_ARG, "%s: token=%d outside [0,%d)", fn, token, T);
+    if (pool == LAFF_SA_POOL_ALL && prepend != LAFF_SA_PREPEND_NONE)
+        return fail(LAFF_E_ARG, "%s: LAFF_SA_POOL_ALL returns the L planes' tokens: no prepended token", fn);
+    a.L = L; a.N = N; a.H = H; a.d = d; a.prepend = prepend; a.pool = pool; a.token = pool == LAFF_SA_POOL_TOKEN ? token : 0;
+    a.l2n = (flags & LAFF_ATT_L2NORM_EACH_HEAD) != 0;
+    a.scale = 1.0f / sqrtf((float)(d / H));
+    a.gamma = gamma; a.beta = beta; a.lde = lde; a.ldon = ldon; a.ldol = ldol;
+    if (N == 0) return LAFF_OK;                 /* empty problem: pointers may be null */
+    const int D = H * d;
+    if (!x || !ldx || !gamma || !beta) return fail(LAFF_E_ARG, "%s: null x / ldx / gamma / beta", fn);
+    if (!aligned16(gamma) || !aligned16(beta)) return fail(LAFF_E_ALIGN, "%s: gamma / beta must be 16-byte aligned", fn);
+    for (int l = 0; l < L; ++l) {
+        if (!x[l]) return fail(LAFF_E_ARG, "%s: plane %d is null", fn, l);
+        if (ldx[l] < D || (ldx[l] & 3)) return fail(LAFF_E_SHAPE, "%s: plane %d ldx=%d (need >= %d, a multiple of 4)", fn, l, ldx[l], D);
+        if (!aligned16(x[l])) return fail(LAFF_E_ALIGN, "%s: plane %d not 16-byte aligned", fn, l);
+        a.x[l] = x[l]; a.ldx[l] = ldx[l];
+    }
+    if (pool == LAFF_SA_POOL_ALL) {
+        if (!S) return fail(LAFF_E_ARG, "%s: null %s", fn, sname);
+        const long long ln = ldon, ll = ldol;
+        if (ldon < D || ldol < D || ((N - 1) * ln + D > ll && (L - 1) * ll + D > ln && N > 1 && L > 1))
+            return fail(LAFF_E_SHAPE, "%s: the pitches of %s (row %d, plane %d) do not hold [N=%d, L=%d, H*d=%d] without overlap", fn, sname,
+                        ldon, ldol, N, L, D);
+        if ((ldon & 3) || (ldol & 3) || !aligned16(S))
+            return fail(LAFF_E_ALIGN, "%s: the rows of %s must be 16-byte aligned (base, row pitch %d, plane pitch %d)", fn, sname, ldon, ldol);
+    } else {
+        if (!g) return fail(LAFF_E_ARG, "%s: null %s", fn, gname);
+        if (lde < D || (lde & 3)) return fail(LAFF_E_SHAPE, "%s: lde=%d (need >= %d, a multiple of 4)", fn, lde, D);
+        if (!aligned16(g)) return fail(LAFF_E_ALIGN, "%s: %s must be 16-byte aligned", fn, gname);
+    }
+    return LAFF_OK;
+}
+
+int laff_selfattn_fuse_backward_plan(int N, int H, int d, int out[2]) {
+    const char* fn = "laff_selfattn_fuse_backward_plan";
+    if (!out) return fail(LAFF_E_ARG, "%s: null out", fn);
+    if (int rc = selfattn_shape(fn, N, H, d)) return rc;
+    int R = 0, P = 0;
+    laff::selfattn_plan(N, H, &R, &P);
+    out[0] = N ? P * 2 * d * (int)sizeof(float) : 0;
+    out[1] = N ? P : 0;
+    return LAFF_OK;
+}
+
+int laff_selfattn_fuse(laff_ctx* ctx, const float* const* x, const int* ldx, int L, int N, int H, int d, const float* gamma,
+                       const float* beta, int prepend, int pool, int token, unsigned flags, float* E, int lde, float* O, int ldon,
+                       int ldol) {
+    const char* fn = "laff_selfattn_fuse";
+    laff::SelfAttnArgs a{};
+    if (int rc = selfattn_check(fn, x, ldx, L, N, H, d, gamma, beta, prepend, pool, token, flags, E, lde, O, ldon, ldol, "E", "O", a)) return rc;
+    CHECK_CTX(ctx);
+    if (N == 0) return LAFF_OK;
+    a.E = E; a.O = O;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_selfattn_fuse(a, ctx->stream));
+    return LAFF_OK;
+}
+
+int laff_selfattn_fuse_backward(laff_ctx* ctx, const float* const* x, const int* ldx, int L, int N, int H, int d, const float* gamma,
+                                const float* beta, int prepend, int pool, int token, unsigned flags, const float* dE, int lde,
+                                const float* dO, int ldon, int ldol, float* const* dx, const int* lddx, float* dgamma, float* dbeta,
+                                void* workspace, size_t workspace_bytes) {
+    const char* fn = "laff_selfattn_fuse_backward";
+    laff::SelfAttnArgs a{};
+    if (int rc = selfattn_check(fn, x, ldx, L, N, H, d, gamma, beta, prepend, pool, token, flags, dE, lde, dO, ldon, ldol, "dE", "dO", a))
+        return rc;
+    if (N > 0 && (!dx || !lddx)) return fail(LAFF_E_ARG, "%s: null dx / lddx", fn);
+    for (int l = 0; l < L && N > 0; ++l) {
+        if (!dx[l]) return fail(LAFF_E_ARG, "%s: plane %d has a null dx", fn, l);
+        if (lddx[l] < H * d || (lddx[l] & 3)) return fail(LAFF_E_SHAPE, "%s: plane %d lddx=%d (need >= %d, a multiple of 4)", fn, l, lddx[l], H * d);
+        if (!aligned16(dx[l])) return fail(LAFF_E_ALIGN, "%s: dx of plane %d not 16-byte aligned", fn, l);
+        a.dx[l] = dx[l]; a.lddx[l] = lddx[l];
+    }
+    if ((dgamma && !aligned16(dgamma)) || (dbeta && !aligned16(dbeta))) return fail(LAFF_E_ALIGN, "%s: dgamma / dbeta must be 16-byte aligned", fn);
+    if ((dgamma || dbeta) && N > 0) {
+        int R = 0, P = 0;
+        laff::selfattn_plan(N, H, &R, &P);
+        if (int rc = need_workspace(fn, workspace, workspace_bytes, (size_t)P * 2 * d * sizeof(float))) return rc;
+        a.part = (float*)workspace;
+    }
+    CHECK_CTX(ctx);
+    if (N == 0 && !dgamma && !dbeta) return LAFF_OK;
+    a.dE = dE; a.dO = dO;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(laff::launch_selfattn_fuse_backward(a, dgamma, dbeta, ctx->stream));
+    return LAFF_OK;
+}
+
 static int fc_backward_shape(const char* fn, int N, int Dk, int D) {
     if (N < 0 || Dk < 1 || D < 1) return fail(LAFF_E_SHAPE, "%s: need N>=0, Dk>=1, D>=1 (N=%d Dk=%d D=%d)", fn, N, Dk, D);
     return LAFF_OK;

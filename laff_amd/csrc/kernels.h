@@ -247,6 +247,31 @@ struct FuseBwdArgs {
 void fuse_bwd_plan(int N, int H, int d, unsigned flags, int* rows_per_block, int* chunks, int* part_rows);
 hipError_t launch_fuse_backward(FuseBwdArgs& a, float* dw, float* db, hipStream_t st);
 
+// selfattn_fuse.hip: the multi-head self-attention fusion block, forward and backward (laff_selfattn_fuse, laff_selfattn_fuse_backward)
+struct SelfAttnArgs {
+    const float* x[MAX_L];    // [N, ldx]
+    float* dx[MAX_L];         // [N, lddx]                     backward
+    int ldx[MAX_L], lddx[MAX_L];
+    int L, N, H, d;
+    int prepend, pool, token; // LAFF_SA_PREPEND_*, LAFF_SA_POOL_*, the token index of LAFF_SA_POOL_TOKEN
+    int l2n;                  // l2norm_each_head
+    float scale;              // (d / H) ^ -0.5
+    const float* gamma;       // [d]
+    const float* beta;        // [d]
+    float* E;                 // [N, lde]   pooled output      forward
+    const float* dE;          // [N, lde]   its gradient       backward
+    int lde;
+    float* O;                 // stacked output (LAFF_SA_POOL_ALL): O[n * ldon + l * ldol + h * d + c]
+    const float* dO;          // its gradient
+    int ldon, ldol;
+    float* part;              // workspace [chunks][2 d], or null when neither dgamma nor dbeta is wanted
+    int groups_per_block, chunks;        // filled by the launchers from selfattn_plan
+};
+// how N * H groups are cut: groups per block (a multiple of 4) and blocks = partial rows of dgamma | dbeta
+void selfattn_plan(int N, int H, int* groups_per_block, int* chunks);
+hipError_t launch_selfattn_fuse(SelfAttnArgs& a, hipStream_t st);
+hipError_t launch_selfattn_fuse_backward(SelfAttnArgs& a, float* dgamma, float* dbeta, hipStream_t st);
+
 // fc_bwd.hip: backward of the FC projection A = act(X W^T + bias) (laff_fc_backward)
 struct FcBwdArgs {
     const float* X;           // [N, ldx >= Dk]   read for dW

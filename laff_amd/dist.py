@@ -215,7 +215,7 @@ class HipBackend:
 
     def _fused_pack(self, layer):
         return (self.precision in ('fp16', 'bf16') and layer is not None and hasattr(layer, 'fuse_planes') and
-                type(layer).__name__ != 'JustAverage')
+                type(layer).__name__ != 'JustAverage' and getattr(layer, 'fused_pack', True))
 
     def pack_gathered(self, E, layer=None):
         """GEMM operand of gathered fp32 embedding rows (N, H, d): bit-for-bit what pack() hands over on a single rank -- the fuse

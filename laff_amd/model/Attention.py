@@ -6,8 +6,10 @@ arguments, parameter names (state_dict keys) and output shapes; forward() runs t
   Attention_1                    /root/reference/model/Attention.py:40-105
   Multi_head_MyApply_Attention   /root/reference/model/Attention.py:473-552
   JustAverage                    /root/reference/model/Attention.py:26-37
+  Multi_head_MyApply_selfAttention   /root/reference/model/Attention.py:317-470   (`laff_selfattn_fuse` and its backward,
+                                 _SelfAttnFn below): the multi-head self-attention baseline of the paper
 
-The other 13 variants of that file are ablation baselines never selected by the shipped scripts
+The other 12 variants of that file are ablation baselines never selected by the shipped scripts
  and are not provided.
 """
 import torch
@@ -319,3 +321,169 @@ class Multi_head_MyApply_Attention(nn.Module):
 
     def get_attention_weight(self, head=0):
         return self.attention_layer[head].get_attention_weight().detach()
+
+
+class _SelfAttnFn(torch.autograd.Function):
+    """ops.selfattn_fuse over plain dense fp32 planes with ops.selfattn_fuse_backward as its backward: E (N, H, d), or the stacked tokens
+    (N, L, H * d) for the 'Attention_1' output type.  The planes come as `stacked`, one (N, L, D) tensor whose slices are read in place
+    and whose gradient is written in place, or one by one in `planes` (then stacked is None).  gamma and beta (the shared LayerNorm)
+    receive gradients.  Saves the inputs only: the backward launch recomputes the forward.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, H, d, output_type, l2norm_each_head, gamma, beta, stacked, *planes):
+        srcs = [stacked[:, l, :] for l in range(stacked.shape[1])] if stacked is not None else list(planes)
+        for t in srcs + [gamma, beta]:
+            if t.dtype != torch.float32:
+                raise TypeError('the differentiable self-attention fusion is fp32 only, got %s' % t.dtype)
+        out = ops.selfattn_fuse([t.detach() for t in srcs], H, d, gamma.detach().contiguous(), beta.detach().contiguous(), output_type,
+                                l2norm_each_head)
+        ctx.save_for_backward(gamma, beta, *([stacked] if stacked is not None else []), *planes)
+        ctx.meta = (H, d, output_type, l2norm_each_head, stacked is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        H, d, output_type, l2n, has_stacked = ctx.meta
+        gamma, beta, *saved = ctx.saved_tensors
+        want = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        out = d_stacked = None
+        if has_stacked:
+            stacked = saved[0]
+            d_stacked = torch.empty_like(stacked, memory_format=torch.contiguous_format)
+            srcs = [stacked[:, l, :] for l in range(stacked.shape[1])]
+            out = [d_stacked[:, l, :] for l in range(stacked.shape[1])]
+        else:
+            srcs = saved
+        dxs, dgamma, dbeta = ops.selfattn_fuse_backward(srcs, H, d, gamma.detach().contiguous(), beta.detach().contiguous(), output_type,
+                                                        l2n, grad, want_param_grads=want, out=out)
+        return (None, None, None, None, dgamma, dbeta, d_stacked) + (tuple(dxs) if not has_stacked else ())
+
+
+class Multi_head_MyApply_selfAttention(nn.Module):
+    """Multi-head self-attention over the L fused features, q = k = v = the head slices, residual + one LayerNorm(dim_per_head) shared
+    by all heads, then the pooling `output_type` names -> (batch, H, dim_per_head), not L2-normalised (except under 'Attention_1',
+    where head h of the L outputs goes through Attention_list[h]).  Constructor arguments, parameter names and output shapes are the
+    reference's.  Refused by name: the output types 'cls_embedding' and 'concat', 'random' in training mode, attention dropout > 0 in
+    training mode, dim_per_head < multi_heads (the reference's scale (d // H) ** -0.5 divides by zero)."""
+
+    fused_pack = False        # the rows are not unit-norm and no 16-bit operand rides on this launch: dist.HipBackend packs them itself
+
+    def __init__(self, embed_dim, multi_heads=None, dim_per_head=None, dropout_rate=None, output_type='mean', encoder_num=0,
+                 l2norm_each_head=False, opt=None):
+        super().__init__()
+        if dropout_rate is None:
+            dropout_rate = 0.0
+        assert dim_per_head == embed_dim // multi_heads
+        if output_type in ('cls_embedding', 'concat'):
+            raise NotImplementedError("my_self_attention output type '%s' has upstream parameters of its own and is not provided" %
+                                      output_type)
+        if output_type not in ops.SELFATTN_OUTPUT_TYPES:
+            raise NotImplementedError('my_self_attention output type %r is not provided (provided: %s)' %
+                                      (output_type, ', '.join(ops.SELFATTN_OUTPUT_TYPES)))
+        if dim_per_head < multi_heads:
+            raise ValueError('my_self_attention: dim_per_head=%d < multi_heads=%d: the scale (dim_per_head // multi_heads) ** -0.5 '
+                             'divides by zero' % (dim_per_head, multi_heads))
+        self.dim_per_head = dim_per_head
+        self.multi_heads = multi_heads
+        self.dropout_rate = float(dropout_rate)
+        self.layer_norm = nn.LayerNorm(dim_per_head)
+        self.l2norm_each_head = l2norm_each_head
+        self.output_type = output_type
+        if output_type == 'Attention_1':
+            self.Attention_list = nn.ModuleList()
+            for _ in range(multi_heads):
+                if opt is None:
+                    self.Attention_list.append(Attention_1(dim_per_head))
+                else:
+                    self.Attention_list.append(Attention_1(dim_per_head, with_ave=opt.attention_param_each_head['with_ave'],
+                                                           mul=opt.attention_param_each_head['mul']))
+
+    def _training_refusals(self):
+        if self.output_type == 'random':
+            raise NotImplementedError("my_self_attention output type 'random' draws from Python's random in training mode and is not "
+                                      "provided there (in eval it is the mean)")
+        if self.dropout_rate > 0:
+            raise NotImplementedError('my_self_attention: attention dropout %g in training mode is not provided (the shipped configs '
+                                      'set 0.0)' % self.dropout_rate)
+        if not self.layer_norm.weight.is_cuda:
+            raise NotImplementedError('training mode: my_self_attention trains on the device only (laff_amd has no CPU path); move the '
+                                      'model to the GPU, or call .eval()')
+
+    def _tail(self, tokens, record_weights):
+        """'Attention_1': head h of the stacked tokens (N, L, H * d) through Attention_list[h], the existing fusion launch on the
+        tokens in place -> (N, H, d).  In training mode under _FuseFn (every head's embedding_common receives its slice of dw, db)."""
+        heads = list(self.Attention_list)
+        a0 = heads[0]
+        flags = ops.attention_flags(a0.with_ave, a0.mul)
+        train = self.training
+        keep = (lambda p: p) if train else (lambda p: p.detach())
+        w = torch.stack([keep(a.embedding_common[0].weight).reshape(-1) for a in heads])
+        b = torch.cat([keep(a.embedding_common[0].bias).reshape(1) for a in heads])
+        gw = torch.cat([a.global_emb_weight_net.weight.detach().reshape(1) for a in heads])
+        if train:
+            E, aw = _FuseFn.apply(self.multi_heads, self.dim_per_head, flags, w, b, gw, tokens)
+            aw = aw.detach()
+        else:
+            E, aw = ops.fuse(_planes_of(tokens), self.multi_heads, self.dim_per_head, w, b, gw, flags, return_weights=True)
+        if record_weights:
+            for h, a in enumerate(heads):
+                a.weights = aw[:, h, :] + gw[h] / aw.shape[2] if a.with_ave else aw[:, h, :]
+        return E
+
+    def _run(self, stacked, srcs, record_weights):
+        rec = getattr(self, 'record_weights', False) if record_weights is None else record_weights
+        H, d = self.multi_heads, self.dim_per_head
+        if self.training:
+            self._training_refusals()
+            out = _SelfAttnFn.apply(H, d, self.output_type, bool(self.l2norm_each_head), self.layer_norm.weight, self.layer_norm.bias,
+                                    stacked, *srcs)
+        else:
+            planes = srcs if stacked is None else [stacked[:, l, :] for l in range(stacked.shape[1])]
+            out = ops.selfattn_fuse(planes, H, d, self.layer_norm.weight.detach(), self.layer_norm.bias.detach(), self.output_type,
+                                    bool(self.l2norm_each_head))
+        return self._tail(out, rec) if self.output_type == 'Attention_1' else out
+
+    def fuse_planes(self, planes, heads=None, l2norm_planes=False, record_weights=None):
+        """The block over a tower's plane descriptors.  Training: plain dense planes under autograd (l2norm_planes and expert rows go
+        through the expert stage upstream).  Eval: a plane that is tiled, carries a folded affine, a deferred activation, a gather or
+        the row norm of l2norm_planes is written out first (one just-average launch of the existing fusion kernel per such plane)."""
+        if self.training:
+            return self._run(None, _train_sources(planes, l2norm_planes), record_weights)
+        D = self.multi_heads * self.dim_per_head
+        srcs = []
+        for p in planes:
+            p = p if isinstance(p, tuple) else (p, False, None, None)
+            plain = not p[1] and p[2] is None and p[3] is None and all(x is None for x in p[4:])
+            if plain and not l2norm_planes:
+                srcs.append(p[0])
+            else:
+                out = ops.fuse([p], self.multi_heads, self.dim_per_head, None, None, None, ops.attention_flags(just_average=True),
+                               l2norm_planes=l2norm_planes)
+                srcs.append(out.view(out.shape[0], D))
+        return self._run(None, srcs, record_weights)
+
+    def forward(self, local_embs, raw_global_emb=None, attn_mask=None):
+        if attn_mask is not None:
+            raise NotImplementedError('attn_mask is never passed on the retrieval path')
+        return self._run(_train_stacked(local_embs), [], True)
+
+    def get_raw_global_emb_weight(self):
+        if hasattr(self, 'Attention_list'):
+            return self.Attention_list[0].get_raw_global_emb_weight()
+        return 0
+
+    def change_raw_global_emb_weight(self, new_value):
+        if hasattr(self, 'Attention_list'):
+            for a in self.Attention_list:
+                a.change_raw_global_emb_weight(new_value)
+        return 0
+
+    def get_attention_weight(self):
+        if not hasattr(self, 'Attention_list'):
+            raise Exception('SelfAttention weights is not applied')
+        weights = None
+        for a in self.Attention_list:
+            w = a.get_attention_weight()
+            weights = w if weights is None else weights + w
+        return weights / self.multi_heads

@@ -40,7 +40,7 @@ import torch.nn.functional as F
 from .. import loss as _loss
 from .. import ops
 from .. import optim as _optim
-from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention
+from .Attention import Attention_1, JustAverage, Multi_head_MyApply_Attention, Multi_head_MyApply_selfAttention
 from .autograd import (_csc_of, _DropoutBnFn, _ExpertStageFn, _FcActFn, _FcConcatFn, _FcConcatGroupedFn, _FcGatherFn, _fp32_params,  # noqa: F401  (kept importable from here)
                        _TileBnFn)
 
@@ -188,6 +188,11 @@ def get_attention_layer(attention_type, common_space_dim, encoder_num, opt):
             common_space_dim, heads, common_space_dim // heads,
             with_ave=opt.attention_param_each_head['with_ave'], mul=opt.attention_param_each_head['mul'],
             split_head=opt.attention_param_each_head['split_head'], l2norm_each_head=opt.attention_l2norm)
+    if attention_type == 'my_self_attention':       # multi_head + official self-attention, the baseline LAFF is compared with
+        heads = opt.multi_head_attention['heads']
+        return Multi_head_MyApply_selfAttention(
+            common_space_dim, heads, common_space_dim // heads, opt.multi_head_attention['dropout'],
+            output_type=opt.my_self_attention_output_type, encoder_num=encoder_num, l2norm_each_head=opt.attention_l2norm, opt=opt)
     raise NotImplementedError("attention type '%s' is an ablation variant outside the LAFF hot path" % attention_type)
 
 

@@ -17,7 +17,8 @@ from ._lib import (ACT, GRU_POOLING, ATT_JUST_AVERAGE, ATT_L2NORM_EACH_HEAD, ATT
                    FcLaunch, FcShape, RerankProblem)
 
 __all__ = ['sim_hist', 'rerank_workspace_bytes', 'rerank_run', 'rerank_tkb', 'frame_preprocess', 'frame_desc_device', 'netvlad_workspace_bytes', 'netvlad_encode', 'netvlad_train_reserve_bytes', 'netvlad_backward_workspace_bytes', 'netvlad_encode_train', 'netvlad_backward', 'bert_workspace_bytes', 'bert_encode', 'clip_pack_weight', 'clip_workspace_bytes', 'clip_encode', 'gru_pack_whh', 'gru_workspace_bytes', 'gru_encode', 'gru_pack_whh_t', 'gru_gather_rows', 'batch_assemble', 'gru_train_reserve_bytes', 'gru_encode_train', 'gru_backward', 'gru_backward_plan', 'gru_backward_workspace_bytes', 'rank_resolve_metrics', 'rank_prepare', 'rank_prepare_text', 'rank_band_video', 'rank_export_pairs', 'rank_resolve_list', 'sim_gemm_banded', 'rank_resolve', 'exact_ranks', 'RankState', 'topk_rows', 'topk_from_operands', 'alloc_scores', 'frame_fuse_grouped', 'fc_act_bn_fused_grouped', 'fused_split_eligible', 'fc_strip_pack', 'fc_strip_eligible', 'fc_act_bn_strip_grouped', 'StripWeights', 'margin_loss', 'dsl_loss', 'margin_loss_scores', 'fc_gather_act_bn', 'fc_act_bn', 'fc_act_bn_grouped', 'fc_act_bn_split_grouped', 'split_rows', 'row_dot_gt', 'rank_metrics_async', 'fuse', 'fuse_backward', 'fc_backward', 'fc_backward_plan', 'csr_transpose', 'fc_gather_backward', 'fc_concat_backward', 'fc_concat_backward_plan', 'dropout_bn_train', 'dropout_bn_train_backward', 'tile_bn_train_plan', 'tile_bn_train', 'tile_bn_train_backward', 'expert_stage_train_plan', 'expert_stage_train', 'expert_stage_train_backward', 'dropout_bn_train_plan', 'optim_plan', 'optim_last_launches', 'grad_sqnorm', 'grad_scale', 'optim_step', 'frame_fuse', 'frame_fuse_backward', 'frame_fuse_backward_plan', 'pack_rows', 'sim_gemm', 'sim_gemm_route', 'SIM_ROUTES', 'fc_route', 'FC_ROUTES', 'FcRoute', 'gather_gt', 'rank_count', 'v2t_count', 'v2t_count_exact', 'reset_contexts', 'FusedPrepare', 'fused_prepare_eligible',
-           'rank_metrics', 'attention_flags', 'PREC', 'default_prescale']
+           'rank_metrics', 'attention_flags', 'PREC', 'default_prescale', 'selfattn_fuse', 'selfattn_fuse_backward',
+           'selfattn_fuse_backward_plan', 'selfattn_mode', 'SELFATTN_OUTPUT_TYPES']
 
 _ctx = {}
 #: the library's LAFF_FC_STRIP_MFMA mode (process-wide; the library reads the variable whenever a context is created, and so does
@@ -1371,6 +1372,104 @@ def fuse_backward(planes, H, d, w, b, gw, flags, grad_E, want_param_grads=True, 
     _call('fuse_backward', lib.laff_fuse_backward, h, xp, xl, L, N, H, d, _ptr(w), _ptr(b), _ptr(gw), flags, _ptr(g), lde, dp, dl,
           _ptr(dw), _ptr(db), _ptr(ws), nbytes)
     return dxs, dw, db
+
+
+SELFATTN_OUTPUT_TYPES = ('mean', 'max', 'first', 'last', 'second', 'third', 'max_embedding', 'mean_embedding', 'random', 'Attention_1')
+
+
+def selfattn_mode(output_type, L):
+    """(prepend, pool, token) of laff_selfattn_fuse for an output type of Multi_head_MyApply_selfAttention over L planes.  'random' is
+    its eval-mode meaning, the mean (model/Attention.py:418-422 of the reference); the caller refuses it in training."""
+    K = _lib.K
+    none, mean, mx, tok = K['LAFF_SA_PREPEND_NONE'], K['LAFF_SA_POOL_MEAN'], K['LAFF_SA_POOL_MAX'], K['LAFF_SA_POOL_TOKEN']
+    table = {'mean': (none, mean, 0), 'random': (none, mean, 0), 'max': (none, mx, 0), 'first': (none, tok, 0),
+             'last': (none, tok, L - 1), 'second': (none, tok, 1 if L >= 2 else 0), 'third': (none, tok, 2 if L >= 3 else 0),
+             'max_embedding': (K['LAFF_SA_PREPEND_MAX'], tok, 0), 'mean_embedding': (K['LAFF_SA_PREPEND_MEAN'], tok, 0),
+             'Attention_1': (none, K['LAFF_SA_POOL_ALL'], 0)}
+    if output_type not in table:
+        raise NotImplementedError('my_self_attention output type %r is not provided (provided: %s)' %
+                                  (output_type, ', '.join(SELFATTN_OUTPUT_TYPES)))
+    return table[output_type]
+
+
+def _selfattn_operands(planes, H, d, gamma, beta):
+    """The planes of a self-attention launch as host arrays -- (N, device, tensors kept alive, pointers, pitches) -- and gamma / beta
+    checked.  A plane whose rows are not 16-byte aligned is copied."""
+    srcs = [dense_plane(p, i) for i, p in enumerate(planes)]
+    N = srcs[0].shape[0]
+    kept, ptrs, lds = _plane_arrays(srcs, 'planes', N, H * d)
+    _vec(gamma, d, 'gamma')
+    _vec(beta, d, 'beta')
+    return N, kept[0].device, kept, ptrs, lds
+
+
+def selfattn_fuse(planes, H, d, gamma, beta, output_type, l2norm_each_head=False, out=None):
+    """The multi-head self-attention fusion block (laff_selfattn_fuse) over L plain dense fp32 planes (N, H * d) -- tensors or
+    (src, False, None, None) tuples; row views with 16-byte aligned rows are read in place --, gamma / beta (d,) the LayerNorm shared by
+    all heads.  Returns E (N, H, d), or for 'Attention_1' the stacked tokens (N, L, H * d).  out: the buffer that receives them
+    (pitches allowed)."""
+    L = len(planes)
+    prepend, pool, token = selfattn_mode(output_type, L)
+    N, dev, kept, ptrs, lds = _selfattn_operands(planes, H, d, gamma, beta)
+    flags = ATT_L2NORM_EACH_HEAD if l2norm_each_head else 0
+    lib, h = _context(dev)
+    if pool == _lib.K['LAFF_SA_POOL_ALL']:
+        O = torch.empty((N, L, H * d), device=dev, dtype=torch.float32) if out is None else out
+        O, ldn, ldl = _stacked3(O, N, L, H * d, 'out')
+        _call('selfattn_fuse', lib.laff_selfattn_fuse, h, ptrs, lds, L, N, H, d, _ptr(gamma), _ptr(beta), prepend, pool, token, flags,
+              None, 0, _ptr(O), ldn, ldl)
+        return O
+    E = torch.empty((N, H, d), device=dev, dtype=torch.float32) if out is None else out
+    E2, lde = _rows(E.view(N, H * d), 'out')
+    _call('selfattn_fuse', lib.laff_selfattn_fuse, h, ptrs, lds, L, N, H, d, _ptr(gamma), _ptr(beta), prepend, pool, token, flags,
+          _ptr(E2), (lde + 3) // 4 * 4 if N <= 1 else lde, None, 0, 0)
+    return E
+
+
+def selfattn_fuse_backward_plan(N, H, d):
+    """laff_selfattn_fuse_backward_plan (host only): (workspace bytes when dgamma / dbeta are asked, partial rows = blocks)."""
+    return _plan_query('laff_selfattn_fuse_backward_plan', 2, N, H, d)
+
+
+def selfattn_fuse_backward(planes, H, d, gamma, beta, output_type, l2norm_each_head, grad, want_param_grads=True, out=None):
+    """Backward of selfattn_fuse (laff_selfattn_fuse_backward): the forward's planes and parameters, grad = the gradient of E ((N, H, d)
+    or (N, H * d), any strides) or, for 'Attention_1', of the stacked tokens (N, L, H * d) (read in place when its rows are 16-byte
+    aligned).  Returns (list of L dx (N, H * d), dgamma (d,), dbeta (d,)) -- the last two None unless want_param_grads.
+    out: a list of L fp32 row views (N, H * d) with 16-byte aligned rows that receive the dx, e.g. the slices of a stacked gradient."""
+    L = len(planes)
+    prepend, pool, token = selfattn_mode(output_type, L)
+    N, dev, kept, ptrs, lds = _selfattn_operands(planes, H, d, gamma, beta)
+    D = H * d
+    flags = ATT_L2NORM_EACH_HEAD if l2norm_each_head else 0
+    _dev(grad, 'grad')
+    gE = gO = None
+    lde = ldn = ldl = 0
+    if pool == _lib.K['LAFF_SA_POOL_ALL']:
+        g = grad
+        if g.dim() == 3 and g.numel() and (g.stride(2) != 1 or g.stride(0) % 4 or g.stride(1) % 4 or g.data_ptr() % 16 or
+                                           (N > 1 and g.stride(0) < D) or (L > 1 and g.stride(1) < D)):
+            g = g.contiguous()
+        gO, ldn, ldl = _stacked3(g, N, L, D, 'grad')
+    else:
+        if grad.numel() != N * D:
+            raise ValueError('grad has %d elements, expected (%d, %d, %d)' % (grad.numel(), N, H, d))
+        gE, lde = _mat(grad.reshape(N, D), 'grad', align16=True)
+        if N <= 1:
+            lde = (lde + 3) // 4 * 4
+    dxs = [torch.empty((N, D), device=dev, dtype=torch.float32) for _ in range(L)] if out is None else list(out)
+    if len(dxs) != L:
+        raise ValueError('out must hold %d tensors' % L)
+    dkept, dptrs, dlds = _plane_arrays(dxs, 'out', N, D)
+    if any(a is not b for a, b in zip(dkept, dxs)):
+        raise ValueError('out must be row views with 16-byte aligned rows')
+    dgamma = torch.empty((d,), device=dev, dtype=torch.float32) if want_param_grads else None
+    dbeta = torch.empty((d,), device=dev, dtype=torch.float32) if want_param_grads else None
+    nbytes = selfattn_fuse_backward_plan(N, H, d)[0] if want_param_grads else 0
+    ws = _workspace(nbytes, dev)
+    lib, h = _context(dev)
+    _call('selfattn_fuse_backward', lib.laff_selfattn_fuse_backward, h, ptrs, lds, L, N, H, d, _ptr(gamma), _ptr(beta), prepend, pool, token,
+          flags, _ptr(gE), lde, _ptr(gO), ldn, ldl, dptrs, dlds, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes)
+    return dxs, dgamma, dbeta
 
 
 def fc_backward_plan(N, Dk, D, want_dx=True, want_dw=True):
